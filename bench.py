@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the DBSCAN + ICP hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode single|blocks|exact|replicas]
+    python bench.py --gpus N --steps K --warmup W [--mode single|blocks|exact|replicas] [--full] [--dump-outputs DIR]
 
-metric = BASELINE.json's "Mpoints/s DBSCAN+label @10M pts"; one JSON line on rank 0 (driver contract).  With
+metric = BASELINE.json's "Mpoints/s DBSCAN+label @10M pts"; one JSON line on rank 0 (driver contract).  A plain run
+sets up, warms up, times the K steps and prints that line (with the per-phase times the timed steps record).  --full
+adds everything else, each outside the timed region: the device-copy ceiling of the roofline, the CPU baselines, the
+side measurements (other densities, the 3-D form, ICP, centroids / matching, the block pipeline) and, in mode blocks,
+the same job through the single-device entry points plus its per-stage times.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (float64 / float32; a fixed, seeded sample of the per-point arrays).  With
 --gpus N > 1 and no WORLD_SIZE in the environment the script starts `python -m torch.distributed.run` itself (as a
 child process, before anything touches the GPU) and relays its output and exit code; a WORLD_SIZE that disagrees with
 --gpus is an error, so a 1-GPU number can never be recorded as an N-GPU run.
@@ -35,7 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X spec sheet
 
 # Algorithmic bytes per point of each kernel phase for the 2-D binary64 path: what the
 # phase must read/write once if every neighbour access hits cache.
@@ -78,9 +83,19 @@ def parse(argv=None):
                     help="default: single at --gpus 1, blocks at --gpus > 1 (see the module docstring)")
     ap.add_argument("--gather-labels", action="store_true",
                     help="mode replicas: also all-gather every rank's int32 labels onto every rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the ICP / block pipeline side measurements")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the copy ceiling, the CPU baselines, the side measurements and "
+                         "(mode blocks) the single-device comparison; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the ICP / block pipeline side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (modes single and blocks)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode not in (None, "single", "blocks"):
+        ap.error("--dump-outputs: modes single and blocks")
+    return args
 
 
 def launch_ranks_if_needed(args):
@@ -301,6 +316,29 @@ def roofline_of(avg, n_points, dim, metric_name):
             "algorithmic_bytes_per_point": bpp, "kernel_ms": avg[dom]}
 
 
+DUMP_SAMPLE = 2_000_000  # per point: index f64 + label f64 + two flags f32 = 24 B, so 48 MB at most
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, n, device, per_point, scalars):
+    """--dump-outputs: what the last timed step computed, as <out_dir>/<name>.npy.  Every per-point array (a device
+    tensor of at least n entries) is written at the same fixed, seeded sample of min(n, DUMP_SAMPLE) indices, kept in
+    ascending order in sample_index.npy; every scalar as a one-element float64 array.  per_point: {name: (tensor,
+    numpy dtype)}; float64 holds int32 labels exactly, float32 the 0/1 flags."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    d_idx = torch.from_numpy(idx).to(device)
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    for name, (t, dtype) in per_point.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t[:n].index_select(0, d_idx).cpu().numpy().astype(dtype))
+    for name, v in scalars.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.array([v], dtype=np.float64))
+
+
 def main():
     args = parse()
     launch_ranks_if_needed(args)
@@ -364,8 +402,12 @@ def main():
         if dist:
             dist.barrier()
 
+    def dump(per_point, scalars):
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, n, dev, per_point, scalars)
+
     if mode == "blocks":
-        # the timed loop runs without per-phase events; one more step afterwards, untimed, collects them
+        # the timed loop runs without per-phase events; with --full one more step afterwards, untimed, collects them
         ctx.timing_enable(False)
         shd = True if args.force_sharded else None
         dt, last = blocks_workload(ctx, coords, dev, 0, args.warmup, motor_dev_ptr=d_coords.data_ptr(), sync=sync,
@@ -373,7 +415,10 @@ def main():
         dt, last = blocks_workload(ctx, coords, dev, args.steps, 0, motor_dev_ptr=d_coords.data_ptr(), sync=sync,
                                    barrier=barrier, sharded=shd)
         cf, total_points = last["cluster_amount"], n
-        if rank == 0:
+        # every rank ends with the full label array
+        dump({"labels": (last["labels"], np.float64)},
+             {k: last[k] for k in ("cluster_amount", "kept", "del_sum", "evals")})
+        if rank == 0 and args.full:
             # the SAME job on one GPU (the single-device entry points), outside the timed region: what the N-GPU line
             # above is a speed-up of
             loc1 = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -481,6 +526,9 @@ def main():
         barrier()
         sync()
         dt = time.perf_counter() - t0
+        if mode == "single":
+            dump({"labels": (d_labels, np.float64), "is_key_point": (d_core, np.float32),
+                  "is_classed": (d_cls, np.float32)}, {"clusters": cf, "dist_evals": ev})
         if not (mode == "exact" or world == 1):
             cf = int(cf.sum().item())
         total_points = world * n
@@ -504,18 +552,20 @@ def main():
 
     out = None
     if rank == 0:
-        # measured device-copy ceiling: 1 GiB device-to-device copy, read + write bytes per second
-        a = torch.empty(1 << 27, dtype=torch.float64, device=dev)
-        b = torch.empty_like(a)
-        b.copy_(a)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
+        copy_gbs = None
+        if args.full:
+            # measured device-copy ceiling: 1 GiB device-to-device copy, read + write bytes per second
+            a = torch.empty(1 << 27, dtype=torch.float64, device=dev)
+            b = torch.empty_like(a)
             b.copy_(a)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbs = 5 * 2 * a.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del a, b
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                b.copy_(a)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbs = 5 * 2 * a.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del a, b
         ms_per_step = dt / args.steps * 1e3
         value = total_points / (dt / args.steps) / 1e6
         avg = {k: float(np.mean(v)) for k, v in phase_ms.items()}
@@ -527,8 +577,9 @@ def main():
         else:
             roof = roofline_of(avg, n, dim, args.metric)
         if roof:
-            roof["copy_ceiling_GBs"] = copy_gbs
-            roof["frac_of_copy_ceiling"] = roof["achieved"] / copy_gbs
+            if copy_gbs is not None:
+                roof["copy_ceiling_GBs"] = copy_gbs
+                roof["frac_of_copy_ceiling"] = roof["achieved"] / copy_gbs
             if mode == "single":
                 total_bpp = sum(ALGO_BYTES_PER_POINT.get(k, 0) for k in avg) + (0 if dim == 2 else 8 * len(avg))
                 roof["pipeline_algorithmic_bytes_per_point"] = total_bpp
@@ -570,8 +621,8 @@ def main():
             out["speedup_vs_single_gpu_same_workload"] = same_single["ms"] / ms_per_step
             out["labels_identical_to_single_gpu_run"] = same_single["labels_identical_to_the_timed_run"]
 
-    # ---- side measurements on rank 0 at N=1 -----------------------------------------------------------
-    extras = rank == 0 and world == 1 and not args.no_extras
+    # ---- side measurements on rank 0 at N=1 (--full) ---------------------------------------------------
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     cen = truth = Mt = None
     if extras and mode == "blocks":
         # the same cloud through the monolithic call, for reference beside the block pipeline
@@ -680,7 +731,7 @@ def main():
             out["block_pipeline"] = {"ms": best * 1e3, "Mpoints_per_s": n / best / 1e6, "blocks": info["nblocks"],
                                      "clusters": fin["cluster_amount"], "eps": 0.07, "min_pts": 7, "pts_in_cell": 200}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cloud, coords, eps, min_pts, metric_id)
         if cen is not None:
             out["cpu_baseline"]["B4_matching"] = cpu_baseline_match(cen, truth, Mt)

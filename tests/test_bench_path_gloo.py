@@ -28,6 +28,19 @@ def test_bench_blocks_step_over_gloo(world, port, tmp_path, oracle):
         assert a[1] == b[0]
 
 
+def test_bench_options():
+    """A plain run is lean (--full is off by default), --steps sets the number of timed steps and must be positive, and
+    --dump-outputs takes the one-cloud modes only."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "d", "--mode", "blocks"])
+    assert a.full and a.dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--mode", "exact", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
 def test_bench_refuses_mismatched_world(tmp_path):
     """--gpus must agree with WORLD_SIZE: a 1-rank run can never be recorded as an N-GPU line."""
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

@@ -11,7 +11,7 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -- python3 bench.py $ARGS > "$OUT/bench_write.log" 2>&1
 # kernel times of the side measurements (ICP, block pipeline, centroids): stats only, L1_2D default run
 if [ -z "$2" ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_extras" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_extras.log" 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_extras" -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > "$OUT/bench_extras.log" 2>&1
 fi
 find "$OUT" -name '*.csv' | head -50
 # keep the merge-back small: the per-dispatch traces can be large
