@@ -377,6 +377,31 @@ int vcp_import_convert(vcp_ctx* ctx, const double* rows, int64_t n, double x_ang
 int vcp_assign_truths(vcp_ctx* ctx, const double* motor, int64_t n, const double* truths_xy,
                       const int32_t* truth_ids, int32_t T, double radius, int32_t* ids, int64_t* outliers);
 
+/* -- k-distance ---------------------------------------------------------------------------------
+ * The k-distance graph of Ester et al. (1996) for choosing DBSCAN's eps (the reference types eps by hand:
+ * Clustering.Designer.cs:86,96, ClusterByMatlab.Designer.cs:86,96).  Exact k nearest neighbours of every point:
+ *   d(i,j)     the binary64 expression vcp_dbscan tests: VCP_L1_2D |dx| + |dy|, VCP_L2_2D sqrt(dx*dx + dy*dy),
+ *              VCP_L2_3D sqrt(dx*dx + dy*dy + dz*dz) (sums left to right, no FMA contraction, correctly rounded
+ *              sqrt); VCP_SIGNED_SUM_2D = VCP_ERR_ARG
+ *   kdist[i]   the k-th smallest value of the multiset { d(i,j) : j = 0..n-1 } -- j = i INCLUDED, like the core
+ *              count of DBImproved.isKeyPoint -- so that for every finite eps >= 0
+ *                vcp_dbscan(..., eps, min_pts = k, in_classed = NULL).is_core[i] == (kdist[i] <= eps)
+ *              bit for bit
+ *   knn [n*k]  may be NULL: row i = the k indices j with the smallest (d(i,j), j) pairs, ascending (a lower index
+ *              wins a tie); the last one's value is kdist[i]
+ * A point with a NaN / infinite coordinate has no neighbour, not even itself: kdist NaN, knn row all -1, and it is
+ * nobody's candidate.  A finite point with fewer than k finite points in the cloud: kdist +inf, the missing slots -1.
+ * coords [n*dim] point-major, dim 2 or 3 (the 2-D metrics read x, y; VCP_L2_3D needs dim 3).  Limits: 1 <= k <= 64
+ * (k < 1: VCP_ERR_ARG, k > 64: VCP_ERR_UNSUPPORTED), n < 2^31 (int32 indices; VCP_ERR_TOO_LARGE beyond); a cloud whose
+ * coordinate differences overflow binary64 is VCP_ERR_UNSUPPORTED, as in vcp_dbscan.  n = 0 does nothing.
+ * Deterministic: two calls on the same input give identical bits.  Timing phases: kdist_bounds, kdist_order,
+ * kdist_search, kdist_heavy (csrc/kdist.hip). */
+int vcp_kdist(vcp_ctx* ctx, const double* coords, int64_t n, int dim, int metric, int k, double* kdist,
+              int32_t* knn);
+/* Same with device pointers (d_knn may be NULL), on the context's stream; returns when the result is in place. */
+int vcp_kdist_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, int metric, int k, double* d_kdist,
+                  int32_t* d_knn);
+
 #ifdef __cplusplus
 }
 #endif

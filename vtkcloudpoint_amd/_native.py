@@ -30,7 +30,7 @@ SYMBOLS = [
     "vcp_selftest_horn", "vcp_create_multi", "vcp_destroy_multi", "vcp_multi_last_error", "vcp_multi_count",
     "vcp_multi_ctx", "vcp_dbscan_blocks_multi", "vcp_blocks_share_plan", "vcp_blocks_plan_dev", "vcp_blocks_plan_cuts",
     "vcp_blocks_build_dev", "vcp_blocks_finish_local_dev", "vcp_blocks_finish_zero_dev", "vcp_blocks_finish_zcoords_dev",
-    "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev",
+    "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev",
 ]
 
 
@@ -172,6 +172,25 @@ class Context:
                                        _ptr(d_labels), _ptr(d_is_core), _ptr(d_is_classed), C.byref(cf),
                                        C.byref(ev)))
         return cf.value, ev.value
+
+    # -- k-distance ------------------------------------------------------------------------------
+    def kdist(self, coords, k, metric=L1_2D, want_knn=False):
+        """Exact k-distance of every point (vcp_kdist): returns (kdist [n] float64, knn [n, k] int32 or None).
+        kdist[i] <= eps  <=>  dbscan(coords, eps, min_pts=k).is_core[i]."""
+        coords = _f64(coords)
+        if coords.ndim != 2:
+            coords = coords.reshape(0, 2)
+        n, dim = coords.shape
+        kd = np.zeros(n, np.float64)
+        knn = np.zeros((n, max(int(k), 0)), np.int32) if want_knn else None
+        self._chk(lib().vcp_kdist(self._h, _ptr(coords), C.c_int64(n), int(dim), int(metric), int(k), _ptr(kd),
+                                  _ptr(knn)))
+        return kd, knn
+
+    def kdist_dev(self, d_coords, n, dim, k, d_kdist, d_knn=None, metric=L1_2D):
+        """Device-pointer form (ints from tensor.data_ptr()); d_knn may be None."""
+        self._chk(lib().vcp_kdist_dev(self._h, _ptr(d_coords), C.c_int64(n), int(dim), int(metric), int(k),
+                                      _ptr(d_kdist), _ptr(d_knn)))
 
     # -- ICP -----------------------------------------------------------------------------------
     def icp(self, model, data, tol=1e-4, max_iter=100, stop_rule=STOP_SSE_DELTA):

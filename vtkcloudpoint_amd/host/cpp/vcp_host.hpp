@@ -244,4 +244,20 @@ inline int RecorrectMatchingPtsByDistance(Context& c, std::vector<Point3D>& cent
   return cnt;
 }
 
+// k-distance of every point for DBImproved with minPts = k (vcp.h: vcp_kdist): kd[i] <= eps exactly when point i is a
+// core point at eps.  L1 on (motor_x, motor_y) by default, X/Y/Z with VCP_L2_3D; knn (may be null) gets n*k indices.
+inline std::vector<double> k_distance(Context& c, const std::vector<Point3D*>& pts, int k, int metric = VCP_L1_2D,
+                                      std::vector<int32_t>* knn = nullptr) {
+  const int64_t n = (int64_t)pts.size();
+  const int dim = metric == VCP_L2_3D ? 3 : 2;
+  std::vector<double> xy(n * dim), kd(n);
+  for (int64_t i = 0; i < n; i++) {
+    if (dim == 3) { xy[3 * i] = pts[i]->X; xy[3 * i + 1] = pts[i]->Y; xy[3 * i + 2] = pts[i]->Z; }
+    else { xy[2 * i] = pts[i]->motor_x; xy[2 * i + 1] = pts[i]->motor_y; }
+  }
+  if (knn) knn->assign(n * (k > 0 ? k : 0), -1);
+  c.check(vcp_kdist(c.get(), xy.data(), n, dim, metric, k, kd.data(), knn ? knn->data() : nullptr));
+  return kd;
+}
+
 }  // namespace vtkPointCloud

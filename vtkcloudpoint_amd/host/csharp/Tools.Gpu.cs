@@ -210,5 +210,42 @@ namespace vtkPointCloud
             for (long t = 0; t < m; t++) clusForMerge.Add(rawData[(int)order[t]]);
             return clusForMerge;
         }
+
+        // k-distance of every point for DBImproved with minPts = minPts (L1 on motor_x / motor_y, what the shipped
+        // DBImproved measures): kd[i] <= eps exactly when the point is a core point at eps (vcp.h: vcp_kdist)
+        public static double[] KDistance(List<Point3D> rawData, int minPts)
+        {
+            int n = rawData.Count;
+            double[] mot = new double[2 * n], kd = new double[n];
+            for (int i = 0; i < n; i++) { mot[2 * i] = rawData[i].motor_x; mot[2 * i + 1] = rawData[i].motor_y; }
+            if (n == 0) return kd;
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_kdist(c.Ctx, mot, n, 2, VcpNative.VCP_L1_2D, minPts, kd, null));
+            return kd;
+        }
+
+        // A HEURISTIC eps for minPts: the knee of the sorted k-distance curve (vtkcloudpoint_amd/kdist.py: eps_from_curve)
+        // -- finite values sorted, the top (1 - topQuantile) dropped, the rest mapped onto [0,1]^2, the value at the
+        // first maximum of x - y.
+        public static double SuggestEps(List<Point3D> rawData, int minPts, double topQuantile = 0.99)
+        {
+            double[] kd = KDistance(rawData, minPts);
+            List<double> v = new List<double>(kd.Length);
+            foreach (double d in kd) if (!double.IsNaN(d) && !double.IsInfinity(d)) v.Add(d);
+            if (v.Count == 0) return double.NaN;
+            v.Sort();
+            double q = Math.Min(Math.Max(topQuantile, 0.0), 1.0);
+            int m = (int)Math.Ceiling(q * (v.Count - 1)) + 1;
+            double lo = v[0], hi = v[m - 1];
+            if (m == 1 || !(hi > lo)) return lo;
+            int best = 0;
+            double bestGap = double.NegativeInfinity;
+            for (int i = 0; i < m; i++)
+            {
+                double gap = (double)i / (m - 1) - (v[i] - lo) / (hi - lo);
+                if (gap > bestGap) { bestGap = gap; best = i; }
+            }
+            return v[best];
+        }
     }
 }

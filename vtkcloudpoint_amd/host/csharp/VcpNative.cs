@@ -77,6 +77,11 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_assign_truths(IntPtr ctx, double[] motor, long n, double[] truths_xy,
             int[] truth_ids, int T, double radius, int[] ids, out long outliers);
 
+        // k-distance graph for choosing eps (no reference counterpart: the dialogs take eps typed by hand,
+        // Clustering.Designer.cs:86,96); knn may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_kdist(IntPtr ctx, double[] coords, long n, int dim, int metric,
+            int k, double[] kdist, int[] knn);
+
         // ---- device-resident forms (IntPtr = device address): for hosts that keep the cloud on the GPU between
         // calls, and for the multi-GPU drivers (one process and one context per GPU) ----
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_dev_alloc(IntPtr ctx, ulong bytes, out IntPtr dptr);
@@ -88,6 +93,8 @@ namespace vtkPointCloud
             out int cf_out, out long dist_evals);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_centroids_dev(IntPtr ctx, IntPtr d_xyz, IntPtr d_motor, IntPtr d_labels,
             long n, int K, IntPtr d_c3, IntPtr d_c2, IntPtr d_counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_kdist_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
+            int k, IntPtr d_kdist, IntPtr d_knn);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_dev(IntPtr ctx, IntPtr d_model, long nm, IntPtr d_data, long nd,
             double tol, int max_iter, int stop_rule, double[] R, double[] T, out double sse, out double rmse, out int iters);
         // block pipeline in stages (per-block step sharded over GPUs, distributed.py: sharded_blocks)
