@@ -94,6 +94,26 @@ def test_errors(vcp_ctx):
     assert e.value.code == -3  # zero-extent first block
 
 
+def test_non_finite_partition_coordinates_then_a_good_call(vcp_ctx, oracle):
+    """A NaN / +-inf key or motor coordinate fails with VCP_ERR_ARG after the selection pass (which then runs on the
+    bounds of the finite coordinates); the same context then clusters a good cloud exactly."""
+    mot = synth.config_cloud(20_000, seed=21)["motor"]
+    key = mot[::-1].copy()
+    for bad in (np.nan, np.inf, -np.inf):
+        k2 = key.copy()
+        k2[7, 1] = bad
+        with pytest.raises(N.VcpError) as e:
+            vcp_ctx.dbscan_blocks(mot, 0.1, 10, 300, 3, key_xy=k2)
+        assert e.value.code == -1
+        m2 = mot.copy()
+        m2[11, 0] = bad
+        with pytest.raises(N.VcpError) as e:
+            vcp_ctx.dbscan_blocks(m2, 0.1, 10, 300, 3)
+        assert e.value.code == -1
+    _same(vcp_ctx.dbscan_blocks(mot, 0.1, 10, 300, 3, key_xy=key), oracle.block_pipeline(mot, 0.1, 10, 300, 3, key_xy=key),
+          "after the failed calls")
+
+
 def test_keyed_partition_getClusterFromList(vcp_ctx, oracle):
     """The 3-D twin (FrmMain.cs:1136-1213, Tools.getListByScale BC/Tools.cs:507-509): blocks are cut on (X, Y), every
     DBImproved still clusters on (motor_x, motor_y).  One-shot and staged forms vs the oracle."""

@@ -32,6 +32,8 @@
 #include <cstring>
 
 #include "blocks_state.hpp"
+#include "bounds.hpp"
+#include "reduce.hpp"
 
 namespace {
 constexpr int BT = 256;
@@ -109,89 +111,6 @@ __device__ __forceinline__ void sel_push(unsigned long long& phi, unsigned long 
   }
 }
 
-__device__ __forceinline__ double wmin(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = fmin(v, __shfl_down(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
-  return v;
-}
-
-// per-workgroup partials [nb][5]: x min, x max, y min, y max, number of non-finite coordinates
-__global__ __launch_bounds__(BT) void k_minmax2_part(const double* __restrict__ c, int64_t n, double* __restrict__ part) {
-  double xmn = INFINITY, xmx = -INFINITY, ymn = INFINITY, ymx = -INFINITY, bad = 0;
-  for (int64_t i = (int64_t)blockIdx.x * BT + threadIdx.x; i < n; i += (int64_t)gridDim.x * BT) {
-    const double2 v = *reinterpret_cast<const double2*>(c + 2 * i);
-    if (!isfinite(v.x) || !isfinite(v.y)) bad += 1.0;
-    xmn = fmin(xmn, v.x);
-    xmx = fmax(xmx, v.x);
-    ymn = fmin(ymn, v.y);
-    ymx = fmax(ymx, v.y);
-  }
-  __shared__ double sm[BT / 64][5];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double a = wmin(xmn), b = wmax(xmx), cc = wmin(ymn), d = wmax(ymx), e = bad;
-#pragma unroll
-  for (int k = 32; k > 0; k >>= 1) e += __shfl_down(e, k, 64);
-  if (lane == 0) {
-    sm[w][0] = a;
-    sm[w][1] = b;
-    sm[w][2] = cc;
-    sm[w][3] = d;
-    sm[w][4] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < BT / 64; k++) {
-      sm[0][0] = fmin(sm[0][0], sm[k][0]);
-      sm[0][1] = fmax(sm[0][1], sm[k][1]);
-      sm[0][2] = fmin(sm[0][2], sm[k][2]);
-      sm[0][3] = fmax(sm[0][3], sm[k][3]);
-      sm[0][4] += sm[k][4];
-    }
-    for (int k = 0; k < 5; k++) part[(size_t)blockIdx.x * 5 + k] = sm[0][k];
-  }
-}
-__global__ __launch_bounds__(BT) void k_minmax2_final(const double* __restrict__ part, int nb, double* __restrict__ out) {
-  double a = INFINITY, b = -INFINITY, c = INFINITY, d = -INFINITY, e = 0;
-  for (int k = threadIdx.x; k < nb; k += BT) {
-    a = fmin(a, part[k * 5]);
-    b = fmax(b, part[k * 5 + 1]);
-    c = fmin(c, part[k * 5 + 2]);
-    d = fmax(d, part[k * 5 + 3]);
-    e += part[k * 5 + 4];
-  }
-  __shared__ double sm[BT / 64][5];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  a = wmin(a);
-  b = wmax(b);
-  c = wmin(c);
-  d = wmax(d);
-#pragma unroll
-  for (int k = 32; k > 0; k >>= 1) e += __shfl_down(e, k, 64);
-  if (lane == 0) {
-    sm[w][0] = a;
-    sm[w][1] = b;
-    sm[w][2] = c;
-    sm[w][3] = d;
-    sm[w][4] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < BT / 64; k++) {
-      sm[0][0] = fmin(sm[0][0], sm[k][0]);
-      sm[0][1] = fmax(sm[0][1], sm[k][1]);
-      sm[0][2] = fmin(sm[0][2], sm[k][2]);
-      sm[0][3] = fmax(sm[0][3], sm[k][3]);
-      sm[0][4] += sm[k][4];
-    }
-    for (int k = 0; k < 5; k++) out[k] = sm[0][k];
-  }
-}
-
 // ---- select ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PT) void k_sel_init(SelState* __restrict__ st, uint32_t* __restrict__ ghist, uint64_t take,
                                                  uint32_t n) {
@@ -209,13 +128,15 @@ __global__ __launch_bounds__(PT) void k_sel_init(SelState* __restrict__ st, uint
   }
 }
 
-// mm: the bounds pass's result in device memory ([0] x min, [2] y min): the selection starts without a host round trip
+// mm: the bounds pass's result in device memory ([0] x min, [1] y min): the selection starts without a host round trip.
+// With a non-finite key (the call then fails after this pass) d is NaN or inf: its bits are still a 64-bit pattern whose
+// digits are in 0..4095, so every key lands inside the histogram whatever the bounds are.
 __global__ __launch_bounds__(PT) void k_sel_hist(const double* __restrict__ key, int64_t n, const double* __restrict__ mm,
                                                  uint32_t chunk, uint32_t pass, const SelState* __restrict__ st,
                                                  uint32_t* __restrict__ ghist) {
   __shared__ uint32_t h[4096];
   if (st->done) return;
-  const double x_Min = mm[0], y_Min = mm[2];
+  const double x_Min = mm[0], y_Min = mm[1];
   for (uint32_t k = threadIdx.x; k < 4096u; k += PT) h[k] = 0u;
   __syncthreads();
   const unsigned long long phi = st->phi, plo = st->plo;
@@ -290,7 +211,7 @@ __global__ __launch_bounds__(PT) void k_sel_collect(const double* __restrict__ k
                                                     uint32_t chunk, SelState* __restrict__ st, Cand* __restrict__ cand,
                                                     double* __restrict__ part) {
   if (st->done || !st->collect) return;
-  const double x_Min = mm[0], y_Min = mm[2];
+  const double x_Min = mm[0], y_Min = mm[1];
   const unsigned long long phi = st->phi, plo = st->plo;
   const uint32_t nbits = 12u * st->pass;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -322,8 +243,8 @@ __global__ __launch_bounds__(PT) void k_sel_collect(const double* __restrict__ k
     }
   }
   __shared__ double sm[PT / 64][2];
-  mx = wmax(mx);
-  my = wmax(my);
+  mx = wave_max(mx);
+  my = wave_max(my);
   if (lane == 0) {
     sm[w][0] = mx;
     sm[w][1] = my;
@@ -383,8 +304,8 @@ __global__ __launch_bounds__(PT) void k_sel_final(SelState* __restrict__ st, con
     my = fmax(my, part[2 * k + 1]);
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  mx = wmax(mx);
-  my = wmax(my);
+  mx = wave_max(mx);
+  my = wave_max(my);
   if (lane == 0) {
     sm[w][0] = mx;
     sm[w][1] = my;
@@ -1028,25 +949,6 @@ __global__ __launch_bounds__(BIG ? 1024 : 128) void k_blk_sort(const Rec32* __re
 
 }  // namespace
 
-int vcp_blocks_ens(vcp_ctx* ctx, DevBuf& b, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return VCP_OK;
-  if (b.p) {
-    VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    VCP_HIP(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-  }
-  const size_t want = bytes + bytes / 8 + 256;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    return vcp_fail(ctx, VCP_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-  }
-  b.cap = want;
-  return VCP_OK;
-}
-
 namespace {
 // out [cols][rows] = in [rows][cols]^T, 32 x 32 tiles through LDS.  The per-chunk counts are written and read chunk-major by
 // the chunked passes (a workgroup's row: coalesced) and scanned bucket-major: with 27 k super-buckets the strided form of
@@ -1085,21 +987,19 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
   s->d_key = d_key;
   s->d_motor = d_motor;
   // bounds (FrmMain.cs:1224-1227) and the finiteness check
-  const int rb = (int)vcp_blocks(n, BT, 1024);
-  VCP_TRY(vcp_blocks_ens(ctx, s->misc, (size_t)(rb * 5 + 64) * 8));
+  const int rb = vcp_bounds_parts(n);
+  VCP_TRY(vcp_blocks_ens(ctx, s->misc, (size_t)(rb * 8 + 64) * 8));
   double* part = s->misc.as<double>();
-  double* out = part + (size_t)rb * 5;
+  double* out = part + (size_t)rb * 8;
   double* h = reinterpret_cast<double*>(ctx->pinned);
   // The bounds stay on the device for the selection's first pass (k_sel_hist / k_sel_collect read them there) and come to
   // the host together with its result: one read-back for bounds + selection instead of two (three with a separate key).
   double* out_motor = out + 8;
   if (keyed) {
     // a non-finite motor coordinate would reach DBImproved only; the partition's own check below covers the keys
-    hipLaunchKernelGGL(k_minmax2_part, dim3(rb), dim3(BT), 0, st, d_motor, n, part);
-    hipLaunchKernelGGL(k_minmax2_final, dim3(1), dim3(BT), 0, st, part, rb, out_motor);
+    VCP_TRY(vcp_bounds_dev(ctx, BoundsSrc{d_motor, n, 2, 2}, part, out_motor));
   }
-  hipLaunchKernelGGL(k_minmax2_part, dim3(rb), dim3(BT), 0, st, d_key, n, part);
-  hipLaunchKernelGGL(k_minmax2_final, dim3(1), dim3(BT), 0, st, part, rb, out);
+  VCP_TRY(vcp_bounds_dev(ctx, BoundsSrc{d_key, n, 2, 2}, part, out));
 
   // chunks of the passes over the list
   int64_t chunk = (n + 255) / 256;
@@ -1131,13 +1031,17 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
     if (pass == 0) VCP_HIP(ctx, hipMemcpyAsync(h, out, 16 * 8, hipMemcpyDeviceToHost, st));  // both sets of bounds
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (pass == 0) {
-      if (keyed && h[8 + 4] != 0.0) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite motor coordinates");
-      if (h[4] != 0.0) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite partition coordinates");
+      if (keyed && h[8 + 6] != 0.0) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite motor coordinates");
+      if (h[6] != 0.0) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite partition coordinates");
       s->x_Min = h[0];
-      s->x_Max = h[1];
-      s->y_Min = h[2];
-      s->y_Max = h[3];
-      for (int k = 0; k < 4; k++) s->mbox[k] = keyed ? h[8 + k] : h[k];
+      s->x_Max = h[3];
+      s->y_Min = h[1];
+      s->y_Max = h[4];
+      const double* mb = keyed ? h + 8 : h;
+      s->mbox[0] = mb[0];
+      s->mbox[1] = mb[3];
+      s->mbox[2] = mb[1];
+      s->mbox[3] = mb[4];
     }
     done = hs->done != 0;
   }

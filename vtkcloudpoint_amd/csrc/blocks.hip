@@ -14,10 +14,6 @@
 // replaced by a stable order; a block-0 point is never also filed under a rectangle; clusterSum is
 // summed deterministically.  The partition (blockpart.hip) sorts nothing; rocPRIM's stable radix sort remains for the
 // rare form of CompleteWork3's order when a block has more cluster ids than the LDS table of the counting sort.
-#include <string.h>  // rocprim's texture_cache_iterator.hpp calls ::memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -25,27 +21,13 @@
 #include <vector>
 
 #include "blocks_state.hpp"
+#include "sort.hpp"
 
 namespace {
 constexpr int BT = 256;
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;
 
 int ens(vcp_ctx* ctx, DevBuf& b, size_t bytes) { return vcp_blocks_ens(ctx, b, bytes); }
-
-template <class K, class V>
-int sort_pairs(vcp_ctx* ctx, BlocksState* s, K* kin, K* kout, V* vin, V* vout, size_t n, int bits) {
-  size_t tb = 0;
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, bits, ctx->stream));
-  VCP_TRY(ens(ctx, s->sorttmp, tb + 64));
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(s->sorttmp.p, tb, kin, kout, vin, vout, n, 0, bits, ctx->stream));
-  return VCP_OK;
-}
-
-int bits_for(uint64_t maxval) {
-  int b = 1;
-  while (b < 64 && (maxval >> b)) b++;
-  return b;
-}
 
 // ---- finish --------------------------------------------------------------------------------------
 // (One lane per position with the lanes of a block combined by ballot and ONE atomicMax / atomicAdd per wave and block
@@ -982,9 +964,9 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
       hipLaunchKernelGGL(k_cluster_sizes, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize);
       hipLaunchKernelGGL(k_iota, dim3(nblk(m)), dim3(BT), 0, st, iota, m);
       VCP_HIP(ctx, hipMemcpyAsync(k1, d_local, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
-      VCP_TRY(sort_pairs(ctx, s, k1, k1o, iota, v1o, (size_t)m, bits_for((uint64_t)m)));  // a local id is at most m
+      VCP_TRY(vcp_sort_pairs(ctx, s->sorttmp, k1, k1o, iota, v1o, (size_t)m, vcp_bits_for((uint64_t)m), false));  // a local id is at most m
       hipLaunchKernelGGL(k_gather_u32, dim3(nblk(m)), dim3(BT), 0, st, blk_t, v1o, m, k2);
-      VCP_TRY(sort_pairs(ctx, s, k2, k1o, v1o, order, (size_t)m, bits_for((uint64_t)s->nblocks)));
+      VCP_TRY(vcp_sort_pairs(ctx, s->sorttmp, k2, k1o, v1o, order, (size_t)m, vcp_bits_for((uint64_t)s->nblocks), false));
     }
     hipLaunchKernelGGL(k_keep, dim3(nblk(nb)), dim3(BT), 0, st, nb, cstart, kb, zb, blockstart, csize, s->small_max, keep,
                        victim_of, dmisc + 2, b_lo);

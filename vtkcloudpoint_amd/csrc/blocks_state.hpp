@@ -53,8 +53,8 @@ struct BlocksState {
 constexpr uint32_t VCP_BIG_BLOCK = 1024;  // blocks beyond this take the workgroup-per-block kernels
 constexpr uint32_t VCP_BRUTE_MAX = 1024;  // largest block the all-pairs kernel takes (its LDS copy of the coordinates)
 
-// ensure capacity of a state-owned buffer (contents are NOT preserved)
-int vcp_blocks_ens(vcp_ctx* ctx, DevBuf& b, size_t bytes);
+// ensure capacity of a state-owned buffer (contents are NOT preserved; the state frees it, not the context)
+inline int vcp_blocks_ens(vcp_ctx* ctx, DevBuf& b, size_t bytes) { return vcp_ensure(ctx, b, bytes, false); }
 
 // The partition (blockpart.hip).  key = the coordinates the partition reads, motor = the coordinates every DBImproved
 // clusters on (the same array unless the caller came through getClusterFromList); both on the device, finite.  Fills

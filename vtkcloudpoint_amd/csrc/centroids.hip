@@ -7,15 +7,13 @@
 // the chunk partials of a cluster are added in chunk order.  The partition depends only on the cluster
 // sizes, so results are run-to-run deterministic; they differ from the sequential sum in the last bits
 // (tests: 1e-12 relative).  Algorithmic bytes: 4 (label) + 24 (xyz) + 16 (motor) per point, read once.
-#include <string.h>  // rocprim's texture_cache_iterator.hpp calls ::memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "reduce.hpp"
+#include "sort.hpp"
 #include "vcp_ctx.hpp"
 
 extern "C" int vcp_dbscan_dev(vcp_ctx*, const double*, int64_t, int, int, double, int, int32_t, const uint8_t*,
@@ -25,44 +23,11 @@ namespace {
 constexpr int CT = 256;
 constexpr int CH = 16384;  // members per chunk
 
-__global__ __launch_bounds__(CT) void k_lab_keys(const int32_t* __restrict__ labels, int64_t n, int32_t K,
-                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                uint32_t* __restrict__ bad) {
-  int64_t i = (int64_t)blockIdx.x * CT + threadIdx.x;
-  if (i >= n) return;
-  int32_t l = labels[i];
-  if (l < 0 || l > K) {  // clusList[p.clusterId - 1] out of range (Tools.cs:185)
-    atomicAdd(bad, 1u);
-    l = 0;
-  }
-  keys[i] = (uint32_t)l;
-  vals[i] = (uint32_t)i;
-}
-
-// Segment bounds from the SORTED labels, no per-point atomics (global atomics run at the memory side here:
-// 5 M adds into 27 k counters cost more than the sort): mark[l] = (last slot of label l) + 1; the exclusive
-// max-scan of the marks is the first slot of every label; counts are the differences.
-__global__ __launch_bounds__(CT) void k_lab_mark(const uint32_t* __restrict__ skey, int64_t n, uint32_t* __restrict__ mark) {
-  int64_t t = (int64_t)blockIdx.x * CT + threadIdx.x;
-  if (t >= n) return;
-  const uint32_t k = skey[t];
-  if (t == n - 1 || skey[t + 1] != k) mark[k] = (uint32_t)t + 1u;
-}
-
-// counts[k] = members of cluster k (k = 0: the noise bucket, reported as 0 chunks), nch[k] = chunks of cluster k
-__global__ __launch_bounds__(CT) void k_nchunks(const uint32_t* __restrict__ segstart, int32_t K,
-                                               uint32_t* __restrict__ counts, uint32_t* __restrict__ nch) {
+// nch[k] = chunks of cluster k (k = 0: the noise bucket, 0 chunks)
+__global__ __launch_bounds__(CT) void k_nchunks(const uint32_t* __restrict__ counts, int32_t K, uint32_t* __restrict__ nch) {
   int k = blockIdx.x * CT + threadIdx.x;
   if (k > K) return;
-  const uint32_t c = segstart[k + 1] - segstart[k];
-  counts[k] = c;
-  nch[k] = k == 0 ? 0u : (c + CH - 1) / CH;
-}
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
+  nch[k] = k == 0 ? 0u : (counts[k] + CH - 1) / CH;
 }
 
 // one workgroup per chunk; chunkstart[k] = first chunk id of cluster k (k in 1..K), segstart[k] = first
@@ -98,19 +63,7 @@ __global__ __launch_bounds__(CT) void k_chunk_sums(const uint32_t* __restrict__ 
       s[4] += motor[2 * (int64_t)i + 1];
     }
   }
-  __shared__ double sm[CT / 64][5];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int a = 0; a < 5; a++) {
-    double v = wsum(s[a]);
-    if (lane == 0) sm[w][a] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    double v = sm[0][threadIdx.x];
-    for (int q = 1; q < CT / 64; q++) v += sm[q][threadIdx.x];
-    partial[(size_t)c * 5 + threadIdx.x] = v;
-  }
+  block_fold<CT>(s, FoldSum(), partial + (size_t)c * 5);
 }
 
 __global__ __launch_bounds__(CT) void k_centroid_final(const double* __restrict__ partial,
@@ -171,19 +124,7 @@ __global__ __launch_bounds__(CT) void k_chunk_sums_w(const uint32_t* __restrict_
       s[3] += w;  // integers below 2^53: exact
     }
   }
-  __shared__ double sm[CT / 64][4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int a = 0; a < 4; a++) {
-    double v = wsum(s[a]);
-    if (lane == 0) sm[w][a] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double v = sm[0][threadIdx.x];
-    for (int q = 1; q < CT / 64; q++) v += sm[q][threadIdx.x];
-    partial[(size_t)c * 4 + threadIdx.x] = v;
-  }
+  block_fold<CT>(s, FoldSum(), partial + (size_t)c * 4);
 }
 
 __global__ __launch_bounds__(CT) void k_centroid_final_w(const double* __restrict__ partial,
@@ -213,32 +154,19 @@ int centroids_dev(vcp_ctx* ctx, const double* d_xyz, const double* d_motor, cons
   if (K == 0) return VCP_OK;
   // aux0: counts [K+2] | nch [K+2] ; aux1: keys in/out ; aux2: vals in/out ; aux3: rocprim temp ; aux4: partial
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)(K + 2) * 4 * 2 + 64));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_aux1, (size_t)(n + 1) * 4 * 2));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_aux2, (size_t)(n + 1) * 4 * 2));
   uint32_t* counts = ctx->b_aux0.as<uint32_t>();
   uint32_t* nch = counts + (K + 2);
   uint32_t* bad = nch + (K + 2);
-  uint32_t* keys_in = ctx->b_aux1.as<uint32_t>();
-  uint32_t* keys_out = keys_in + (n + 1);
-  uint32_t* vals_in = ctx->b_aux2.as<uint32_t>();
-  uint32_t* vals_out = vals_in + (n + 1);
   vcp_phase(ctx, "centroid_sort");
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux5, (size_t)(K + 4) * 4));
   uint32_t* segstart = ctx->b_aux5.as<uint32_t>();  // [K+2]: first sorted slot of label k; [K+1] = n
   VCP_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)(K + 2) * 4 * 2 + 64, st));
   VCP_HIP(ctx, hipMemsetAsync(segstart, 0, (size_t)(K + 4) * 4, st));
-  hipLaunchKernelGGL(k_lab_keys, dim3(vcp_blocks(n, CT)), dim3(CT), 0, st, d_labels, n, K, keys_in, vals_in, bad);
-  int bits = 1;
-  while (((int64_t)1 << bits) <= K) bits++;
-  size_t temp_bytes = 0;
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, bits, st));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_aux3, temp_bytes + 64));
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(ctx->b_aux3.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0,
-                                         bits, st));
+  const uint32_t* vals_out = nullptr;
+  VCP_TRY(vcp_group_by_label(ctx, d_labels, nullptr, n, K, ctx->b_aux1, ctx->b_aux2, ctx->b_aux3, segstart, counts, bad,
+                             &vals_out));
   vcp_phase(ctx, "centroid_reduce");
-  if (n > 0) hipLaunchKernelGGL(k_lab_mark, dim3(vcp_blocks(n, CT)), dim3(CT), 0, st, keys_out, n, segstart);
-  VCP_TRY(vcp_exclusive_max_scan_u32(ctx, segstart, segstart, K + 2, nullptr));
-  hipLaunchKernelGGL(k_nchunks, dim3(vcp_blocks(K + 1, CT)), dim3(CT), 0, st, segstart, K, counts, nch);
+  hipLaunchKernelGGL(k_nchunks, dim3(vcp_blocks(K + 1, CT)), dim3(CT), 0, st, counts, K, nch);
   uint32_t* d_tot = bad + 4;
   VCP_TRY(vcp_exclusive_scan_u32(ctx, nch, nch, K + 2, d_tot));  // nch -> chunkstart, [K+1] = total chunks
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);

@@ -21,13 +21,10 @@
 // no pair of shown points sits within the rounding band of the threshold (checked too).  A cloud that fails both, an e < 0
 // or NaN (a point is then not its own neighbour: the class leaves seeds unclassed) and non-finite coordinates take the
 // pair-by-pair form of dbpairs.hip: the C#'s expression on every pair, O(n^2), up to 2^21 points.
-#include <string.h>
-
-#include <rocprim/rocprim.hpp>
-
 #include <cmath>
 
 #include "dbscan_engine.hpp"
+#include "sort.hpp"
 
 namespace {
 constexpr int DT = 256;
@@ -206,10 +203,7 @@ int vcp_db_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, d
   vcp_phase(ctx, "db_sort");
   VCP_HIP(ctx, hipMemsetAsync(ctr, 0, 8 * 8, st));
   hipLaunchKernelGGL(k_db_key, dim3(vcp_blocks(n, DT)), dim3(DT), 0, st, d_coords, n, stride, d_mask, key_in, idx_in, ctr);
-  size_t tb = 0;
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, key_in, key_out, idx_in, idx_out, (size_t)n, 0, 64, st));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_aux3, tb + 64));
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(ctx->b_aux3.p, tb, key_in, key_out, idx_in, idx_out, (size_t)n, 0, 64, st));
+  VCP_TRY(vcp_sort_pairs(ctx, ctx->b_aux3, key_in, key_out, idx_in, idx_out, (size_t)n, 64));
   VCP_HIP(ctx, hipMemcpyAsync(hc, ctr, 8 * 8, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipStreamSynchronize(st));
   const uint32_t m = (uint32_t)hc[0];

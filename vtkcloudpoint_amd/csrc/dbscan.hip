@@ -34,6 +34,7 @@
 #include <limits>
 #include <vector>
 
+#include "bounds.hpp"
 #include "dbscan_engine.hpp"
 #include "grid_common.hpp"
 
@@ -111,134 +112,6 @@ __device__ __forceinline__ bool within_scr(const float* qf, const float* cf, Scr
   load_exact<GD>(xs, p, q);
   load_exact<GD>(xs, j, r);
   return within<METRIC>(q, r, thr);
-}
-
-// ---- bounds ---------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = fmin(v, __shfl_down(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
-  return v;
-}
-
-// out[0..2] = min, out[3..5] = max, out[6] = number of non-finite coordinates seen
-__device__ __forceinline__ void block_minmax(double* mn, double* mx, double bad, double* __restrict__ out8) {
-  __shared__ double sm[TPB / 64][7];
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    double lo = wave_min(mn[a]), hi = wave_max(mx[a]);
-    if (lane == 0) {
-      sm[w][a] = lo;
-      sm[w][3 + a] = hi;
-    }
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d, 64);
-  if (lane == 0) sm[w][6] = bad;
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    double v = sm[0][threadIdx.x];
-    for (int k = 1; k < TPB / 64; k++)
-      v = threadIdx.x < 3 ? fmin(v, sm[k][threadIdx.x]) : threadIdx.x < 6 ? fmax(v, sm[k][threadIdx.x]) : v + sm[k][6];
-    out8[threadIdx.x] = v;
-  }
-}
-
-// partial[b*8 + a] = min of axis a, partial[b*8 + 3 + a] = max over finite values, partial[b*8 + 6] = #non-finite
-template <int GD, bool GROUPED>
-__global__ __launch_bounds__(TPB) void k_bounds(const double* __restrict__ c, int64_t n, int stride,
-                                               const int32_t* __restrict__ group, int glo, int ghi,
-                                               double* __restrict__ partial) {
-  double mn[3], mx[3], bad = 0;
-  for (int a = 0; a < 3; a++) {
-    mn[a] = INFINITY;
-    mx[a] = -INFINITY;
-  }
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    if (GROUPED) {
-      int g = group[i];
-      if (g < glo || g >= ghi) continue;
-    }
-    double q[3];
-    load_in<GD>(c, i, stride, q);  // (one 16-byte load per point where the layout allows: 68 -> 40 us at 10 M points)
-#pragma unroll
-    for (int a = 0; a < GD; a++) {
-      const double v = q[a];
-      if (isfinite(v)) {
-        mn[a] = fmin(mn[a], v);
-        mx[a] = fmax(mx[a], v);
-      } else {
-        bad += 1.0;
-      }
-    }
-  }
-  block_minmax(mn, mx, bad, partial + (size_t)blockIdx.x * 8);
-}
-
-__global__ __launch_bounds__(TPB) void k_bounds_final(const double* __restrict__ partial, int nb,
-                                                     double* __restrict__ out) {
-  double mn[3], mx[3], bad = 0;
-  for (int a = 0; a < 3; a++) {
-    mn[a] = INFINITY;
-    mx[a] = -INFINITY;
-  }
-  for (int b = threadIdx.x; b < nb; b += TPB) {
-    for (int a = 0; a < 3; a++) {
-      mn[a] = fmin(mn[a], partial[b * 8 + a]);
-      mx[a] = fmax(mx[a], partial[b * 8 + 3 + a]);
-    }
-    bad += partial[b * 8 + 6];
-  }
-  block_minmax(mn, mx, bad, out);
-}
-
-// Trimmed moments for a robust grid range: per axis the count, sum and sum of squares (about mid[a]) of the
-// finite values inside [lo[a], hi[a]].  partial[b*9 + 3*a + {0,1,2}].  Only used when the eps-grid over the full
-// bounding box would not fit the cell budget (a few far outliers would otherwise coarsen the grid for everybody).
-struct Range3 {
-  double lo[3], hi[3], mid[3];
-};
-template <int GD, bool GROUPED>
-__global__ __launch_bounds__(TPB) void k_moments(const double* __restrict__ c, int64_t n, int stride,
-                                                const int32_t* __restrict__ group, int glo, int ghi, Range3 R,
-                                                double* __restrict__ partial) {
-  double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    if (GROUPED) {
-      int g = group[i];
-      if (g < glo || g >= ghi) continue;
-    }
-#pragma unroll
-    for (int a = 0; a < GD; a++) {
-      const double v = c[i * stride + a];
-      if (v >= R.lo[a] && v <= R.hi[a]) {
-        const double d = v - R.mid[a];
-        m[3 * a] += 1.0;
-        m[3 * a + 1] += d;
-        m[3 * a + 2] += d * d;
-      }
-    }
-  }
-  __shared__ double sm[TPB / 64][9];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    double v = m[k];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    if (lane == 0) sm[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    double v = sm[0][threadIdx.x];
-    for (int k = 1; k < TPB / 64; k++) v += sm[k][threadIdx.x];
-    partial[(size_t)blockIdx.x * 9 + threadIdx.x] = v;
-  }
 }
 
 // Order in which the counting kernels walk the candidate rows: the row of the point's OWN cell first, then the rows that
@@ -1653,19 +1526,17 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
 
   // 1. bounds over finite coordinates
   vcp_phase(ctx, "bounds");
-  const int rb = (int)vcp_blocks(n, TPB, 1024);
+  const int rb = vcp_bounds_parts(n);
   VCP_TRY(vcp_ensure(ctx, ctx->b_misc, (size_t)(rb * 8 + 96) * sizeof(double)));
   double* d_part = ctx->b_misc.as<double>();
   double* d_bounds = d_part + (size_t)rb * 8;
   double* h = reinterpret_cast<double*>(ctx->pinned);
+  const BoundsSrc src{d_coords, n, GD, stride, d_group, glo, ghi};
   if (ext && ext->h_bbox) {  // the caller has seen every point: finite, inside this box
     for (int a = 0; a < 6; a++) h[a] = ext->h_bbox[a];
     h[6] = 0.0;
   } else {
-    hipLaunchKernelGGL((k_bounds<GD, GROUPED>), dim3(rb), dim3(TPB), 0, st, d_coords, n, stride, d_group, glo, ghi, d_part);
-    hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(TPB), 0, st, d_part, rb, d_bounds);
-    VCP_HIP(ctx, hipMemcpyAsync(h, d_bounds, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-    VCP_HIP(ctx, hipStreamSynchronize(st));
+    VCP_TRY(vcp_bounds(ctx, src, d_part, d_bounds, h));
   }
   const bool all_finite = h[6] == 0.0;
 
@@ -1747,41 +1618,10 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
       return c;
     };
     double lo[3] = {h[0], h[1], h[2]}, hi[3] = {h[3], h[4], h[5]};
-    const bool no_trim = ext && ext->no_trim;
-    for (int it = 0; it < 8 && !no_trim && cellw >= 0.0 && std::isfinite(cellw) && !(cells_needed(lo, hi) <= (double)budget); it++) {
-      Range3 R;
-      for (int a = 0; a < 3; a++) {
-        R.lo[a] = lo[a];
-        R.hi[a] = hi[a];
-        R.mid[a] = 0.5 * lo[a] + 0.5 * hi[a];
-      }
-      VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)rb * 9 * sizeof(double)));
-      double* d_mom = ctx->b_aux0.as<double>();
-      hipLaunchKernelGGL((k_moments<GD, GROUPED>), dim3(rb), dim3(TPB), 0, st, d_coords, n, stride, d_group, glo, ghi, R,
-                         d_mom);
-      std::vector<double> hm((size_t)rb * 9);
-      VCP_HIP(ctx, hipMemcpyAsync(hm.data(), d_mom, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      VCP_HIP(ctx, hipStreamSynchronize(st));
-      bool changed = false;
-      for (int a = 0; a < GD; a++) {
-        double cnt = 0, s1 = 0, s2 = 0;
-        for (int b = 0; b < rb; b++) {
-          cnt += hm[(size_t)b * 9 + 3 * a];
-          s1 += hm[(size_t)b * 9 + 3 * a + 1];
-          s2 += hm[(size_t)b * 9 + 3 * a + 2];
-        }
-        if (!(cnt > 0)) continue;
-        const double mean = s1 / cnt, var = std::fmax(s2 / cnt - mean * mean, 0.0);
-        const double c0 = R.mid[a] + mean, w = 8.0 * std::sqrt(var) + 4.0 * cellw;
-        const double nlo = std::fmax(lo[a], c0 - w), nhi = std::fmin(hi[a], c0 + w);
-        if (nlo > lo[a] || nhi < hi[a]) changed = true;
-        if (nlo <= nhi) {
-          lo[a] = nlo;
-          hi[a] = nhi;
-        }
-      }
-      if (!changed) break;
-    }
+    if (!(ext && ext->no_trim) && cellw >= 0.0 && std::isfinite(cellw))
+      VCP_TRY(vcp_robust_range(
+          ctx, src, ctx->b_aux0, lo, hi, [&](double, double) { return 4.0 * cellw; },
+          [&](const double* l, const double* u) { return cells_needed(l, u) <= (double)budget; }));
     for (int a = 0; a < GD; a++) {
       h[a] = lo[a];
       h[3 + a] = hi[a];

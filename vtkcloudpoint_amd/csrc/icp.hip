@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "nngrid.hpp"
+#include "reduce.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
@@ -41,11 +42,6 @@ struct IcpState {
   int round, done, failed, pad;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
 
 // bounding box of the model -> centre and half extent in the state (single workgroup: models are small).  A model
 // with non-finite coordinates gets an infinite scale: every data point is then resolved in binary64.
@@ -69,12 +65,7 @@ __global__ __launch_bounds__(ITPB) void k_model_frame(const double* __restrict__
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    double l = lo[a], h = hi[a];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      l = fmin(l, __shfl_down(l, d, 64));
-      h = fmax(h, __shfl_down(h, d, 64));
-    }
+    const double l = wave_min(lo[a]), h = wave_max(hi[a]);
     if (lane == 0) {
       sl[w][a] = l;
       sh[w][a] = h;
@@ -305,20 +296,7 @@ __global__ __launch_bounds__(TB) void k_icp_pass(const double* __restrict__ mode
     const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
     s[15] += e0 * e0 + e1 * e1 + e2 * e2;
   }
-  __shared__ double sm[TB / 64][16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    double v = wave_sum(s[k]);
-    if (lane == 0) sm[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < TB / 64; k++) v += sm[k][threadIdx.x];
-    partial[(size_t)blockIdx.x * 16 + threadIdx.x] = v;
-  }
+  block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
 }
 
 // ---- small models (nm <= 512: MainForm's 100 truths, C3) ---------------------------------------------------
@@ -459,20 +437,7 @@ __global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict_
       s[15] += e0 * e0 + e1 * e1 + e2 * e2;
     }
   }
-  __shared__ double sm[TB / 64][16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    double v = wave_sum(s[k]);
-    if (lane == 0) sm[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < TB / 64; k++) v += sm[k][threadIdx.x];
-    partial[(size_t)blockIdx.x * 16 + threadIdx.x] = v;
-  }
+  block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
 }
 
 // ---- Horn's unit-quaternion closed form (host and device: same code, same rounding) -----------------
@@ -646,22 +611,9 @@ __device__ __forceinline__ void icp_step_body(const double* __restrict__ partial
     for (int k = 0; k < 16; k++)
       s[k] += partial[(size_t)b * 16 + k];
   }
-  __shared__ double sm2[TB / 64][16];
   __shared__ double tot[16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    double v = wave_sum(s[k]);
-    if (lane == 0) sm2[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double v = sm2[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < TB / 64; k++) v += sm2[k][threadIdx.x];
-    tot[threadIdx.x] = v;
-    st->sums[threadIdx.x] = v;
-  }
+  block_fold<TB>(s, FoldSum(), tot);
+  if (threadIdx.x < 16) st->sums[threadIdx.x] = tot[threadIdx.x];
   __syncthreads();
   if (threadIdx.x != 0) return;
   if (a.mode == MODE_SUMS_ONLY) {

@@ -6,9 +6,9 @@
 // (kdist_k[i] <= eps) for every finite eps.
 //
 // Passes:
-//   bounds  finite bounding box and the non-finite count (one pass + a per-block host reduction); then the lattice box is
-//           trimmed to mean +- 8 sigma of the points inside it, repeatedly (the robust range of dbscan.hip's grid): a few
-//           far outliers land in the EDGE codes of the lattice instead of stretching it for everybody.
+//   bounds  bounding box of the finite coordinates and the non-finite point count (bounds.hip); then the lattice box is
+//           trimmed to mean +- 8 sigma of the values inside it, repeatedly (vcp_robust_range, as for dbscan.hip's grid): a
+//           few far outliers land in the EDGE codes of the lattice instead of stretching it for everybody.
 //   order   per point a 60-bit Morton key of its lattice codes (2^30 codes per axis in 2-D, 2^20 in 3-D, cubic cells;
 //           code 0 / 2^L - 1 = everything below / above the box on that axis; non-finite points get a key after every
 //           finite one), one rocPRIM radix sort of (key, index), a gather of the coordinates into key order, and a dense
@@ -32,14 +32,11 @@
 // gap times w = 1 / s (1 - 2^-30).  Both metrics are >= the largest |coordinate difference| up to one rounding
 // (monotone roundings; the sqrt is correctly rounded), so an outside point's d exceeds the bound times (1 - 2^-50).
 // kth < bound therefore proves no outside point can enter the top k, ties by index included.
-#include <string.h>  // rocprim's texture_cache_iterator.hpp calls ::memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include <climits>
 #include <cmath>
-#include <vector>
 
+#include "bounds.hpp"
+#include "sort.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
@@ -129,91 +126,6 @@ __device__ __forceinline__ double dist(const double* q, const double4& r) {
 }
 
 __device__ __forceinline__ bool lt(double a, int i, double b, int j) { return a < b || (a == b && i < j); }
-
-// ---- bounds ----------------------------------------------------------------------------------------------------
-// part[b*8 + a] = min, [3 + a] = max over FINITE points (all GD coordinates finite), [6] = non-finite points
-template <int GD>
-__global__ __launch_bounds__(KT) void k_kd_bounds(const double* __restrict__ c, int64_t n, int stride,
-                                                 double* __restrict__ part) {
-  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY}, bad = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT) {
-    double q[3];
-    load_pt<GD>(c, i, stride, q);
-    if (!finite_pt<GD>(q)) {
-      bad += 1.0;
-      continue;
-    }
-#pragma unroll
-    for (int a = 0; a < GD; a++) {
-      mn[a] = fmin(mn[a], q[a]);
-      mx[a] = fmax(mx[a], q[a]);
-    }
-  }
-  __shared__ double sm[KT / 64][7];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      mn[a] = fmin(mn[a], __shfl_down(mn[a], d, 64));
-      mx[a] = fmax(mx[a], __shfl_down(mx[a], d, 64));
-    }
-    bad += __shfl_down(bad, d, 64);
-  }
-  if (lane == 0) {
-    for (int a = 0; a < 3; a++) {
-      sm[wv][a] = mn[a];
-      sm[wv][3 + a] = mx[a];
-    }
-    sm[wv][6] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    double v = sm[0][threadIdx.x];
-    for (int w = 1; w < KT / 64; w++)
-      v = threadIdx.x < 3 ? fmin(v, sm[w][threadIdx.x]) : threadIdx.x < 6 ? fmax(v, sm[w][threadIdx.x]) : v + sm[w][6];
-    part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
-  }
-}
-
-// per axis the count, sum and sum of squares (about mid[a]) of the finite points' values inside [lo[a], hi[a]]:
-// part[b*9 + 3a + {0,1,2}] (fixed reduction order: deterministic)
-struct Box {
-  double lo[3], hi[3], mid[3];
-};
-template <int GD>
-__global__ __launch_bounds__(KT) void k_kd_moments(const double* __restrict__ c, int64_t n, int stride, Box B,
-                                                  double* __restrict__ part) {
-  double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT) {
-    double q[3];
-    load_pt<GD>(c, i, stride, q);
-    if (!finite_pt<GD>(q)) continue;
-#pragma unroll
-    for (int a = 0; a < GD; a++) {
-      if (q[a] >= B.lo[a] && q[a] <= B.hi[a]) {
-        const double v = q[a] - B.mid[a];
-        m[3 * a] += 1.0;
-        m[3 * a + 1] += v;
-        m[3 * a + 2] += v * v;
-      }
-    }
-  }
-  __shared__ double sm[KT / 64][9];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-    for (int t = 0; t < 9; t++) m[t] += __shfl_down(m[t], d, 64);
-  if (lane == 0)
-    for (int t = 0; t < 9; t++) sm[wv][t] = m[t];
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    double v = sm[0][threadIdx.x];
-    for (int w = 1; w < KT / 64; w++) v += sm[w][threadIdx.x];
-    part[(size_t)blockIdx.x * 9 + threadIdx.x] = v;
-  }
-}
 
 // ---- order -------------------------------------------------------------------------------------------------------
 template <int GD>
@@ -549,22 +461,14 @@ int run_kdist(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, int m
 
   // 1. bounds and the trimmed lattice box
   vcp_phase(ctx, "kdist_bounds");
-  const int rb = (int)vcp_blocks(n, KT, 1024);
-  VCP_TRY(vcp_ensure(ctx, ctx->b_kd_part, (size_t)rb * 9 * sizeof(double)));
+  const int rb = vcp_bounds_parts(n);
+  VCP_TRY(vcp_ensure(ctx, ctx->b_kd_part, (size_t)(rb * 8 + 8) * sizeof(double)));
   double* d_part = ctx->b_kd_part.as<double>();
-  hipLaunchKernelGGL((k_kd_bounds<GD>), dim3(rb), dim3(KT), 0, st, d_coords, n, stride, d_part);
-  std::vector<double> hp((size_t)rb * 9);
-  VCP_HIP(ctx, hipMemcpyAsync(hp.data(), d_part, (size_t)rb * 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-  VCP_HIP(ctx, hipStreamSynchronize(st));
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, bad = 0.0;
-  for (int b = 0; b < rb; b++) {
-    for (int t = 0; t < 3; t++) {
-      lo[t] = std::fmin(lo[t], hp[(size_t)b * 8 + t]);
-      hi[t] = std::fmax(hi[t], hp[(size_t)b * 8 + 3 + t]);
-    }
-    bad += hp[(size_t)b * 8 + 6];
-  }
-  const uint32_t nf = (uint32_t)(n - (int64_t)bad);
+  double* h = reinterpret_cast<double*>(ctx->pinned);
+  const BoundsSrc src{d_coords, n, GD, stride};
+  VCP_TRY(vcp_bounds(ctx, src, d_part, d_part + (size_t)rb * 8, h));
+  double lo[3] = {h[0], h[1], h[2]}, hi[3] = {h[3], h[4], h[5]};
+  const uint32_t nf = (uint32_t)(n - (int64_t)h[6]);
   for (int t = GD; t < 3; t++) lo[t] = hi[t] = 0.0;
   if (nf > 0)
     for (int t = 0; t < GD; t++)
@@ -572,36 +476,10 @@ int run_kdist(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, int m
         return vcp_fail(ctx, VCP_ERR_UNSUPPORTED, "the cloud's extent overflows binary64 (coordinate differences are infinite)");
   if (nf == 0) lo[0] = lo[1] = lo[2] = hi[0] = hi[1] = hi[2] = 0.0;
   // robust range: mean +- 8 sigma of the points inside, repeated while it shrinks
-  for (int it = 0; it < 8 && nf > 1; it++) {
-    Box B;
-    for (int t = 0; t < 3; t++) {
-      B.lo[t] = lo[t];
-      B.hi[t] = hi[t];
-      B.mid[t] = 0.5 * lo[t] + 0.5 * hi[t];
-    }
-    hipLaunchKernelGGL((k_kd_moments<GD>), dim3(rb), dim3(KT), 0, st, d_coords, n, stride, B, d_part);
-    VCP_HIP(ctx, hipMemcpyAsync(hp.data(), d_part, (size_t)rb * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-    VCP_HIP(ctx, hipStreamSynchronize(st));
-    bool changed = false;
-    for (int t = 0; t < GD; t++) {
-      double cnt = 0, s1 = 0, s2 = 0;
-      for (int b = 0; b < rb; b++) {
-        cnt += hp[(size_t)b * 9 + 3 * t];
-        s1 += hp[(size_t)b * 9 + 3 * t + 1];
-        s2 += hp[(size_t)b * 9 + 3 * t + 2];
-      }
-      if (!(cnt > 0)) continue;
-      const double mean = s1 / cnt, var = std::fmax(s2 / cnt - mean * mean, 0.0);
-      const double c0 = B.mid[t] + mean, wd = 8.0 * std::sqrt(var) + 1e-9 * (hi[t] - lo[t]);
-      const double nlo = std::fmax(lo[t], c0 - wd), nhi = std::fmin(hi[t], c0 + wd);
-      if (nlo <= nhi && (nlo > lo[t] || nhi < hi[t])) {
-        lo[t] = nlo;
-        hi[t] = nhi;
-        changed = true;
-      }
-    }
-    if (!changed) break;
-  }
+  if (nf > 1)
+    VCP_TRY(vcp_robust_range(
+        ctx, src, ctx->b_kd_part, lo, hi, [](double l, double u) { return 1e-9 * (u - l); },
+        [](const double*, const double*) { return false; }));
   double ext = 0.0;
   for (int t = 0; t < GD; t++) ext = std::fmax(ext, hi[t] - lo[t]);
   double s = (double)((1u << L) - 2) / ext;
@@ -636,10 +514,7 @@ int run_kdist(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, int m
   a.heavy = ctx->b_kd_heavy.as<uint32_t>();
   a.heavy_cnt = heavy_cnt;
   hipLaunchKernelGGL((k_kd_keys<GD>), dim3(nb), dim3(KT), 0, st, d_coords, n, stride, a, kin, vin);
-  size_t tb = 0;
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, (size_t)n, 0, KEYBITS + 1, st));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_kd_tmp, tb));
-  VCP_HIP(ctx, rocprim::radix_sort_pairs(ctx->b_kd_tmp.p, tb, kin, kout, vin, vout, (size_t)n, 0, KEYBITS + 1, st));
+  VCP_TRY(vcp_sort_pairs(ctx, ctx->b_kd_tmp, kin, kout, vin, vout, (size_t)n, KEYBITS + 1));
   double4* rec = ctx->b_kd_rec.as<double4>();
   hipLaunchKernelGGL((k_kd_gather<GD>), dim3(nb), dim3(KT), 0, st, d_coords, n, stride, vout, a, rec);
   VCP_HIP(ctx, hipMemsetAsync(start, 0, cells * 4 + 4, st));  // the marks and the heavy counter

@@ -11,48 +11,16 @@
 // (stable rocPRIM radix sort by label).  Every choice the C# makes sequentially ("first in the list wins") is
 // an argmin over (value, list position), so the parallel reductions reproduce it exactly; the arithmetic is
 // binary64 without FMA contraction, sqrt and division correctly rounded: results are bit-identical to the oracle.
-#include <string.h>  // rocprim's texture_cache_iterator.hpp calls ::memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include <cmath>
 #include <cstring>
 
+#include "sort.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
 constexpr int MT = 256;
 constexpr int HMAX = 2048;  // hull points kept in LDS (32 KB); a larger hull is reported as VCP_ERR_TOO_LARGE
 constexpr double DMAX = 1.7976931348623157e308;
-
-__global__ __launch_bounds__(MT) void k_mcc_keys(const int32_t* __restrict__ labels, const int64_t* __restrict__ order,
-                                                int64_t m, int32_t K, uint32_t* __restrict__ keys,
-                                                uint32_t* __restrict__ vals, uint32_t* __restrict__ bad) {
-  int64_t t = (int64_t)blockIdx.x * MT + threadIdx.x;
-  if (t >= m) return;
-  int64_t i = order ? order[t] : t;
-  int32_t l = labels[i];
-  if (l < 0 || l > K) {
-    atomicAdd(bad, 1u);
-    l = 0;
-  }
-  keys[t] = (uint32_t)l;
-  vals[t] = (uint32_t)i;
-}
-
-// segment bounds from the sorted keys (no per-point atomics): mark[l] = (last position of label l) + 1, an
-// exclusive max-scan of the marks is the first position of every label, counts are the differences
-__global__ __launch_bounds__(MT) void k_mcc_mark(const uint32_t* __restrict__ skey, int64_t m, uint32_t* __restrict__ mark) {
-  int64_t t = (int64_t)blockIdx.x * MT + threadIdx.x;
-  if (t >= m) return;
-  const uint32_t k = skey[t];
-  if (t == m - 1 || skey[t + 1] != k) mark[k] = (uint32_t)t + 1u;
-}
-__global__ __launch_bounds__(MT) void k_mcc_counts(const uint32_t* __restrict__ segstart, int32_t K,
-                                                  uint32_t* __restrict__ counts) {
-  int k = blockIdx.x * MT + threadIdx.x;
-  if (k <= K) counts[k] = segstart[k + 1] - segstart[k];
-}
 
 __global__ __launch_bounds__(MT) void k_mcc_gather(const double* __restrict__ xy, const uint32_t* __restrict__ idx,
                                                   int64_t m, double* __restrict__ cxy) {
@@ -306,11 +274,6 @@ __global__ __launch_bounds__(MT) void k_mcc(const double* __restrict__ cxy, cons
   }
 }
 
-int bits_for_u32(uint64_t maxval) {
-  int b = 1;
-  while (b < 32 && (maxval >> b)) b++;
-  return b;
-}
 }  // namespace
 
 extern "C" int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, const int64_t* order, int64_t m, int64_t n,
@@ -327,8 +290,6 @@ extern "C" int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, co
   VCP_TRY(vcp_ensure(ctx, ctx->b_in3, nn * 4));
   VCP_TRY(vcp_ensure(ctx, ctx->b_in2, mm * 8));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (kk + 4) * 4 * 2 + 64));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_aux1, (mm + 1) * 4 * 2));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_aux2, (mm + 1) * 4 * 2));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux4, mm * 16));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux5, mm));
   VCP_TRY(vcp_ensure(ctx, ctx->b_out0, kk * 16));
@@ -343,25 +304,13 @@ extern "C" int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, co
   uint32_t* counts = ctx->b_aux0.as<uint32_t>();   // [K+2], label 0 included
   uint32_t* segstart = counts + (K + 4);
   uint32_t* bad = segstart + (K + 4);
-  uint32_t* keys_in = ctx->b_aux1.as<uint32_t>();
-  uint32_t* keys_out = keys_in + (mm + 1);
-  uint32_t* vals_in = ctx->b_aux2.as<uint32_t>();
-  uint32_t* vals_out = vals_in + (mm + 1);
   VCP_HIP(ctx, hipMemsetAsync(counts, 0, (kk + 4) * 4 * 2 + 64, st));
-  if (m > 0) {
-    hipLaunchKernelGGL(k_mcc_keys, dim3(vcp_blocks(m, MT)), dim3(MT), 0, st, ctx->b_in3.as<int32_t>(),
-                       order ? ctx->b_in2.as<int64_t>() : nullptr, m, K, keys_in, vals_in, bad);
-    size_t tb = 0;
-    const int bits = bits_for_u32((uint64_t)K);
-    VCP_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, (size_t)m, 0, bits, st));
-    VCP_TRY(vcp_ensure(ctx, ctx->b_aux3, tb + 64));
-    VCP_HIP(ctx, rocprim::radix_sort_pairs(ctx->b_aux3.p, tb, keys_in, keys_out, vals_in, vals_out, (size_t)m, 0, bits, st));
-    hipLaunchKernelGGL(k_mcc_gather, dim3(vcp_blocks(m, MT)), dim3(MT), 0, st, ctx->b_in0.as<double>(), vals_out, m,
+  const uint32_t* sorted = nullptr;
+  VCP_TRY(vcp_group_by_label(ctx, ctx->b_in3.as<int32_t>(), order ? ctx->b_in2.as<int64_t>() : nullptr, m, K, ctx->b_aux1,
+                             ctx->b_aux2, ctx->b_aux3, segstart, counts, bad, &sorted));
+  if (m > 0)
+    hipLaunchKernelGGL(k_mcc_gather, dim3(vcp_blocks(m, MT)), dim3(MT), 0, st, ctx->b_in0.as<double>(), sorted, m,
                        ctx->b_aux4.as<double>());
-  }
-  if (m > 0) hipLaunchKernelGGL(k_mcc_mark, dim3(vcp_blocks(m, MT)), dim3(MT), 0, st, keys_out, m, segstart);
-  VCP_TRY(vcp_exclusive_max_scan_u32(ctx, segstart, segstart, K + 2, nullptr));  // segstart[K+1] = m
-  hipLaunchKernelGGL(k_mcc_counts, dim3(vcp_blocks(K + 1, MT)), dim3(MT), 0, st, segstart, K, counts);
   hipLaunchKernelGGL(k_mcc, dim3(K), dim3(MT), 0, st, ctx->b_aux4.as<double>(), segstart, counts, ctx->b_aux5.as<uint8_t>(),
                      ctx->b_out0.as<double>(), ctx->b_out2.as<double>(), ctx->b_out1.as<uint8_t>(), ctx->b_out3.as<int32_t>());
   VCP_HIP(ctx, hipGetLastError());

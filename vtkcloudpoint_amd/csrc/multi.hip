@@ -57,23 +57,9 @@ static int mfail(vcp_multi* m, int code, const std::string& msg) {
 
 // grow-only device buffer on the device of context c (the buffer is NOT registered with the context: vcp_multi owns it)
 static int mensure(vcp_ctx* c, DevBuf& b, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return VCP_OK;
+  if (b.cap >= bytes && b.cap > 0) return VCP_OK;
   VCP_TRY(vcp_bind(c));
-  if (b.p) {
-    VCP_HIP(c, hipStreamSynchronize(c->stream));
-    VCP_HIP(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-  }
-  const size_t want = bytes + bytes / 8 + 256;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    return vcp_fail(c, VCP_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-  }
-  b.cap = want;
-  return VCP_OK;
+  return vcp_ensure(c, b, bytes, false);
 }
 
 extern "C" {

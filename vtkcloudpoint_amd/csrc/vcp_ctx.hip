@@ -22,7 +22,7 @@ int vcp_bind(vcp_ctx* ctx) {
   return VCP_OK;
 }
 
-int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes) {
+int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes, bool listed) {
   if (bytes == 0) bytes = 16;
   if (b.cap >= bytes) return VCP_OK;
   if (b.p) {
@@ -31,7 +31,7 @@ int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes) {
     b.p = nullptr;
     b.cap = 0;
   }
-  if (!b.registered) {  // a buffer whose regrow failed (p == nullptr again) must not be listed twice
+  if (listed && !b.registered) {  // a buffer whose regrow failed (p == nullptr again) must not be listed twice
     ctx->bufs.push_back(&b);
     b.registered = true;
   }

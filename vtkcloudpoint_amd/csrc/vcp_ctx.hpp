@@ -33,7 +33,8 @@ struct vcp_ctx {
   // pinned scratch for tiny readbacks (64 KB).  Who reads back where (byte offsets; a context runs one call at a time on
   // one stream, and every user has consumed its words before the call that wrote them returns or goes on):
   //   [0, 1024)     the DBSCAN engine: bounds, counters, work sizes (dbscan.hip); the block partition's bounds (blockpart.hip);
-  //                 the finish stage's counters (blocks.hip)
+  //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
+  //                 nearest-neighbour grid's bounds (nngrid.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip)
   //   [2048, 2064)  DB pair by pair: next seed / frontier size (dbpairs.hip)
@@ -45,9 +46,9 @@ struct vcp_ctx {
   uint32_t scan_gen = 0;  // generation number of the scan descriptors in b_scan_tmp (vcp_ctx.hip: k_scan)
   // workspace
   std::vector<DevBuf*> bufs;
-  DevBuf b_cellcnt, b_cellof, b_rank, b_sorted, b_sidx, b_flags, b_parent, b_minord, b_seedflag,
+  DevBuf b_cellof, b_rank, b_sidx, b_flags, b_parent, b_minord, b_seedflag,
       b_rootcl, b_clseed, b_scan_tmp, b_misc, b_in0, b_in1, b_in2, b_in3, b_out0, b_out1, b_out2,
-      b_out3, b_icp_part, b_aux0, b_aux1, b_aux2, b_aux3, b_aux4, b_aux5, b_pos, b_labk, b_sgroup, b_wl, b_skey, b_sorttmp, b_hist, b_rec, b_nn_misc, b_nn_cells, b_nn_cid, b_nn_rec, b_nn_cur, b_nbr, b_nboff, b_sorted32, b_self, b_outcur, b_fineq, b_rec2, b_bstart, b_ctw, b_ctd, b_bstate;
+      b_out3, b_icp_part, b_aux0, b_aux1, b_aux2, b_aux3, b_aux4, b_aux5, b_pos, b_labk, b_sgroup, b_wl, b_hist, b_rec, b_nn_misc, b_nn_cells, b_nn_cid, b_nn_rec, b_nn_cur, b_nbr, b_nboff, b_sorted32, b_self, b_outcur, b_fineq, b_rec2, b_bstart, b_ctw, b_ctd, b_bstate;
   // k-distance (kdist.hip)
   DevBuf b_kd_in, b_kd_out, b_kd_outk, b_kd_part, b_kd_key, b_kd_val, b_kd_rec, b_kd_start, b_kd_heavy, b_kd_tmp;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
@@ -79,8 +80,9 @@ void* vcp_stage(vcp_ctx* ctx, size_t bytes);
     if (rc__ != VCP_OK) return rc__; \
   } while (0)
 
-// ensure capacity (contents are NOT preserved)
-int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes);
+// ensure capacity (contents are NOT preserved).  listed: the context frees the buffer on destroy (vcp_ctx::bufs); a
+// buffer owned by some other state, which frees it itself, passes false.
+int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes, bool listed = true);
 // bind the calling thread to the context's device
 int vcp_bind(vcp_ctx* ctx);
 // timing
