@@ -1,6 +1,7 @@
 """Worker for tests/test_pipeline_gloo.py: one rank of a gloo group running the product's sharded-pipeline driver
-(vtkcloudpoint_amd.distributed.sharded_pipeline: plan / cuts / build / cluster / local merge, the nine-word exchange, the
-noise pass as exact_slabs, the all-gather of (index, label) pairs) on CPU tensors, with the oracle-backed stand-in
+(vtkcloudpoint_amd.distributed.sharded_pipeline: plan / cuts / build / cluster / local merge, the exchange of ten words
+per rank, the global noise pass over the gathered active noise points (or exact_slabs with noise="slabs"), the
+all-gather of (index, label) pairs) on CPU tensors, with the oracle-backed stand-in
 (oracle.binding.StagedPipeline) in place of the HIP context.  Every rank's result is checked against the oracle's
 single-process pipeline."""
 import json

@@ -99,6 +99,9 @@ def test_block_range_plan_for_2_3_8_ranks():
             sizes[rng.integers(0, nb)] = 5000  # one block that dwarfs the rest
         if trial % 7 == 0:
             sizes[:] = 0
+        heavy = trial % 3 == 1 and nb > 1
+        if heavy:  # the last bucket (the points in no block) holds more than any rank's fair share
+            sizes[-1] = 10 * int(sizes[:-1].sum()) + 100
         bs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
         m = int(bs[-1])
         for world in (1, 2, 3, 8):
@@ -112,3 +115,109 @@ def test_block_range_plan_for_2_3_8_ranks():
                 share = np.diff(bs[cuts].astype(np.int64))
                 assert share.sum() == m
                 assert share.max() <= m / world + sizes.max()  # never worse than one block over the fair share
+            if heavy and world > 1:  # the ranks behind the heavy bucket get the empty share [nb, nb)
+                assert all(cuts[r] == nb for r in range(1, world)), (trial, world, cuts)
+                assert cuts[world - 1] == nb
+
+
+# ---- the C# and Python bindings against the header -------------------------------------------------------------------
+# A parameter's width class is what the calling convention passes: a 32-bit integer, a 64-bit integer, a double or an
+# address (pointers, arrays, C# out / ref / arrays / IntPtr).  A binding whose arity or classes differ from the header hands
+# the library a register it never set, and the library may write through it.
+_C_CLASS = {"int": "i32", "int32_t": "i32", "uint32_t": "i32", "unsigned": "i32", "int64_t": "i64", "uint64_t": "i64",
+            "double": "f64"}
+_CS_CLASS = {"int": "i32", "uint": "i32", "long": "i64", "ulong": "i64", "double": "f64", "IntPtr": "ptr"}
+
+
+def _header_prototypes():
+    with open(os.path.join(ROOT, "include", "vcp.h")) as f:
+        src = f.read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    src = re.sub(r"^\s*#[^\n]*", "", src, flags=re.M)
+    protos = {}
+    for stmt in src.replace("{", ";").replace("}", ";").split(";"):
+        m = re.search(r"\b(vcp_[a-z0-9_]+)\s*\(([^()]*)\)\s*$", stmt, re.S)
+        if not m:
+            continue
+        name, params = m.group(1), " ".join(m.group(2).split())
+        classes = []
+        if params not in ("", "void"):
+            for p in params.split(","):
+                p = p.strip()
+                if "*" in p or "[" in p:
+                    classes.append("ptr")
+                    continue
+                words = [w for w in p.split() if w != "const"]
+                assert len(words) == 2 and words[0] in _C_CLASS, (name, p)
+                classes.append(_C_CLASS[words[0]])
+        assert name not in protos, name
+        protos[name] = classes
+    return protos
+
+
+def _csharp_imports():
+    imports = []
+    d = os.path.join(ROOT, "vtkcloudpoint_amd", "host", "csharp")
+    for fn in sorted(os.listdir(d)):
+        if not fn.endswith(".cs"):
+            continue
+        with open(os.path.join(d, fn)) as f:
+            src = f.read()
+        n_dll = len(re.findall(r"\[DllImport\b", src))
+        found = re.findall(r"\[DllImport\b[^\]]*\]\s*(?:(?:public|internal|private|static|unsafe)\s+)*extern\s+[\w\[\]]+\s+"
+                           r"(\w+)\s*\(([^)]*)\)\s*;", src, re.S)
+        assert len(found) == n_dll, "%s: %d DllImports, %d parsed" % (fn, n_dll, len(found))
+        for name, params in found:
+            classes = []
+            for p in " ".join(params.split()).split(","):
+                p = p.strip()
+                if not p:
+                    continue
+                words = [w for w in p.split() if not w.startswith("[")]
+                if words[0] in ("out", "ref") or words[0].endswith("[]") or words[0] == "string":
+                    classes.append("ptr")
+                else:
+                    assert len(words) == 2 and words[0] in _CS_CLASS, (fn, name, p)
+                    classes.append(_CS_CLASS[words[0]])
+            imports.append((fn, name, classes))
+    return imports
+
+
+def test_csharp_dllimports_match_the_header():
+    """Every DllImport in host/csharp/*.cs names a vcp.h function and passes the header's parameters: the same count,
+    each of the same width class."""
+    protos = _header_prototypes()
+    assert len(protos) >= 25 and protos["vcp_blocks_finish_zero_dev"] == ["ptr", "i32", "ptr", "ptr"]
+    imports = _csharp_imports()
+    assert len(imports) >= 40
+    bad = []
+    for fn, name, classes in imports:
+        if name not in protos:
+            bad.append("%s: %s is not in vcp.h" % (fn, name))
+        elif classes != protos[name]:
+            bad.append("%s: %s(%s), vcp.h has (%s)" % (fn, name, ", ".join(classes), ", ".join(protos[name])))
+    assert not bad, "\n".join(bad)
+
+
+def test_python_binding_calls_pass_the_header_arity():
+    """Every lib().vcp_*(...) call in _native.py passes as many arguments as the vcp.h prototype has parameters."""
+    import ast
+    protos = _header_prototypes()
+    with open(os.path.join(ROOT, "vtkcloudpoint_amd", "_native.py")) as f:
+        tree = ast.parse(f.read())
+    calls = []
+    for node in ast.walk(tree):
+        if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)):
+            continue
+        base = node.func.value
+        if not (isinstance(base, ast.Call) and isinstance(base.func, ast.Name) and base.func.id == "lib"):
+            continue
+        name = node.func.attr
+        assert name in protos, "%s (line %d) is not in vcp.h" % (name, node.lineno)
+        assert not node.keywords and not any(isinstance(a, ast.Starred) for a in node.args), name
+        calls.append((name, node.lineno, len(node.args)))
+    assert len(calls) >= 50
+    bad = ["%s (line %d): %d arguments, vcp.h has %d" % (nm, ln, k, len(protos[nm]))
+           for nm, ln, k in calls if k != len(protos[nm])]
+    assert not bad, "\n".join(bad)

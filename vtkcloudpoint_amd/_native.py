@@ -499,7 +499,9 @@ def blocks_share_plan(blockstart, world):
 
 class MultiContext:
     """vcp_multi: several GPUs driven from this one process (one vcp_ctx and one host thread per listed device; an id
-    may repeat).  dbscan_blocks = Context.dbscan_blocks with the per-block step sharded over the devices."""
+    may repeat).  dbscan_blocks = Context.dbscan_blocks with every stage sharded over the devices: each one plans the
+    partition, then builds, clusters and merges its own share of the blocks; device 0 runs the global noise pass and
+    assembles the outputs."""
 
     def __init__(self, device_ids):
         ids = (C.c_int * len(device_ids))(*[int(d) for d in device_ids])

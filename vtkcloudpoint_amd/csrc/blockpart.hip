@@ -1117,8 +1117,10 @@ int vcp_blocks_build(vcp_ctx* ctx, BlocksState* s, uint32_t S_lo, uint32_t S_hi,
   const size_t nl = (size_t)(n_loc > 0 ? n_loc : 1);
   s->S_lo = S_lo;
   s->S_hi = S_hi;
-  s->b_lo = (int64_t)S_lo << fsh;
-  s->b_hi = std::min<int64_t>((int64_t)S_hi << fsh, s->nblocks);
+  // clamped to the blocks: a share of the last super-bucket alone (the points in no block, fsh = 0) or a share with no
+  // super-bucket at all ([NS, NS): more ranks than the point count can feed) holds no block, [nblocks, nblocks)
+  s->b_lo = std::min<int64_t>((int64_t)S_lo << fsh, s->nblocks);
+  s->b_hi = std::max<int64_t>(s->b_lo, std::min<int64_t>((int64_t)S_hi << fsh, s->nblocks));
   s->n_loc = n_loc;
   const bool has_dropped = S_hi == NS;
   SelState* d_sel = s->sel.as<SelState>();

@@ -900,6 +900,9 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
   BlocksState* s = ctx->blocks;
   hipStream_t st = ctx->stream;
   const int64_t m = s->m, nb = s->b_hi - s->b_lo;  // blocks of the share
+  if (nb < 0 || s->b_hi > s->nblocks || (nb == 0 && m != 0))
+    return vcp_fail(ctx, VCP_ERR_ARG, "share of blocks [%lld, %lld) of %lld", (long long)s->b_lo, (long long)s->b_hi,
+                    (long long)s->nblocks);
   const uint32_t b_lo = (uint32_t)s->b_lo;
   const uint32_t* blockstart = s->blockstart.as<uint32_t>() + s->b_lo;
   VCP_TRY(ens(ctx, s->kb, (size_t)(nb + 2) * 4));
