@@ -221,3 +221,25 @@ def test_python_binding_calls_pass_the_header_arity():
     bad = ["%s (line %d): %d arguments, vcp.h has %d" % (nm, ln, k, len(protos[nm]))
            for nm, ln, k in calls if k != len(protos[nm])]
     assert not bad, "\n".join(bad)
+
+
+def test_kernels_launch_only_through_vcp_launch():
+    """Every kernel launch in the library goes through VCP_LAUNCH (csrc/vcp_ctx.hpp), which refuses a dispatch the runtime
+    would wrap and names the kernel of a launch that fails.  Its definition is the one place that calls the launch API."""
+    csrc = os.path.join(ROOT, "vtkcloudpoint_amd", "csrc")
+    raw = re.compile(r"hipLaunchKernel|<<<|hipModuleLaunchKernel|hipExtLaunchKernel")
+    launcher = re.compile(r"^#define VCP_LAUNCH\(.*?[^\\]\n", flags=re.M | re.S)
+    bad, uses = [], 0
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".hpp")):
+            continue
+        with open(os.path.join(csrc, fn)) as f:
+            text = f.read()
+        if fn == "vcp_ctx.hpp":
+            defs = launcher.findall(text)
+            assert len(defs) == 1 and len(raw.findall(defs[0])) == 1, "the definition of VCP_LAUNCH"
+            text = launcher.sub(lambda m: "\n" * m.group(0).count("\n"), text)
+        uses += len(re.findall(r"\bVCP_LAUNCH\(ctx, ", text))
+        bad += ["%s:%d" % (fn, text.count("\n", 0, m.start()) + 1) for m in raw.finditer(text)]
+    assert not bad, "launches outside VCP_LAUNCH: " + ", ".join(bad)
+    assert uses >= 100

@@ -1018,15 +1018,15 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
   uint32_t* ghist = reinterpret_cast<uint32_t*>(s->sel.as<char>() + 256);
   double* selpart = reinterpret_cast<double*>(s->sel.as<char>() + 256 + 4096 * 4);
   static_assert(sizeof(SelState) <= 256, "SelState");
-  hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(PT), 0, st, d_sel, ghist, (uint64_t)s->take, (uint32_t)n);
+  VCP_LAUNCH(ctx, k_sel_init, dim3(1), dim3(PT), 0, st, d_sel, ghist, (uint64_t)s->take, (uint32_t)n);
   SelState* hs = reinterpret_cast<SelState*>(reinterpret_cast<char*>(ctx->pinned) + 1024);
   bool done = false;
   for (uint32_t pass = 0; pass < 8 && !done; pass++) {
-    hipLaunchKernelGGL(k_sel_hist, dim3(nchunk), dim3(PT), 0, st, d_key, n, out, (uint32_t)chunk, pass, d_sel, ghist);
-    hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(PT), 0, st, d_sel, ghist);
-    hipLaunchKernelGGL(k_sel_collect, dim3(nchunk), dim3(PT), 0, st, d_key, n, out, (uint32_t)chunk, d_sel,
-                       s->cand.as<Cand>(), selpart);
-    hipLaunchKernelGGL(k_sel_final, dim3(1), dim3(PT), 0, st, d_sel, s->cand.as<Cand>(), selpart, nchunk);
+    VCP_LAUNCH(ctx, k_sel_hist, dim3(nchunk), dim3(PT), 0, st, d_key, n, out, (uint32_t)chunk, pass, d_sel, ghist);
+    VCP_LAUNCH(ctx, k_sel_pick, dim3(1), dim3(PT), 0, st, d_sel, ghist);
+    VCP_LAUNCH(ctx, k_sel_collect, dim3(nchunk), dim3(PT), 0, st, d_key, n, out, (uint32_t)chunk, d_sel,
+                    s->cand.as<Cand>(), selpart);
+    VCP_LAUNCH(ctx, k_sel_final, dim3(1), dim3(PT), 0, st, d_sel, s->cand.as<Cand>(), selpart, nchunk);
     VCP_HIP(ctx, hipMemcpyAsync(hs, d_sel, sizeof(SelState), hipMemcpyDeviceToHost, st));
     if (pass == 0) VCP_HIP(ctx, hipMemcpyAsync(h, out, 16 * 8, hipMemcpyDeviceToHost, st));  // both sets of bounds
     VCP_HIP(ctx, hipStreamSynchronize(st));
@@ -1057,8 +1057,7 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
   s->rows = (int)fr + 1;
   s->cols = (int)fc + 1;
   s->nblocks = (int64_t)s->rows * s->cols;
-  // (2^26 - 4: the kernels with a wave per block launch nblocks * 64 threads, and a launch holds fewer than 2^32)
-  if (s->nblocks > ((int64_t)1 << 26) - 4) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "%lld blocks", (long long)s->nblocks);
+  if (s->nblocks > VCP_MAX_BLOCKS) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "%lld blocks", (long long)s->nblocks);
 
   // block of every point (FrmMain.cs:1259-1285, Tools.cs:510-513) and the population of every super-bucket
   const PartP P{s->x_Min, s->x_Max, s->y_Min, s->y_Max, s->cell_x, s->cell_y, 1.0 / s->cell_x, 1.0 / s->cell_y, s->rows, s->cols};
@@ -1083,20 +1082,19 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
     VCP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_blk_scatter), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)(MAXS * 4)));
   }
-  hipLaunchKernelGGL(k_blk_hist, dim3(nchunk), dim3(PT), (size_t)NS * 4, st, d_key, n, P, s->key_T, s->idx_T, nblocks, fsh, NS,
-                     (uint32_t)chunk, nchunk, s->blockof.as<int32_t>(), s->counts_t.as<uint32_t>());
+  VCP_LAUNCH(ctx, k_blk_hist, dim3(nchunk), dim3(PT), (size_t)NS * 4, st, d_key, n, P, s->key_T, s->idx_T, nblocks, fsh, NS,
+                  (uint32_t)chunk, nchunk, s->blockof.as<int32_t>(), s->counts_t.as<uint32_t>());
   // chunk-major counts -> bucket-major, scanned (the positions of every (bucket, chunk) run), and back for the scatter
-  hipLaunchKernelGGL(k_transpose_u32, dim3((NS + 31) / 32, (nchunk + 31) / 32), dim3(BT), 0, st, s->counts_t.as<uint32_t>(),
-                     counts, nchunk, NS);
+  VCP_LAUNCH(ctx, k_transpose_u32, dim3((NS + 31) / 32, (nchunk + 31) / 32), dim3(BT), 0, st, s->counts_t.as<uint32_t>(),
+                  counts, nchunk, NS);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, counts, counts, (int64_t)nc, total));
-  hipLaunchKernelGGL(k_transpose_u32, dim3((nchunk + 31) / 32, (NS + 31) / 32), dim3(BT), 0, st, counts,
-                     s->counts_t.as<uint32_t>(), NS, nchunk);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_transpose_u32, dim3((nchunk + 31) / 32, (NS + 31) / 32), dim3(BT), 0, st, counts,
+                  s->counts_t.as<uint32_t>(), NS, nchunk);
   s->h_sbstart.clear();
   if (want_cuts) {
     VCP_TRY(vcp_blocks_ens(ctx, s->sbstart, ((size_t)NS + 2) * 4));
-    hipLaunchKernelGGL(k_sb_starts, dim3(vcp_blocks((int64_t)NS + 1, BT)), dim3(BT), 0, st, counts, total, nchunk, NS,
-                       s->sbstart.as<uint32_t>());
+    VCP_LAUNCH(ctx, k_sb_starts, dim3(vcp_blocks((int64_t)NS + 1, BT)), dim3(BT), 0, st, counts, total, nchunk, NS,
+                    s->sbstart.as<uint32_t>());
     s->h_sbstart.resize((size_t)NS + 1);
     VCP_HIP(ctx, hipMemcpyAsync(s->h_sbstart.data(), s->sbstart.p, ((size_t)NS + 1) * 4, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
@@ -1169,40 +1167,39 @@ int vcp_blocks_build(vcp_ctx* ctx, BlocksState* s, uint32_t S_lo, uint32_t S_hi,
   const uint32_t b_lo = (uint32_t)s->b_lo;
   const unsigned nbl = (unsigned)std::max<int64_t>(s->b_hi - s->b_lo, 1);
   if (S_hi > S_lo) {
-    hipLaunchKernelGGL(k_blk_scatter, dim3(nchunk), dim3(PT), lds_h, st, s->d_key, s->d_motor, n, s->x_Min, s->y_Min, nblocks,
-                       fsh, NS, s->chunk, nchunk, s->blockof.as<int32_t>(), s->counts_t.as<uint32_t>(), rec, S_lo, S_hi, off0);
+    VCP_LAUNCH(ctx, k_blk_scatter, dim3(nchunk), dim3(PT), lds_h, st, s->d_key, s->d_motor, n, s->x_Min, s->y_Min, nblocks,
+                    fsh, NS, s->chunk, nchunk, s->blockof.as<int32_t>(), s->counts_t.as<uint32_t>(), rec, S_lo, S_hi, off0);
     if (fsh == 0) {
       // every block its own super-bucket: the scattered records ARE the block-major list; the two arrays swap roles
       const PartP P{s->x_Min, s->x_Max, s->y_Min, s->y_Max, s->cell_x, s->cell_y, 1.0 / s->cell_x, 1.0 / s->cell_y, s->rows,
                     s->cols};
-      hipLaunchKernelGGL(k_blk_starts, dim3(vcp_blocks((int64_t)(S_hi - S_lo), BT)), dim3(BT), 0, st, counts, total, nchunk, NS,
-                         nblocks, P, s->key_T, blockstart, s->biglist.as<uint32_t>(), d_sel, s->binfo.as<BigInfo>(),
-                         s->slicelist.as<uint2>(), fall, S_lo, S_hi, off0);
+      VCP_LAUNCH(ctx, k_blk_starts, dim3(vcp_blocks((int64_t)(S_hi - S_lo), BT)), dim3(BT), 0, st, counts, total, nchunk, NS,
+                      nblocks, P, s->key_T, blockstart, s->biglist.as<uint32_t>(), d_sel, s->binfo.as<BigInfo>(),
+                      s->slicelist.as<uint2>(), fall, S_lo, S_hi, off0);
       std::swap(rec, rec2);
     } else {
-      hipLaunchKernelGGL(k_blk_split, dim3(S_hi - S_lo), dim3(PT), 0, st, rec, rec2, counts, total, nchunk, NS, fsh, nblocks,
-                         blockstart, s->biglist.as<uint32_t>(), d_sel, s->binfo.as<BigInfo>(), s->slicelist.as<uint2>(), fall,
-                         S_lo, S_hi, off0);
+      VCP_LAUNCH(ctx, k_blk_split, dim3(S_hi - S_lo), dim3(PT), 0, st, rec, rec2, counts, total, nchunk, NS, fsh, nblocks,
+                      blockstart, s->biglist.as<uint32_t>(), d_sel, s->binfo.as<BigInfo>(), s->slicelist.as<uint2>(), fall,
+                      S_lo, S_hi, off0);
     }
 #define VCP_SORT_ARGS(list) rec2, rec, blockstart, nblocks, list, d_sel, fall, gcnt, s->stage.as<KeyPart>(),              \
                             s->rank.as<uint32_t>(), s->motor_bm.as<double>(), s->bl.as<uint32_t>(), s->blk_t.as<uint32_t>(), \
                             b_lo, has_dropped ? 1 : 0, s->brute_thr ? s->grp_big.as<int32_t>() : nullptr, s->brute_thr, \
                             (uint32_t)(s->b_hi - s->b_lo)
     if (s->b_hi > s->b_lo)
-      hipLaunchKernelGGL((k_blk_sort<false, false>), dim3(std::min(nbl, 1u << 22)), dim3(128), 0, st, VCP_SORT_ARGS(nullptr));
+      VCP_LAUNCH(ctx, (k_blk_sort<false, false>), dim3(std::min(nbl, 1u << 22)), dim3(128), 0, st, VCP_SORT_ARGS(nullptr));
     const unsigned gsl = (unsigned)std::min<size_t>(2048, nbig_cap + nl / SLICE);
-    hipLaunchKernelGGL(k_big_count, dim3(gsl), dim3(PT), 0, st, rec2, s->binfo.as<BigInfo>(), s->slicelist.as<uint2>(), d_sel,
-                       gcnt);
-    hipLaunchKernelGGL(k_big_scan, dim3((unsigned)std::min<size_t>(1024, nbig_cap)), dim3(BT), 0, st, s->binfo.as<BigInfo>(),
-                       d_sel, gcnt, vlist);
-    hipLaunchKernelGGL(k_big_move, dim3(gsl), dim3(PT), 0, st, rec2, rec, s->binfo.as<BigInfo>(), s->slicelist.as<uint2>(),
-                       d_sel, gcnt);
-    hipLaunchKernelGGL((k_blk_sort<false, true>), dim3((unsigned)std::min<size_t>(8192, nvirt_cap)), dim3(128), 0, st,
-                       VCP_SORT_ARGS(vlist));
-    hipLaunchKernelGGL((k_blk_sort<true, true>), dim3(256), dim3(1024), 0, st, VCP_SORT_ARGS(fall));
+    VCP_LAUNCH(ctx, k_big_count, dim3(gsl), dim3(PT), 0, st, rec2, s->binfo.as<BigInfo>(), s->slicelist.as<uint2>(), d_sel,
+                    gcnt);
+    VCP_LAUNCH(ctx, k_big_scan, dim3((unsigned)std::min<size_t>(1024, nbig_cap)), dim3(BT), 0, st, s->binfo.as<BigInfo>(),
+                    d_sel, gcnt, vlist);
+    VCP_LAUNCH(ctx, k_big_move, dim3(gsl), dim3(PT), 0, st, rec2, rec, s->binfo.as<BigInfo>(), s->slicelist.as<uint2>(),
+                    d_sel, gcnt);
+    VCP_LAUNCH(ctx, (k_blk_sort<false, true>), dim3((unsigned)std::min<size_t>(8192, nvirt_cap)), dim3(128), 0, st,
+                    VCP_SORT_ARGS(vlist));
+    VCP_LAUNCH(ctx, (k_blk_sort<true, true>), dim3(256), dim3(1024), 0, st, VCP_SORT_ARGS(fall));
 #undef VCP_SORT_ARGS
   }
-  VCP_HIP(ctx, hipGetLastError());
   // host copy of the share's block starts [b_lo, b_hi] (positions relative to the share)
   s->h_blockstart.assign((size_t)nblocks + 2, 0u);
   if (S_hi > S_lo) {

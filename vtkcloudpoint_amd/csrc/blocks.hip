@@ -480,8 +480,6 @@ __global__ __launch_bounds__(BT) void k_scatter_pairs(const int64_t* __restrict_
   else *bad = 1u;
 }
 
-unsigned nblk(int64_t n) { return vcp_blocks(n, BT); }
-
 // key_in: the coordinates the PARTITION reads -- (motor_x, motor_y) in getClusterFromMotor (FrmMain.cs:1214-1291,
 // Tools.getListByScale2), (X, Y) in its twin getClusterFromList (:1136-1213, Tools.getListByScale :507-509); the
 // per-block DBImproved and the noise pass always cluster on motor (StartCode :2785-2786, BC/DBImproved.cs:16-21).
@@ -836,17 +834,16 @@ int blocks_cluster(vcp_ctx* ctx, int32_t lo, int32_t hi, int32_t* d_local, int64
     unsigned long long* bc = s->brutecnt.as<unsigned long long>();  // [64][2]: op counter, clusters of the small blocks
     VCP_HIP(ctx, hipEventRecord(s->ev_fork, ctx->stream));
     VCP_HIP(ctx, hipStreamWaitEvent(s->side, s->ev_fork, 0));
-    hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(BT), 0, s->side, reinterpret_cast<uint32_t*>(bc), 256u);
+    VCP_LAUNCH(ctx, k_zero_words, dim3(1), dim3(BT), 0, s->side, reinterpret_cast<uint32_t*>(bc), 256u);
     const unsigned gb = (unsigned)std::min<int64_t>((int64_t)hi - lo, (int64_t)1 << 22);
-    hipLaunchKernelGGL(k_block_brute<BRT>, dim3(gb), dim3(BRT), 0, s->side, s->motor_bm.as<double>(),
-                       s->blockstart.as<uint32_t>(), (uint32_t)lo, (uint32_t)hi, 0u, thr, s->eps, s->min_pts, s->x_Min, s->y_Min,
-                       d_local, bc);
+    VCP_LAUNCH(ctx, k_block_brute<BRT>, dim3(gb), dim3(BRT), 0, s->side, s->motor_bm.as<double>(),
+                    s->blockstart.as<uint32_t>(), (uint32_t)lo, (uint32_t)hi, 0u, thr, s->eps, s->min_pts, s->x_Min, s->y_Min,
+                    d_local, bc);
     if (thr > (uint32_t)BRT && any_mid)
-      hipLaunchKernelGGL(k_block_brute<BRUTE_CAP>, dim3(gb), dim3(BRT), 0, s->side, s->motor_bm.as<double>(),
-                         s->blockstart.as<uint32_t>(), (uint32_t)lo, (uint32_t)hi, (uint32_t)BRT, thr, s->eps, s->min_pts,
-                         s->x_Min, s->y_Min, d_local, bc);
+      VCP_LAUNCH(ctx, k_block_brute<BRUTE_CAP>, dim3(gb), dim3(BRT), 0, s->side, s->motor_bm.as<double>(),
+                      s->blockstart.as<uint32_t>(), (uint32_t)lo, (uint32_t)hi, (uint32_t)BRT, thr, s->eps, s->min_pts,
+                      s->x_Min, s->y_Min, d_local, bc);
     VCP_HIP(ctx, hipMemcpyAsync(hb, bc, 128 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->side));
-    VCP_HIP(ctx, hipGetLastError());
   }
   if (pts_big > 0) {
     DbscanExt ext;
@@ -870,7 +867,6 @@ int blocks_cluster(vcp_ctx* ctx, int32_t lo, int32_t hi, int32_t* d_local, int64
       return rc;
     }
   }
-  VCP_HIP(ctx, hipGetLastError());
   if (pts_small > 0) {
     VCP_HIP(ctx, hipStreamSynchronize(s->side));
     for (int k = 0; k < 64; k++) {
@@ -914,11 +910,12 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
   uint32_t* cstart = s->cstart.as<uint32_t>();
   // [0] total clusters, [1] kept, [2] err, [3] Z, [4] id table overflow, [5] request to an earlier share, [6..8] k_last_entry
   uint32_t* dmisc = s->misc.as<uint32_t>();
-  const unsigned nbw = (unsigned)((std::max<int64_t>(nb, 1) + BT / 64 - 1) / (BT / 64));  // one wave per block
-  hipLaunchKernelGGL(k_block_stats<1>, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, nullptr, kb, zb, dmisc, b_lo);
+  const unsigned nbw = vcp_blocks(nb, BT / 64);  // one wave per block
+  static_assert(vcp_launch_ok(dim3(vcp_blocks(VCP_MAX_BLOCKS, BT / 64)), dim3(BT), 0), "the wave-per-block launches wrap");
+  VCP_LAUNCH(ctx, k_block_stats<1>, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, nullptr, kb, zb, dmisc, b_lo);
   if (s->nbig)
-    hipLaunchKernelGGL(k_block_stats<16>, dim3(s->nbig), dim3(1024), 0, st, d_local, blockstart, nb,
-                       s->biglist.as<uint32_t>(), kb, zb, dmisc, b_lo);
+    VCP_LAUNCH(ctx, k_block_stats<16>, dim3(s->nbig), dim3(1024), 0, st, d_local, blockstart, nb,
+                    s->biglist.as<uint32_t>(), kb, zb, dmisc, b_lo);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, kb, cstart, nb + 1, dmisc));  // cstart[nb] = total clusters
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
   // The number of clusters sizes two arrays and a scan.  When this context clustered every block of the share itself (one
@@ -950,11 +947,11 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
   bool by_sort = force_sort || getenv("VCP_BLOCKS_ORDER_SORT") != nullptr;  // (the variable: test switch)
   for (;;) {
     if (m > 0 && !by_sort) {
-      hipLaunchKernelGGL(k_block_order, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize, order,
-                         dmisc + 4);
+      VCP_LAUNCH(ctx, k_block_order, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize, order,
+                      dmisc + 4);
       if (s->nbig)
-        hipLaunchKernelGGL(k_block_order_big, dim3(s->nbig), dim3(64 * OBW), 0, st, d_local, blockstart, kb,
-                           s->biglist.as<uint32_t>(), cstart, csize, order, dmisc + 4, b_lo);
+        VCP_LAUNCH(ctx, k_block_order_big, dim3(s->nbig), dim3(64 * OBW), 0, st, d_local, blockstart, kb,
+                        s->biglist.as<uint32_t>(), cstart, csize, order, dmisc + 4, b_lo);
     } else if (m > 0) {
       VCP_TRY(ens(ctx, s->tmp0, (size_t)(m + 1) * 8));
       VCP_TRY(ens(ctx, s->tmp1, (size_t)(m + 1) * 8));
@@ -964,20 +961,21 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
       uint32_t* v1o = s->tmp1.as<uint32_t>();
       uint32_t* k2 = v1o + (m + 1);
       VCP_HIP(ctx, hipMemsetAsync(csize, 0, (size_t)(totalC + 2) * 4, st));
-      hipLaunchKernelGGL(k_cluster_sizes, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize);
-      hipLaunchKernelGGL(k_iota, dim3(nblk(m)), dim3(BT), 0, st, iota, m);
+      VCP_LAUNCH(ctx, k_cluster_sizes, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize);
+      VCP_LAUNCH(ctx, k_iota, dim3(vcp_blocks(m, BT)), dim3(BT), 0, st, iota, m);
       VCP_HIP(ctx, hipMemcpyAsync(k1, d_local, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
       VCP_TRY(vcp_sort_pairs(ctx, s->sorttmp, k1, k1o, iota, v1o, (size_t)m, vcp_bits_for((uint64_t)m), false));  // a local id is at most m
-      hipLaunchKernelGGL(k_gather_u32, dim3(nblk(m)), dim3(BT), 0, st, blk_t, v1o, m, k2);
+      VCP_LAUNCH(ctx, k_gather_u32, dim3(vcp_blocks(m, BT)), dim3(BT), 0, st, blk_t, v1o, m, k2);
       VCP_TRY(vcp_sort_pairs(ctx, s->sorttmp, k2, k1o, v1o, order, (size_t)m, vcp_bits_for((uint64_t)s->nblocks), false));
     }
-    hipLaunchKernelGGL(k_keep, dim3(nblk(nb)), dim3(BT), 0, st, nb, cstart, kb, zb, blockstart, csize, s->small_max, keep,
-                       victim_of, dmisc + 2, b_lo);
+    VCP_LAUNCH(ctx, k_keep, dim3(vcp_blocks(nb, BT)), dim3(BT), 0, st, nb, cstart, kb, zb, blockstart, csize, s->small_max,
+                    keep, victim_of, dmisc + 2, b_lo);
     VCP_TRY(vcp_exclusive_scan_u32(ctx, keep, keeprank, (int64_t)totalC + 1, dmisc + 1));
-    hipLaunchKernelGGL(k_newlab, dim3(nblk(m)), dim3(BT), 0, st, d_local, blk_t, m, cstart, keep, keeprank, newlab, b_lo);
-    hipLaunchKernelGGL(k_victims, dim3(nblk(nb)), dim3(BT), 0, st, nb, victim_of, blockstart, order, newlab);
+    VCP_LAUNCH(ctx, k_newlab, dim3(vcp_blocks(m, BT)), dim3(BT), 0, st, d_local, blk_t, m, cstart, keep, keeprank, newlab,
+                    b_lo);
+    VCP_LAUNCH(ctx, k_victims, dim3(vcp_blocks(nb, BT)), dim3(BT), 0, st, nb, victim_of, blockstart, order, newlab);
     if (!sharded) break;  // (the single device reads the counters once, after the zero list: finish_zero)
-    hipLaunchKernelGGL(k_last_entry, dim3(1), dim3(BT), 0, st, nb, blockstart, order, newlab, dmisc);
+    VCP_LAUNCH(ctx, k_last_entry, dim3(1), dim3(BT), 0, st, nb, blockstart, order, newlab, dmisc);
     VCP_HIP(ctx, hipMemcpyAsync(hp, dmisc, 48, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (hp[4] == 0 || by_sort) break;
@@ -1009,7 +1007,7 @@ int finish_zero(vcp_ctx* ctx, bool sharded, int zero_last, bool* again) {
   int32_t* newlab = s->newlab.as<int32_t>();
   uint32_t* order = s->order.as<uint32_t>();
   if (again) *again = false;
-  if (sharded && zero_last) hipLaunchKernelGGL(k_zero_one, dim3(1), dim3(1), 0, st, newlab, dmisc);
+  if (sharded && zero_last) VCP_LAUNCH(ctx, k_zero_one, dim3(1), dim3(1), 0, st, newlab, dmisc);
   // zero list (FrmMain.cs:1510-1515)
   const int64_t nw = (m + 31) / 32;  // words of the two bitmaps; each buffer: [nw + 2] word counts, then [nw] words
   VCP_TRY(ens(ctx, s->zflag, (size_t)(2 * nw + 4) * 4));
@@ -1029,8 +1027,8 @@ int finish_zero(vcp_ctx* ctx, bool sharded, int zero_last, bool* again) {
   B.r2 = 2.0 * s->eps * (1.0 + 1.0 / 1099511627776.0);
   static const bool band_off = getenv("VCP_NOISE_ALL") != nullptr;  // test switch: the whole zero list
   B.all_active = (s->d_key != s->d_motor || !(s->eps >= 0.0) || !std::isfinite(B.r2) || band_off) ? 1 : 0;
-  hipLaunchKernelGGL(k_zero_flag, dim3(nblk(m)), dim3(BT), 0, st, newlab, order, m, zcnt, zcnt + nw + 2, s->f_local,
-                     s->motor_bm.as<double>(), s->blk_t.as<uint32_t>(), B, acnt, acnt + nw + 2);
+  VCP_LAUNCH(ctx, k_zero_flag, dim3(vcp_blocks(m, BT)), dim3(BT), 0, st, newlab, order, m, zcnt, zcnt + nw + 2,
+                  s->f_local, s->motor_bm.as<double>(), s->blk_t.as<uint32_t>(), B, acnt, acnt + nw + 2);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, zcnt, zcnt, nw + 1, dmisc + 3));
   VCP_TRY(vcp_exclusive_scan_u32(ctx, acnt, acnt, nw + 1, dmisc + 9));
   VCP_HIP(ctx, hipMemcpyAsync(hp, dmisc, 48, hipMemcpyDeviceToHost, st));
@@ -1056,11 +1054,10 @@ int finish_zcoords(vcp_ctx* ctx, double* d_zcoords, int64_t* d_merge_order, int 
   const int64_t m = s->m;
   const int64_t nw = (m + 31) / 32;
   if (m > 0)
-    hipLaunchKernelGGL(k_compact, dim3(nblk(m)), dim3(BT), 0, st, s->zflag.as<uint32_t>(), s->zflag.as<uint32_t>() + nw + 2,
-                       s->order.as<uint32_t>(), s->bl.as<uint32_t>(), s->motor_bm.as<double>(), m, s->f_Z,
-                       s->tmp2.as<uint32_t>() /* zrank: free again (it held the identity of the library-sort order) */,
-                       d_zcoords, d_merge_order, swap_xy, s->zlist.as<uint32_t>(), s->zlist.as<uint32_t>() + nw + 2);
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_compact, dim3(vcp_blocks(m, BT)), dim3(BT), 0, st, s->zflag.as<uint32_t>(),
+                    s->zflag.as<uint32_t>() + nw + 2, s->order.as<uint32_t>(), s->bl.as<uint32_t>(), s->motor_bm.as<double>(), m,
+                    s->f_Z, s->tmp2.as<uint32_t>() /* zrank: free again (it held the identity of the library-sort order) */,
+                    d_zcoords, d_merge_order, swap_xy, s->zlist.as<uint32_t>(), s->zlist.as<uint32_t>() + nw + 2);
   return VCP_OK;
 }
 
@@ -1109,9 +1106,8 @@ int blocks_finish(vcp_ctx* ctx, const int32_t* d_local, int64_t evals_blocks, in
     ev = (int64_t)Z * ((int64_t)Z + K + twice);
   }
   // labels by original index: kept clusters and the noise pass result, one scatter
-  hipLaunchKernelGGL(k_final_labels, dim3(nblk(n)), dim3(BT), 0, st, newlab, A > 0 ? s->zlab.as<int32_t>() : nullptr, zrank,
-                     s->bl.as<uint32_t>(), m, n, d_labels);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_final_labels, dim3(vcp_blocks(n, BT)), dim3(BT), 0, st, newlab, A > 0 ? s->zlab.as<int32_t>() : nullptr,
+                  zrank, s->bl.as<uint32_t>(), m, n, d_labels);
   VCP_HIP(ctx, hipStreamSynchronize(st));
   if (kept_o) *kept_o = (int32_t)kept;
   if (del_o) *del_o = (int32_t)delSum;
@@ -1340,9 +1336,8 @@ int vcp_blocks_finish_pairs_dev(vcp_ctx* ctx, int32_t kept_offset, const int32_t
   if (s->n_loc > 0 && !d_pairs) return vcp_fail(ctx, VCP_ERR_ARG, "null buffer");
   if (s->f_A > 0 && !d_zlab) return vcp_fail(ctx, VCP_ERR_ARG, "null buffer");
   if (s->n_loc > 0)
-    hipLaunchKernelGGL(k_pairs, dim3(nblk(s->n_loc)), dim3(BT), 0, ctx->stream, s->newlab.as<int32_t>(), d_zlab,
-                       s->tmp2.as<uint32_t>(), s->bl.as<uint32_t>(), s->m, s->n_loc, kept_offset, d_pairs);
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_pairs, dim3(vcp_blocks(s->n_loc, BT)), dim3(BT), 0, ctx->stream, s->newlab.as<int32_t>(), d_zlab,
+                    s->tmp2.as<uint32_t>(), s->bl.as<uint32_t>(), s->m, s->n_loc, kept_offset, d_pairs);
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VCP_OK;
 }
@@ -1356,7 +1351,7 @@ int vcp_scatter_pairs_dev(vcp_ctx* ctx, const int64_t* d_pairs, int64_t count, i
   VCP_TRY(vcp_ensure(ctx, ctx->b_misc, 256));
   uint32_t* bad = ctx->b_misc.as<uint32_t>();
   VCP_HIP(ctx, hipMemsetAsync(bad, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(k_scatter_pairs, dim3(nblk(count)), dim3(BT), 0, ctx->stream, d_pairs, count, n, d_labels, bad);
+  VCP_LAUNCH(ctx, k_scatter_pairs, dim3(vcp_blocks(count, BT)), dim3(BT), 0, ctx->stream, d_pairs, count, n, d_labels, bad);
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(hp, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));

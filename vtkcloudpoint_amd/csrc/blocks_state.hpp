@@ -50,6 +50,9 @@ struct BlocksState {
   bool ready = false;
 };
 
+// most blocks a partition may have (VCP_ERR_TOO_LARGE beyond): the kernels with a wave per block launch
+// vcp_blocks(nblocks, BT / 64) workgroups of BT threads, and blocks.hip asserts that such a launch does not wrap
+constexpr int64_t VCP_MAX_BLOCKS = ((int64_t)1 << 26) - 4;
 constexpr uint32_t VCP_BIG_BLOCK = 1024;  // blocks beyond this take the workgroup-per-block kernels
 constexpr uint32_t VCP_BRUTE_MAX = 1024;  // largest block the all-pairs kernel takes (its LDS copy of the coordinates)
 

@@ -78,14 +78,15 @@ __global__ __launch_bounds__(BT) void k_moments(const double* __restrict__ c, in
 }
 
 template <int GD, bool GROUPED>
-void launch_bounds(const BoundsSrc& s, int rb, hipStream_t st, double* d_part) {
-  hipLaunchKernelGGL((k_bounds<GD, GROUPED>), dim3(rb), dim3(BT), 0, st, s.c, s.n, s.stride, s.group, s.glo, s.ghi,
-                     d_part);
+int launch_bounds(vcp_ctx* ctx, const BoundsSrc& s, int rb, hipStream_t st, double* d_part) {
+  VCP_LAUNCH(ctx, (k_bounds<GD, GROUPED>), dim3(rb), dim3(BT), 0, st, s.c, s.n, s.stride, s.group, s.glo, s.ghi, d_part);
+  return VCP_OK;
 }
 template <int GD, bool GROUPED>
-void launch_moments(const BoundsSrc& s, int rb, hipStream_t st, const Range3& R, double* d_part) {
-  hipLaunchKernelGGL((k_moments<GD, GROUPED>), dim3(rb), dim3(BT), 0, st, s.c, s.n, s.stride, s.group, s.glo, s.ghi, R,
-                     d_part);
+int launch_moments(vcp_ctx* ctx, const BoundsSrc& s, int rb, hipStream_t st, const Range3& R, double* d_part) {
+  VCP_LAUNCH(ctx, (k_moments<GD, GROUPED>), dim3(rb), dim3(BT), 0, st, s.c, s.n, s.stride, s.group, s.glo, s.ghi, R,
+                  d_part);
+  return VCP_OK;
 }
 }  // namespace
 
@@ -95,14 +96,13 @@ int vcp_bounds_dev(vcp_ctx* ctx, const BoundsSrc& s, double* d_part, double* d_o
   const int rb = vcp_bounds_parts(s.n);
   hipStream_t st = ctx->stream;
   if (s.gd == 2) {
-    if (s.group) launch_bounds<2, true>(s, rb, st, d_part);
-    else launch_bounds<2, false>(s, rb, st, d_part);
+    if (s.group) VCP_TRY((launch_bounds<2, true>(ctx, s, rb, st, d_part)));
+    else VCP_TRY((launch_bounds<2, false>(ctx, s, rb, st, d_part)));
   } else {
-    if (s.group) launch_bounds<3, true>(s, rb, st, d_part);
-    else launch_bounds<3, false>(s, rb, st, d_part);
+    if (s.group) VCP_TRY((launch_bounds<3, true>(ctx, s, rb, st, d_part)));
+    else VCP_TRY((launch_bounds<3, false>(ctx, s, rb, st, d_part)));
   }
-  hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(BT), 0, st, d_part, rb, d_out);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_bounds_final, dim3(1), dim3(BT), 0, st, d_part, rb, d_out);
   return VCP_OK;
 }
 
@@ -130,11 +130,11 @@ int vcp_robust_range(vcp_ctx* ctx, const BoundsSrc& s, DevBuf& part, double* lo,
       R.mid[a] = 0.5 * lo[a] + 0.5 * hi[a];
     }
     if (s.gd == 2) {
-      if (s.group) launch_moments<2, true>(s, rb, st, R, d_mom);
-      else launch_moments<2, false>(s, rb, st, R, d_mom);
+      if (s.group) VCP_TRY((launch_moments<2, true>(ctx, s, rb, st, R, d_mom)));
+      else VCP_TRY((launch_moments<2, false>(ctx, s, rb, st, R, d_mom)));
     } else {
-      if (s.group) launch_moments<3, true>(s, rb, st, R, d_mom);
-      else launch_moments<3, false>(s, rb, st, R, d_mom);
+      if (s.group) VCP_TRY((launch_moments<3, true>(ctx, s, rb, st, R, d_mom)));
+      else VCP_TRY((launch_moments<3, false>(ctx, s, rb, st, R, d_mom)));
     }
     VCP_HIP(ctx, hipMemcpyAsync(hm.data(), d_mom, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));

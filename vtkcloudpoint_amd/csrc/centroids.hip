@@ -166,7 +166,7 @@ int centroids_dev(vcp_ctx* ctx, const double* d_xyz, const double* d_motor, cons
   VCP_TRY(vcp_group_by_label(ctx, d_labels, nullptr, n, K, ctx->b_aux1, ctx->b_aux2, ctx->b_aux3, segstart, counts, bad,
                              &vals_out));
   vcp_phase(ctx, "centroid_reduce");
-  hipLaunchKernelGGL(k_nchunks, dim3(vcp_blocks(K + 1, CT)), dim3(CT), 0, st, counts, K, nch);
+  VCP_LAUNCH(ctx, k_nchunks, dim3(vcp_blocks(K + 1, CT)), dim3(CT), 0, st, counts, K, nch);
   uint32_t* d_tot = bad + 4;
   VCP_TRY(vcp_exclusive_scan_u32(ctx, nch, nch, K + 2, d_tot));  // nch -> chunkstart, [K+1] = total chunks
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
@@ -179,11 +179,10 @@ int centroids_dev(vcp_ctx* ctx, const double* d_xyz, const double* d_motor, cons
   if (wa) {
     uint32_t* empty = bad + 2;
     if (nchunks > 0)
-      hipLaunchKernelGGL(k_chunk_sums_w, dim3(nchunks), dim3(CT), 0, st, vals_out, segstart, counts, nch, K, d_xyz,
-                         wa->cluster_id, wa->pts_count, wa->ignore_dup, partial);
-    hipLaunchKernelGGL(k_centroid_final_w, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, partial, counts, nch, K, d_c3,
-                       d_counts, empty);
-    VCP_HIP(ctx, hipGetLastError());
+      VCP_LAUNCH(ctx, k_chunk_sums_w, dim3(nchunks), dim3(CT), 0, st, vals_out, segstart, counts, nch, K, d_xyz,
+                      wa->cluster_id, wa->pts_count, wa->ignore_dup, partial);
+    VCP_LAUNCH(ctx, k_centroid_final_w, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, partial, counts, nch, K, d_c3,
+                    d_counts, empty);
     VCP_HIP(ctx, hipMemcpyAsync(hp, empty, 4, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (hp[0] != 0)
@@ -191,11 +190,10 @@ int centroids_dev(vcp_ctx* ctx, const double* d_xyz, const double* d_motor, cons
     return VCP_OK;
   }
   if (nchunks > 0)
-    hipLaunchKernelGGL(k_chunk_sums, dim3(nchunks), dim3(CT), 0, st, vals_out, segstart, counts, nch, K, d_xyz, d_motor,
-                       partial);
-  hipLaunchKernelGGL(k_centroid_final, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, partial, counts, nch, K,
-                     d_xyz != nullptr, d_motor != nullptr, d_c3, d_c2, d_counts);
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_chunk_sums, dim3(nchunks), dim3(CT), 0, st, vals_out, segstart, counts, nch, K, d_xyz, d_motor,
+                    partial);
+  VCP_LAUNCH(ctx, k_centroid_final, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, partial, counts, nch, K,
+                  d_xyz != nullptr, d_motor != nullptr, d_c3, d_c2, d_counts);
   return VCP_OK;
 }
 
@@ -361,10 +359,9 @@ int vcp_merge_centroids(vcp_ctx* ctx, const double* cxy, const int32_t* ids, int
   uint32_t* merged = first + (K + 2);
   VCP_HIP(ctx, hipMemsetAsync(first, 0xFF, (size_t)(K + 2) * 4, st));
   VCP_HIP(ctx, hipMemsetAsync(merged, 0, 16, st));
-  hipLaunchKernelGGL(k_first_of, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, ctx->b_out0.as<int32_t>(), K, K, first);
-  hipLaunchKernelGGL(k_map_to, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, ctx->b_out0.as<int32_t>(),
-                     ctx->b_in3.as<int32_t>(), first, K, ctx->b_out3.as<int32_t>(), merged);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_first_of, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, ctx->b_out0.as<int32_t>(), K, K, first);
+  VCP_LAUNCH(ctx, k_map_to, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, ctx->b_out0.as<int32_t>(),
+                  ctx->b_in3.as<int32_t>(), first, K, ctx->b_out3.as<int32_t>(), merged);
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(map_to, ctx->b_out3.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipMemcpyAsync(hp, merged, 4, hipMemcpyDeviceToHost, st));
@@ -400,11 +397,11 @@ int vcp_refresh_by_dictionary(vcp_ctx* ctx, const double* xyz, const double* mot
   uint32_t* flag = ctx->b_out3.as<uint32_t>();
   uint32_t* bad = flag + (K + 2);
   VCP_HIP(ctx, hipMemsetAsync(bad, 0, 32, st));
-  hipLaunchKernelGGL(k_survivor_flag, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, ctx->b_in1.as<int32_t>(), K, flag, bad);
+  VCP_LAUNCH(ctx, k_survivor_flag, dim3(vcp_blocks(K, CT)), dim3(CT), 0, st, ctx->b_in1.as<int32_t>(), K, flag, bad);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, flag, flag, K, bad + 1));
   if (n > 0)
-    hipLaunchKernelGGL(k_relabel, dim3(vcp_blocks(n, CT)), dim3(CT), 0, st, ctx->b_in3.as<int32_t>(), n, K,
-                       ctx->b_in1.as<int32_t>(), flag, bad);
+    VCP_LAUNCH(ctx, k_relabel, dim3(vcp_blocks(n, CT)), dim3(CT), 0, st, ctx->b_in3.as<int32_t>(), n, K,
+                    ctx->b_in1.as<int32_t>(), flag, bad);
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(hp, bad, 8, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipStreamSynchronize(st));
@@ -416,7 +413,7 @@ int vcp_refresh_by_dictionary(vcp_ctx* ctx, const double* xyz, const double* mot
                         ctx->b_out2.as<int64_t>()));
   if (nk > 0) {
     VCP_HIP(ctx, hipMemsetAsync(bad, 0, 8, st));
-    hipLaunchKernelGGL(k_count_zero, dim3(vcp_blocks(nk, CT)), dim3(CT), 0, st, ctx->b_out2.as<int64_t>(), nk, bad);
+    VCP_LAUNCH(ctx, k_count_zero, dim3(vcp_blocks(nk, CT)), dim3(CT), 0, st, ctx->b_out2.as<int64_t>(), nk, bad);
     VCP_HIP(ctx, hipMemcpyAsync(hp, bad, 4, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (hp[0] != 0)

@@ -202,7 +202,7 @@ int vcp_db_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, d
   unsigned long long* hc = reinterpret_cast<unsigned long long*>(ctx->pinned) + 128;
   vcp_phase(ctx, "db_sort");
   VCP_HIP(ctx, hipMemsetAsync(ctr, 0, 8 * 8, st));
-  hipLaunchKernelGGL(k_db_key, dim3(vcp_blocks(n, DT)), dim3(DT), 0, st, d_coords, n, stride, d_mask, key_in, idx_in, ctr);
+  VCP_LAUNCH(ctx, k_db_key, dim3(vcp_blocks(n, DT)), dim3(DT), 0, st, d_coords, n, stride, d_mask, key_in, idx_in, ctr);
   VCP_TRY(vcp_sort_pairs(ctx, ctx->b_aux3, key_in, key_out, idx_in, idx_out, (size_t)n, 64));
   VCP_HIP(ctx, hipMemcpyAsync(hc, ctr, 8 * 8, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipStreamSynchronize(st));
@@ -215,9 +215,9 @@ int vcp_db_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, d
   const double maxabs = have ? std::ldexp(1.0, top + 1) : 0.0;
   const double band = exact ? 0.0 : 16.0 * 4.0 * maxabs * 2.220446049250313e-16;
   vcp_phase(ctx, "db_reach");
-  if (m > 0) hipLaunchKernelGGL(k_db_unkey, dim3(vcp_blocks(m, DT)), dim3(DT), 0, st, key_out, idx_out, m, sk, pos);
-  hipLaunchKernelGGL(k_db_reach, dim3(vcp_blocks((int64_t)m + 1, DT)), dim3(DT), 0, st, sk, idx_out, m, eps, min_pts, band,
-                     d_in_classed, R, lp1, ctr);
+  if (m > 0) VCP_LAUNCH(ctx, k_db_unkey, dim3(vcp_blocks(m, DT)), dim3(DT), 0, st, key_out, idx_out, m, sk, pos);
+  VCP_LAUNCH(ctx, k_db_reach, dim3(vcp_blocks((int64_t)m + 1, DT)), dim3(DT), 0, st, sk, idx_out, m, eps, min_pts, band,
+                  d_in_classed, R, lp1, ctr);
   if (!exact) {
     // a neighbour candidate within rounding of the threshold while the coordinates share no binary grid: the signed-sum
     // relation is not provably 1-D -- decided before anything is written to the caller's arrays
@@ -226,16 +226,15 @@ int vcp_db_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, d
     if (hc[2] != 0) return VCP_DB_PAIRS();
   }
   VCP_TRY(vcp_exclusive_max_scan_u32(ctx, lp1, lp1, (int64_t)m + 1, nullptr));
-  hipLaunchKernelGGL(k_db_fixed, dim3(vcp_blocks((int64_t)m + 2, DT)), dim3(DT), 0, st, lp1, R, m, xs);
+  VCP_LAUNCH(ctx, k_db_fixed, dim3(vcp_blocks((int64_t)m + 2, DT)), dim3(DT), 0, st, lp1, R, m, xs);
   VCP_TRY(vcp_exclusive_max_scan_u32(ctx, xs, xs, (int64_t)m + 2, nullptr));
   vcp_phase(ctx, "db_seeds");
-  hipLaunchKernelGGL(k_db_efin, dim3(vcp_blocks(n + 1, DT)), dim3(DT), 0, st, n, d_mask, d_in_classed, pos, R, xs, m, min_pts,
-                     efin);
+  VCP_LAUNCH(ctx, k_db_efin, dim3(vcp_blocks(n + 1, DT)), dim3(DT), 0, st, n, d_mask, d_in_classed, pos, R, xs, m, min_pts,
+                  efin);
   VCP_TRY(vcp_exclusive_max_scan_u32(ctx, efin, efin, n + 1, nullptr));
   for (int phase = 0; phase < 2; phase++)
-    hipLaunchKernelGGL(k_db_out, dim3(vcp_blocks(n, DT)), dim3(DT), 0, st, n, d_mask, d_in_classed, pos, R, efin, min_pts, cf_in,
-                       d_labels, d_is_core, d_is_classed, ctr, phase);
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_db_out, dim3(vcp_blocks(n, DT)), dim3(DT), 0, st, n, d_mask, d_in_classed, pos, R, efin, min_pts, cf_in,
+                    d_labels, d_is_core, d_is_classed, ctr, phase);
   VCP_HIP(ctx, hipMemcpyAsync(hc, ctr, 8 * 8, hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));
   VCP_HIP(ctx, hipStreamSynchronize(st));

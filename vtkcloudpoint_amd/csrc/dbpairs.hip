@@ -154,14 +154,14 @@ int vcp_db_pairs_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int str
   uint32_t* h_word = reinterpret_cast<uint32_t*>(ctx->pinned) + 512;
   const unsigned nb = vcp_blocks(n, PT);
   vcp_phase(ctx, "db_pairs_count");
-  hipLaunchKernelGGL(k_dbp_init, dim3(nb), dim3(PT), 0, st, n, d_in_classed, classed, firstseed, d_labels, ctr);
-  hipLaunchKernelGGL(k_dbp_count, dim3(nb), dim3(PT), 0, st, d_coords, n, stride, d_mask, eps, min_pts, core, ctr);
+  VCP_LAUNCH(ctx, k_dbp_init, dim3(nb), dim3(PT), 0, st, n, d_in_classed, classed, firstseed, d_labels, ctr);
+  VCP_LAUNCH(ctx, k_dbp_count, dim3(nb), dim3(PT), 0, st, d_coords, n, stride, d_mask, eps, min_pts, core, ctr);
   vcp_phase(ctx, "db_pairs_clusters");
   int32_t K = 0;
   uint32_t from = 0;
   while ((int64_t)from < n) {
     VCP_HIP(ctx, hipMemsetAsync(d_word, 0xFF, 4, st));
-    hipLaunchKernelGGL(k_dbp_next, dim3(vcp_blocks(n - from, PT)), dim3(PT), 0, st, n, from, d_mask, classed, core, d_word);
+    VCP_LAUNCH(ctx, k_dbp_next, dim3(vcp_blocks(n - from, PT)), dim3(PT), 0, st, n, from, d_mask, classed, core, d_word);
     VCP_HIP(ctx, hipMemcpyAsync(h_word, d_word, 4, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     const uint32_t seed = h_word[0];
@@ -173,8 +173,8 @@ int vcp_db_pairs_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int str
     int cur = 0, first = 1;
     while (nf > 0) {
       VCP_HIP(ctx, hipMemsetAsync(d_word, 0, 4, st));
-      hipLaunchKernelGGL(k_dbp_level, dim3(nb), dim3(PT), 0, st, d_coords, n, stride, d_mask, eps, front[cur], nf, seed,
-                         cf_in + K, first, core, classed, firstseed, d_labels, front[cur ^ 1], d_word, ctr);
+      VCP_LAUNCH(ctx, k_dbp_level, dim3(nb), dim3(PT), 0, st, d_coords, n, stride, d_mask, eps, front[cur], nf, seed,
+                      cf_in + K, first, core, classed, firstseed, d_labels, front[cur ^ 1], d_word, ctr);
       VCP_HIP(ctx, hipMemcpyAsync(h_word + 1, d_word, 4, hipMemcpyDeviceToHost, st));
       VCP_HIP(ctx, hipStreamSynchronize(st));
       nf = h_word[1];
@@ -183,10 +183,9 @@ int vcp_db_pairs_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int str
     }
     from = seed + 1u;
   }
-  hipLaunchKernelGGL(k_dbp_final, dim3(nb), dim3(PT), 0, st, n, d_mask, d_in_classed, core, classed, firstseed, d_is_core,
-                     d_is_classed, ctr);
+  VCP_LAUNCH(ctx, k_dbp_final, dim3(nb), dim3(PT), 0, st, n, d_mask, d_in_classed, core, classed, firstseed, d_is_core,
+                  d_is_classed, ctr);
   unsigned long long* hc = reinterpret_cast<unsigned long long*>(ctx->pinned) + 128;
-  VCP_HIP(ctx, hipGetLastError());
   VCP_HIP(ctx, hipMemcpyAsync(hc, ctr, 8 * 8, hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));
   VCP_HIP(ctx, hipStreamSynchronize(st));

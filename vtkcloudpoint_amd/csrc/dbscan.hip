@@ -1508,7 +1508,7 @@ Screen screen_bounds(int metric, int gd, double thr, double E) {
 // workgroups per band of a work list: a band holds at most ceil(n / (8*LCHUNK)) entries
 unsigned list_perblk(int64_t n) {
   const int64_t band = (n + 8 * LCHUNK - 1) / (8 * LCHUNK) + 1;
-  return (unsigned)((band + TPB - 1) / TPB);
+  return vcp_blocks(band, TPB);
 }
 
 // GD = dimension of the metric (grid and sorted copy); `stride` = doubles per input point
@@ -1553,7 +1553,7 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
       uint32_t* d_tot = reinterpret_cast<uint32_t*>(d_bounds + 8);
       unsigned long long unclassed = (unsigned long long)n;
       if (d_in_classed) {
-        hipLaunchKernelGGL(k_unclassed_flag, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n);
+        VCP_LAUNCH(ctx, k_unclassed_flag, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n);
         VCP_TRY(vcp_exclusive_scan_u32(ctx, f, f, n, d_tot));
         uint32_t* hu = reinterpret_cast<uint32_t*>(ctx->pinned) + 32;
         VCP_HIP(ctx, hipMemcpyAsync(hu, d_tot, 4, hipMemcpyDeviceToHost, st));
@@ -1562,9 +1562,8 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
       }
       const int core = n >= (int64_t)min_pts;
       const int have_seed = unclassed > 0;
-      hipLaunchKernelGGL(k_all_pairs, dim3(nb), dim3(TPB), 0, st, d_in_classed, n, core, have_seed, cf_in, d_labels,
-                         d_is_core, d_is_classed);
-      VCP_HIP(ctx, hipGetLastError());
+      VCP_LAUNCH(ctx, k_all_pairs, dim3(nb), dim3(TPB), 0, st, d_in_classed, n, core, have_seed, cf_in, d_labels,
+                      d_is_core, d_is_classed);
       VCP_TRY(vcp_phase_finish(ctx));
       VCP_HIP(ctx, hipStreamSynchronize(st));
       const int made = core && have_seed;
@@ -1774,62 +1773,61 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
   static const bool core_global = getenv("VCP_CORE_GLOBAL") != nullptr;  // test switch: grouped calls through k_core
   if constexpr (GD == 2) {
     if (!GROUPED || !core_global)
-      hipLaunchKernelGGL((k_core_lds<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 0, st, xs, g, thr, min_pts, ct, sgroup, flags,
-                         parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
+      VCP_LAUNCH(ctx, (k_core_lds<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 0, st, xs, g, thr, min_pts, ct, sgroup, flags,
+                      parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
     else
-      hipLaunchKernelGGL((k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, xs, g, thr, min_pts, ct,
-                         sgroup, flags, parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
+      VCP_LAUNCH(ctx, (k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, xs, g, thr, min_pts, ct,
+                      sgroup, flags, parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
   } else
-    hipLaunchKernelGGL((k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, xs, g, thr, min_pts, ct,
-                       sgroup, flags, parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
+    VCP_LAUNCH(ctx, (k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, xs, g, thr, min_pts, ct,
+                    sgroup, flags, parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
   // ONE scan over both count arrays (they are adjacent): the B half comes out offset by everything before it, which
   // its readers take off again (scan[0]); the two pad words between the halves are never written and cancel the same way
   VCP_TRY(vcp_exclusive_scan_u32(ctx, blkE, blkE, 2 * ((int64_t)nb + 2), nullptr));
-  hipLaunchKernelGGL(k_wl_fill, dim3(nb), dim3(TPB), 0, st, flags, ct, blkE, blkB, wlE.list, wlB.list,
-                     seedflag, nw, counters, GROUPED ? ext->d_group_twice : nullptr, (uint32_t)(GROUPED ? G : 0));
+  VCP_LAUNCH(ctx, k_wl_fill, dim3(nb), dim3(TPB), 0, st, flags, ct, blkE, blkB, wlE.list, wlB.list,
+                  seedflag, nw, counters, GROUPED ? ext->d_group_twice : nullptr, (uint32_t)(GROUPED ? G : 0));
 
   // 6. components of the expanding points
   vcp_phase(ctx, "union");
   // phases 1-2 pay for their extra search pass in 2-D (3 rows); in 3-D (9 rows) they do not (measured: +28 %)
   const bool pre = GD == 2 || no.NB > 0;  // with lists the forest costs no search, so it pays in 3-D too
   if (no.NB > 0) {
-    hipLaunchKernelGGL(k_union_init_list, dim3(nbl), dim3(TPB), 0, st, flags, parent, no, wlE);
+    VCP_LAUNCH(ctx, k_union_init_list, dim3(nbl), dim3(TPB), 0, st, flags, parent, no, wlE);
     static const int join_all = getenv("VCP_JOIN_ALL") ? atoi(getenv("VCP_JOIN_ALL")) : -1;  // test switch
     const bool all = join_all >= 0 ? join_all != 0 : (uint64_t)n >= (uint64_t)g.ncells;
-    if (all) hipLaunchKernelGGL(k_flatten0<2>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
-    else hipLaunchKernelGGL(k_flatten0<1>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
-    hipLaunchKernelGGL(k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
+    if (all) VCP_LAUNCH(ctx, k_flatten0<2>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
+    else VCP_LAUNCH(ctx, k_flatten0<1>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
+    VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
   } else if (GD == 2) {
-    hipLaunchKernelGGL((k_union_init<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                       flags, parent, wlE, sorted32, sc);
-    hipLaunchKernelGGL(k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
+    VCP_LAUNCH(ctx, (k_union_init<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
+                    flags, parent, wlE, sorted32, sc);
+    VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
   }
   const bool dense = pre && (uint64_t)n > (uint64_t)DENSE_PER_CELL * g.ncells;
   if (dense) {
     VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, ((size_t)nb * (TPB / 64) + 2) * 4));  // one word per wave of k_chunkroot
     uint32_t* chunkroot = ctx->b_aux0.as<uint32_t>();
-    hipLaunchKernelGGL(k_chunkroot, dim3(nb), dim3(TPB), 0, st, parent, ct, chunkroot);
-    hipLaunchKernelGGL((k_union<GD, METRIC, GROUPED, true, true>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                       parent, wlE, sorted32, sc, chunkroot);
+    VCP_LAUNCH(ctx, k_chunkroot, dim3(nb), dim3(TPB), 0, st, parent, ct, chunkroot);
+    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, true, true>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
+                    parent, wlE, sorted32, sc, chunkroot);
   } else if (pre)
-    hipLaunchKernelGGL((k_union<GD, METRIC, GROUPED, true>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                       parent, wlE, sorted32, sc);
+    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, true>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
+                    parent, wlE, sorted32, sc);
   else
-    hipLaunchKernelGGL((k_union<GD, METRIC, GROUPED, false>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                       parent, wlE, sorted32, sc);
+    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, false>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
+                    parent, wlE, sorted32, sc);
   vcp_phase(ctx, "flatten_number");
   if ((uint64_t)n >= (uint64_t)g.ncells)
-    hipLaunchKernelGGL(k_flatten<true>, dim3(nbl), dim3(TPB), 0, st, parent, sord, minord, wlE);
+    VCP_LAUNCH(ctx, k_flatten<true>, dim3(nbl), dim3(TPB), 0, st, parent, sord, minord, wlE);
   else
-    hipLaunchKernelGGL(k_flatten<false>, dim3(nbl), dim3(TPB), 0, st, parent, sord, minord, wlE);
+    VCP_LAUNCH(ctx, k_flatten<false>, dim3(nbl), dim3(TPB), 0, st, parent, sord, minord, wlE);
   if (!GROUPED && ext && ext->slab) {
     // staged call: hand the local components to the caller and keep the grid state for vcp_slab_finish
     vcp_phase(ctx, "slab_components");
-    hipLaunchKernelGGL(k_slab_count, dim3(nb), dim3(TPB), 0, st, parent, flags, ct, blkE);
+    VCP_LAUNCH(ctx, k_slab_count, dim3(nb), dim3(TPB), 0, st, parent, flags, ct, blkE);
     VCP_TRY(vcp_exclusive_scan_u32(ctx, blkE, blkE, (int64_t)nb + 1, nullptr));
-    hipLaunchKernelGGL(k_slab_fill, dim3(nb), dim3(TPB), 0, st, parent, flags, minord, ct, blkE, clseed);
-    hipLaunchKernelGGL(k_slab_out, dim3(nb), dim3(TPB), 0, st, n, pos, flags, parent, minord, ext->d_slab_rep, d_is_core);
-    VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_slab_fill, dim3(nb), dim3(TPB), 0, st, parent, flags, minord, ct, blkE, clseed);
+    VCP_LAUNCH(ctx, k_slab_out, dim3(nb), dim3(TPB), 0, st, n, pos, flags, parent, minord, ext->d_slab_rep, d_is_core);
     uint32_t* hn = reinterpret_cast<uint32_t*>(ctx->pinned) + 64;
     VCP_HIP(ctx, hipMemcpyAsync(hn, blkE + nb, 4, hipMemcpyDeviceToHost, st));
     VCP_TRY(vcp_phase_finish(ctx));
@@ -1849,21 +1847,21 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
     if (cf_out) *cf_out = (int32_t)hn[0];
     return VCP_OK;
   }
-  hipLaunchKernelGGL(k_seedflag, dim3(nbl), dim3(TPB), 0, st, parent, minord, seedflag, wlE);
-  hipLaunchKernelGGL(k_seed_popc, dim3(vcp_blocks(nw, TPB)), dim3(TPB), 0, st, seedflag, nw, seedpref);
+  VCP_LAUNCH(ctx, k_seedflag, dim3(nbl), dim3(TPB), 0, st, parent, minord, seedflag, wlE);
+  VCP_LAUNCH(ctx, k_seed_popc, dim3(vcp_blocks(nw, TPB)), dim3(TPB), 0, st, seedflag, nw, seedpref);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, seedpref, seedpref, nw, d_total));
-  hipLaunchKernelGGL(k_rootk, dim3(nbl), dim3(TPB), 0, st, parent, minord, seedflag, seedpref, rootk, clseed, wlE);
+  VCP_LAUNCH(ctx, k_rootk, dim3(nbl), dim3(TPB), 0, st, parent, minord, seedflag, seedpref, rootk, clseed, wlE);
 
   // 7. border rule, then outputs in caller order
   vcp_phase(ctx, "border");
-  hipLaunchKernelGGL(k_labk_rest, dim3(nb), dim3(TPB), 0, st, flags, parent, rootk, labk, ct);
+  VCP_LAUNCH(ctx, k_labk_rest, dim3(nb), dim3(TPB), 0, st, flags, parent, rootk, labk, ct);
   if (no.NB > 0)
-    hipLaunchKernelGGL(k_border_list<GROUPED>, dim3(nbl), dim3(TPB), 0, st, sgroup, flags, sord, rootk, clseed, labk, counters,
-                       GROUPED ? ext->d_group_twice : nullptr, no, wlB);
+    VCP_LAUNCH(ctx, k_border_list<GROUPED>, dim3(nbl), dim3(TPB), 0, st, sgroup, flags, sord, rootk, clseed, labk, counters,
+                    GROUPED ? ext->d_group_twice : nullptr, no, wlB);
   else
-    hipLaunchKernelGGL((k_border<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup, flags,
-                       parent, sord, rootk, clseed, labk, counters, GROUPED ? ext->d_group_twice : nullptr, wlB, 0u, NONE,
-                       sorted32, sc);
+    VCP_LAUNCH(ctx, (k_border<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup, flags,
+                    parent, sord, rootk, clseed, labk, counters, GROUPED ? ext->d_group_twice : nullptr, wlB, 0u, NONE,
+                    sorted32, sc);
   if (part_out) {
     GridOutputArgs oa;
     oa.n = n;
@@ -1878,20 +1876,19 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
     VCP_TRY(vcp_grid_output_partition(ctx, oa));
   } else {
     vcp_phase(ctx, "output");
-    hipLaunchKernelGGL((k_output<GROUPED>), dim3(nb), dim3(TPB), 0, st, n, pos, labk, d_in_classed, d_group,
-                       GROUPED ? ext->d_groupstart : nullptr, seedflag, seedpref, cf_in, d_labels, d_is_core, d_is_classed,
-                       counters);
+    VCP_LAUNCH(ctx, (k_output<GROUPED>), dim3(nb), dim3(TPB), 0, st, n, pos, labk, d_in_classed, d_group,
+                    GROUPED ? ext->d_groupstart : nullptr, seedflag, seedpref, cf_in, d_labels, d_is_core, d_is_classed,
+                    counters);
   }
   if (!GROUPED && min_pts <= 0 && !all_finite)
-    hipLaunchKernelGGL(k_lonely_seeds<GD>, dim3(nb), dim3(TPB), 0, st, d_coords, n, stride, d_in_classed, d_is_classed,
-                       counters);
+    VCP_LAUNCH(ctx, k_lonely_seeds<GD>, dim3(nb), dim3(TPB), 0, st, d_coords, n, stride, d_in_classed, d_is_classed,
+                    counters);
   if (GROUPED) {
-    hipLaunchKernelGGL(k_group_stats, dim3(vcp_blocks(G, TPB)), dim3(TPB), 0, st, G, glo, ghi, ext->d_groupstart,
-                       seedflag, seedpref, ext->d_group_twice, ext->d_group_nclus, counters + 3, ext->skip_upto);
+    VCP_LAUNCH(ctx, k_group_stats, dim3(vcp_blocks(G, TPB)), dim3(TPB), 0, st, G, glo, ghi, ext->d_groupstart,
+                    seedflag, seedpref, ext->d_group_twice, ext->d_group_nclus, counters + 3, ext->skip_upto);
     if (ext->d_group_evals)
       VCP_HIP(ctx, hipMemcpyAsync(ext->d_group_evals, counters + 3, 8, hipMemcpyDeviceToDevice, st));
   }
-  VCP_HIP(ctx, hipGetLastError());
   unsigned long long* hc = reinterpret_cast<unsigned long long*>(ctx->pinned) + 8;
   VCP_HIP(ctx, hipMemcpyAsync(hc, counters, 68 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));
@@ -1940,16 +1937,15 @@ int run_slab_finish(vcp_ctx* ctx, const SlabState& ss, const uint32_t* d_map_rep
   unsigned long long* counters = reinterpret_cast<unsigned long long*>(ctx->b_misc.as<double>() + (size_t)rb * 8 + 8);
   vcp_phase(ctx, "slab_roots");
   VCP_HIP(ctx, hipMemsetAsync(counters, 0, 68 * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_slab_rootk, dim3(nb), dim3(TPB), 0, st, parent, flags, minord, ct, d_map_rep, d_map_k,
-                     (uint32_t)ss.n_comp, rootk, counters);
+  VCP_LAUNCH(ctx, k_slab_rootk, dim3(nb), dim3(TPB), 0, st, parent, flags, minord, ct, d_map_rep, d_map_k,
+                  (uint32_t)ss.n_comp, rootk, counters);
   vcp_phase(ctx, "border");
-  hipLaunchKernelGGL(k_labk_rest, dim3(nb), dim3(TPB), 0, st, flags, parent, rootk, labk, ct);
-  hipLaunchKernelGGL((k_border<GD, METRIC, false>), dim3(nbl), dim3(TPB), 0, st, ss.xs, g, ss.thr,
-                     ct, nullptr, flags, parent, sord, rootk, clseed, labk, counters, nullptr, wlB, own_lo, own_span,
-                     ctx->b_sorted32.as<float>(), ss.sc);
+  VCP_LAUNCH(ctx, k_labk_rest, dim3(nb), dim3(TPB), 0, st, flags, parent, rootk, labk, ct);
+  VCP_LAUNCH(ctx, (k_border<GD, METRIC, false>), dim3(nbl), dim3(TPB), 0, st, ss.xs, g, ss.thr,
+                  ct, nullptr, flags, parent, sord, rootk, clseed, labk, counters, nullptr, wlB, own_lo, own_span,
+                  ctx->b_sorted32.as<float>(), ss.sc);
   vcp_phase(ctx, "output");
-  hipLaunchKernelGGL(k_slab_output, dim3(nb), dim3(TPB), 0, st, n, pos, labk, d_tab_gid, d_labels, d_is_classed);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_slab_output, dim3(nb), dim3(TPB), 0, st, n, pos, labk, d_tab_gid, d_labels, d_is_classed);
   unsigned long long* hc = reinterpret_cast<unsigned long long*>(ctx->pinned) + 8;
   VCP_HIP(ctx, hipMemcpyAsync(hc, counters, 68 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));
@@ -1973,12 +1969,11 @@ int run_degenerate(vcp_ctx* ctx, int64_t n, int min_pts, int32_t cf_in, const ui
   VCP_TRY(vcp_ensure(ctx, ctx->b_misc, 64));
   uint32_t* f = ctx->b_seedflag.as<uint32_t>();
   uint32_t* d_total = ctx->b_misc.as<uint32_t>();
-  hipLaunchKernelGGL(k_unclassed_flag, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n);
+  VCP_LAUNCH(ctx, k_unclassed_flag, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, f, f, n, d_total));
   const int all_core = 0 >= min_pts;  // tmpList.Count (0) >= minPts, BaseClass/DBImproved.cs:105
-  hipLaunchKernelGGL(k_degenerate, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n, cf_in, all_core,
-                     d_in_classed == nullptr, d_labels, d_is_core, d_is_classed);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_degenerate, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n, cf_in, all_core,
+                  d_in_classed == nullptr, d_labels, d_is_core, d_is_classed);
   uint32_t* hu = reinterpret_cast<uint32_t*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(hu, d_total, 4, hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));

@@ -797,20 +797,20 @@ int build(vcp_ctx* ctx, const GridBuildArgs& a) {
   uint2* queue = reinterpret_cast<uint2*>(ctx->b_fineq.as<char>() + 64);
   vcp_phase(ctx, "part_hist");
   const uint32_t csh_a = pg.csh + pg.a;  // the coarse passes split by super-bucket
-  hipLaunchKernelGGL((k_part_hist<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_h, st, a.d_coords, a.n, a.stride, a.g,
-                     a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, qcount, a.ctcount);
+  VCP_LAUNCH(ctx, (k_part_hist<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_h, st, a.d_coords, a.n, a.stride, a.g,
+                  a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, qcount, a.ctcount);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, counts, counts, (int64_t)nc, total));
   vcp_phase(ctx, "part_scatter");
-  hipLaunchKernelGGL((k_part_scatter<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_h, st, a.d_coords, a.n, a.stride, a.g,
-                     a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, rec, a.pos);
+  VCP_LAUNCH(ctx, (k_part_scatter<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_h, st, a.d_coords, a.n, a.stride, a.g,
+                  a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, rec, a.pos);
   const uint32_t* bstart = counts;
   uint32_t bstride = pg.nchunk;
   if (pg.a > 0) {
     vcp_phase(ctx, "part_split");
     VCP_TRY(vcp_ensure(ctx, ctx->b_rec2, (size_t)a.n * sizeof(Rec)));
     VCP_TRY(vcp_ensure(ctx, ctx->b_bstart, ((size_t)pg.B + 2) * 4));
-    hipLaunchKernelGGL(k_part_split<GD>, dim3(pg.NS), dim3(FT), 0, st, rec, ctx->b_rec2.as<Rec>(), counts, total, pg.nchunk,
-                       pg.NS, pg.a, pg.csh, pg.B, a.g, ctx->b_bstart.as<uint32_t>());
+    VCP_LAUNCH(ctx, k_part_split<GD>, dim3(pg.NS), dim3(FT), 0, st, rec, ctx->b_rec2.as<Rec>(), counts, total, pg.nchunk,
+                    pg.NS, pg.a, pg.csh, pg.B, a.g, ctx->b_bstart.as<uint32_t>());
     rec = ctx->b_rec2.as<Rec>();
     bstart = ctx->b_bstart.as<uint32_t>();
     bstride = 1;
@@ -819,22 +819,21 @@ int build(vcp_ctx* ctx, const GridBuildArgs& a) {
   VCP_TRY(vcp_ensure(ctx, ctx->b_rank, (size_t)a.n * 4));  // ranks inside the cell, written for large buckets only
   VCP_TRY(vcp_ensure(ctx, ctx->b_bstate, (size_t)pg.B + 16));
   uint8_t* bstate = ctx->b_bstate.as<uint8_t>();
-  hipLaunchKernelGGL((k_part_fine_small<GD, GROUPED>), dim3(pg.B), dim3(FS), 0, st, rec, bstart, bstride, total, pg.B, pg.csh,
-                     a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount, bstate, a.sorted32, a.sord,
-                     a.sidx, a.sgroup, a.flags, a.pos);
-  hipLaunchKernelGGL((k_part_fine<GD, GROUPED>), dim3(pg.B), dim3(FT), lds_f, st, rec, ctx->b_rank.as<uint32_t>(), bstart,
-                     bstride, total, pg.B, pg.csh, a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount,
-                     a.sorted32, a.sord, a.sidx, a.sgroup, a.flags, a.pos, queue, qcount, bstate);
+  VCP_LAUNCH(ctx, (k_part_fine_small<GD, GROUPED>), dim3(pg.B), dim3(FS), 0, st, rec, bstart, bstride, total, pg.B, pg.csh,
+                  a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount, bstate, a.sorted32, a.sord,
+                  a.sidx, a.sgroup, a.flags, a.pos);
+  VCP_LAUNCH(ctx, (k_part_fine<GD, GROUPED>), dim3(pg.B), dim3(FT), lds_f, st, rec, ctx->b_rank.as<uint32_t>(), bstart,
+                  bstride, total, pg.B, pg.csh, a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount,
+                  a.sorted32, a.sord, a.sidx, a.sgroup, a.flags, a.pos, queue, qcount, bstate);
   {
     const size_t lds_w = (size_t)wcap(GD) * ((GD == 2 ? 8 : 16) + 4);
     VCP_TRY(allow_lds(ctx, k_part_fine_windows<GD, GROUPED>, lds_w));
     const unsigned gw = (unsigned)std::min<size_t>(768, (size_t)a.n / wcap(GD) + 1);  // 3 workgroups per CU (48 KB LDS each in 2-D)
     const CellTab ct{a.ctwords, a.ctdense, a.ctcount + 1};
-    hipLaunchKernelGGL((k_part_fine_windows<GD, GROUPED>), dim3(gw), dim3(FT), lds_w, st, rec, ctx->b_rank.as<uint32_t>(),
-                       bstart, bstride, total, pg.B, a.g, a.d_ord, a.d_in_classed, a.d_group, ct, a.sorted32,
-                       a.sord, a.sidx, a.sgroup, a.flags, a.pos, queue, qcount);
+    VCP_LAUNCH(ctx, (k_part_fine_windows<GD, GROUPED>), dim3(gw), dim3(FT), lds_w, st, rec, ctx->b_rank.as<uint32_t>(),
+                    bstart, bstride, total, pg.B, a.g, a.d_ord, a.d_in_classed, a.d_group, ct, a.sorted32,
+                    a.sord, a.sidx, a.sgroup, a.flags, a.pos, queue, qcount);
   }
-  VCP_HIP(ctx, hipGetLastError());
   return VCP_OK;
 }
 
@@ -865,12 +864,11 @@ static int output_partition(vcp_ctx* ctx, const GridOutputArgs& a) {
   // every fallible host step comes BEFORE the scatter: between the two kernels the window cursors are not zero
   VCP_TRY(allow_lds(ctx, k_out_write<OWSH>, (size_t)4 << OWSH));
   vcp_phase(ctx, "out_scatter");
-  hipLaunchKernelGGL(k_out_scatter<OWSH>, dim3(vcp_blocks(a.n, OT * OPT)), dim3(OT), (size_t)OB * 4, st, a.sord, a.labk, a.n,
-                     OB, gcur, rec);
+  VCP_LAUNCH(ctx, k_out_scatter<OWSH>, dim3(vcp_blocks(a.n, OT * OPT)), dim3(OT), (size_t)OB * 4, st, a.sord, a.labk, a.n,
+                  OB, gcur, rec);
   vcp_phase(ctx, "out_write");
-  hipLaunchKernelGGL(k_out_write<OWSH>, dim3(OB), dim3(OWT), (size_t)4 << OWSH, st, rec, a.n, a.have_in_classed, a.cf_in,
-                     a.labels, a.is_core, a.is_classed, a.counters, gcur);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_out_write<OWSH>, dim3(OB), dim3(OWT), (size_t)4 << OWSH, st, rec, a.n, a.have_in_classed, a.cf_in,
+                  a.labels, a.is_core, a.is_classed, a.counters, gcur);
   return VCP_OK;
 }
 

@@ -48,13 +48,13 @@ int vcp_group_by_label(vcp_ctx* ctx, const int32_t* d_labels, const int64_t* d_o
   uint32_t* vals_in = vals.as<uint32_t>();
   uint32_t* vals_out = vals_in + (m + 1);
   if (m > 0) {
-    hipLaunchKernelGGL(k_label_keys, dim3(vcp_blocks(m, GT)), dim3(GT), 0, st, d_labels, d_order, m, K, keys_in, vals_in,
-                       bad);
+    VCP_LAUNCH(ctx, k_label_keys, dim3(vcp_blocks(m, GT)), dim3(GT), 0, st, d_labels, d_order, m, K, keys_in, vals_in,
+                    bad);
     VCP_TRY(vcp_sort_pairs(ctx, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)m, vcp_bits_for((uint64_t)K)));
-    hipLaunchKernelGGL(k_label_marks, dim3(vcp_blocks(m, GT)), dim3(GT), 0, st, keys_out, m, segstart);
+    VCP_LAUNCH(ctx, k_label_marks, dim3(vcp_blocks(m, GT)), dim3(GT), 0, st, keys_out, m, segstart);
   }
   VCP_TRY(vcp_exclusive_max_scan_u32(ctx, segstart, segstart, (int64_t)K + 2, nullptr));  // segstart[K + 1] = m
-  hipLaunchKernelGGL(k_label_counts, dim3(vcp_blocks((int64_t)K + 1, GT)), dim3(GT), 0, st, segstart, K, counts);
+  VCP_LAUNCH(ctx, k_label_counts, dim3(vcp_blocks((int64_t)K + 1, GT)), dim3(GT), 0, st, segstart, K, counts);
   *sorted = vals_out;
   return VCP_OK;
 }

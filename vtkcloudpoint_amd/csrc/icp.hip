@@ -709,30 +709,29 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   *h_st = init;
   VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, sizeof(IcpState), hipMemcpyHostToDevice, st));
   if (!grid) {  // the binary32 screening frame and copy serve the full scans only
-    hipLaunchKernelGGL(k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st);
-    hipLaunchKernelGGL(k_model32, dim3(vcp_blocks(nm, ITPB)), dim3(ITPB), 0, st, d_model, nm, d_st, model32);
+    VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st);
+    VCP_LAUNCH(ctx, k_model32, dim3(vcp_blocks(nm, ITPB)), dim3(ITPB), 0, st, d_model, nm, d_st, model32);
   }
   int launched = 0;
   for (;;) {
     const int batch = mode == MODE_SUMS_ONLY ? 1 : std::min(ICP_BATCH, max_iter - launched);
     for (int b = 0; b < batch; b++) {
 #define VCP_PASS(TBV, TL) \
-  hipLaunchKernelGGL((k_icp_pass<TBV, TL>), dim3(nb), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part, d_nn, ng)
+  VCP_LAUNCH(ctx, (k_icp_pass<TBV, TL>), dim3(nb), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part, d_nn, ng)
       if (small && grid) VCP_PASS(64, 2);
       else if (grid) VCP_PASS(ITPB, 2);
       else if (small && tiled) VCP_PASS(64, 1);
       else if (tiled) VCP_PASS(ITPB, 1);
       else if (small)
-        hipLaunchKernelGGL(k_icp_pass_small<64>, dim3(nb), dim3(64), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part,
-                           d_nn, imask, tolk);
+        VCP_LAUNCH(ctx, k_icp_pass_small<64>, dim3(nb), dim3(64), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part,
+                        d_nn, imask, tolk);
       else
-        hipLaunchKernelGGL(k_icp_pass_small<ITPB>, dim3(nb), dim3(ITPB), 0, st, d_model, model32, (int)nm, d_data, nd, d_st,
-                           part, d_nn, imask, tolk);
+        VCP_LAUNCH(ctx, k_icp_pass_small<ITPB>, dim3(nb), dim3(ITPB), 0, st, d_model, model32, (int)nm, d_data, nd, d_st,
+                        part, d_nn, imask, tolk);
 #undef VCP_PASS
-      hipLaunchKernelGGL(k_icp_step, dim3(1), dim3(ITPB), 0, st, part, nb, d_st, sa);
+      VCP_LAUNCH(ctx, k_icp_step, dim3(1), dim3(ITPB), 0, st, part, nb, d_st, sa);
     }
     launched += batch;
-    VCP_HIP(ctx, hipGetLastError());
     VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, sizeof(IcpState), hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (h_st->done || launched >= max_iter || mode == MODE_SUMS_ONLY) break;

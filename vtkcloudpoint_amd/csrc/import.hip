@@ -163,19 +163,18 @@ extern "C" int vcp_import_convert(vcp_ctx* ctx, const double* rows, int64_t n, d
   ImpP P{x_angle, y_angle, xdir, ydir};
   double* q = dedupe ? ctx->b_aux4.as<double>() : nullptr;
   const unsigned nb = vcp_blocks(n, IT);
-  hipLaunchKernelGGL(k_import_convert, dim3(nb), dim3(IT), 0, st, ctx->b_in0.as<double>(), n, P, ctx->b_out0.as<double>(),
-                     q, ctx->b_out1.as<uint8_t>());
+  VCP_LAUNCH(ctx, k_import_convert, dim3(nb), dim3(IT), 0, st, ctx->b_in0.as<double>(), n, P, ctx->b_out0.as<double>(),
+                  q, ctx->b_out1.as<uint8_t>());
   unsigned long long* counters = ctx->b_out2.as<unsigned long long>();
   VCP_HIP(ctx, hipMemsetAsync(counters, 0, 64 * 8, st));
   if (dedupe) {
     uint32_t* table = ctx->b_aux1.as<uint32_t>();
     VCP_HIP(ctx, hipMemsetAsync(table, 0xFF, (size_t)cap * 4, st));
-    hipLaunchKernelGGL(k_import_insert, dim3(nb), dim3(IT), 0, st, q, ctx->b_out1.as<uint8_t>(), n, table,
-                       (uint32_t)(cap - 1));
-    hipLaunchKernelGGL(k_import_mark, dim3(nb), dim3(IT), 0, st, q, ctx->b_out1.as<uint8_t>(), n, table,
-                       (uint32_t)(cap - 1), counters);
+    VCP_LAUNCH(ctx, k_import_insert, dim3(nb), dim3(IT), 0, st, q, ctx->b_out1.as<uint8_t>(), n, table,
+                    (uint32_t)(cap - 1));
+    VCP_LAUNCH(ctx, k_import_mark, dim3(nb), dim3(IT), 0, st, q, ctx->b_out1.as<uint8_t>(), n, table,
+                    (uint32_t)(cap - 1), counters);
   }
-  VCP_HIP(ctx, hipGetLastError());
   unsigned long long* hp = reinterpret_cast<unsigned long long*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(xyz, ctx->b_out0.p, (size_t)n * 24, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipMemcpyAsync(state, ctx->b_out1.p, (size_t)n, hipMemcpyDeviceToHost, st));

@@ -438,18 +438,19 @@ __global__ __launch_bounds__(64) void k_kd_heavy(KArgs a) {
   }
 }
 template <int GD, int METRIC, int K>
-void launch_search(vcp_ctx* ctx, const KArgs& a) {
-  hipLaunchKernelGGL((k_kd_search<GD, METRIC, K>), dim3(vcp_blocks(a.nf, KT)), dim3(KT), 0, ctx->stream, a);
+int launch_search(vcp_ctx* ctx, const KArgs& a) {
+  VCP_LAUNCH(ctx, (k_kd_search<GD, METRIC, K>), dim3(vcp_blocks(a.nf, KT)), dim3(KT), 0, ctx->stream, a);
   vcp_phase(ctx, "kdist_heavy");
-  hipLaunchKernelGGL((k_kd_heavy<GD, METRIC, K>), dim3(8192), dim3(64), 0, ctx->stream, a);  // persistent over the list
+  VCP_LAUNCH(ctx, (k_kd_heavy<GD, METRIC, K>), dim3(8192), dim3(64), 0, ctx->stream, a);  // persistent over the list
+  return VCP_OK;
 }
 
 template <int GD, int METRIC>
-void launch_k(vcp_ctx* ctx, const KArgs& a) {
-  if (a.k <= 8) launch_search<GD, METRIC, 8>(ctx, a);
-  else if (a.k <= 16) launch_search<GD, METRIC, 16>(ctx, a);
-  else if (a.k <= 32) launch_search<GD, METRIC, 32>(ctx, a);
-  else launch_search<GD, METRIC, 64>(ctx, a);
+int launch_k(vcp_ctx* ctx, const KArgs& a) {
+  if (a.k <= 8) return launch_search<GD, METRIC, 8>(ctx, a);
+  if (a.k <= 16) return launch_search<GD, METRIC, 16>(ctx, a);
+  if (a.k <= 32) return launch_search<GD, METRIC, 32>(ctx, a);
+  return launch_search<GD, METRIC, 64>(ctx, a);
 }
 
 template <int GD>
@@ -513,13 +514,13 @@ int run_kdist(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, int m
   uint32_t* heavy_cnt = start + cells;
   a.heavy = ctx->b_kd_heavy.as<uint32_t>();
   a.heavy_cnt = heavy_cnt;
-  hipLaunchKernelGGL((k_kd_keys<GD>), dim3(nb), dim3(KT), 0, st, d_coords, n, stride, a, kin, vin);
+  VCP_LAUNCH(ctx, (k_kd_keys<GD>), dim3(nb), dim3(KT), 0, st, d_coords, n, stride, a, kin, vin);
   VCP_TRY(vcp_sort_pairs(ctx, ctx->b_kd_tmp, kin, kout, vin, vout, (size_t)n, KEYBITS + 1));
   double4* rec = ctx->b_kd_rec.as<double4>();
-  hipLaunchKernelGGL((k_kd_gather<GD>), dim3(nb), dim3(KT), 0, st, d_coords, n, stride, vout, a, rec);
+  VCP_LAUNCH(ctx, (k_kd_gather<GD>), dim3(nb), dim3(KT), 0, st, d_coords, n, stride, vout, a, rec);
   VCP_HIP(ctx, hipMemsetAsync(start, 0, cells * 4 + 4, st));  // the marks and the heavy counter
   if (nf > 0) {
-    hipLaunchKernelGGL((k_kd_marks<GD>), dim3(vcp_blocks(nf, KT)), dim3(KT), 0, st, kout, nf, G, start);
+    VCP_LAUNCH(ctx, (k_kd_marks<GD>), dim3(vcp_blocks(nf, KT)), dim3(KT), 0, st, kout, nf, G, start);
     VCP_TRY(vcp_exclusive_max_scan_u32(ctx, start, start, (int64_t)cells, nullptr));
   }
   a.rec = rec;
@@ -530,13 +531,12 @@ int run_kdist(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, int m
   if (nf > 0) {
     vcp_phase(ctx, "kdist_search");
     if constexpr (GD == 2) {
-      if (metric == VCP_L1_2D) launch_k<2, VCP_L1_2D>(ctx, a);
-      else launch_k<2, VCP_L2_2D>(ctx, a);
+      if (metric == VCP_L1_2D) VCP_TRY((launch_k<2, VCP_L1_2D>(ctx, a)));
+      else VCP_TRY((launch_k<2, VCP_L2_2D>(ctx, a)));
     } else {
-      launch_k<3, VCP_L2_3D>(ctx, a);
+      VCP_TRY((launch_k<3, VCP_L2_3D>(ctx, a)));
     }
   }
-  VCP_HIP(ctx, hipGetLastError());
   VCP_TRY(vcp_phase_finish(ctx));
   VCP_HIP(ctx, hipStreamSynchronize(st));
   return VCP_OK;

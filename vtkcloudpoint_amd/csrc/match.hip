@@ -249,16 +249,15 @@ extern "C" int vcp_assign_truths(vcp_ctx* ctx, const double* motor, int64_t n, c
     VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in2.p, h_sxy.data(), h_sxy.size() * 8, hipMemcpyHostToDevice, st));
     VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in3.p, h_sid.data(), h_sid.size() * 4, hipMemcpyHostToDevice, st));
     VCP_HIP(ctx, hipMemcpyAsync(ctx->b_aux1.p, h_sorig.data(), h_sorig.size() * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_assign_truths_grid, dim3(vcp_blocks(n, 256)), dim3(256), 0, st, ctx->b_in0.as<double>(), n, tg,
-                       ctx->b_aux0.as<uint32_t>(), ctx->b_in2.as<double>(), ctx->b_in3.as<int32_t>(),
-                       ctx->b_aux1.as<int32_t>(), radius, ctx->b_out0.as<int32_t>(), ctx->b_out2.as<unsigned long long>());
+    VCP_LAUNCH(ctx, k_assign_truths_grid, dim3(vcp_blocks(n, 256)), dim3(256), 0, st, ctx->b_in0.as<double>(), n, tg,
+                    ctx->b_aux0.as<uint32_t>(), ctx->b_in2.as<double>(), ctx->b_in3.as<int32_t>(),
+                    ctx->b_aux1.as<int32_t>(), radius, ctx->b_out0.as<int32_t>(), ctx->b_out2.as<unsigned long long>());
     VCP_HIP(ctx, hipStreamSynchronize(st));  // the host vectors above are the source of the async copies
   } else {
-    hipLaunchKernelGGL(k_assign_truths, dim3(vcp_blocks(n, 256)), dim3(256), 0, st, ctx->b_in0.as<double>(), n,
-                       ctx->b_in2.as<double>(), ctx->b_in3.as<int32_t>(), T, radius, ctx->b_out0.as<int32_t>(),
-                       ctx->b_out2.as<unsigned long long>());
+    VCP_LAUNCH(ctx, k_assign_truths, dim3(vcp_blocks(n, 256)), dim3(256), 0, st, ctx->b_in0.as<double>(), n,
+                    ctx->b_in2.as<double>(), ctx->b_in3.as<int32_t>(), T, radius, ctx->b_out0.as<int32_t>(),
+                    ctx->b_out2.as<unsigned long long>());
   }
-  VCP_HIP(ctx, hipGetLastError());
   unsigned long long* hp = reinterpret_cast<unsigned long long*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(ids, ctx->b_out0.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipMemcpyAsync(hp, ctx->b_out2.p, 32 * 8, hipMemcpyDeviceToHost, st));
@@ -321,12 +320,11 @@ extern "C" int vcp_match(vcp_ctx* ctx, const double* centers, int32_t K, const d
   int32_t* o_n = reinterpret_cast<int32_t*>(dout + o_near);
   double* o_d = reinterpret_cast<double*>(dout + o_dist);
   if (grid)
-    hipLaunchKernelGGL(k_match<true>, dim3(vcp_blocks((int64_t)K * nng::NNG, MT)), dim3(MT), 0, st, d_cen, K, d_tru, T, m,
-                       max_dist, o_x, o_f, o_n, o_d, cnt, ng);
+    VCP_LAUNCH(ctx, k_match<true>, dim3(vcp_blocks((int64_t)K * nng::NNG, MT)), dim3(MT), 0, st, d_cen, K, d_tru, T, m,
+                    max_dist, o_x, o_f, o_n, o_d, cnt, ng);
   else
-    hipLaunchKernelGGL(k_match<false>, dim3(vcp_blocks(K, MT)), dim3(MT), 0, st, d_cen, K, d_tru, T, m, max_dist, o_x,
-                       o_f, o_n, o_d, cnt, ng);
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_match<false>, dim3(vcp_blocks(K, MT)), dim3(MT), 0, st, d_cen, K, d_tru, T, m, max_dist, o_x,
+                    o_f, o_n, o_d, cnt, ng);
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
   if (stage) {
     VCP_HIP(ctx, hipMemcpyAsync(stage, dout, out_bytes, hipMemcpyDeviceToHost, st));

@@ -309,11 +309,10 @@ extern "C" int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, co
   VCP_TRY(vcp_group_by_label(ctx, ctx->b_in3.as<int32_t>(), order ? ctx->b_in2.as<int64_t>() : nullptr, m, K, ctx->b_aux1,
                              ctx->b_aux2, ctx->b_aux3, segstart, counts, bad, &sorted));
   if (m > 0)
-    hipLaunchKernelGGL(k_mcc_gather, dim3(vcp_blocks(m, MT)), dim3(MT), 0, st, ctx->b_in0.as<double>(), sorted, m,
-                       ctx->b_aux4.as<double>());
-  hipLaunchKernelGGL(k_mcc, dim3(K), dim3(MT), 0, st, ctx->b_aux4.as<double>(), segstart, counts, ctx->b_aux5.as<uint8_t>(),
-                     ctx->b_out0.as<double>(), ctx->b_out2.as<double>(), ctx->b_out1.as<uint8_t>(), ctx->b_out3.as<int32_t>());
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, k_mcc_gather, dim3(vcp_blocks(m, MT)), dim3(MT), 0, st, ctx->b_in0.as<double>(), sorted, m,
+                    ctx->b_aux4.as<double>());
+  VCP_LAUNCH(ctx, k_mcc, dim3(K), dim3(MT), 0, st, ctx->b_aux4.as<double>(), segstart, counts, ctx->b_aux5.as<uint8_t>(),
+                  ctx->b_out0.as<double>(), ctx->b_out2.as<double>(), ctx->b_out1.as<uint8_t>(), ctx->b_out3.as<int32_t>());
   uint32_t* hp = reinterpret_cast<uint32_t*>(ctx->pinned);
   VCP_HIP(ctx, hipMemcpyAsync(hp, bad, 4, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipMemcpyAsync(centers, ctx->b_out0.p, kk * 16, hipMemcpyDeviceToHost, st));

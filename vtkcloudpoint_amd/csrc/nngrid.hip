@@ -90,11 +90,10 @@ int vcp_nngrid_build(vcp_ctx* ctx, const double* d_pts, int64_t n, NNGrid* out) 
   uint32_t* cid = ctx->b_nn_cid.as<uint32_t>();
   double4* rec = ctx->b_nn_rec.as<double4>();
   VCP_HIP(ctx, hipMemsetAsync(cells, 0, (size_t)(ncells + 2) * 4, st));
-  hipLaunchKernelGGL(k_nn_count, dim3(vcp_blocks(n, NT)), dim3(NT), 0, st, d_pts, n, g, cid, cells);
+  VCP_LAUNCH(ctx, k_nn_count, dim3(vcp_blocks(n, NT)), dim3(NT), 0, st, d_pts, n, g, cid, cells);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, cells, cells, ncells + 1, nullptr));
   VCP_HIP(ctx, hipMemcpyAsync(cur, cells, (size_t)(ncells + 1) * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(k_nn_scatter, dim3(vcp_blocks(n, NT)), dim3(NT), 0, st, d_pts, n, cid, cur, rec);
-  VCP_HIP(ctx, hipGetLastError());
+  VCP_LAUNCH(ctx, k_nn_scatter, dim3(vcp_blocks(n, NT)), dim3(NT), 0, st, d_pts, n, cid, cur, rec);
   g.cellstart = cells;
   g.rec = rec;
   *out = g;

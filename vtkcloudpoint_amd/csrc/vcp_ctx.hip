@@ -243,12 +243,11 @@ static int scan_u32(vcp_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, int64_t
   unsigned long long* desc = reinterpret_cast<unsigned long long*>(ctx->b_scan_tmp.as<char>() + 64);
   const bool vec = (((uintptr_t)d_in | (uintptr_t)d_out) & 15u) == 0;
   if (vec)
-    hipLaunchKernelGGL((k_scan<true, MX>), dim3((unsigned)nt), dim3(ST), 0, st, d_in, d_out, n, (uint32_t)nt, ctx->scan_gen,
-                       ticket, desc, d_total);
+    VCP_LAUNCH(ctx, (k_scan<true, MX>), dim3((unsigned)nt), dim3(ST), 0, st, d_in, d_out, n, (uint32_t)nt, ctx->scan_gen,
+                    ticket, desc, d_total);
   else
-    hipLaunchKernelGGL((k_scan<false, MX>), dim3((unsigned)nt), dim3(ST), 0, st, d_in, d_out, n, (uint32_t)nt, ctx->scan_gen,
-                       ticket, desc, d_total);
-  VCP_HIP(ctx, hipGetLastError());
+    VCP_LAUNCH(ctx, (k_scan<false, MX>), dim3((unsigned)nt), dim3(ST), 0, st, d_in, d_out, n, (uint32_t)nt, ctx->scan_gen,
+                    ticket, desc, d_total);
   return VCP_OK;
 }
 

@@ -90,12 +90,42 @@ void vcp_phase_reset(vcp_ctx* ctx);
 void vcp_phase(vcp_ctx* ctx, const char* name);  // marks the start of a phase
 int vcp_phase_finish(vcp_ctx* ctx);              // closes the last phase, syncs, fills last_timing
 
-static inline unsigned vcp_blocks(int64_t n, int per_block, int cap = 1 << 30) {
+constexpr unsigned vcp_blocks(int64_t n, int per_block, int cap = 1 << 30) {
   int64_t b = (n + per_block - 1) / per_block;
   if (b < 1) b = 1;
   if (b > cap) b = cap;
   return (unsigned)b;
 }
+
+// Whether the runtime can represent a dispatch of `grid` workgroups of `block` threads with `lds` bytes of dynamic LDS.
+// It does not refuse more than 2^32 - 1 work-items on an axis: it wraps the count and dispatches fewer workgroups.  The
+// LDS limit is gfx950's 160 KB (beyond 64 KB a kernel has to be allowed through hipFuncSetAttribute).
+constexpr bool vcp_launch_ok(dim3 grid, dim3 block, size_t lds) {
+  return grid.x >= 1 && grid.y >= 1 && grid.z >= 1 && block.x >= 1 && block.y >= 1 && block.z >= 1 &&
+         (uint64_t)grid.x * block.x <= 0xFFFFFFFFu && (uint64_t)grid.y * block.y <= 0xFFFFFFFFu &&
+         (uint64_t)grid.z * block.z <= 0xFFFFFFFFu && block.x <= 1024 && block.y <= 1024 && block.z <= 1024 &&
+         (uint64_t)block.x * block.y * block.z <= 1024 && lds <= 160 * 1024;
+}
+static_assert(vcp_launch_ok(dim3((1u << 24) - 1), dim3(256), 0) && !vcp_launch_ok(dim3(1u << 24), dim3(256), 0));
+static_assert(vcp_launch_ok(dim3(1), dim3(1024), 0) && !vcp_launch_ok(dim3(1), dim3(1025), 0));
+static_assert(vcp_launch_ok(dim3(1), dim3(64), 163840) && !vcp_launch_ok(dim3(1), dim3(64), 163841));
+static_assert(!vcp_launch_ok(dim3(0), dim3(64), 0) && !vcp_launch_ok(dim3(1, 1, 0), dim3(64), 0) &&
+                  !vcp_launch_ok(dim3(1), dim3(64, 0), 0));
+
+// Launches `kernel` (grid, block, dynamic LDS bytes, stream, arguments) in a function that returns a vcp status: a
+// dispatch that vcp_launch_ok refuses is VCP_ERR_TOO_LARGE before anything is enqueued, a launch error VCP_ERR_HIP, both
+// naming the kernel.  grid, block and lds are evaluated once; a templated kernel stays in parentheses.
+#define VCP_LAUNCH(ctx, kernel, grid, block, lds, stream, ...)                                                         \
+  do {                                                                                                                 \
+    const dim3 g__ = (grid), b__ = (block);                                                                            \
+    const size_t l__ = (lds);                                                                                          \
+    if (!vcp_launch_ok(g__, b__, l__))                                                                                 \
+      return vcp_fail((ctx), VCP_ERR_TOO_LARGE, "%s: grid %ux%ux%u, block %ux%ux%u, lds %zu", #kernel, g__.x, g__.y,   \
+                      g__.z, b__.x, b__.y, b__.z, l__);                                                                \
+    hipLaunchKernelGGL(kernel, g__, b__, l__, stream, __VA_ARGS__);                                                    \
+    const hipError_t e__ = hipGetLastError();                                                                          \
+    if (e__ != hipSuccess) return vcp_fail((ctx), VCP_ERR_HIP, "%s: %s", #kernel, hipGetErrorString(e__));             \
+  } while (0)
 
 // exclusive scan of n uint32 (in place allowed: out may equal in); writes the grand total to
 // d_total (device uint32) if non-null.  Defined in scan.hip.
