@@ -339,6 +339,38 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
                     int max_iter, int max_landmarks, int start_by_matching_centroids, double M[16],
                     double* mean_dist, int32_t* iters);
 
+/* -- multi-start ICP ----------------------------------------------------------------------------
+ * vcp_icp_vtklike falls into a local minimum on checkerboard-like truths (the reference's README, "bugs known"; its
+ * workaround is a hand-placed start, FrmMain.cs:3471-3537, and typed axis directions, :912-913).  This runs the
+ * vcp_icp_vtklike loop from n_poses starts in one call, scores each result and keeps the best:
+ *   per pose h     the vcp_icp_vtklike loop with start_by_matching_centroids on -- the same landmarks (step = ns /
+ *                  max_landmarks when ns > max_landmarks), exactly max_iter rounds, the same NN, sums, Horn solve and
+ *                  composition R <- R1 R, T <- R1 T + T1, the same mean_dist (RMS landmark-to-closest distance of the
+ *                  last round) -- from R = R0_h, T = T0_h
+ *   init_R         [n_poses*9] row-major, used as given; a reflection (det -1) is allowed and kept (Horn's R1 is
+ *                  proper): that covers an unknown axis direction.  NULL: R0_h = Rz(theta_h) = [[c,-s,0],[s,c,0],
+ *                  [0,0,1]], theta_h = h * (2 pi / n_poses) in binary64, c = cos, s = sin of the C library; h = 0 is
+ *                  exactly the identity
+ *   init_T         [n_poses*3].  NULL: T0_h = mt - R0_h ms, with ms, mt the source and target means computed as
+ *                  vcp_icp_vtklike does (sequential binary64 sums over all points, one division) and R0_h ms row by
+ *                  row, left to right -- for R0 = I bit-identical to vcp_icp_vtklike's start
+ *   inliers[h]     over ALL ns source points under M_h = [R_h | T_h]: points whose nearest target is closer than
+ *                  inlier_dist, by vcp_match's arithmetic and rule, so inliers[h] == vcp_match(source, target, M_h,
+ *                  inlier_dist).count_matched; inlier_dist = +inf is allowed
+ *   best           the pose with the most inliers; ties go to the smaller mean_dist, then to the lower h.  M_best =
+ *                  its 4x4 row-major matrix, laid out like vcp_icp_vtklike's M
+ *   M_all [n_poses*16], mean_dist [n_poses], inliers [n_poses] may each be NULL; M_best and best are required.
+ * The result of pose h is bit-identical whatever other poses share the call: each pose's partition into workgroups and
+ * reduction order are those of a single run.  n_poses = 1 with init_R = init_T = NULL equals vcp_icp_vtklike
+ * (start_by_matching_centroids = 1) bit for bit (M, mean_dist).  Errors: those of vcp_icp_vtklike; n_poses < 1,
+ * inlier_dist NaN or <= 0, a non-finite entry of init_R / init_T: VCP_ERR_ARG; n_poses > 4096: VCP_ERR_UNSUPPORTED; a
+ * failed Horn solve in any pose: VCP_ERR_ARG.  Deterministic.  Timing phases: icpms_rounds, icpms_score
+ * (csrc/icp.hip). */
+int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                       int32_t n_poses, const double* init_R, const double* init_T, int max_iter,
+                       int max_landmarks, double inlier_dist, double M_best[16], int32_t* best,
+                       double* M_all, double* mean_dist, int32_t* inliers);
+
 /* -- minimal bounding circles ---------------------------------------------
  * Replaces Tools.getCircles (BC/Tools.cs:394-409) / Geometry.FindMinimalBoundingCircle
  * (BC/Geometry.cs:247-319; gift-wrap hull :122-208, circle through 2 or 3 hull points :260-312): for

@@ -30,7 +30,7 @@ SYMBOLS = [
     "vcp_selftest_horn", "vcp_create_multi", "vcp_destroy_multi", "vcp_multi_last_error", "vcp_multi_count",
     "vcp_multi_ctx", "vcp_dbscan_blocks_multi", "vcp_blocks_share_plan", "vcp_blocks_plan_dev", "vcp_blocks_plan_cuts",
     "vcp_blocks_build_dev", "vcp_blocks_finish_local_dev", "vcp_blocks_finish_zero_dev", "vcp_blocks_finish_zcoords_dev",
-    "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev",
+    "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
 ]
 
 
@@ -473,6 +473,35 @@ class Context:
                                         C.c_int64(len(target)), int(max_iter), int(max_landmarks),
                                         int(start_by_centroids), _ptr(M), C.byref(md), C.byref(it)))
         return dict(M=M.reshape(4, 4), mean_dist=md.value, iters=it.value)
+
+    def icp_multistart(self, source, target, poses=36, init_T=None, max_iter=100, max_landmarks=200,
+                       inlier_dist=np.inf):
+        """icp_vtklike (centroid start) from H start rotations in one call, scored by inliers (vcp_icp_multistart).
+        poses: an int H (the library's Rz(h * 2 pi / H), h = 0 the identity) or an [H, 3, 3] array of start rotations;
+        init_T: None (T0 = target mean - R0 source mean) or [H, 3].  inliers[h] = vcp_match(source, target, M_all[h],
+        inlier_dist).count_matched.  Returns dict(best, M [4,4], M_all [H,4,4], mean_dist [H], inliers [H])."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        if isinstance(poses, (int, np.integer)):
+            H, init_R = int(poses), None
+        else:
+            init_R = _f64(poses).reshape(-1, 9)
+            H = len(init_R)
+        if init_T is not None:
+            init_T = _f64(init_T, 3)
+            if len(init_T) != H:
+                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
+        n = max(H, 0)
+        M = np.zeros(16)
+        M_all = np.zeros((n, 16))
+        md = np.zeros(n)
+        inl = np.zeros(n, np.int32)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_icp_multistart(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
+                                           C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T),
+                                           int(max_iter), int(max_landmarks), C.c_double(inlier_dist), _ptr(M),
+                                           C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl)
 
     def import_convert(self, rows, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True):
         """MainForm.AddFolder per-row work: dict(xyz [n,3], state [n] (0 filtered / 1 kept / 2 duplicate), kept, duplicates)."""

@@ -10,6 +10,10 @@
 //               the stop rule (:149,:180) and composes R <- R1 R, T <- R1 T + T1 (:149-177) in the state.
 // The host enqueues rounds in batches of 8 and reads the 430-byte state back once per batch; kernels of rounds
 // after the stop see state.done and return at once.
+// Multi-start (vcp_icp_multistart): H independent states run side by side -- blockIdx.y of the pass selects the state
+// and its slice of partial rows, k_icp_step runs one workgroup per state, and each state's partition into workgroups and
+// reduction order are those of a single run, so every pose's bits are independent of the batch.  k_icpms_score then
+// counts, per pose, the source points vcp_match would call matched.
 //
 // Nearest neighbour: the model index is wave-uniform, so model points come through the scalar cache, four per
 // trip.  Distances are first screened in binary32 (three FMAs per pair) with a rigorous rounding bound; only model points whose
@@ -21,6 +25,7 @@
 #include <cstring>
 #include <vector>
 
+#include "match.hpp"
 #include "nngrid.hpp"
 #include "reduce.hpp"
 #include "vcp_ctx.hpp"
@@ -30,6 +35,7 @@ namespace {
 constexpr int ITPB = 256;
 constexpr int ICP_MAX_BLOCKS = 1024;
 constexpr int ICP_BATCH = 8;  // rounds enqueued per host synchronisation
+constexpr int ICPMS_MAX_POSES = 4096;
 
 enum { MODE_REFERENCE = 0, MODE_VTK = 1, MODE_SUMS_ONLY = 2 };
 
@@ -43,9 +49,10 @@ struct IcpState {
 };
 
 
-// bounding box of the model -> centre and half extent in the state (single workgroup: models are small).  A model
+// bounding box of the model -> centre and half extent in the nst states (single workgroup: models are small).  A model
 // with non-finite coordinates gets an infinite scale: every data point is then resolved in binary64.
-__global__ __launch_bounds__(ITPB) void k_model_frame(const double* __restrict__ m, int64_t nm, IcpState* __restrict__ st) {
+__global__ __launch_bounds__(ITPB) void k_model_frame(const double* __restrict__ m, int64_t nm, IcpState* __restrict__ st,
+                                                     int nst) {
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   bool bad = false;
   for (int64_t j = threadIdx.x; j < nm; j += ITPB) {
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(ITPB) void k_model_frame(const double* __restrict__
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double mm = 0.0;
+    double mm = 0.0, cen[3];
     for (int a = 0; a < 3; a++) {
       double l = sl[0][a], h = sh[0][a];
       for (int k = 1; k < ITPB / 64; k++) {
@@ -81,10 +88,13 @@ __global__ __launch_bounds__(ITPB) void k_model_frame(const double* __restrict__
         h = fmax(h, sh[k][a]);
       }
       const double c = 0.5 * l + 0.5 * h;
-      st->cen[a] = sbad ? 0.0 : c;
+      cen[a] = sbad ? 0.0 : c;
       mm = fmax(mm, fmax(h - c, c - l));
     }
-    st->mmax = sbad ? INFINITY : mm;
+    for (int k = 0; k < nst; k++) {
+      for (int a = 0; a < 3; a++) st[k].cen[a] = cen[a];
+      st[k].mmax = sbad ? INFINITY : mm;
+    }
   }
 }
 
@@ -116,6 +126,8 @@ __global__ __launch_bounds__(TB) void k_icp_pass(const double* __restrict__ mode
                                                 int nm, const double* __restrict__ data, int64_t nd,
                                                 const IcpState* __restrict__ st, double* __restrict__ partial,
                                                 int32_t* __restrict__ nn, NNGrid ng) {
+  st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
+  partial += (size_t)blockIdx.y * gridDim.x * 16;
   if (st->done) return;
   constexpr bool TILED = NNMODE == 1, GRID = NNMODE == 2;
   __shared__ float4 tile[TILED ? MTILE : 1];
@@ -323,6 +335,8 @@ __global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict_
                                                       int nm, const double* __restrict__ data, int64_t nd,
                                                       const IcpState* __restrict__ st, double* __restrict__ partial,
                                                       int32_t* __restrict__ nn, uint32_t imask, double tolk) {
+  st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
+  partial += (size_t)blockIdx.y * gridDim.x * 16;
   if (st->done) return;
   double R[9], T[3];
 #pragma unroll
@@ -663,8 +677,11 @@ __device__ __forceinline__ void icp_step_body(const double* __restrict__ partial
   if (!go || round >= a.max_iter) st->done = 1;
 }
 
+// one workgroup per state: blockIdx.x selects the state and its nb partial rows
 __global__ __launch_bounds__(ITPB) void k_icp_step(const double* __restrict__ partial, int nb, IcpState* __restrict__ st,
                                                   StepArgs a) {
+  st += blockIdx.x;
+  partial += (size_t)blockIdx.x * nb * 16;
   if (st->done) return;
   icp_step_body<ITPB>(partial, nb, st, a);
 }
@@ -674,9 +691,17 @@ void identity(IcpState& s) {
   s.R[0] = s.R[4] = s.R[8] = 1.0;
 }
 
-// Runs rounds on device-resident model/data until the state says done.  `init` carries the starting R,T.
-int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState& init,
-            double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn) {
+// device layout of b_icp_part: the states first, the partial rows from the next 256-byte boundary
+size_t icp_states_bytes(int nst) { return ((size_t)nst * sizeof(IcpState) + 255) & ~(size_t)255; }
+IcpState* icp_states(vcp_ctx* ctx) { return ctx->b_icp_part.as<IcpState>(); }
+
+// Runs rounds on device-resident model/data until the states say done.  `init` carries the starting R,T of nst
+// independent states (nst > 1: vcp_icp_multistart, MODE_VTK), `out` receives them.  all_rounds: enqueue every round
+// and synchronise once (a fixed round count needs nothing back in between).  ng_out (may be NULL) receives the
+// model's grid; ng_out->rec == nullptr when the full scans serve the model.
+int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState* init,
+            int nst, double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn, bool all_rounds,
+            NNGrid* ng_out) {
   hipStream_t st = ctx->stream;
   // small data sets: one wave per workgroup so that they reach more CUs; large models: LDS tiles
   const bool small0 = nd <= (int64_t)64 * ICP_MAX_BLOCKS;
@@ -689,6 +714,7 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     if (grc == VCP_OK) grid = true;
     else if (grc != VCP_ERR_UNSUPPORTED) return grc;
   }
+  if (ng_out) *ng_out = ng;
   const bool tiled = nm > 512 && !grid;
   const bool small = grid ? nd * nng::NNG <= (int64_t)64 * ICP_MAX_BLOCKS : small0;
   const int tb = small ? 64 : ITPB;
@@ -699,46 +725,94 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   const uint32_t imask = (1u << ib) - 1u;
   double tolk = 1.0;  // smallest power of two >= (54 + 9 * 2^ib) * 2^-24
   while (tolk * 0.5 >= (54.0 + 9.0 * (double)(1u << ib)) / 16777216.0) tolk *= 0.5;
-  VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, (size_t)ICP_MAX_BLOCKS * 16 * sizeof(double) + sizeof(IcpState) + 256));
+  // the nst states (icp_states), then [nst][nb][16] partial rows
+  const size_t st_bytes = icp_states_bytes(nst);
+  VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + (size_t)nst * nb * 16 * sizeof(double)));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)nm * sizeof(float4) + 64));
-  double* part = ctx->b_icp_part.as<double>();
-  IcpState* d_st = reinterpret_cast<IcpState*>(part + (size_t)ICP_MAX_BLOCKS * 16);
+  IcpState* d_st = icp_states(ctx);
+  double* part = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes);
   const StepArgs sa{(long long)nd, tol, stop_rule, max_iter, mode};
   float4* model32 = ctx->b_aux0.as<float4>();
-  IcpState* h_st = reinterpret_cast<IcpState*>(ctx->pinned);
-  *h_st = init;
-  VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, sizeof(IcpState), hipMemcpyHostToDevice, st));
+  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 ? ctx->pinned : vcp_stage(ctx, (size_t)nst * sizeof(IcpState)));
+  if (!h_st) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
+  std::memcpy(h_st, init, (size_t)nst * sizeof(IcpState));
+  VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, (size_t)nst * sizeof(IcpState), hipMemcpyHostToDevice, st));
   if (!grid) {  // the binary32 screening frame and copy serve the full scans only
-    VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st);
+    VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st, nst);
     VCP_LAUNCH(ctx, k_model32, dim3(vcp_blocks(nm, ITPB)), dim3(ITPB), 0, st, d_model, nm, d_st, model32);
   }
+  auto all_done = [&]() {
+    for (int k = 0; k < nst; k++)
+      if (!h_st[k].done) return false;
+    return true;
+  };
   int launched = 0;
   for (;;) {
-    const int batch = mode == MODE_SUMS_ONLY ? 1 : std::min(ICP_BATCH, max_iter - launched);
+    const int batch = mode == MODE_SUMS_ONLY ? 1 : std::min(all_rounds ? max_iter : ICP_BATCH, max_iter - launched);
     for (int b = 0; b < batch; b++) {
 #define VCP_PASS(TBV, TL) \
-  VCP_LAUNCH(ctx, (k_icp_pass<TBV, TL>), dim3(nb), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part, d_nn, ng)
+  VCP_LAUNCH(ctx, (k_icp_pass<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part, \
+             d_nn, ng)
       if (small && grid) VCP_PASS(64, 2);
       else if (grid) VCP_PASS(ITPB, 2);
       else if (small && tiled) VCP_PASS(64, 1);
       else if (tiled) VCP_PASS(ITPB, 1);
       else if (small)
-        VCP_LAUNCH(ctx, k_icp_pass_small<64>, dim3(nb), dim3(64), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part,
-                        d_nn, imask, tolk);
-      else
-        VCP_LAUNCH(ctx, k_icp_pass_small<ITPB>, dim3(nb), dim3(ITPB), 0, st, d_model, model32, (int)nm, d_data, nd, d_st,
+        VCP_LAUNCH(ctx, k_icp_pass_small<64>, dim3(nb, nst), dim3(64), 0, st, d_model, model32, (int)nm, d_data, nd, d_st,
                         part, d_nn, imask, tolk);
+      else
+        VCP_LAUNCH(ctx, k_icp_pass_small<ITPB>, dim3(nb, nst), dim3(ITPB), 0, st, d_model, model32, (int)nm, d_data, nd,
+                        d_st, part, d_nn, imask, tolk);
 #undef VCP_PASS
-      VCP_LAUNCH(ctx, k_icp_step, dim3(1), dim3(ITPB), 0, st, part, nb, d_st, sa);
+      VCP_LAUNCH(ctx, k_icp_step, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, sa);
     }
     launched += batch;
-    VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, sizeof(IcpState), hipMemcpyDeviceToHost, st));
+    VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, (size_t)nst * sizeof(IcpState), hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
-    if (h_st->done || launched >= max_iter || mode == MODE_SUMS_ONLY) break;
+    if (all_done() || launched >= max_iter || mode == MODE_SUMS_ONLY) break;
   }
-  *out = *h_st;
-  if (out->failed) return vcp_fail(ctx, VCP_ERR_ARG, "Horn solve failed (non-finite sums)");
+  std::memcpy(out, h_st, (size_t)nst * sizeof(IcpState));
+  for (int k = 0; k < nst; k++)
+    if (out[k].failed) return vcp_fail(ctx, VCP_ERR_ARG, "Horn solve failed (non-finite sums)%s", nst > 1 ? " in a pose" : "");
   return VCP_OK;
+}
+
+// Inlier score of vcp_icp_multistart: grid (source points [x NNG lanes], poses).  Per pose h, M_h = [R_h | T_h] from the
+// final state, then exactly k_match's arithmetic (match.hpp); a point counts when its nearest target is closer than
+// max_dist.  One integer atomic per workgroup and pose: deterministic.
+template <bool GRID>
+__global__ __launch_bounds__(ITPB) void k_icpms_score(const double* __restrict__ src, int64_t ns,
+                                                     const double* __restrict__ tgt, int nt,
+                                                     const IcpState* __restrict__ st, double max_dist,
+                                                     uint32_t* __restrict__ count, NNGrid ng) {
+  constexpr int LPQ = GRID ? nng::NNG : 1;  // lanes per source point
+  const int h = blockIdx.y;
+  const int64_t j = ((int64_t)blockIdx.x * ITPB + threadIdx.x) / LPQ;
+  const int sub = (int)(threadIdx.x & (LPQ - 1));
+  double M[16];  // what vcp_icp_vtklike returns as M
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) M[4 * r + c] = st[h].R[3 * r + c];
+    M[4 * r + 3] = st[h].T[r];
+  }
+  bool hit = false;
+  if (j < ns) {  // uniform per NNG-lane group: the grid query's shuffles stay within live groups
+    double m[3];
+    mtc::transform(M, src[3 * j], src[3 * j + 1], src[3 * j + 2], m);
+    int best;
+    const double bd = mtc::nearest<GRID>(tgt, nt, ng, m, sub, best);
+    hit = bd < max_dist && sub == 0;
+  }
+  __shared__ uint32_t wc[ITPB / 64];
+  const unsigned long long b = __ballot(hit);
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < ITPB / 64; w++) t += wc[w];
+    if (t) atomicAdd(&count[h], t);
+  }
 }
 
 }  // namespace
@@ -765,7 +839,8 @@ int vcp_icp_dev(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d
   vcp_phase(ctx, "icp_rounds");
   IcpState init, fin;
   identity(init);  // round 1 matches the raw data (P = copy of data, :22); 1*x + 0*y + 0*z is exact
-  VCP_TRY(icp_run(ctx, d_model, nm, d_data, nd, init, tol, stop_rule, max_iter, MODE_REFERENCE, &fin, nullptr));
+  VCP_TRY(icp_run(ctx, d_model, nm, d_data, nd, &init, 1, tol, stop_rule, max_iter, MODE_REFERENCE, &fin, nullptr, false,
+                  nullptr));
   VCP_TRY(vcp_phase_finish(ctx));
   // R, T are written once some round has asked to continue (:149-162); if round 1 already stops they stay
   // whatever the caller passed in
@@ -831,8 +906,8 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
   VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in0.p, target, (size_t)nt * 24, hipMemcpyHostToDevice, ctx->stream));
   VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in2.p, a.data(), (size_t)nb * 24, hipMemcpyHostToDevice, ctx->stream));
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `a` is a local buffer
-  VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init, 0.0, VCP_STOP_SSE_DELTA, max_iter,
-                  MODE_VTK, &fin, nullptr));
+  VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, &init, 1, 0.0, VCP_STOP_SSE_DELTA,
+                  max_iter, MODE_VTK, &fin, nullptr, false, nullptr));
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) M[4 * r + c] = fin.R[3 * r + c];
     M[4 * r + 3] = fin.T[r];
@@ -841,6 +916,119 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
   M[15] = 1;
   if (mean_dist) *mean_dist = std::sqrt(fin.d / (double)nb);
   if (iters_o) *iters_o = fin.round;
+  return VCP_OK;
+}
+
+// Multi-start form of vcp_icp_vtklike (vcp.h): the same landmarks, rounds and arithmetic per pose, from H starts at
+// once; the target's grid (or screening frame) is built once and serves every pose and the score.
+int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                       int32_t n_poses, const double* init_R, const double* init_T, int max_iter, int max_landmarks,
+                       double inlier_dist, double M_best[16], int32_t* best, double* M_all, double* mean_dist,
+                       int32_t* inliers) {
+  if (!ctx) return VCP_ERR_ARG;
+  if (ns <= 0 || nt <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty source or target");
+  if (max_iter < 1 || max_landmarks < 1 || !source || !target || !M_best || !best)
+    return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
+  if (nt >= 0x7FFFFFFFLL / 3) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "target too large");
+  if (n_poses < 1) return vcp_fail(ctx, VCP_ERR_ARG, "n_poses < 1");
+  if (n_poses > ICPMS_MAX_POSES) return vcp_fail(ctx, VCP_ERR_UNSUPPORTED, "n_poses > %d", ICPMS_MAX_POSES);
+  if (!(inlier_dist > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "inlier_dist must be > 0 (+inf allowed)");
+  for (int64_t k = 0; k < (int64_t)n_poses * 9 && init_R; k++)
+    if (!std::isfinite(init_R[k])) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite init_R");
+  for (int64_t k = 0; k < (int64_t)n_poses * 3 && init_T; k++)
+    if (!std::isfinite(init_T[k])) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite init_T");
+  VCP_TRY(vcp_bind(ctx));
+  vcp_phase_reset(ctx);
+  vcp_phase(ctx, "icpms_rounds");
+  int64_t step = 1;
+  if (ns > max_landmarks) step = ns / max_landmarks;
+  const int64_t nb = ns / step;
+  std::vector<double> a((size_t)3 * nb);
+  for (int64_t i = 0, j = 0; i < nb; i++, j += step)
+    for (int c = 0; c < 3; c++) a[3 * i + c] = source[3 * j + c];
+  // source and target means exactly as vcp_icp_vtklike's centroid start computes them
+  double ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
+  if (!init_T) {
+    for (int64_t i = 0; i < ns; i++)
+      for (int c = 0; c < 3; c++) ms[c] += source[3 * i + c];
+    for (int64_t i = 0; i < nt; i++)
+      for (int c = 0; c < 3; c++) mt[c] += target[3 * i + c];
+    for (int c = 0; c < 3; c++) {
+      ms[c] = ms[c] / (double)ns;
+      mt[c] = mt[c] / (double)nt;
+    }
+  }
+  std::vector<IcpState> init((size_t)n_poses), fin((size_t)n_poses);
+  for (int h = 0; h < n_poses; h++) {
+    IcpState& s = init[h];
+    identity(s);
+    if (init_R) {
+      std::memcpy(s.R, init_R + 9 * (size_t)h, sizeof(s.R));
+    } else {  // Rz(theta_h); 0 - s keeps h = 0 exactly the identity (no -0)
+      const double th = (double)h * (2.0 * M_PI / (double)n_poses), c = std::cos(th), sn = std::sin(th);
+      const double R0[9] = {c, 0.0 - sn, 0.0, sn, c, 0.0, 0.0, 0.0, 1.0};
+      std::memcpy(s.R, R0, sizeof(s.R));
+    }
+    if (init_T) {
+      std::memcpy(s.T, init_T + 3 * (size_t)h, sizeof(s.T));
+    } else {  // T0 = mt - R0 ms, R0 ms row by row, left to right
+      for (int r = 0; r < 3; r++) s.T[r] = mt[r] - (s.R[3 * r] * ms[0] + s.R[3 * r + 1] * ms[1] + s.R[3 * r + 2] * ms[2]);
+    }
+  }
+  hipStream_t st = ctx->stream;
+  VCP_TRY(vcp_ensure(ctx, ctx->b_in0, (size_t)nt * 24));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_in2, (size_t)nb * 24));
+  if (step > 1) VCP_TRY(vcp_ensure(ctx, ctx->b_in3, (size_t)ns * 24));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_out0, (size_t)n_poses * 4));
+  VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in0.p, target, (size_t)nt * 24, hipMemcpyHostToDevice, st));
+  VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in2.p, a.data(), (size_t)nb * 24, hipMemcpyHostToDevice, st));
+  if (step > 1) VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in3.p, source, (size_t)ns * 24, hipMemcpyHostToDevice, st));
+  VCP_HIP(ctx, hipStreamSynchronize(st));  // `a` is a local buffer
+  NNGrid ng{};
+  VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init.data(), n_poses, 0.0,
+                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng));
+  // score every pose over ALL source points with vcp_match's arithmetic, on the grid the rounds used (vcp_match bins
+  // a target of more than 512 points too, and falls back to the full scan on the same condition)
+  vcp_phase(ctx, "icpms_score");
+  const double* d_src = step > 1 ? ctx->b_in3.as<double>() : ctx->b_in2.as<double>();  // step 1: the landmarks are all
+  const IcpState* d_st = icp_states(ctx);
+  uint32_t* d_cnt = ctx->b_out0.as<uint32_t>();
+  VCP_HIP(ctx, hipMemsetAsync(d_cnt, 0, (size_t)n_poses * 4, st));
+  if (ng.rec)
+    VCP_LAUNCH(ctx, k_icpms_score<true>, dim3(vcp_blocks(ns * nng::NNG, ITPB), n_poses), dim3(ITPB), 0, st, d_src, ns,
+               ctx->b_in0.as<double>(), (int)nt, d_st, inlier_dist, d_cnt, ng);
+  else
+    VCP_LAUNCH(ctx, k_icpms_score<false>, dim3(vcp_blocks(ns, ITPB), n_poses), dim3(ITPB), 0, st, d_src, ns,
+               ctx->b_in0.as<double>(), (int)nt, d_st, inlier_dist, d_cnt, ng);
+  uint32_t* h_cnt = reinterpret_cast<uint32_t*>(vcp_stage(ctx, (size_t)n_poses * 4));
+  if (!h_cnt) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of the scores");
+  VCP_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_poses * 4, hipMemcpyDeviceToHost, st));
+  VCP_HIP(ctx, hipStreamSynchronize(st));
+  VCP_TRY(vcp_phase_finish(ctx));
+  // most inliers, then the smaller mean distance, then the lower index
+  int b = 0;
+  for (int h = 0; h < n_poses; h++) {
+    const double md = std::sqrt(fin[h].d / (double)nb), mb = std::sqrt(fin[b].d / (double)nb);
+    if (h_cnt[h] > h_cnt[b] || (h_cnt[h] == h_cnt[b] && md < mb)) b = h;
+    if (M_all) {
+      double* M = M_all + 16 * (size_t)h;
+      for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) M[4 * r + c] = fin[h].R[3 * r + c];
+        M[4 * r + 3] = fin[h].T[r];
+      }
+      M[12] = M[13] = M[14] = 0;
+      M[15] = 1;
+    }
+    if (mean_dist) mean_dist[h] = md;
+    if (inliers) inliers[h] = (int32_t)h_cnt[h];
+  }
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) M_best[4 * r + c] = fin[b].R[3 * r + c];
+    M_best[4 * r + 3] = fin[b].T[r];
+  }
+  M_best[12] = M_best[13] = M_best[14] = 0;
+  M_best[15] = 1;
+  *best = b;
   return VCP_OK;
 }
 
@@ -867,8 +1055,8 @@ int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* da
   identity(init);
   if (R) std::memcpy(init.R, R, sizeof(init.R));
   if (T) std::memcpy(init.T, T, sizeof(init.T));
-  VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, init, 0.0, VCP_STOP_SSE_DELTA, 1,
-                  MODE_SUMS_ONLY, &fin, nn ? ctx->b_out0.as<int32_t>() : nullptr));
+  VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, &init, 1, 0.0, VCP_STOP_SSE_DELTA, 1,
+                  MODE_SUMS_ONLY, &fin, nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr));
   std::memcpy(sums, fin.sums, sizeof(fin.sums));
   if (nn) {
     VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <vector>
 
-#include "nngrid.hpp"
+#include "match.hpp"
 #include <cstring>
 #include "vcp_ctx.hpp"
 
@@ -20,7 +20,7 @@ struct M16 {
 };
 
 // GRID: the truths have been binned (nngrid.hpp); the search compares (sqrt distance, truth index) pairs, i.e. returns
-// what the sequential strict-`<` scan over the correctly rounded distances returns.
+// what the sequential strict-`<` scan over the correctly rounded distances returns.  The arithmetic is match.hpp's.
 template <bool GRID>
 __global__ __launch_bounds__(MT) void k_match(const double* __restrict__ centers, int K, const double* __restrict__ truths,
                                              int T, M16 M, double max_dist, double* __restrict__ mxyz,
@@ -31,36 +31,15 @@ __global__ __launch_bounds__(MT) void k_match(const double* __restrict__ centers
   const int sub = (int)(threadIdx.x & (LPQ - 1));
   bool hit = false;
   if (j < K) {
-    const double c0 = centers[3 * j], c1 = centers[3 * j + 1], c2 = centers[3 * j + 2];
     double m[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) m[r] = c0 * M.m[4 * r] + c1 * M.m[4 * r + 1] + c2 * M.m[4 * r + 2] + M.m[4 * r + 3];
+    mtc::transform(M.m, centers[3 * j], centers[3 * j + 1], centers[3 * j + 2], m);
     if (mxyz && sub == 0) {
       mxyz[3 * j] = m[0];
       mxyz[3 * j + 1] = m[1];
       mxyz[3 * j + 2] = m[2];
     }
-    int best = 0;
-    double bd;
-    if (GRID) {
-      nng::query<true>(ng, m, sub, best, bd);
-      // the distance the C# holds for the winner (NaN / infinity included: the query only orders finite values)
-      double dx = truths[3 * best] - m[0], dy = truths[3 * best + 1] - m[1], dz = truths[3 * best + 2] - m[2];
-      bd = sqrt(dx * dx + dy * dy + dz * dz);
-    } else {
-      {
-        double dx = truths[0] - m[0], dy = truths[1] - m[1], dz = truths[2] - m[2];
-        bd = sqrt(dx * dx + dy * dy + dz * dz);
-      }
-      for (int i = 1; i < T; i++) {
-        double dx = truths[3 * i] - m[0], dy = truths[3 * i + 1] - m[1], dz = truths[3 * i + 2] - m[2];
-        double d = sqrt(dx * dx + dy * dy + dz * dz);
-        if (d < bd) {
-          bd = d;
-          best = i;
-        }
-      }
-    }
+    int best;
+    const double bd = mtc::nearest<GRID>(truths, T, ng, m, sub, best);
     hit = bd < max_dist && sub == 0;
     if (sub == 0) {
       nearest[j] = best;

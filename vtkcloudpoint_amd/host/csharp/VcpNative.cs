@@ -65,6 +65,12 @@ namespace vtkPointCloud
             long nt, int max_iter, int max_landmarks, int start_by_matching_centroids, double[] M, out double mean_dist,
             out int iters);
 
+        // the same loop from n_poses start rotations (null init_R: Rz(h * 2 pi / n_poses)), best pose by inliers;
+        // M_all, mean_dist and inliers may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_multistart(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int n_poses, double[] init_R, double[] init_T, int max_iter, int max_landmarks, double inlier_dist,
+            double[] M_best, out int best, double[] M_all, double[] mean_dist, int[] inliers);
+
         // Tools.getCircles / Geometry.FindMinimalBoundingCircle (Tools.cs:394-409, Geometry.cs:247-319)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_mcc(IntPtr ctx, double[] xy, int[] labels, long[] order, long m, long n,
             int K, double[] centers, double[] radius, byte[] valid, int[] hull_n);

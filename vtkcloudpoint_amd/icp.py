@@ -1,4 +1,7 @@
-"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses."""
+"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start ICP for
+MainForm.ICP's centroid-to-truth matching."""
+import math
+
 import numpy as np
 
 from . import _native
@@ -145,3 +148,38 @@ class ICP:
             return []
         _, nn = ctx.icp_sums(xyz_array(model), xyz_array(data))
         return [model[int(j)] for j in nn]
+
+
+def rotations_about_z(n, mirror=False):
+    """[n, 3, 3] rotations Rz(h * 2 pi / n), h = 0..n-1 (element 0 exactly the identity); mirror=True appends the n
+    reflections Rz(theta) @ diag(1, -1, 1) (det -1: the source's y axis reversed), giving [2n, 3, 3]."""
+    n = int(n)
+    out = []
+    for h in range(n):
+        t = h * (2.0 * math.pi / n)
+        c, s = math.cos(t), math.sin(t)
+        out.append([[c, 0.0 - s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    if mirror:
+        for h in range(n):
+            c, s = out[h][0][0], out[h][1][0]
+            out.append([[c, s, 0.0], [s, 0.0 - c, 0.0], [0.0, 0.0, 1.0]])
+    return np.array(out, dtype=np.float64).reshape(-1, 3, 3)
+
+
+def multistart_icp(centers, truths, n_angles=36, mirror=False, init_T=None, max_iter=100, max_landmarks=200,
+                   inlier_dist=np.inf, ctx=None):
+    """MainForm.ICP()'s match of cluster centroids to truth points, started from n_angles rotations about z (and their
+    mirror images with mirror=True) instead of the centroid start alone; the pose with the most centroids within
+    inlier_dist of a truth wins.  centers / truths: [n, 3] arrays or lists of points with X, Y, Z.  Returns
+    Context.icp_multistart's dict (best, M, M_all, mean_dist, inliers)."""
+    ctx = ctx or default_context()
+    src = _points(centers)
+    tgt = _points(truths)
+    poses = rotations_about_z(n_angles, mirror) if mirror else int(n_angles)
+    return ctx.icp_multistart(src, tgt, poses, init_T, max_iter, max_landmarks, inlier_dist)
+
+
+def _points(p):
+    if isinstance(p, np.ndarray):
+        return p
+    return xyz_array(p)
