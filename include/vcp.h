@@ -77,7 +77,17 @@ int vcp_selftest_scan_dev(vcp_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, i
 /* Self-test of the Horn step of vcp_icp (BC/ICP.cs:53-124, intended arithmetic), run on the HOST from the same source
  * the device executes per round: sums[16] as vcp_icp_sums returns them, nd data points.  use_v != 0: V [16] is the
  * eigenvector basis of a previous round (warm start; a basis that is not orthonormal to 1e-9 -- NaN included -- is
- * replaced by the identity) and receives the basis found.  Returns 1 (solved), 0 (degenerate) or VCP_ERR_ARG.
+ * replaced by the identity) and receives the basis found.  Returns 1 (solved), 0 (failed) or VCP_ERR_ARG (NULL sums,
+ * R1 or T1, nd <= 0, use_v without V).  sums[15] is not read.
+ * 1 means: R1 is orthonormal with det +1 to 32 u (u = 2^-53), maximises sum_ab R[a][b] m[b][a] to 64 u big, and lies
+ * within 150 u (cond + 1) of the exact solution of the same sums, T1 within 150 u (cond + 1)(|muP|max + 1) + 4 u |T1|,
+ * where m = S/N - muP muY^T, big = max(|sums[6..14]|/nd, |muP_a muY_b|) and cond = big over the gap between the two
+ * largest eigenvalues of Horn's 4x4 matrix (a tie, e.g. a collinear cloud: any of the equally good rotations).  That
+ * holds for every finite input whose means, products muP_a muY_b and sums/nd stay normal binary64 numbers: the step is
+ * exactly invariant under a power-of-two scaling of the coordinates (R1 bit-identical, T1 scaled).  All-zero sums are
+ * coincident points: R1 = I, T1 = 0.  Outside that range -- NaN or an infinity in any of sums[0..14], or sums so large
+ * that Horn's matrix overflows -- the answer is 0 and R1 and T1 are not written.  cond grows with the square of the
+ * clouds' distance from the origin: see DESIGN.md, "Accuracy of the Horn step".
  * Needs no device and no context. */
 int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v, double R1[9], double T1[3]);
 

@@ -512,6 +512,13 @@ __host__ __device__ inline void jacobi4(double (&A)[4][4], double (&V)[4][4]) {
 // A basis that is not finite or has drifted from orthonormal (first round, failed round) is replaced by the identity.
 __host__ __device__ inline bool horn(const double s[16], long long nd, double R1[9], double T1[3], double* Vst) {
   const double N = (double)nd;
+  double Q[4][4], V[4][4];
+  if (Vst) {  // read first: on the device the loads then fly while the divisions below run
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) V[i][j] = Vst[4 * i + j];
+  }
   double muP[3], muY[3], m[3][3];
   for (int a = 0; a < 3; a++) {
     muP[a] = s[a] / N;
@@ -521,21 +528,41 @@ __host__ __device__ inline bool horn(const double s[16], long long nd, double R1
     for (int c = 0; c < 3; c++) m[r][c] = s[6 + 3 * r + c] / N - muP[r] * muY[c];
   const double tr = m[0][0] + m[1][1] + m[2][2];
   const double delta[3] = {m[1][2] - m[2][1], m[2][0] - m[0][2], m[0][1] - m[1][0]};
-  double Q[4][4], V[4][4];
   Q[0][0] = tr;
   for (int i = 0; i < 3; i++) {
     Q[0][i + 1] = Q[i + 1][0] = delta[i];
     for (int j = 0; j < 3; j++) Q[i + 1][j + 1] = m[i][j] + m[j][i] - (i == j ? tr : 0.0);
   }
+  // Q goes into the sweeps divided by the power of two that brings its largest entry into [0.5, 1): jacobi4's stop test
+  // squares the entries, and beyond about 2^+-256 the squares overflow or flush to zero, which ended the sweeps before
+  // the first rotation with "solved".  The division is exact and R1 depends on the eigenvectors alone, so nothing
+  // changes where the squares were in range.  A non-finite entry (non-finite sums, or sums that overflow here) fails the
+  // solve: an infinite off-diagonal entry passed the same stop test.  Tested per entry: fmax would drop a NaN.  The
+  // verdict is returned at the end, not here: a branch at this point keeps the device compiler from issuing the loads
+  // of the basis early, and the failing case may take as long as it likes.
+  double rmax[4];  // per row of the upper triangle: four short chains instead of one of ten
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    rmax[i] = 0.0;
+#pragma unroll
+    for (int j = i; j < 4; j++) {
+      const double a = fabs(Q[i][j]);
+      finite = finite && (a <= 1.7976931348623157e308);  // false for NaN
+      rmax[i] = a > rmax[i] ? a : rmax[i];
+    }
+  }
+  const double m01 = rmax[0] > rmax[1] ? rmax[0] : rmax[1], m23 = rmax[2] > rmax[3] ? rmax[2] : rmax[3];
+  const double qmax = finite ? (m01 > m23 ? m01 : m23) : 0.0;
+  int e;  // 0 for qmax = 0 (coincident points, or a Q that fails anyway)
+  (void)frexp(qmax, &e);
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) Q[i][j] = ldexp(Q[i][j], -e);
   bool warm = Vst != nullptr;
   if (warm) {
     bool ortho = true;  // | V^T V - I |_max <= 1e-9, tested per entry: fmax would drop a NaN
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        V[i][j] = Vst[4 * i + j];
-      }
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -592,7 +619,7 @@ __host__ __device__ inline bool horn(const double s[16], long long nd, double R1
       for (int k = 0; k < 4; k++) q[k] = V[k][i];
     }
   const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  if (!(nrm > 0.0) || !(nrm <= 1.7976931348623157e308)) return false;
+  if (!finite || !(nrm > 0.0) || !(nrm <= 1.7976931348623157e308)) return false;
   for (int i = 0; i < 4; i++) q[i] /= nrm;
   // CalculateRotation, BaseClass/ICP.cs:274-285
   R1[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3];
