@@ -392,6 +392,74 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
 int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, const int64_t* order, int64_t m,
             int64_t n, int32_t K, double* centers, double* radius, uint8_t* valid, int32_t* hull_n);
 
+/* -- cluster shapes and the radius / aspect filter ------------------------------------------------
+ * The reference rejects clusters "based on the circumscribed circle and the circumscribed rectangle" (its README):
+ * MainForm.FilterClustersByRadius (FrmMain.cs:1905-1920: radius > r fills filterID) and removePointByRadius
+ * (:3743-3746 -> Tools.removeFilterPointFromClustering, BC/Tools.cs:70-74, a stable RemoveAll).  One pass per cluster
+ * gives the convex hull, the minimal bounding circle and the minimum-area bounding rectangle.
+ *
+ * Inputs and the circle outputs (centers, radius, valid, hull_n) are vcp_mcc's, bit for bit.
+ *
+ * Hull.  The hull of cluster k is the array hull[0..h) vcp_mcc builds (Geometry.MakeConvexHull, BC/Geometry.cs:122-208:
+ * lowest y then lowest x, gift wrapping on the pseudo-angle, first in list order on ties; `order` decides list order).
+ * It is returned as indices into the caller's point array: hull_off [K+1] = prefix sums of the hull sizes
+ * (hull_off[0] = 0; a cluster with valid != 1 contributes 0), hull_idx [hull_off[K]] (the caller provides room for m
+ * entries).  Among points with equal coordinates the index is the one the C# picks: the first in list order that is
+ * still in the list.
+ *
+ * Rectangle.  All arithmetic binary64, every operation rounded on its own, sqrt and / correctly rounded.  For hull
+ * edge i, a = hull[i], b = hull[(i+1) % h]:
+ *     dx = b.x - a.x;  dy = b.y - a.y;  L2 = dx*dx + dy*dy              edge skipped unless 0 < L2 < +inf
+ *     for every hull point p:  rx = p.x - a.x;  ry = p.y - a.y
+ *                              u = rx*dx + ry*dy;   v = ry*dx - rx*dy
+ *     U = max u - min u;  V = max v - min v;  area_i = (U * V) / L2
+ * Minima and maxima are exact; one that is zero counts as +0; a NaN among the u, v makes the edge no candidate, and so
+ * does an area that is not < +inf.  The rectangle of the cluster is that of the candidate with the smallest area_i,
+ * the lowest i on ties (that a minimum-area enclosing rectangle has a side on a hull edge: Freeman & Shapira 1975).
+ *   rect_valid [K]   1 when valid == 1 and some edge is a candidate (for finite input that does not overflow:
+ *                    valid == 1 && hull_n >= 2), else 0; then rect_len = 0, rect_edge = -1 and the four corners are
+ *                    hull[0] (valid == 1) or (0, 0) (valid == 0: a cluster of <= 3 points has no hull)
+ *   rect_edge [K]    the chosen i
+ *   rect_len [K*2]   (U / sqrt(L2), V / sqrt(L2)): the side along the hull edge first
+ *   rect_xy [K*8]    the corners (min u, min v), (max u, min v), (max u, max v), (min u, max v) as
+ *                    x = a.x + (u*dx - v*dy) / L2,  y = a.y + (u*dy + v*dx) / L2
+ * Any of the four rect_* may be NULL; hull_off and hull_idx: both or neither; hull_n may be NULL.  With all six NULL
+ * the call is vcp_mcc.  This is the rectangle by definition, not a port: BC/Polygon.cs (FindSmallestBoundingRectangle)
+ * has no caller in the reference and is not transcribed.
+ * Errors and limits are vcp_mcc's: a label outside 0..K VCP_ERR_INDEX, a hull beyond 2048 points VCP_ERR_TOO_LARGE, a
+ * cluster without a finite point VCP_ERR_EMPTY; K == 0 does nothing.  Deterministic.  Timing phases: shapes_group
+ * (members by cluster), shapes_fit (hull + circle + rectangle, one kernel), shapes_hull (offsets and export). */
+int vcp_cluster_shapes(vcp_ctx* ctx, const double* xy, const int32_t* labels, const int64_t* order, int64_t m,
+                       int64_t n, int32_t K, double* centers, double* radius, uint8_t* valid, int32_t* hull_n,
+                       double* rect_xy, double* rect_len, int32_t* rect_edge, uint8_t* rect_valid,
+                       int32_t* hull_off, int32_t* hull_idx);
+/* Same with device pointers, on the context's stream; returns when the result is in place (K bytes are read back for
+ * the error check). */
+int vcp_cluster_shapes_dev(vcp_ctx* ctx, const double* d_xy, const int32_t* d_labels, const int64_t* d_order,
+                           int64_t m, int64_t n, int32_t K, double* d_centers, double* d_radius, uint8_t* d_valid,
+                           int32_t* d_hull_n, double* d_rect_xy, double* d_rect_len, int32_t* d_rect_edge,
+                           uint8_t* d_rect_valid, int32_t* d_hull_off, int32_t* d_hull_idx);
+
+/* The filter.  Plain comparisons, so a NaN or +inf threshold switches its criterion off, as `radius > r` does in the C#:
+ *     filtered[k] = valid[k] == 1 && ( radius[k] > max_radius
+ *                                   || (rect_valid[k] == 1 && max(len0, len1) > max_aspect * min(len0, len1)) )
+ *     keep[i]     = !(1 <= labels[i] <= K && filtered[labels[i] - 1])         label 0 (noise) is always kept
+ *     kept_idx    = the indices i with keep[i], ascending (RemoveAll is stable); *n_kept of them
+ * No division: a cluster on a line (V == 0) is filtered by any finite max_aspect, a single repeated point by none.
+ * labels [n]; radius, valid [K]; rect_len [K*2] and rect_valid [K] may be NULL together (no aspect criterion);
+ * filtered [K] (the reference's filterID as flags; *n_filtered of them set); keep [n] and kept_idx [n] may be NULL,
+ * n_filtered and n_kept too.  Cluster ids are not renumbered (the C# does not either).  A label outside 0..K is
+ * VCP_ERR_INDEX.  Timing phase: filter. */
+int vcp_cluster_filter(vcp_ctx* ctx, const int32_t* labels, int64_t n, int32_t K, const double* radius,
+                       const uint8_t* valid, const double* rect_len, const uint8_t* rect_valid, double max_radius,
+                       double max_aspect, uint8_t* filtered, uint8_t* keep, int32_t* kept_idx, int32_t* n_filtered,
+                       int64_t* n_kept);
+/* Same with device pointers; the two counts stay host pointers (16 bytes read back). */
+int vcp_cluster_filter_dev(vcp_ctx* ctx, const int32_t* d_labels, int64_t n, int32_t K, const double* d_radius,
+                           const uint8_t* d_valid, const double* d_rect_len, const uint8_t* d_rect_valid,
+                           double max_radius, double max_aspect, uint8_t* d_filtered, uint8_t* d_keep,
+                           int32_t* d_kept_idx, int32_t* n_filtered, int64_t* n_kept);
+
 /* -- matching ------------------------------------------------------------------------------
  * Replaces MainForm.calMatchedCoords (FrmMain.cs:3572-3587) + RecorrectMatchingPtsByDistance
  * (:3588-3618, getDisP :829-835): matched = M * (c,1); nearest truth by Euclidean distance

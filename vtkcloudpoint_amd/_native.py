@@ -31,6 +31,7 @@ SYMBOLS = [
     "vcp_multi_ctx", "vcp_dbscan_blocks_multi", "vcp_blocks_share_plan", "vcp_blocks_plan_dev", "vcp_blocks_plan_cuts",
     "vcp_blocks_build_dev", "vcp_blocks_finish_local_dev", "vcp_blocks_finish_zero_dev", "vcp_blocks_finish_zcoords_dev",
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
+    "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
 ]
 
 
@@ -450,6 +451,74 @@ class Context:
         self._chk(lib().vcp_mcc(self._h, _ptr(xy), _ptr(labels), _ptr(order), C.c_int64(m), C.c_int64(n), C.c_int32(K),
                                 _ptr(centers), _ptr(radius), _ptr(valid), _ptr(hn)))
         return dict(centers=centers, radius=radius, valid=valid, hull_n=hn)
+
+    # -- cluster shapes and the radius / aspect filter -------------------------------------------------
+    def cluster_shapes(self, xy, labels, K, order=None, rect=True, hull=True):
+        """vcp_cluster_shapes: hull, minimal bounding circle and minimum-area bounding rectangle of every cluster.
+        Returns mcc()'s dict plus rect_xy [K,4,2], rect_len [K,2], rect_edge [K], rect_valid [K] (rect) and hull_off
+        [K+1], hull_idx [hull_off[K]] = indices into xy (hull)."""
+        xy = _f64(xy, 2)
+        labels = np.ascontiguousarray(labels, np.int32)
+        order = None if order is None else np.ascontiguousarray(order, np.int64)
+        n = len(labels)
+        m = n if order is None else len(order)
+        centers = np.zeros((K, 2))
+        radius = np.zeros(K)
+        valid = np.zeros(K, np.uint8)
+        hn = np.zeros(K, np.int32)
+        rxy = np.zeros((K, 4, 2)) if rect else None
+        rlen = np.zeros((K, 2)) if rect else None
+        redge = np.full(K, -1, np.int32) if rect else None
+        rval = np.zeros(K, np.uint8) if rect else None
+        hoff = np.zeros(K + 1, np.int32) if hull else None
+        hidx = np.zeros(max(m, 1), np.int32) if hull else None
+        self._chk(lib().vcp_cluster_shapes(self._h, _ptr(xy), _ptr(labels), _ptr(order), C.c_int64(m), C.c_int64(n),
+                                           C.c_int32(K), _ptr(centers), _ptr(radius), _ptr(valid), _ptr(hn), _ptr(rxy),
+                                           _ptr(rlen), _ptr(redge), _ptr(rval), _ptr(hoff), _ptr(hidx)))
+        out = dict(centers=centers, radius=radius, valid=valid, hull_n=hn)
+        if rect:
+            out.update(rect_xy=rxy, rect_len=rlen, rect_edge=redge, rect_valid=rval)
+        if hull:
+            out.update(hull_off=hoff, hull_idx=hidx[: hoff[K]].copy())
+        return out
+
+    def cluster_shapes_dev(self, d_xy, d_labels, d_order, m, n, K, d_centers, d_radius, d_valid, d_hull_n=None,
+                           d_rect_xy=None, d_rect_len=None, d_rect_edge=None, d_rect_valid=None, d_hull_off=None,
+                           d_hull_idx=None):
+        """Device-pointer form (ints from tensor.data_ptr()); the outputs after d_valid may be None."""
+        self._chk(lib().vcp_cluster_shapes_dev(self._h, _ptr(d_xy), _ptr(d_labels), _ptr(d_order), C.c_int64(m),
+                                               C.c_int64(n), C.c_int32(K), _ptr(d_centers), _ptr(d_radius), _ptr(d_valid),
+                                               _ptr(d_hull_n), _ptr(d_rect_xy), _ptr(d_rect_len), _ptr(d_rect_edge),
+                                               _ptr(d_rect_valid), _ptr(d_hull_off), _ptr(d_hull_idx)))
+
+    def cluster_filter(self, labels, K, radius, valid, rect_len=None, rect_valid=None, max_radius=np.inf,
+                       max_aspect=np.inf):
+        """vcp_cluster_filter: dict(filtered [K], keep [n], kept_idx [n_kept], n_filtered, n_kept)."""
+        labels = np.ascontiguousarray(labels, np.int32)
+        n = len(labels)
+        radius = _f64(radius)
+        valid = np.ascontiguousarray(valid, np.uint8)
+        rect_len = None if rect_len is None else _f64(rect_len, 2)
+        rect_valid = None if rect_valid is None else np.ascontiguousarray(rect_valid, np.uint8)
+        filtered = np.zeros(K, np.uint8)
+        keep = np.zeros(n, np.uint8)
+        kept = np.zeros(max(n, 1), np.int32)
+        nf, nk = C.c_int32(0), C.c_int64(0)
+        self._chk(lib().vcp_cluster_filter(self._h, _ptr(labels), C.c_int64(n), C.c_int32(K), _ptr(radius), _ptr(valid),
+                                           _ptr(rect_len), _ptr(rect_valid), C.c_double(max_radius),
+                                           C.c_double(max_aspect), _ptr(filtered), _ptr(keep), _ptr(kept), C.byref(nf),
+                                           C.byref(nk)))
+        return dict(filtered=filtered, keep=keep, kept_idx=kept[: nk.value].copy(), n_filtered=nf.value, n_kept=nk.value)
+
+    def cluster_filter_dev(self, d_labels, n, K, d_radius, d_valid, d_rect_len, d_rect_valid, max_radius, max_aspect,
+                           d_filtered, d_keep=None, d_kept_idx=None):
+        """Device-pointer form; returns (n_filtered, n_kept)."""
+        nf, nk = C.c_int32(0), C.c_int64(0)
+        self._chk(lib().vcp_cluster_filter_dev(self._h, _ptr(d_labels), C.c_int64(n), C.c_int32(K), _ptr(d_radius),
+                                               _ptr(d_valid), _ptr(d_rect_len), _ptr(d_rect_valid),
+                                               C.c_double(max_radius), C.c_double(max_aspect), _ptr(d_filtered),
+                                               _ptr(d_keep), _ptr(d_kept_idx), C.byref(nf), C.byref(nk)))
+        return nf.value, nk.value
 
     def assign_truths(self, motor, truths_xy, truth_ids, radius):
         """MainForm.refreshClusList: (ids [n], number of points with no truth within radius)."""

@@ -51,6 +51,9 @@ struct vcp_ctx {
       b_out3, b_icp_part, b_aux0, b_aux1, b_aux2, b_aux3, b_aux4, b_aux5, b_pos, b_labk, b_sgroup, b_wl, b_hist, b_rec, b_nn_misc, b_nn_cells, b_nn_cid, b_nn_rec, b_nn_cur, b_nbr, b_nboff, b_sorted32, b_self, b_outcur, b_fineq, b_rec2, b_bstart, b_ctw, b_ctd, b_bstate;
   // k-distance (kdist.hip)
   DevBuf b_kd_in, b_kd_out, b_kd_outk, b_kd_part, b_kd_key, b_kd_val, b_kd_rec, b_kd_start, b_kd_heavy, b_kd_tmp;
+  // cluster shapes and the cluster filter (shapes.hip): hull points per member slot, the host forms' rectangle / hull /
+  // filter outputs, the filter's keep flags and their scan
+  DevBuf b_sh_hull, b_sh_out, b_sh_flag;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

@@ -198,6 +198,65 @@ struct Tools {
       if (map_to[k] != 0) dick[ids[k]] = map_to[k];
     return dick;
   }
+  // The circumscribed rectangle of every cluster that has one (vcp.h, "cluster shapes"): clusID = position + 1
+  struct Rect2D {
+    int clusID = 0;
+    double len0 = 0, len1 = 0;  // the side on the hull edge first
+    double corners[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  };
+  static std::vector<Rect2D> getRectangles(Context& c, const std::vector<ClusObj>& clusList, bool is3D) {
+    std::vector<Rect2D> rects;
+    const int32_t K = (int32_t)clusList.size();
+    std::vector<double> xy;
+    std::vector<int32_t> lab;
+    for (int32_t j = 0; j < K; j++)
+      for (const Point3D* p : clusList[j].li) {
+        xy.push_back(is3D ? p->X : p->motor_x);
+        xy.push_back(is3D ? p->Y : p->motor_y);
+        lab.push_back(j + 1);
+      }
+    const int64_t n = (int64_t)lab.size();
+    if (K == 0 || n == 0) return rects;
+    std::vector<double> cen(2 * K), rad(K), rxy(8 * K), rlen(2 * K);
+    std::vector<uint8_t> valid(K), rvalid(K);
+    c.check(vcp_cluster_shapes(c.get(), xy.data(), lab.data(), nullptr, n, n, K, cen.data(), rad.data(), valid.data(),
+                               nullptr, rxy.data(), rlen.data(), nullptr, rvalid.data(), nullptr, nullptr));
+    for (int32_t j = 0; j < K; j++) {
+      if (!rvalid[j]) continue;
+      Rect2D r;
+      r.clusID = j + 1;
+      r.len0 = rlen[2 * j];
+      r.len1 = rlen[2 * j + 1];
+      for (int q = 0; q < 8; q++) r.corners[q] = rxy[8 * j + q];
+      rects.push_back(r);
+    }
+    return rects;
+  }
+  // Tools.cs:70-74: the stable RemoveAll of every point whose clusterId is listed
+  static void removeFilterPointFromClustering(Context& c, std::vector<Point3D*>& dataSet, const std::vector<int>& filterID) {
+    if (filterID.empty() || dataSet.empty()) return;
+    int32_t K = 0;
+    for (int id : filterID) K = id > K ? id : K;
+    if (K <= 0) return;
+    // every listed id: a cluster of radius 1 against max_radius 0; the other ids are not valid, so never filtered
+    std::vector<double> rad(K, 0.0);
+    std::vector<uint8_t> valid(K, 0), filtered(K, 0);
+    for (int id : filterID)
+      if (id >= 1) rad[id - 1] = 1.0, valid[id - 1] = 1;
+    const int64_t n = (int64_t)dataSet.size();
+    std::vector<int32_t> lab(n), kept(n);
+    for (int64_t i = 0; i < n; i++) {
+      const int l = dataSet[i]->clusterId;
+      lab[i] = (l >= 1 && l <= K) ? l : 0;  // an id beyond the list is in nobody's filterID
+    }
+    int32_t nf = 0;
+    int64_t nk = 0;
+    c.check(vcp_cluster_filter(c.get(), lab.data(), n, K, rad.data(), valid.data(), nullptr, nullptr, 0.0, INFINITY,
+                               filtered.data(), nullptr, kept.data(), &nf, &nk));
+    std::vector<Point3D*> out((size_t)nk);
+    for (int64_t t = 0; t < nk; t++) out[t] = dataSet[kept[t]];
+    dataSet.swap(out);
+  }
 };
 
 // MainForm.getClusterFromMotor + DoWork3/StartCode + CompleteWork3 (FrmMain.cs:1214-1291, :2782-2794, :1432-1520)

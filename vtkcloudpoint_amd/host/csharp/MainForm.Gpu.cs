@@ -1,8 +1,9 @@
 // MainForm.Gpu.cs -- the MainForm members on the hot path, as a drop-in: MainForm is already `partial`
 // (FrmMain.cs / FrmMain.Designer.cs); delete calMatchedCoords + RecorrectMatchingPtsByDistance (FrmMain.cs:3572-3618),
-// refreshClusList (:3437-3467) and ICP() (:841-907) from FrmMain.cs, replace the row loop of AddFolder (:991-1090) by
+// refreshClusList (:3437-3467), ICP() (:841-907), FilterClustersByRadius (:1905-1920) and removePointByRadius (:3743-3746)
+// from FrmMain.cs, replace the row loop of AddFolder (:991-1090) by
 // the call shown at AddScanRows below, and add this file.  Field names are the reference's own (centers, trues,
-// rawData, clusList, truePointCloud, truePointVertices, M, ren, vtkControl, matchedID, x_angle, y_angle, pathList,
+// rawData, clusList, circles, filterID, clusterSum, truePointCloud, truePointVertices, M, ren, vtkControl, matchedID, x_angle, y_angle, pathList,
 // PtsInRegionTxt, toolStripStatusLabelCurrentPointCount, trueScale, centroidScale, scale, clock, clock_y, clock_x).
 using System;
 using System.Collections.Generic;
@@ -248,6 +249,50 @@ namespace vtkPointCloud
                 rawData.Add(point);
             }
             return duplicates;
+        }
+
+        // FrmMain.cs:1905-1920: filterID = the clusters whose circumscribed circle exceeds `radius`.  The circles of
+        // clusters 1..clusterSum (Tools.getCircles: clusID = position + 1) go to vcp_cluster_filter as one array each;
+        // a cluster without a circle (<= 3 points) is never listed.
+        public void FilterClustersByRadius(double radius)
+        {
+            FilterClusters(radius, double.PositiveInfinity);
+            this.toolStripStatusLabel2.Text = "超过阈值半径聚类数：" + filterID.Count;
+            showCircle(circles, 2, rawData, centers);
+        }
+
+        // The README's second criterion ("length / width ratio", on the circumscribed rectangle): filterID = the clusters
+        // whose longer side exceeds `aspect` times the shorter one.  No counterpart body in FrmMain.cs.
+        public void FilterClustersByAspect(double aspect)
+        {
+            FilterClusters(double.PositiveInfinity, aspect);
+            this.toolStripStatusLabel2.Text = "超过阈值长宽比聚类数：" + filterID.Count;
+        }
+
+        void FilterClusters(double maxRadius, double maxAspect)
+        {
+            filterID.Clear();
+            int K = clusterSum;
+            if (K <= 0) return;
+            double[] rad = new double[K], rlen = new double[2 * K];
+            byte[] valid = new byte[K], rvalid = new byte[K], filtered = new byte[K];
+            foreach (Point2D c in circles) { rad[c.clusID - 1] = c.radius; valid[c.clusID - 1] = 1; }
+            bool aspect = !double.IsPositiveInfinity(maxAspect) && !double.IsNaN(maxAspect);
+            if (aspect)
+                foreach (Tools.Rect2D r in Tools.getRectangles(clusList, false))
+                { rlen[2 * (r.clusID - 1)] = r.len0; rlen[2 * (r.clusID - 1) + 1] = r.len1; rvalid[r.clusID - 1] = 1; }
+            int nf; long nk;
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_cluster_filter(lease.Ctx, new int[0], 0, K, rad, valid, aspect ? rlen : null,
+                    aspect ? rvalid : null, maxRadius, maxAspect, filtered, null, null, out nf, out nk));
+            for (int j = 0; j < K; j++) if (filtered[j] != 0) filterID.Add(j + 1);
+        }
+
+        // FrmMain.cs:3743-3746
+        public void removePointByRadius()
+        {
+            Tools.removeFilterPointFromClustering(ref rawData, filterID);
+            Tools.removeFilterPointFromClustering(ref centers, filterID);
         }
     }
 }

@@ -1,5 +1,5 @@
 // Tools.Gpu.cs -- the Tools statics on the hot path, as a drop-in: add `partial` to the declaration in
-// vtkPointCloud/BaseClass/Tools.cs:11 (`partial class Tools`), delete the six originals named below from that file
+// vtkPointCloud/BaseClass/Tools.cs:11 (`partial class Tools`), delete the originals named below from that file
 // (same names, same signatures, same in-place effects) and add this file to the project.  Nothing else in Tools.cs
 // changes; the callers (FrmMain.cs:1533, Clustering.cs:125-181, SureDistanceFilter.cs:74, FrmMain.cs:1539-1540) stay
 // as they are.
@@ -172,6 +172,72 @@ namespace vtkPointCloud
                 circles.Add(c);
             }
             return circles;
+        }
+
+        // The circumscribed rectangle the reference's README pairs with the circle (no body in Tools.cs; vcp.h, "cluster
+        // shapes"): one Rect2D per cluster that has one -- more than 3 points that are not all equal -- from the same
+        // pass that gives getCircles its circles.  clusID = position + 1, like getCircles.
+        public class Rect2D
+        {
+            public int clusID;
+            public double len0, len1;              // the side on the hull edge first
+            public double[] corners = new double[8];
+            public double Aspect { get { return Math.Max(len0, len1) / Math.Min(len0, len1); } }   // +inf on a line
+        }
+
+        static public List<Rect2D> getRectangles(List<ClusObj> clusList, bool is3D)
+        {
+            List<Rect2D> rects = new List<Rect2D>();
+            int K = clusList.Count, n = 0;
+            for (int j = 0; j < K; j++) n += clusList[j].li.Count;
+            if (K == 0 || n == 0) return rects;
+            double[] xy = new double[2 * n];
+            int[] lab = new int[n];
+            int t = 0;
+            for (int j = 0; j < K; j++)
+                foreach (Point3D p in clusList[j].li)
+                {
+                    xy[2 * t] = is3D ? p.X : p.motor_x; xy[2 * t + 1] = is3D ? p.Y : p.motor_y; lab[t] = j + 1; t++;
+                }
+            double[] cen = new double[2 * K], rad = new double[K], rxy = new double[8 * K], rlen = new double[2 * K];
+            byte[] valid = new byte[K], rvalid = new byte[K];
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_cluster_shapes(c.Ctx, xy, lab, null, n, n, K, cen, rad, valid, null, rxy, rlen,
+                    null, rvalid, null, null));
+            for (int j = 0; j < K; j++)
+            {
+                if (rvalid[j] == 0) continue;
+                Rect2D r = new Rect2D();
+                r.clusID = j + 1; r.len0 = rlen[2 * j]; r.len1 = rlen[2 * j + 1];
+                Array.Copy(rxy, 8 * j, r.corners, 0, 8);
+                rects.Add(r);
+            }
+            return rects;
+        }
+
+        // Tools.removeFilterPointFromClustering, Tools.cs:70-74: the stable RemoveAll, with the membership test of
+        // filterID.Contains done once per cluster id on the GPU side of vcp_cluster_filter (labels beyond the largest
+        // filtered id are kept, like Contains would)
+        static public void removeFilterPointFromClustering(ref List<Point3D> dataSet, List<int> filterID)
+        {
+            if (filterID.Count == 0) return;
+            int n = dataSet.Count, K = 0;
+            foreach (int id in filterID) K = Math.Max(K, id);
+            if (n == 0 || K <= 0) return;
+            // every listed id becomes a cluster of radius 1 against max_radius 0; other ids are not valid, so never filtered
+            double[] rad = new double[K];
+            byte[] valid = new byte[K], filtered = new byte[K];
+            foreach (int id in filterID) if (id >= 1) { rad[id - 1] = 1.0; valid[id - 1] = 1; }
+            int[] lab = new int[n], kept = new int[n];
+            for (int i = 0; i < n; i++) { int l = dataSet[i].clusterId; lab[i] = (l >= 1 && l <= K) ? l : 0; }
+            int nf; long nk;
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_cluster_filter(c.Ctx, lab, n, K, rad, valid, null, null, 0.0, double.PositiveInfinity,
+                    filtered, null, kept, out nf, out nk));
+            List<Point3D> outp = new List<Point3D>((int)nk);
+            for (long t = 0; t < nk; t++) outp.Add(dataSet[kept[t]]);
+            dataSet.Clear();
+            dataSet.AddRange(outp);   // RemoveAll mutates the list the caller holds
         }
 
         // MainForm.getClusterFromMotor + DoWork3 + the labelling half of CompleteWork3

@@ -75,6 +75,18 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_mcc(IntPtr ctx, double[] xy, int[] labels, long[] order, long m, long n,
             int K, double[] centers, double[] radius, byte[] valid, int[] hull_n);
 
+        // hull + circle + minimum-area bounding rectangle of every cluster (vcp.h, "cluster shapes"); every array after
+        // valid may be null (hull_off / hull_idx: both or neither)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_shapes(IntPtr ctx, double[] xy, int[] labels, long[] order, long m,
+            long n, int K, double[] centers, double[] radius, byte[] valid, int[] hull_n, double[] rect_xy, double[] rect_len,
+            int[] rect_edge, byte[] rect_valid, int[] hull_off, int[] hull_idx);
+
+        // MainForm.FilterClustersByRadius (FrmMain.cs:1905-1920) with the length / width criterion beside it, and the
+        // stable removal of Tools.removeFilterPointFromClustering (Tools.cs:70-74); rect_len / rect_valid, keep, kept_idx may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_filter(IntPtr ctx, int[] labels, long n, int K, double[] radius,
+            byte[] valid, double[] rect_len, byte[] rect_valid, double max_radius, double max_aspect, byte[] filtered,
+            byte[] keep, int[] kept_idx, out int n_filtered, out long n_kept);
+
         // per-row work of MainForm.AddFolder (FrmMain.cs:1011-1090)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_import_convert(IntPtr ctx, double[] rows, long n, double x_angle,
             double y_angle, int xdir, int ydir, int dedupe, double[] xyz, byte[] state, out long kept, out long duplicates);
@@ -99,6 +111,12 @@ namespace vtkPointCloud
             out int cf_out, out long dist_evals);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_centroids_dev(IntPtr ctx, IntPtr d_xyz, IntPtr d_motor, IntPtr d_labels,
             long n, int K, IntPtr d_c3, IntPtr d_c2, IntPtr d_counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_shapes_dev(IntPtr ctx, IntPtr d_xy, IntPtr d_labels, IntPtr d_order,
+            long m, long n, int K, IntPtr d_centers, IntPtr d_radius, IntPtr d_valid, IntPtr d_hull_n, IntPtr d_rect_xy,
+            IntPtr d_rect_len, IntPtr d_rect_edge, IntPtr d_rect_valid, IntPtr d_hull_off, IntPtr d_hull_idx);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_filter_dev(IntPtr ctx, IntPtr d_labels, long n, int K,
+            IntPtr d_radius, IntPtr d_valid, IntPtr d_rect_len, IntPtr d_rect_valid, double max_radius, double max_aspect,
+            IntPtr d_filtered, IntPtr d_keep, IntPtr d_kept_idx, out int n_filtered, out long n_kept);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_kdist_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
             int k, IntPtr d_kdist, IntPtr d_knn);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_dev(IntPtr ctx, IntPtr d_model, long nm, IntPtr d_data, long nd,

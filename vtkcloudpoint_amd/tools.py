@@ -141,6 +141,65 @@ def getCircles(clusList, is3D, ctx=None):
 Tools.getCircles = staticmethod(getCircles)
 
 
+class Rect2D:
+    """Minimum-area bounding rectangle of one cluster (include/vcp.h, "cluster shapes"): the four corners, the two
+    side lengths (the side on the hull edge first) and clusID = position + 1, like the circles."""
+
+    def __init__(self, corners, len0, len1, cluID=0):
+        self.corners = np.array(corners, np.float64).reshape(4, 2)
+        self.len0, self.len1, self.clusID = float(len0), float(len1), int(cluID)
+
+
+def _cluster_arrays(clusList, is3D):
+    pts, lab = [], []
+    for j, ob in enumerate(clusList):
+        for p in ob.li:
+            pts.append((p.X, p.Y) if is3D else (p.motor_x, p.motor_y))
+            lab.append(j + 1)
+    return np.array(pts, np.float64).reshape(-1, 2), np.array(lab, np.int32)
+
+
+def getRectangles(clusList, is3D, ctx=None):
+    """The circumscribed rectangle the reference's README pairs with the circle: one Rect2D per cluster that has one
+    (more than 3 points, not all equal), from the pass that also gives getCircles its circles (vcp_cluster_shapes)."""
+    ctx = ctx or default_context()
+    K = len(clusList)
+    xy, lab = _cluster_arrays(clusList, is3D)
+    if K == 0 or not len(lab):
+        return []
+    r = ctx.cluster_shapes(xy, lab, K, hull=False)
+    return [Rect2D(r["rect_xy"][j], r["rect_len"][j, 0], r["rect_len"][j, 1], j + 1) for j in range(K) if r["rect_valid"][j]]
+
+
+def filterClusters(clusList, is3D, max_radius=np.inf, max_aspect=np.inf, ctx=None):
+    """MainForm.FilterClustersByRadius (FrmMain.cs:1905-1920) with the README's length / width criterion beside it:
+    the filterID list (clusID = position + 1) of the clusters whose circle radius exceeds max_radius or whose rectangle
+    is longer than max_aspect times its width.  A NaN or infinite threshold switches its criterion off."""
+    ctx = ctx or default_context()
+    K = len(clusList)
+    xy, lab = _cluster_arrays(clusList, is3D)
+    if K == 0 or not len(lab):
+        return []
+    r = ctx.cluster_shapes(xy, lab, K, hull=False)
+    f = ctx.cluster_filter(lab, K, r["radius"], r["valid"], r["rect_len"], r["rect_valid"], max_radius, max_aspect)
+    return [j + 1 for j in range(K) if f["filtered"][j]]
+
+
+def removeFilterPointFromClustering(dataSet, filterID):
+    """Tools.removeFilterPointFromClustering (BaseClass/Tools.cs:70-74): a stable RemoveAll, in place (the C# takes the
+    list by ref), of every point whose clusterId is listed.  Host-side: the bulk form over arrays is
+    vcp_cluster_filter's kept_idx."""
+    if len(filterID) == 0:
+        return
+    ids = set(int(i) for i in filterID)
+    dataSet[:] = [p for p in dataSet if p.clusterId not in ids]
+
+
+Tools.getRectangles = staticmethod(getRectangles)
+Tools.filterClusters = staticmethod(filterClusters)
+Tools.removeFilterPointFromClustering = staticmethod(removeFilterPointFromClustering)
+
+
 class ClusterPipeline:
     """The MainForm state and methods on the path: getClusterFromMotor + DoWork3/StartCode + CompleteWork3
     (FrmMain.cs:1214-1291, :1340-1361, :2782-2794, :1432-1544) as one blocking call."""
