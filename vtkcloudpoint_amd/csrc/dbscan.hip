@@ -6,15 +6,16 @@
 // C#'s (SSE2) evaluation -- everywhere else; the grid only proposes candidates and is conservative by construction
 // (cell edge = eps + the rounding of the binary32 coordinates it bins on, candidates re-tested).
 //
-// Data layout in HBM (n points, original index i, cell-ordered position p, GD = dimension of the metric):
-//   cellcnt [ncells+1] u32   first position of each cell (x-fastest linear cell id)
+// Data layout in HBM (n points, nin <= n of them in this call's grid, original index i, cell-ordered position p, GD =
+// dimension of the metric; the host's view of these arrays is `Workspace`, carved from the context's buffers by ws_carve):
+//   CellTab                  first position of each cell (x-fastest linear cell id), 16 bytes per word of 32 cells plus the
+//                            full starts of the populous words (grid_common.hpp); built by the partition (gridbuild.hip)
 //   sorted32[nin] f32x2 / x4 coordinates relative to the grid origin in binary32, cell order: binning and screening
-//   (binary64 coordinates)   read through ExactSrc: the caller's array by index after the partition build
-//                            (gridbuild.hip), a cell-ordered copy `sorted` after the sort-based build (grids too large
-//                            for the partition: cellof / skey = cell ids by index / in cell order, rocPRIM radix sort)
+//   (binary64 coordinates)   stay in the caller's array, read by index through ExactSrc where the screen cannot decide
 //   pos     [n] u32          position of original index i (NONE = excluded from this call); not built when the output
 //                            goes through the partition's windows
 //   sord    [nin] u32        "list position" of the point (original index, or the caller's ord)
+//   cellof  [nin] u32        (b_cellof) original index of the point, written only with d_ord, where sord is not the index
 //   sgroup  [nin] i32        group (block) of the point, grouped calls only
 //   flags   [nin] u8         bit0 core, bit1 classed on entry, bit2 expanding, bit3 border candidate; high nibble:
 //                            number of recorded neighbours (nbr / nboff: the lists, packed per block of 256 positions)
@@ -24,8 +25,10 @@
 //   seedflag[n/32] u32       bitmap of seed list positions; seedpref = popcount prefix per word
 //   rootk   [nin] u32        seed rank of the point's cluster (NONE = not expanding); clseed [K]: seed per rank
 //   labk    [nin] u32        per point: (1 + seed rank of its final cluster, 0 = none) << 2 | core | classed<<1
-// Passes: bounds -> grid build (partition, or cell keys / sort / cell starts / gather) -> core count + lists + work
-// lists -> union -> flatten / number -> border -> output.
+//   counters[CNT_WORDS] u64  the totals a call reads back (grid_common.hpp: CNT_*)
+// Passes (run_dbscan, one stage function each): bounds -> all-pairs early-out -> grid geometry (host) -> grid build
+// (partition) -> core count + lists + work lists -> union -> flatten / number (staged calls stop here and hand over:
+// vcp_slab_finish does the rest) -> border -> output -> readback.
 #include <string.h>
 
 #include <cmath>
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(TPB) void k_wl_fill(const uint8_t* __restrict__ fla
   }
   if (blockIdx.x == 0) {
     for (uint32_t wd = gridDim.x * 8u + threadIdx.x; wd < nw; wd += TPB) seedflag[wd] = 0u;
-    if (threadIdx.x < 68) counters[threadIdx.x] = 0ull;
+    if (threadIdx.x < CNT_WORDS) counters[threadIdx.x] = 0ull;
   }
   const uint32_t nin = *ct.nin;
   const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -1080,7 +1083,7 @@ __global__ __launch_bounds__(TPB) void k_rootk(const uint32_t* __restrict__ pare
   }
 }
 
-// border points the C# queried twice: one atomic per WORKGROUP, spread over 32 slots (counters[36..68)).  One atomic
+// border points the C# queried twice: one atomic per WORKGROUP, spread over the CNT_SPREAD slots at CNT_TWICE.  One atomic
 // per wave on a single word cost 0.2 ms here: about half of 53 k waves hit it, and same-address atomics serialise at
 // ~11 ns each.
 __device__ __forceinline__ void twice_add(unsigned twice, unsigned long long* __restrict__ counters) {
@@ -1091,7 +1094,7 @@ __device__ __forceinline__ void twice_add(unsigned twice, unsigned long long* __
   if (threadIdx.x == 0) {
     unsigned t = 0;
     for (int k = 0; k < TPB / 64; k++) t += tw[k];
-    if (t) atomicAdd(&counters[36 + (blockIdx.x & 31)], (unsigned long long)t);
+    if (t) atomicAdd(&counters[CNT_TWICE + (blockIdx.x & (CNT_SPREAD - 1))], (unsigned long long)t);
   }
 }
 
@@ -1271,7 +1274,7 @@ __global__ __launch_bounds__(TPB) void k_output(int64_t n, const uint32_t* __res
     if (threadIdx.x == 0) {
       unsigned t = 0;
       for (int k = 0; k < TPB / 64; k++) t += wcnt[k];
-      if (t) atomicAdd(&counters[4 + (blockIdx.x & 31)], (unsigned long long)t);
+      if (t) atomicAdd(&counters[CNT_UNCLASSED + (blockIdx.x & (CNT_SPREAD - 1))], (unsigned long long)t);
     }
   }
 }
@@ -1511,76 +1514,289 @@ unsigned list_perblk(int64_t n) {
   return vcp_blocks(band, TPB);
 }
 
-// GD = dimension of the metric (grid and sorted copy); `stride` = doubles per input point
-template <int GD, int METRIC, bool GROUPED>
-int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, double eps, int min_pts, int32_t cf_in,
-               const uint8_t* d_in_classed, int32_t* d_labels, uint8_t* d_is_core, uint8_t* d_is_classed,
-               int32_t* cf_out, int64_t* dist_evals, const DbscanExt* ext) {
-  hipStream_t st = ctx->stream;
-  const unsigned nb = vcp_blocks(n, TPB);
-  const int32_t* d_group = GROUPED ? ext->d_group : nullptr;
-  const uint32_t* d_ord = ext ? ext->d_ord : nullptr;
-  const int G = GROUPED ? ext->G : 0;
-  const int glo = GROUPED ? ext->only_lo : 0;
-  const int ghi = GROUPED ? (ext->only_hi < 0 ? G : ext->only_hi) : 0;
+// ---- the host driver ---------------------------------------------------------------------------------------------------
+// Developer switches, read from the environment once per process; tools/gpu/ab.sh runs the benchmark once per value of one
+// of them.  None changes a result, only the path that computes it.
+//   VCP_CELL_BUDGET=k  grid cells per point the grid may have before it is coarsened (default 32, clamped to 1..4096)
+//   VCP_NO_SCREEN      no binary32 screen: every candidate pair takes the exact binary64 test
+//   VCP_NO_LISTS       no recorded neighbour lists (NbrOut::NB = 0): the union and the border rule search again
+//   VCP_CORE_CAP=k     entries a core point keeps of its list, instead of the choice between CORE_LIST and all of them
+//   VCP_CORE_GLOBAL    grouped calls count through k_core instead of k_core_lds
+//   VCP_JOIN_ALL=0|1   whether every expanding point joins along its list (k_flatten0<2>) or only the roots, instead of
+//                      the choice by points per cell
+struct Switches {
+  int64_t cells_per_point;
+  bool screen_off, lists_off, core_global;
+  int core_cap, join_all;  // -1 = not set
+};
+const Switches& switches() {
+  static const Switches sw = [] {
+    Switches s;
+    const char* e = getenv("VCP_CELL_BUDGET");
+    const long v = e ? atol(e) : 32;
+    s.cells_per_point = (int64_t)(v < 1 ? 1 : v > 4096 ? 4096 : v);
+    s.screen_off = getenv("VCP_NO_SCREEN") != nullptr;
+    s.lists_off = getenv("VCP_NO_LISTS") != nullptr;
+    s.core_global = getenv("VCP_CORE_GLOBAL") != nullptr;
+    s.core_cap = getenv("VCP_CORE_CAP") ? atoi(getenv("VCP_CORE_CAP")) : -1;
+    s.join_all = getenv("VCP_JOIN_ALL") ? atoi(getenv("VCP_JOIN_ALL")) : -1;
+    return s;
+  }();
+  return sw;
+}
 
-  // 1. bounds over finite coordinates
+// The engine's readbacks: laid over the first bytes of ctx->pinned (vcp_ctx.hpp lists who else reads back there).  Every
+// field is consumed right after the synchronisation that follows its copy.
+struct EnginePinned {
+  double bounds[8];  // min x, y, z, max x, y, z, number of points with a non-finite coordinate (vcp_bounds writes these 7)
+  uint32_t unclassed;                     // all-pairs and degenerate calls: points not classed on entry
+  uint32_t n_comp;                        // staged calls: local components
+  unsigned long long counters[CNT_WORDS];  // the device counter block
+};
+static_assert(sizeof(EnginePinned) <= 1024, "the engine's region of vcp_ctx::pinned");
+EnginePinned* engine_pinned(vcp_ctx* ctx) { return reinterpret_cast<EnginePinned*>(ctx->pinned); }
+
+// One engine call: the caller's arguments (vcp_dbscan_engine fills them in this order) and what the stages derive from them.
+struct Call {
+  const double* d_coords;
+  int64_t n;
+  int stride, metric;  // doubles per input point
+  double eps;
+  int min_pts;
+  int32_t cf_in;
+  const uint8_t* d_in_classed;
+  int32_t* d_labels;
+  uint8_t *d_is_core, *d_is_classed;
+  int32_t* cf_out;
+  int64_t* dist_evals;
+  const DbscanExt* ext;
+  // call_derive
+  int gd = 2;  // dimension of the metric (grid and sorted32)
+  unsigned nb = 0;
+  const int32_t* d_group = nullptr;
+  const uint32_t* d_ord = nullptr;
+  uint32_t* d_group_twice = nullptr;
+  int G = 0, glo = 0, ghi = 0;
+  bool slab = false;
+  // stage_bounds
+  double* h = nullptr;  // EnginePinned::bounds; grid_geometry narrows it to the grid's range
+  bool all_finite = false;
+  // run_dbscan, grid_geometry
+  double thr = 0.0;
+  GridP g;
+  Screen sc{-1.0f, INFINITY};
+  bool flags_set = false, part_out = false;
+  ExactSrc xs{nullptr, nullptr, 0};   // stage_grid_build
+  NbrOut no{nullptr, nullptr, 0, 0};  // stage_core
+};
+void call_derive(Call& c) {
+  const DbscanExt* ext = c.ext;
+  const bool grouped = ext && ext->d_group;
+  c.gd = c.metric == VCP_L2_3D ? 3 : 2;
+  c.nb = vcp_blocks(c.n, TPB);
+  c.d_group = grouped ? ext->d_group : nullptr;
+  c.d_ord = ext ? ext->d_ord : nullptr;
+  c.d_group_twice = grouped ? ext->d_group_twice : nullptr;
+  c.G = grouped ? ext->G : 0;
+  c.glo = grouped ? ext->only_lo : 0;
+  c.ghi = grouped ? (ext->only_hi < 0 ? c.G : ext->only_hi) : 0;
+  c.slab = ext && ext->slab;
+}
+BoundsSrc bounds_src(const Call& c) { return BoundsSrc{c.d_coords, c.n, c.gd, c.stride, c.d_group, c.glo, c.ghi}; }
+
+// The engine's view of the context's workspace buffers.  ws_reserve_misc / ws_reserve size them, misc_carve / ws_carve
+// are the only places that know where things lie inside them; nothing is kept between calls (vcp_slab_finish carves
+// again from (n, nb, ncells) in SlabState).
+// b_misc is needed before the grid is known: [rb * 8] partials of the bounds pass | [8] bounds | the counter block.
+struct MiscView {
+  double* d_part;
+  double* d_bounds;
+  unsigned long long* counters;  // [CNT_WORDS] (grid_common.hpp)
+  uint32_t* d_total;             // the u32 in counters[CNT_SEED_TOTAL]
+};
+struct Workspace : MiscView {
+  uint4* ctwords;     // the cell table (grid_common.hpp: CellTab): 16 bytes per word of 32 cells,
+  uint32_t* ctdense;  // the full starts of the populous words,
+  uint32_t* ctcount;  // and two counters behind the words: [0] populous words, [1] points in the grid
+  CellTab ct;
+  uint32_t *cellof, *pos, *sord, *parent, *minord, *rootk, *clseed, *labk;  // (the file's header says what they hold)
+  float* sorted32;
+  uint8_t* flags;
+  int32_t* sgroup;     // grouped calls only
+  uint32_t nw;         // bitmap words: positions 0..n (rank(n) = seed total)
+  uint32_t* seedflag;  // seed bitmap [nw]
+  uint32_t* seedpref;  // per-word prefix [nw] (16-B aligned)
+  // b_wl: [nb + 2] entry counts per block of the E list | [nb + 2] of the B list | [n] E list | [n] B list
+  uint32_t *blkE, *blkB;
+  WorkList wlE, wlB;
+  unsigned nbl;  // workgroups of a list kernel: see wl_fetch
+};
+
+int ws_reserve_misc(vcp_ctx* ctx, int64_t n) {
+  return vcp_ensure(ctx, ctx->b_misc, (size_t)(vcp_bounds_parts(n) * 8 + 96) * sizeof(double));
+}
+MiscView misc_carve(vcp_ctx* ctx, int64_t n) {
+  MiscView m;
+  m.d_part = ctx->b_misc.as<double>();
+  m.d_bounds = m.d_part + (size_t)vcp_bounds_parts(n) * 8;
+  m.counters = reinterpret_cast<unsigned long long*>(m.d_bounds + 8);
+  m.d_total = reinterpret_cast<uint32_t*>(m.counters + CNT_SEED_TOTAL);
+  return m;
+}
+static_assert((8 + CNT_WORDS) <= 96, "b_misc: bounds and counters behind the partials");
+
+int ws_reserve(vcp_ctx* ctx, int64_t n, unsigned nb, int gd, bool grouped, uint32_t ncells) {
+  const size_t ctw = vcp_ct_words(ncells), ctd = vcp_ct_dense_cap(n, ncells);
+  VCP_TRY(vcp_ensure(ctx, ctx->b_ctw, ctw * 16 + 64));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_ctd, ctd * 128));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_cellof, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_pos, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_sorted32, (size_t)n * (gd == 2 ? 2 : 4) * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_sidx, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_flags, (size_t)n));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_parent, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_minord, (size_t)n * 4));
+  const uint32_t nw = (uint32_t)(n / 32 + 2);
+  VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, ((size_t)nw * 2 + 8) * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_rootcl, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_clseed, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_labk, (size_t)n * 4));
+  if (grouped) VCP_TRY(vcp_ensure(ctx, ctx->b_sgroup, (size_t)n * 4));
+  VCP_TRY(vcp_ensure(ctx, ctx->b_wl, ((size_t)n * 2 + (size_t)(nb + 2) * 2) * 4 + 256));
+  return VCP_OK;
+}
+Workspace ws_carve(vcp_ctx* ctx, int64_t n, unsigned nb, bool grouped, uint32_t ncells) {
+  Workspace w;
+  static_cast<MiscView&>(w) = misc_carve(ctx, n);
+  w.ctwords = ctx->b_ctw.as<uint4>();
+  w.ctdense = ctx->b_ctd.as<uint32_t>();
+  w.ctcount = reinterpret_cast<uint32_t*>(ctx->b_ctw.as<char>() + vcp_ct_words(ncells) * 16);
+  w.ct = CellTab{w.ctwords, w.ctdense, w.ctcount + 1};
+  w.cellof = ctx->b_cellof.as<uint32_t>();
+  w.pos = ctx->b_pos.as<uint32_t>();
+  w.sorted32 = ctx->b_sorted32.as<float>();
+  w.sord = ctx->b_sidx.as<uint32_t>();
+  w.flags = ctx->b_flags.as<uint8_t>();
+  w.parent = ctx->b_parent.as<uint32_t>();
+  w.minord = ctx->b_minord.as<uint32_t>();
+  w.nw = (uint32_t)(n / 32 + 2);
+  w.seedflag = ctx->b_seedflag.as<uint32_t>();
+  w.seedpref = w.seedflag + ((w.nw + 3) & ~3u);
+  w.rootk = ctx->b_rootcl.as<uint32_t>();
+  w.clseed = ctx->b_clseed.as<uint32_t>();
+  w.labk = ctx->b_labk.as<uint32_t>();
+  w.sgroup = grouped ? ctx->b_sgroup.as<int32_t>() : nullptr;
+  w.blkE = ctx->b_wl.as<uint32_t>();
+  w.blkB = w.blkE + (nb + 2);
+  w.wlE.list = w.blkB + (nb + 2);
+  w.wlB.list = w.wlE.list + n;
+  w.wlE.scan = w.blkE;
+  w.wlB.scan = w.blkB;
+  w.wlE.nblk = w.wlB.nblk = nb;
+  w.wlE.perblk = w.wlB.perblk = list_perblk(n);
+  w.nbl = 8u * LCHUNK * w.wlE.perblk;
+  return w;
+}
+
+// What a call reads back when its last kernel is enqueued: the counter block, summed to the totals the host needs.
+// Closes the last phase and synchronises.
+struct Totals {
+  uint32_t K;                      // clusters
+  unsigned long long unclassed;    // points not classed on entry (counted only with an isClassed input)
+  unsigned long long twice;        // border points queried twice
+  unsigned long long slot0;        // CNT_LONELY / CNT_MISSING
+  unsigned long long group_evals;  // grouped calls
+};
+int read_totals(vcp_ctx* ctx, const MiscView& ws, Totals& t) {
+  unsigned long long* hc = engine_pinned(ctx)->counters;
+  VCP_HIP(ctx, hipMemcpyAsync(hc, ws.counters, CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  VCP_TRY(vcp_phase_finish(ctx));
+  VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  t.K = *reinterpret_cast<uint32_t*>(hc + CNT_SEED_TOTAL);
+  t.slot0 = hc[CNT_LONELY];
+  t.group_evals = hc[CNT_GROUP_EVALS];
+  t.unclassed = t.twice = 0;
+  for (int k = 0; k < CNT_SPREAD; k++) {
+    t.unclassed += hc[CNT_UNCLASSED + k];
+    t.twice += hc[CNT_TWICE + k];
+  }
+  return VCP_OK;
+}
+
+// 1. bounds over the finite coordinates: the caller's box, or the bounds pass
+int stage_bounds(vcp_ctx* ctx, Call& c) {
   vcp_phase(ctx, "bounds");
-  const int rb = vcp_bounds_parts(n);
-  VCP_TRY(vcp_ensure(ctx, ctx->b_misc, (size_t)(rb * 8 + 96) * sizeof(double)));
-  double* d_part = ctx->b_misc.as<double>();
-  double* d_bounds = d_part + (size_t)rb * 8;
-  double* h = reinterpret_cast<double*>(ctx->pinned);
-  const BoundsSrc src{d_coords, n, GD, stride, d_group, glo, ghi};
-  if (ext && ext->h_bbox) {  // the caller has seen every point: finite, inside this box
-    for (int a = 0; a < 6; a++) h[a] = ext->h_bbox[a];
+  VCP_TRY(ws_reserve_misc(ctx, c.n));
+  double* h = engine_pinned(ctx)->bounds;
+  if (c.ext && c.ext->h_bbox) {  // the caller has seen every point: finite, inside this box
+    for (int a = 0; a < 6; a++) h[a] = c.ext->h_bbox[a];
     h[6] = 0.0;
   } else {
-    VCP_TRY(vcp_bounds(ctx, src, d_part, d_bounds, h));
+    const MiscView m = misc_carve(ctx, c.n);
+    VCP_TRY(vcp_bounds(ctx, bounds_src(c), m.d_part, m.d_bounds, h));
   }
-  const bool all_finite = h[6] == 0.0;
+  c.h = h;
+  c.all_finite = h[6] == 0.0;
+  return VCP_OK;
+}
 
-  const double thr = (METRIC == VCP_L1_2D) ? eps : l2_threshold(eps);
-  if (!GROUPED && all_finite && !(ext && ext->slab)) {
-    // monotone rounding: |dx| <= hi-lo on every axis, so the box measure bounds every pair's distance form
-    const double wx = h[3] - h[0], wy = h[4] - h[1], wz = GD == 3 ? h[5] - h[2] : 0.0;
-    const double box = METRIC == VCP_L1_2D ? std::fabs(wx) + std::fabs(wy)
-                       : METRIC == VCP_L2_2D ? wx * wx + wy * wy : wx * wx + wy * wy + wz * wz;
-    if (box <= thr) {
-      vcp_phase(ctx, "all_pairs");
-      VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, (size_t)(n + 2) * 4));
-      uint32_t* f = ctx->b_seedflag.as<uint32_t>();
-      uint32_t* d_tot = reinterpret_cast<uint32_t*>(d_bounds + 8);
-      unsigned long long unclassed = (unsigned long long)n;
-      if (d_in_classed) {
-        VCP_LAUNCH(ctx, k_unclassed_flag, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n);
-        VCP_TRY(vcp_exclusive_scan_u32(ctx, f, f, n, d_tot));
-        uint32_t* hu = reinterpret_cast<uint32_t*>(ctx->pinned) + 32;
-        VCP_HIP(ctx, hipMemcpyAsync(hu, d_tot, 4, hipMemcpyDeviceToHost, st));
-        VCP_HIP(ctx, hipStreamSynchronize(st));
-        unclassed = hu[0];
-      }
-      const int core = n >= (int64_t)min_pts;
-      const int have_seed = unclassed > 0;
-      VCP_LAUNCH(ctx, k_all_pairs, dim3(nb), dim3(TPB), 0, st, d_in_classed, n, core, have_seed, cf_in, d_labels,
-                      d_is_core, d_is_classed);
-      VCP_TRY(vcp_phase_finish(ctx));
-      VCP_HIP(ctx, hipStreamSynchronize(st));
-      const int made = core && have_seed;
-      if (cf_out) *cf_out = cf_in + made;
-      if (dist_evals) *dist_evals = (int64_t)(unclassed + (unsigned long long)made) * n;
-      return VCP_OK;
-    }
+// f[i] = 1 where point i is not classed on entry, scanned in place (its rank among them); their number goes to *d_total
+int unclassed_ranks(vcp_ctx* ctx, const Call& c, uint32_t* f, uint32_t* d_total) {
+  VCP_LAUNCH(ctx, k_unclassed_flag, dim3(c.nb), dim3(TPB), 0, ctx->stream, c.d_in_classed, f, c.n);
+  return vcp_exclusive_scan_u32(ctx, f, f, c.n, d_total);
+}
+
+// the measure of the bounding box in the metric's distance form.  Monotone rounding: |dx| <= hi-lo on every axis, so it
+// bounds every pair's distance form
+template <int GD, int METRIC>
+double box_measure(const double* h) {
+  const double wx = h[3] - h[0], wy = h[4] - h[1], wz = GD == 3 ? h[5] - h[2] : 0.0;
+  return METRIC == VCP_L1_2D ? std::fabs(wx) + std::fabs(wy)
+         : METRIC == VCP_L2_2D ? wx * wx + wy * wy : wx * wx + wy * wy + wz * wz;
+}
+
+// the whole cloud fits inside one eps-ball (k_all_pairs)
+int run_all_pairs(vcp_ctx* ctx, const Call& c) {
+  hipStream_t st = ctx->stream;
+  const int64_t n = c.n;
+  vcp_phase(ctx, "all_pairs");
+  VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, (size_t)(n + 2) * 4));
+  uint32_t* f = ctx->b_seedflag.as<uint32_t>();
+  uint32_t* d_tot = reinterpret_cast<uint32_t*>(misc_carve(ctx, n).counters);  // (the counter block is not in use yet)
+  unsigned long long unclassed = (unsigned long long)n;
+  if (c.d_in_classed) {
+    VCP_TRY(unclassed_ranks(ctx, c, f, d_tot));
+    uint32_t* hu = &engine_pinned(ctx)->unclassed;
+    VCP_HIP(ctx, hipMemcpyAsync(hu, d_tot, 4, hipMemcpyDeviceToHost, st));
+    VCP_HIP(ctx, hipStreamSynchronize(st));
+    unclassed = hu[0];
   }
+  const int core = n >= (int64_t)c.min_pts;
+  const int have_seed = unclassed > 0;
+  VCP_LAUNCH(ctx, k_all_pairs, dim3(c.nb), dim3(TPB), 0, st, c.d_in_classed, n, core, have_seed, c.cf_in, c.d_labels,
+                  c.d_is_core, c.d_is_classed);
+  VCP_TRY(vcp_phase_finish(ctx));
+  VCP_HIP(ctx, hipStreamSynchronize(st));
+  const int made = core && have_seed;
+  if (c.cf_out) *c.cf_out = c.cf_in + made;
+  if (c.dist_evals) *c.dist_evals = (int64_t)(unclassed + (unsigned long long)made) * n;
+  return VCP_OK;
+}
 
-  // 2. grid geometry (host): cell edge a hair above eps; coarsen until the cell count fits
+// 2. grid geometry (host): cell edge a hair above eps; coarsen until the cell count fits.  Fills c.g and narrows c.h to
+// the grid's range; Emax = largest |coordinate - grid origin| over the finite input.
+int grid_geometry(vcp_ctx* ctx, Call& c, const Switches& sw, double& Emax) {
+  const int GD = c.gd;
+  const int64_t n = c.n;
+  const double eps = c.eps;
+  double* h = c.h;
+  GridP& g = c.g;
   double bbox[6];  // the true bounding box of the finite coordinates (the grid range below may get trimmed)
   for (int a = 0; a < 3; a++) {
     const bool have = a < GD && h[3 + a] >= h[a];
     bbox[a] = have ? h[a] : 0.0;
     bbox[3 + a] = have ? h[3 + a] : 0.0;
   }
-  GridP g;
   double range = 0.0;
   for (int a = 0; a < 3; a++) {
     double lo = a < GD ? h[a] : 0.0, hi = a < GD ? h[3 + a] : 0.0;
@@ -1591,12 +1807,7 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
     range = std::fmax(range, hi - lo);
   }
   double cellw = eps * (1.0 + 1.0 / 1048576.0);
-  static const int64_t cells_per_point = [] {  // (VCP_CELL_BUDGET: test switch)
-    const char* e = getenv("VCP_CELL_BUDGET");
-    const long v = e ? atol(e) : 32;
-    return (int64_t)(v < 1 ? 1 : v > 4096 ? 4096 : v);
-  }();
-  int64_t budget = n * cells_per_point;
+  int64_t budget = n * sw.cells_per_point;
   if (budget < (1 << 16)) budget = 1 << 16;
   if (budget > ((int64_t)1 << 31) - 16) budget = ((int64_t)1 << 31) - 16;  // cell ids and ncells + 1 stay in 31 bits
   // Robust range.  Cell indices are clamped to the grid, so ANY origin and extent give correct results (a point
@@ -1612,14 +1823,14 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
       double r = 0.0;
       for (int a = 0; a < GD; a++) r = std::fmax(r, hi[a] - lo[a]);
       const double cw = std::fmax(cellw, r / 1048575.0);
-      double c = 1.0;
-      for (int a = 0; a < GD; a++) c *= std::floor((hi[a] - lo[a]) / cw) + 1.0;
-      return c;
+      double cells = 1.0;
+      for (int a = 0; a < GD; a++) cells *= std::floor((hi[a] - lo[a]) / cw) + 1.0;
+      return cells;
     };
     double lo[3] = {h[0], h[1], h[2]}, hi[3] = {h[3], h[4], h[5]};
-    if (!(ext && ext->no_trim) && cellw >= 0.0 && std::isfinite(cellw))
+    if (!(c.ext && c.ext->no_trim) && cellw >= 0.0 && std::isfinite(cellw))
       VCP_TRY(vcp_robust_range(
-          ctx, src, ctx->b_aux0, lo, hi, [&](double, double) { return 4.0 * cellw; },
+          ctx, bounds_src(c), ctx->b_aux0, lo, hi, [&](double, double) { return 4.0 * cellw; },
           [&](const double* l, const double* u) { return cells_needed(l, u) <= (double)budget; }));
     for (int a = 0; a < GD; a++) {
       h[a] = lo[a];
@@ -1654,7 +1865,7 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
   }
   if (ncells > budget) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "grid does not fit the cell budget");
   // largest |coordinate - grid origin| over the finite input: the true bounding box, not the (possibly trimmed) grid
-  double Emax = 0.0;
+  Emax = 0.0;
   for (int a = 0; a < GD; a++) Emax = std::fmax(Emax, std::fmax(std::fabs(bbox[a] - g.mn[a]), std::fabs(bbox[3 + a] - g.mn[a])));
   if (!std::isfinite(Emax))
     return vcp_fail(ctx, VCP_ERR_UNSUPPORTED, "the cloud's extent overflows binary64 (coordinate - origin is infinite)");
@@ -1666,243 +1877,259 @@ int run_dbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, doub
   if (Emax > 1e30 || (Emax > 0.0 && Emax < 1e-20)) g.scale = std::ldexp(1.0, -std::ilogb(Emax));
   g.inv_h = std::isinf(cellw) ? 0.0 : 1.0 / (cellw * g.scale);
   g.ncells = (uint32_t)ncells;
+  return VCP_OK;
+}
 
-  // 3. workspace
-  // the cell table (grid_common.hpp: CellTab): 16 bytes per word of 32 cells, the full starts of the populous words, and
-  // two counters
-  const size_t ctw = vcp_ct_words(g.ncells), ctd = vcp_ct_dense_cap(n, g.ncells);
-  VCP_TRY(vcp_ensure(ctx, ctx->b_ctw, ctw * 16 + 64));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_ctd, ctd * 128));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_cellof, (size_t)n * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_pos, (size_t)n * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_sorted32, (size_t)n * (GD == 2 ? 2 : 4) * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_sidx, (size_t)n * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_flags, (size_t)n));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_parent, (size_t)n * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_minord, (size_t)n * 4));
-  const uint32_t nw = (uint32_t)(n / 32 + 2);  // bitmap words: positions 0..n (rank(n) = seed total)
-  VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, ((size_t)nw * 2 + 8) * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_rootcl, (size_t)n * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_clseed, (size_t)n * 4));
-  VCP_TRY(vcp_ensure(ctx, ctx->b_labk, (size_t)n * 4));
-  if (GROUPED) VCP_TRY(vcp_ensure(ctx, ctx->b_sgroup, (size_t)n * 4));
-  uint4* ctwords = ctx->b_ctw.as<uint4>();
-  uint32_t* ctcount = reinterpret_cast<uint32_t*>(ctx->b_ctw.as<char>() + ctw * 16);  // [0] populous words, [1] points in the grid
-  const CellTab ct{ctwords, ctx->b_ctd.as<uint32_t>(), ctcount + 1};
-  uint32_t* cellof = ctx->b_cellof.as<uint32_t>();
-  uint32_t* pos = ctx->b_pos.as<uint32_t>();
-  float* sorted32 = ctx->b_sorted32.as<float>();
-  static const bool screen_off = getenv("VCP_NO_SCREEN") != nullptr;
-  // the screen compares values of the SCALED copies: threshold and extent in the same units
-  Screen sc = screen_bounds(METRIC, GD, METRIC == VCP_L1_2D ? thr * g.scale : thr * g.scale * g.scale, Emax * g.scale);
-  if (screen_off) sc = Screen{-1.0f, INFINITY};
-  uint32_t* sord = ctx->b_sidx.as<uint32_t>();
-  uint8_t* flags = ctx->b_flags.as<uint8_t>();
-  uint32_t* parent = ctx->b_parent.as<uint32_t>();
-  uint32_t* minord = ctx->b_minord.as<uint32_t>();
-  uint32_t* seedflag = ctx->b_seedflag.as<uint32_t>();  // seed bitmap [nw]
-  uint32_t* seedpref = seedflag + ((nw + 3) & ~3u);      // per-word prefix [nw] (16-B aligned)
-  uint32_t* rootk = ctx->b_rootcl.as<uint32_t>();
-  uint32_t* clseed = ctx->b_clseed.as<uint32_t>();
-  uint32_t* labk = ctx->b_labk.as<uint32_t>();
-  int32_t* sgroup = GROUPED ? ctx->b_sgroup.as<int32_t>() : nullptr;
-  // [0] lonely seeds (min_pts <= 0, non-finite points), [1] border points queried twice, [2] seed total (u32), [3] grouped evals, [4..36) unclassed slots
-  unsigned long long* counters = reinterpret_cast<unsigned long long*>(d_bounds + 8);
-  uint32_t* d_total = reinterpret_cast<uint32_t*>(counters + 2);
+// 4. cell order: two-level partition that carries the binary32 coordinates and emits the cell table (gridbuild.hip);
+//    its output pass needs no caller-order -> cell-order map (pos).  The binary64 coordinates stay in the caller's
+//    array and are read by index where a screened pair needs the exact test.
+int stage_grid_build(vcp_ctx* ctx, Call& c, const Workspace& ws) {
+  GridBuildArgs ga;
+  ga.d_coords = c.d_coords;
+  ga.n = c.n;
+  ga.stride = c.stride;
+  ga.gd = c.gd;
+  ga.g = c.g;
+  ga.d_group = c.d_group;
+  ga.glo = c.glo;
+  ga.ghi = c.ghi;
+  ga.d_ord = c.d_ord;
+  ga.d_in_classed = c.d_in_classed;
+  ga.ctwords = ws.ctwords;
+  ga.ctdense = ws.ctdense;
+  ga.ctcount = ws.ctcount;
+  ga.sidx = c.d_ord ? ws.cellof : nullptr;  // the point's index where sord holds the caller's list position instead
+  ga.sorted32 = ws.sorted32;
+  ga.sord = ws.sord;
+  ga.sgroup = ws.sgroup;
+  ga.flags = ws.flags;
+  ga.pos = c.part_out ? nullptr : ws.pos;
+  VCP_TRY(vcp_grid_build_partition(ctx, ga));
+  c.xs = ExactSrc{c.d_coords, c.d_ord ? ws.cellof : ws.sord, c.stride};  // staged calls: kept for vcp_slab_finish (SlabState.xs)
+  return VCP_OK;
+}
 
-  // 4. cell order: two-level partition that carries the binary32 coordinates and emits the cell table (gridbuild.hip);
-  //    its output pass needs no caller-order -> cell-order map (pos).  The binary64 coordinates stay in the caller's
-  //    array and are read by index where a screened pair needs the exact test.
-  // flags before the core count: the build stores the callers' isClassed bits; without them the core count starts every
-  // byte itself and nothing has to be there
-  const bool flags_set = d_in_classed != nullptr;
-  const bool part_out = !GROUPED && !d_ord && !(ext && ext->slab) && n <= ((int64_t)1 << 27);
-  {
-    GridBuildArgs ga;
-    ga.d_coords = d_coords;
-    ga.n = n;
-    ga.stride = stride;
-    ga.gd = GD;
-    ga.g = g;
-    ga.d_group = d_group;
-    ga.glo = glo;
-    ga.ghi = ghi;
-    ga.d_ord = d_ord;
-    ga.d_in_classed = d_in_classed;
-    ga.ctwords = ctwords;
-    ga.ctdense = ctx->b_ctd.as<uint32_t>();
-    ga.ctcount = ctcount;
-    ga.sidx = d_ord ? cellof : nullptr;  // the point's index where sord holds the caller's list position instead
-    ga.sorted32 = sorted32;
-    ga.sord = sord;
-    ga.sgroup = sgroup;
-    ga.flags = flags;
-    ga.pos = part_out ? nullptr : pos;
-    VCP_TRY(vcp_grid_build_partition(ctx, ga));
-  }
-  const ExactSrc xs{d_coords, d_ord ? cellof : sord, stride};  // staged calls: kept for vcp_slab_finish (SlabState.xs)
-
-  // 5. core flags + work lists (expanding points; non-core points that have a neighbour)
+// 5. core flags + work lists (expanding points; non-core points that have a neighbour)
+template <int GD, int METRIC, bool GROUPED>
+int stage_core(vcp_ctx* ctx, Call& c, const Workspace& ws, const Switches& sw) {
+  hipStream_t st = ctx->stream;
+  const int64_t n = c.n;
+  const unsigned nb = c.nb;
   vcp_phase(ctx, "core_count");
-  WorkList wlE, wlB;
-  VCP_TRY(vcp_ensure(ctx, ctx->b_wl, ((size_t)n * 2 + (size_t)(nb + 2) * 2) * 4 + 256));
-  uint32_t* blkE = ctx->b_wl.as<uint32_t>();
-  uint32_t* blkB = blkE + (nb + 2);
-  wlE.list = blkB + (nb + 2);
-  wlB.list = wlE.list + n;
-  wlE.scan = blkE;
-  wlB.scan = blkB;
-  wlE.nblk = wlB.nblk = nb;
-  wlE.perblk = wlB.perblk = list_perblk(n);
-  const unsigned nbl = 8u * LCHUNK * wlE.perblk;  // list kernels: see wl_fetch
   // neighbour lists (see NbrOut): off when the caller passes isClassed (classed core points need the full search), for
   // staged calls (vcp_slab_finish searches again with the resolved ids) and for min_pts outside 2..16
-  static const bool lists_off = getenv("VCP_NO_LISTS") != nullptr;
-  NbrOut no{nullptr, nullptr, 0, 0};
-  if (!lists_off && !d_in_classed && !(ext && ext->slab) && min_pts >= 2 && min_pts <= 16) {
-    no.NB = min_pts - 1;
+  NbrOut& no = c.no;
+  if (!sw.lists_off && !c.d_in_classed && !c.slab && c.min_pts >= 2 && c.min_pts <= 16) {
+    no.NB = c.min_pts - 1;
     VCP_TRY(vcp_ensure(ctx, ctx->b_nbr, (size_t)no.NB * (size_t)nb * TPB * 4));
     VCP_TRY(vcp_ensure(ctx, ctx->b_nboff, (size_t)nb * TPB * 2));
     no.nbr = ctx->b_nbr.as<uint32_t>();
     no.off = ctx->b_nboff.as<uint16_t>();
-    static const int cap_env = getenv("VCP_CORE_CAP") ? atoi(getenv("VCP_CORE_CAP")) : -1;  // test switch
-    no.core_cap = (GD == 2 && (uint64_t)n < (uint64_t)g.ncells) ? std::min(no.NB, CORE_LIST) : no.NB;
-    if (cap_env >= 0) no.core_cap = std::min(no.NB, cap_env);
+    no.core_cap = (GD == 2 && (uint64_t)n < (uint64_t)c.g.ncells) ? std::min(no.NB, CORE_LIST) : no.NB;
+    if (sw.core_cap >= 0) no.core_cap = std::min(no.NB, sw.core_cap);
   }
   const size_t lds_nb = (size_t)no.NB * TPB * 4;
-  static const bool core_global = getenv("VCP_CORE_GLOBAL") != nullptr;  // test switch: grouped calls through k_core
+  bool tiled = false;  // 2-D: the LDS tile kernel, unless the switch sends a grouped call through k_core
   if constexpr (GD == 2) {
-    if (!GROUPED || !core_global)
-      VCP_LAUNCH(ctx, (k_core_lds<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 0, st, xs, g, thr, min_pts, ct, sgroup, flags,
-                      parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
-    else
-      VCP_LAUNCH(ctx, (k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, xs, g, thr, min_pts, ct,
-                      sgroup, flags, parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
-  } else
-    VCP_LAUNCH(ctx, (k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, xs, g, thr, min_pts, ct,
-                    sgroup, flags, parent, minord, blkE, blkB, no, sorted32, sc, flags_set);
+    if (!GROUPED || !sw.core_global) {
+      VCP_LAUNCH(ctx, (k_core_lds<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 0, st, c.xs, c.g, c.thr, c.min_pts, ws.ct,
+                      ws.sgroup, ws.flags, ws.parent, ws.minord, ws.blkE, ws.blkB, no, ws.sorted32, c.sc, c.flags_set);
+      tiled = true;
+    }
+  }
+  if (!tiled)
+    VCP_LAUNCH(ctx, (k_core<GD, METRIC, GROUPED>), dim3(nb), dim3(TPB), 2 * lds_nb, st, c.xs, c.g, c.thr, c.min_pts, ws.ct,
+                    ws.sgroup, ws.flags, ws.parent, ws.minord, ws.blkE, ws.blkB, no, ws.sorted32, c.sc, c.flags_set);
   // ONE scan over both count arrays (they are adjacent): the B half comes out offset by everything before it, which
   // its readers take off again (scan[0]); the two pad words between the halves are never written and cancel the same way
-  VCP_TRY(vcp_exclusive_scan_u32(ctx, blkE, blkE, 2 * ((int64_t)nb + 2), nullptr));
-  VCP_LAUNCH(ctx, k_wl_fill, dim3(nb), dim3(TPB), 0, st, flags, ct, blkE, blkB, wlE.list, wlB.list,
-                  seedflag, nw, counters, GROUPED ? ext->d_group_twice : nullptr, (uint32_t)(GROUPED ? G : 0));
+  VCP_TRY(vcp_exclusive_scan_u32(ctx, ws.blkE, ws.blkE, 2 * ((int64_t)nb + 2), nullptr));
+  VCP_LAUNCH(ctx, k_wl_fill, dim3(nb), dim3(TPB), 0, st, ws.flags, ws.ct, ws.blkE, ws.blkB, ws.wlE.list, ws.wlB.list,
+                  ws.seedflag, ws.nw, ws.counters, c.d_group_twice, (uint32_t)(GROUPED ? c.G : 0));
+  return VCP_OK;
+}
 
-  // 6. components of the expanding points
+// 6. components of the expanding points
+template <int GD, int METRIC, bool GROUPED>
+int stage_union(vcp_ctx* ctx, const Call& c, const Workspace& ws, const Switches& sw) {
+  hipStream_t st = ctx->stream;
+  const int64_t n = c.n;
+  const unsigned nb = c.nb, nbl = ws.nbl;
+  const GridP& g = c.g;
+  const NbrOut& no = c.no;
   vcp_phase(ctx, "union");
   // phases 1-2 pay for their extra search pass in 2-D (3 rows); in 3-D (9 rows) they do not (measured: +28 %)
   const bool pre = GD == 2 || no.NB > 0;  // with lists the forest costs no search, so it pays in 3-D too
   if (no.NB > 0) {
-    VCP_LAUNCH(ctx, k_union_init_list, dim3(nbl), dim3(TPB), 0, st, flags, parent, no, wlE);
-    static const int join_all = getenv("VCP_JOIN_ALL") ? atoi(getenv("VCP_JOIN_ALL")) : -1;  // test switch
-    const bool all = join_all >= 0 ? join_all != 0 : (uint64_t)n >= (uint64_t)g.ncells;
-    if (all) VCP_LAUNCH(ctx, k_flatten0<2>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
-    else VCP_LAUNCH(ctx, k_flatten0<1>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
-    VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
+    VCP_LAUNCH(ctx, k_union_init_list, dim3(nbl), dim3(TPB), 0, st, ws.flags, ws.parent, no, ws.wlE);
+    const bool all = sw.join_all >= 0 ? sw.join_all != 0 : (uint64_t)n >= (uint64_t)g.ncells;
+    if (all) VCP_LAUNCH(ctx, k_flatten0<2>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
+    else VCP_LAUNCH(ctx, k_flatten0<1>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
+    VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
   } else if (GD == 2) {
-    VCP_LAUNCH(ctx, (k_union_init<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                    flags, parent, wlE, sorted32, sc);
-    VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, parent, wlE, flags, no);
+    VCP_LAUNCH(ctx, (k_union_init<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, c.xs, g, c.thr, ws.ct, ws.sgroup,
+                    ws.flags, ws.parent, ws.wlE, ws.sorted32, c.sc);
+    VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
   }
   const bool dense = pre && (uint64_t)n > (uint64_t)DENSE_PER_CELL * g.ncells;
   if (dense) {
     VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, ((size_t)nb * (TPB / 64) + 2) * 4));  // one word per wave of k_chunkroot
     uint32_t* chunkroot = ctx->b_aux0.as<uint32_t>();
-    VCP_LAUNCH(ctx, k_chunkroot, dim3(nb), dim3(TPB), 0, st, parent, ct, chunkroot);
-    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, true, true>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                    parent, wlE, sorted32, sc, chunkroot);
+    VCP_LAUNCH(ctx, k_chunkroot, dim3(nb), dim3(TPB), 0, st, ws.parent, ws.ct, chunkroot);
+    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, true, true>), dim3(nbl), dim3(TPB), 0, st, c.xs, g, c.thr, ws.ct,
+                    ws.sgroup, ws.parent, ws.wlE, ws.sorted32, c.sc, chunkroot);
   } else if (pre)
-    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, true>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                    parent, wlE, sorted32, sc);
+    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, true>), dim3(nbl), dim3(TPB), 0, st, c.xs, g, c.thr, ws.ct, ws.sgroup,
+                    ws.parent, ws.wlE, ws.sorted32, c.sc);
   else
-    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, false>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup,
-                    parent, wlE, sorted32, sc);
-  vcp_phase(ctx, "flatten_number");
-  if ((uint64_t)n >= (uint64_t)g.ncells)
-    VCP_LAUNCH(ctx, k_flatten<true>, dim3(nbl), dim3(TPB), 0, st, parent, sord, minord, wlE);
-  else
-    VCP_LAUNCH(ctx, k_flatten<false>, dim3(nbl), dim3(TPB), 0, st, parent, sord, minord, wlE);
-  if (!GROUPED && ext && ext->slab) {
-    // staged call: hand the local components to the caller and keep the grid state for vcp_slab_finish
-    vcp_phase(ctx, "slab_components");
-    VCP_LAUNCH(ctx, k_slab_count, dim3(nb), dim3(TPB), 0, st, parent, flags, ct, blkE);
-    VCP_TRY(vcp_exclusive_scan_u32(ctx, blkE, blkE, (int64_t)nb + 1, nullptr));
-    VCP_LAUNCH(ctx, k_slab_fill, dim3(nb), dim3(TPB), 0, st, parent, flags, minord, ct, blkE, clseed);
-    VCP_LAUNCH(ctx, k_slab_out, dim3(nb), dim3(TPB), 0, st, n, pos, flags, parent, minord, ext->d_slab_rep, d_is_core);
-    uint32_t* hn = reinterpret_cast<uint32_t*>(ctx->pinned) + 64;
-    VCP_HIP(ctx, hipMemcpyAsync(hn, blkE + nb, 4, hipMemcpyDeviceToHost, st));
-    VCP_TRY(vcp_phase_finish(ctx));
-    VCP_HIP(ctx, hipStreamSynchronize(st));
-    if (!ctx->slab) ctx->slab = new SlabState();
-    SlabState& ss = *ctx->slab;
-    ss.valid = true;
-    ss.gd = GD;
-    ss.metric = METRIC;
-    ss.n = n;
-    ss.n_comp = hn[0];
-    ss.g = g;
-    ss.thr = thr;
-    ss.sc = sc;
-    ss.xs = xs;
-    ss.nb = nb;
-    if (cf_out) *cf_out = (int32_t)hn[0];
-    return VCP_OK;
-  }
-  VCP_LAUNCH(ctx, k_seedflag, dim3(nbl), dim3(TPB), 0, st, parent, minord, seedflag, wlE);
-  VCP_LAUNCH(ctx, k_seed_popc, dim3(vcp_blocks(nw, TPB)), dim3(TPB), 0, st, seedflag, nw, seedpref);
-  VCP_TRY(vcp_exclusive_scan_u32(ctx, seedpref, seedpref, nw, d_total));
-  VCP_LAUNCH(ctx, k_rootk, dim3(nbl), dim3(TPB), 0, st, parent, minord, seedflag, seedpref, rootk, clseed, wlE);
+    VCP_LAUNCH(ctx, (k_union<GD, METRIC, GROUPED, false>), dim3(nbl), dim3(TPB), 0, st, c.xs, g, c.thr, ws.ct, ws.sgroup,
+                    ws.parent, ws.wlE, ws.sorted32, c.sc);
+  return VCP_OK;
+}
 
-  // 7. border rule, then outputs in caller order
-  vcp_phase(ctx, "border");
-  VCP_LAUNCH(ctx, k_labk_rest, dim3(nb), dim3(TPB), 0, st, flags, parent, rootk, labk, ct);
-  if (no.NB > 0)
-    VCP_LAUNCH(ctx, k_border_list<GROUPED>, dim3(nbl), dim3(TPB), 0, st, sgroup, flags, sord, rootk, clseed, labk, counters,
-                    GROUPED ? ext->d_group_twice : nullptr, no, wlB);
+// staged call: hand the local components to the caller and keep the grid state for vcp_slab_finish
+int stage_slab_handoff(vcp_ctx* ctx, const Call& c, const Workspace& ws) {
+  hipStream_t st = ctx->stream;
+  const unsigned nb = c.nb;
+  vcp_phase(ctx, "slab_components");
+  VCP_LAUNCH(ctx, k_slab_count, dim3(nb), dim3(TPB), 0, st, ws.parent, ws.flags, ws.ct, ws.blkE);
+  VCP_TRY(vcp_exclusive_scan_u32(ctx, ws.blkE, ws.blkE, (int64_t)nb + 1, nullptr));
+  VCP_LAUNCH(ctx, k_slab_fill, dim3(nb), dim3(TPB), 0, st, ws.parent, ws.flags, ws.minord, ws.ct, ws.blkE, ws.clseed);
+  VCP_LAUNCH(ctx, k_slab_out, dim3(nb), dim3(TPB), 0, st, c.n, ws.pos, ws.flags, ws.parent, ws.minord, c.ext->d_slab_rep,
+                  c.d_is_core);
+  uint32_t* hn = &engine_pinned(ctx)->n_comp;
+  VCP_HIP(ctx, hipMemcpyAsync(hn, ws.blkE + nb, 4, hipMemcpyDeviceToHost, st));
+  VCP_TRY(vcp_phase_finish(ctx));
+  VCP_HIP(ctx, hipStreamSynchronize(st));
+  if (!ctx->slab) ctx->slab = new SlabState();
+  SlabState& ss = *ctx->slab;
+  ss.valid = true;
+  ss.gd = c.gd;
+  ss.metric = c.metric;
+  ss.n = c.n;
+  ss.n_comp = hn[0];
+  ss.g = c.g;
+  ss.thr = c.thr;
+  ss.sc = c.sc;
+  ss.xs = c.xs;
+  ss.nb = nb;
+  if (c.cf_out) *c.cf_out = (int32_t)hn[0];
+  return VCP_OK;
+}
+
+// flatten and number: every expanding point under its root, the roots with their component's seed (minord); then the
+// seeds' bitmap, its popcount prefix, and per root the rank of its seed (= the cluster's number).  A staged call ends
+// between the two, with the hand-off.
+template <bool GROUPED>
+int stage_flatten_number(vcp_ctx* ctx, const Call& c, const Workspace& ws) {
+  hipStream_t st = ctx->stream;
+  const unsigned nbl = ws.nbl;
+  vcp_phase(ctx, "flatten_number");
+  if ((uint64_t)c.n >= (uint64_t)c.g.ncells)
+    VCP_LAUNCH(ctx, k_flatten<true>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.sord, ws.minord, ws.wlE);
   else
-    VCP_LAUNCH(ctx, (k_border<GD, METRIC, GROUPED>), dim3(nbl), dim3(TPB), 0, st, xs, g, thr, ct, sgroup, flags,
-                    parent, sord, rootk, clseed, labk, counters, GROUPED ? ext->d_group_twice : nullptr, wlB, 0u, NONE,
-                    sorted32, sc);
-  if (part_out) {
+    VCP_LAUNCH(ctx, k_flatten<false>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.sord, ws.minord, ws.wlE);
+  if (!GROUPED && c.slab) return stage_slab_handoff(ctx, c, ws);
+  VCP_LAUNCH(ctx, k_seedflag, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.minord, ws.seedflag, ws.wlE);
+  VCP_LAUNCH(ctx, k_seed_popc, dim3(vcp_blocks(ws.nw, TPB)), dim3(TPB), 0, st, ws.seedflag, ws.nw, ws.seedpref);
+  VCP_TRY(vcp_exclusive_scan_u32(ctx, ws.seedpref, ws.seedpref, ws.nw, ws.d_total));
+  VCP_LAUNCH(ctx, k_rootk, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.minord, ws.seedflag, ws.seedpref, ws.rootk, ws.clseed,
+                  ws.wlE);
+  return VCP_OK;
+}
+
+// 7. border rule
+template <int GD, int METRIC, bool GROUPED>
+int stage_border(vcp_ctx* ctx, const Call& c, const Workspace& ws) {
+  hipStream_t st = ctx->stream;
+  vcp_phase(ctx, "border");
+  VCP_LAUNCH(ctx, k_labk_rest, dim3(c.nb), dim3(TPB), 0, st, ws.flags, ws.parent, ws.rootk, ws.labk, ws.ct);
+  if (c.no.NB > 0)
+    VCP_LAUNCH(ctx, k_border_list<GROUPED>, dim3(ws.nbl), dim3(TPB), 0, st, ws.sgroup, ws.flags, ws.sord, ws.rootk,
+                    ws.clseed, ws.labk, ws.counters, c.d_group_twice, c.no, ws.wlB);
+  else
+    VCP_LAUNCH(ctx, (k_border<GD, METRIC, GROUPED>), dim3(ws.nbl), dim3(TPB), 0, st, c.xs, c.g, c.thr, ws.ct, ws.sgroup,
+                    ws.flags, ws.parent, ws.sord, ws.rootk, ws.clseed, ws.labk, ws.counters, c.d_group_twice, ws.wlB, 0u,
+                    NONE, ws.sorted32, c.sc);
+  return VCP_OK;
+}
+
+// outputs in caller order; the lonely seeds of min_pts <= 0 and the statistics of a grouped call
+template <int GD, bool GROUPED>
+int stage_output(vcp_ctx* ctx, const Call& c, const Workspace& ws) {
+  hipStream_t st = ctx->stream;
+  const int64_t n = c.n;
+  const unsigned nb = c.nb;
+  const DbscanExt* ext = c.ext;
+  if (c.part_out) {
     GridOutputArgs oa;
     oa.n = n;
-    oa.sord = sord;
-    oa.labk = labk;
-    oa.have_in_classed = d_in_classed != nullptr;
-    oa.cf_in = cf_in;
-    oa.labels = d_labels;
-    oa.is_core = d_is_core;
-    oa.is_classed = d_is_classed;
-    oa.counters = counters;
+    oa.sord = ws.sord;
+    oa.labk = ws.labk;
+    oa.have_in_classed = c.d_in_classed != nullptr;
+    oa.cf_in = c.cf_in;
+    oa.labels = c.d_labels;
+    oa.is_core = c.d_is_core;
+    oa.is_classed = c.d_is_classed;
+    oa.counters = ws.counters;
     VCP_TRY(vcp_grid_output_partition(ctx, oa));
   } else {
     vcp_phase(ctx, "output");
-    VCP_LAUNCH(ctx, (k_output<GROUPED>), dim3(nb), dim3(TPB), 0, st, n, pos, labk, d_in_classed, d_group,
-                    GROUPED ? ext->d_groupstart : nullptr, seedflag, seedpref, cf_in, d_labels, d_is_core, d_is_classed,
-                    counters);
+    VCP_LAUNCH(ctx, (k_output<GROUPED>), dim3(nb), dim3(TPB), 0, st, n, ws.pos, ws.labk, c.d_in_classed, c.d_group,
+                    GROUPED ? ext->d_groupstart : nullptr, ws.seedflag, ws.seedpref, c.cf_in, c.d_labels, c.d_is_core,
+                    c.d_is_classed, ws.counters);
   }
-  if (!GROUPED && min_pts <= 0 && !all_finite)
-    VCP_LAUNCH(ctx, k_lonely_seeds<GD>, dim3(nb), dim3(TPB), 0, st, d_coords, n, stride, d_in_classed, d_is_classed,
-                    counters);
+  if (!GROUPED && c.min_pts <= 0 && !c.all_finite)
+    VCP_LAUNCH(ctx, k_lonely_seeds<GD>, dim3(nb), dim3(TPB), 0, st, c.d_coords, n, c.stride, c.d_in_classed,
+                    c.d_is_classed, ws.counters + CNT_LONELY);
   if (GROUPED) {
-    VCP_LAUNCH(ctx, k_group_stats, dim3(vcp_blocks(G, TPB)), dim3(TPB), 0, st, G, glo, ghi, ext->d_groupstart,
-                    seedflag, seedpref, ext->d_group_twice, ext->d_group_nclus, counters + 3, ext->skip_upto);
+    VCP_LAUNCH(ctx, k_group_stats, dim3(vcp_blocks(c.G, TPB)), dim3(TPB), 0, st, c.G, c.glo, c.ghi, ext->d_groupstart,
+                    ws.seedflag, ws.seedpref, ext->d_group_twice, ext->d_group_nclus, ws.counters + CNT_GROUP_EVALS,
+                    ext->skip_upto);
     if (ext->d_group_evals)
-      VCP_HIP(ctx, hipMemcpyAsync(ext->d_group_evals, counters + 3, 8, hipMemcpyDeviceToDevice, st));
+      VCP_HIP(ctx, hipMemcpyAsync(ext->d_group_evals, ws.counters + CNT_GROUP_EVALS, 8, hipMemcpyDeviceToDevice, st));
   }
-  unsigned long long* hc = reinterpret_cast<unsigned long long*>(ctx->pinned) + 8;
-  VCP_HIP(ctx, hipMemcpyAsync(hc, counters, 68 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  VCP_TRY(vcp_phase_finish(ctx));
-  VCP_HIP(ctx, hipStreamSynchronize(st));
-  const uint32_t K = *reinterpret_cast<uint32_t*>(hc + 2);
-  unsigned long long unclassed = (unsigned long long)n;  // nobody classed on entry
-  if (d_in_classed) {
-    unclassed = 0;
-    for (int k = 0; k < 32; k++) unclassed += hc[4 + k];
-  }
-  if (cf_out) *cf_out = cf_in + (int32_t)K;
-  unsigned long long twice_total = 0;
-  for (int k = 0; k < 32; k++) twice_total += hc[36 + k];
-  if (dist_evals) *dist_evals = GROUPED ? (int64_t)hc[3] : (int64_t)(unclassed + twice_total + K - hc[0]) * n;
+  return VCP_OK;
+}
+
+// GD = dimension of the metric (grid and sorted32).  The passes of the file's header, in order.
+template <int GD, int METRIC, bool GROUPED>
+int run_dbscan(vcp_ctx* ctx, Call& c) {
+  const Switches& sw = switches();
+  // 1. bounds; a cloud that fits inside one eps-ball ends here
+  VCP_TRY(stage_bounds(ctx, c));
+  c.thr = (METRIC == VCP_L1_2D) ? c.eps : l2_threshold(c.eps);
+  if (!GROUPED && c.all_finite && !c.slab && box_measure<GD, METRIC>(c.h) <= c.thr) return run_all_pairs(ctx, c);
+
+  // 2. grid geometry, and the screen that goes with it
+  double Emax = 0.0;
+  VCP_TRY(grid_geometry(ctx, c, sw, Emax));
+  // the screen compares values of the SCALED copies: threshold and extent in the same units
+  c.sc = screen_bounds(METRIC, GD, METRIC == VCP_L1_2D ? c.thr * c.g.scale : c.thr * c.g.scale * c.g.scale, Emax * c.g.scale);
+  if (sw.screen_off) c.sc = Screen{-1.0f, INFINITY};
+
+  // 3. workspace
+  VCP_TRY(ws_reserve(ctx, c.n, c.nb, GD, GROUPED, c.g.ncells));
+  const Workspace ws = ws_carve(ctx, c.n, c.nb, GROUPED, c.g.ncells);
+  // flags before the core count: the build stores the callers' isClassed bits; without them the core count starts every
+  // byte itself and nothing has to be there
+  c.flags_set = c.d_in_classed != nullptr;
+  c.part_out = !GROUPED && !c.d_ord && !c.slab && c.n <= ((int64_t)1 << 27);
+  // 4. - 7. the passes on the device
+  VCP_TRY(stage_grid_build(ctx, c, ws));
+  VCP_TRY((stage_core<GD, METRIC, GROUPED>(ctx, c, ws, sw)));
+  VCP_TRY((stage_union<GD, METRIC, GROUPED>(ctx, c, ws, sw)));
+  VCP_TRY(stage_flatten_number<GROUPED>(ctx, c, ws));
+  if (!GROUPED && c.slab) return VCP_OK;  // staged call: handed over, vcp_slab_finish does the rest
+  VCP_TRY((stage_border<GD, METRIC, GROUPED>(ctx, c, ws)));
+  VCP_TRY((stage_output<GD, GROUPED>(ctx, c, ws)));
+
+  // 8. readback
+  Totals t;
+  VCP_TRY(read_totals(ctx, ws, t));
+  const unsigned long long unclassed = c.d_in_classed ? t.unclassed : (unsigned long long)c.n;  // else nobody classed on entry
+  if (c.cf_out) *c.cf_out = c.cf_in + (int32_t)t.K;
+  if (c.dist_evals)
+    *c.dist_evals = GROUPED ? (int64_t)t.group_evals : (int64_t)(unclassed + t.twice + t.K - t.slot0) * c.n;
   return VCP_OK;
 }
 
@@ -1913,73 +2140,45 @@ int run_slab_finish(vcp_ctx* ctx, const SlabState& ss, const uint32_t* d_map_rep
   hipStream_t st = ctx->stream;
   const int64_t n = ss.n;
   const unsigned nb = ss.nb;
-  const GridP g = ss.g;
-  const size_t ctw = vcp_ct_words(g.ncells);
-  const CellTab ct{ctx->b_ctw.as<uint4>(), ctx->b_ctd.as<uint32_t>(),
-                   reinterpret_cast<uint32_t*>(ctx->b_ctw.as<char>() + ctw * 16) + 1};
-  uint32_t* pos = ctx->b_pos.as<uint32_t>();
-  uint32_t* sord = ctx->b_sidx.as<uint32_t>();
-  uint8_t* flags = ctx->b_flags.as<uint8_t>();
-  uint32_t* parent = ctx->b_parent.as<uint32_t>();
-  uint32_t* minord = ctx->b_minord.as<uint32_t>();
-  uint32_t* rootk = ctx->b_rootcl.as<uint32_t>();
-  uint32_t* clseed = ctx->b_clseed.as<uint32_t>();  // the caller's table of global seeds (copied in by now)
-  uint32_t* labk = ctx->b_labk.as<uint32_t>();
-  WorkList wlB;
-  uint32_t* blkE = ctx->b_wl.as<uint32_t>();
-  uint32_t* blkB = blkE + (nb + 2);
-  wlB.list = blkB + (nb + 2) + n;
-  wlB.scan = blkB;
-  wlB.nblk = nb;
-  wlB.perblk = list_perblk(n);
-  const unsigned nbl = 8u * LCHUNK * wlB.perblk;
-  const int rb = (int)vcp_blocks(n, TPB, 1024);
-  unsigned long long* counters = reinterpret_cast<unsigned long long*>(ctx->b_misc.as<double>() + (size_t)rb * 8 + 8);
+  const Workspace ws = ws_carve(ctx, n, nb, false, ss.g.ncells);  // (clseed: the caller's table of global seeds by now)
   vcp_phase(ctx, "slab_roots");
-  VCP_HIP(ctx, hipMemsetAsync(counters, 0, 68 * sizeof(unsigned long long), st));
-  VCP_LAUNCH(ctx, k_slab_rootk, dim3(nb), dim3(TPB), 0, st, parent, flags, minord, ct, d_map_rep, d_map_k,
-                  (uint32_t)ss.n_comp, rootk, counters);
+  VCP_HIP(ctx, hipMemsetAsync(ws.counters, 0, CNT_WORDS * sizeof(unsigned long long), st));
+  VCP_LAUNCH(ctx, k_slab_rootk, dim3(nb), dim3(TPB), 0, st, ws.parent, ws.flags, ws.minord, ws.ct, d_map_rep, d_map_k,
+                  (uint32_t)ss.n_comp, ws.rootk, ws.counters + CNT_MISSING);
   vcp_phase(ctx, "border");
-  VCP_LAUNCH(ctx, k_labk_rest, dim3(nb), dim3(TPB), 0, st, flags, parent, rootk, labk, ct);
-  VCP_LAUNCH(ctx, (k_border<GD, METRIC, false>), dim3(nbl), dim3(TPB), 0, st, ss.xs, g, ss.thr,
-                  ct, nullptr, flags, parent, sord, rootk, clseed, labk, counters, nullptr, wlB, own_lo, own_span,
-                  ctx->b_sorted32.as<float>(), ss.sc);
+  VCP_LAUNCH(ctx, k_labk_rest, dim3(nb), dim3(TPB), 0, st, ws.flags, ws.parent, ws.rootk, ws.labk, ws.ct);
+  VCP_LAUNCH(ctx, (k_border<GD, METRIC, false>), dim3(ws.nbl), dim3(TPB), 0, st, ss.xs, ss.g, ss.thr, ws.ct, nullptr,
+                  ws.flags, ws.parent, ws.sord, ws.rootk, ws.clseed, ws.labk, ws.counters, nullptr, ws.wlB, own_lo,
+                  own_span, ws.sorted32, ss.sc);
   vcp_phase(ctx, "output");
-  VCP_LAUNCH(ctx, k_slab_output, dim3(nb), dim3(TPB), 0, st, n, pos, labk, d_tab_gid, d_labels, d_is_classed);
-  unsigned long long* hc = reinterpret_cast<unsigned long long*>(ctx->pinned) + 8;
-  VCP_HIP(ctx, hipMemcpyAsync(hc, counters, 68 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  VCP_TRY(vcp_phase_finish(ctx));
-  VCP_HIP(ctx, hipStreamSynchronize(st));
-  if (hc[0] != 0)
-    return vcp_fail(ctx, VCP_ERR_ARG, "%llu local components are missing from the map", hc[0]);
-  if (twice) {
-    *twice = 0;
-    for (int k = 0; k < 32; k++) *twice += (int64_t)hc[36 + k];
-  }
+  VCP_LAUNCH(ctx, k_slab_output, dim3(nb), dim3(TPB), 0, st, n, ws.pos, ws.labk, d_tab_gid, d_labels, d_is_classed);
+  Totals t;
+  VCP_TRY(read_totals(ctx, ws, t));
+  if (t.slot0 != 0)
+    return vcp_fail(ctx, VCP_ERR_ARG, "%llu local components are missing from the map", t.slot0);
+  if (twice) *twice = (int64_t)t.twice;
   return VCP_OK;
 }
 
-int run_degenerate(vcp_ctx* ctx, int64_t n, int min_pts, int32_t cf_in, const uint8_t* d_in_classed,
-                   int32_t* d_labels, uint8_t* d_is_core, uint8_t* d_is_classed, int32_t* cf_out,
-                   int64_t* dist_evals) {
+// eps < 0 or NaN: nobody has a neighbour, not even itself (k_degenerate)
+int run_degenerate(vcp_ctx* ctx, const Call& c) {
   hipStream_t st = ctx->stream;
-  const unsigned nb = vcp_blocks(n, TPB);
+  const int64_t n = c.n;
   vcp_phase(ctx, "degenerate");
   VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, (size_t)(n + 2) * 4));
   VCP_TRY(vcp_ensure(ctx, ctx->b_misc, 64));
   uint32_t* f = ctx->b_seedflag.as<uint32_t>();
   uint32_t* d_total = ctx->b_misc.as<uint32_t>();
-  VCP_LAUNCH(ctx, k_unclassed_flag, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n);
-  VCP_TRY(vcp_exclusive_scan_u32(ctx, f, f, n, d_total));
-  const int all_core = 0 >= min_pts;  // tmpList.Count (0) >= minPts, BaseClass/DBImproved.cs:105
-  VCP_LAUNCH(ctx, k_degenerate, dim3(nb), dim3(TPB), 0, st, d_in_classed, f, n, cf_in, all_core,
-                  d_in_classed == nullptr, d_labels, d_is_core, d_is_classed);
-  uint32_t* hu = reinterpret_cast<uint32_t*>(ctx->pinned);
+  VCP_TRY(unclassed_ranks(ctx, c, f, d_total));
+  const int all_core = 0 >= c.min_pts;  // tmpList.Count (0) >= minPts, BaseClass/DBImproved.cs:105
+  VCP_LAUNCH(ctx, k_degenerate, dim3(c.nb), dim3(TPB), 0, st, c.d_in_classed, f, n, c.cf_in, all_core,
+                  c.d_in_classed == nullptr, c.d_labels, c.d_is_core, c.d_is_classed);
+  uint32_t* hu = &engine_pinned(ctx)->unclassed;
   VCP_HIP(ctx, hipMemcpyAsync(hu, d_total, 4, hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));
   VCP_HIP(ctx, hipStreamSynchronize(st));
-  if (cf_out) *cf_out = cf_in + (all_core ? (int32_t)hu[0] : 0);
-  if (dist_evals) *dist_evals = (int64_t)hu[0] * n;
+  if (c.cf_out) *c.cf_out = c.cf_in + (all_core ? (int32_t)hu[0] : 0);
+  if (c.dist_evals) *c.dist_evals = (int64_t)hu[0] * n;
   return VCP_OK;
 }
 
@@ -2024,18 +2223,17 @@ int vcp_dbscan_engine(vcp_ctx* ctx, const double* d_coords, int64_t n, int strid
     ctx->last_timing.clear();
     return VCP_OK;
   }
+  Call c{d_coords, n, stride, metric, eps, min_pts, cf_in, d_in_classed, d_labels, d_is_core, d_is_classed, cf_out,
+         dist_evals, ext};
+  call_derive(c);
   if (!(eps >= 0.0)) {
     if (grouped) return vcp_fail(ctx, VCP_ERR_ARG, "grouped DBSCAN needs eps >= 0");
-    return run_degenerate(ctx, n, min_pts, cf_in, d_in_classed, d_labels, d_is_core, d_is_classed, cf_out, dist_evals);
+    return run_degenerate(ctx, c);
   }
-#define VCP_RUN(D, M, GR)                                                                                        \
-  return run_dbscan<D, M, GR>(ctx, d_coords, n, stride, eps, min_pts, cf_in, d_in_classed, d_labels, d_is_core, \
-                              d_is_classed, cf_out, dist_evals, ext)
-  if (grouped) VCP_RUN(2, VCP_L1_2D, true);
-  if (metric == VCP_L1_2D) VCP_RUN(2, VCP_L1_2D, false);
-  if (metric == VCP_L2_2D) VCP_RUN(2, VCP_L2_2D, false);
-  VCP_RUN(3, VCP_L2_3D, false);
-#undef VCP_RUN
+  if (grouped) return run_dbscan<2, VCP_L1_2D, true>(ctx, c);
+  if (metric == VCP_L1_2D) return run_dbscan<2, VCP_L1_2D, false>(ctx, c);
+  if (metric == VCP_L2_2D) return run_dbscan<2, VCP_L2_2D, false>(ctx, c);
+  return run_dbscan<3, VCP_L2_3D, false>(ctx, c);
 }
 
 extern "C" {

@@ -9,11 +9,25 @@ constexpr int TPB = 256;
 constexpr uint8_t F_CORE = 1, F_CLASSED = 2, F_EXPAND = 4, F_BCAND = 8;
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
+// The engine's device counter block: CNT_WORDS 64-bit words behind the bounds in b_misc (dbscan.hip: ws_carve), zeroed
+// by k_wl_fill (vcp_slab_finish: a memset), read back whole when a call ends (read_totals).
+//   [CNT_LONELY]      vcp_dbscan_engine: lonely seeds (min_pts <= 0, non-finite points: k_lonely_seeds)
+//   [CNT_MISSING]     the same word in vcp_slab_finish: local components missing from the caller's map (k_slab_rootk)
+//   [CNT_SEED_TOTAL]  number of clusters, a u32 in the word's low half: the total of the seed bitmap's scan
+//   [CNT_GROUP_EVALS] grouped calls: sum of the groups' distance evaluations (k_group_stats)
+//   [CNT_UNCLASSED, + CNT_SPREAD)  points not classed on entry, only counted with an isClassed input (k_output, k_out_write)
+//   [CNT_TWICE, + CNT_SPREAD)      border points queried twice (twice_add)
+// The last two take one atomic per workgroup, on slot blockIdx.x mod CNT_SPREAD (a single hot word serialises).  Word 1
+// is unused.
+constexpr int CNT_LONELY = 0, CNT_MISSING = 0, CNT_SEED_TOTAL = 2, CNT_GROUP_EVALS = 3;
+constexpr int CNT_SPREAD = 32;
+constexpr int CNT_UNCLASSED = 4, CNT_TWICE = CNT_UNCLASSED + CNT_SPREAD, CNT_WORDS = CNT_TWICE + CNT_SPREAD;
+
 struct GridP {
   double mn[3];
   double inv_h;     // cells per unit of the SCALED relative coordinate
   double scale;     // power of two applied to (coordinate - origin) before it is rounded to binary32: 1 unless the cloud's
-                    // extent is outside the range where binary32 keeps its relative precision (run_dbscan)
+                    // extent is outside the range where binary32 keeps its relative precision (dbscan.hip: grid_geometry)
   int D[3];         // cells per axis
   uint32_t ncells;
 };
@@ -31,7 +45,7 @@ __device__ __forceinline__ uint32_t cell_id(const GridP& g, int cx, int cy, int 
 // The grid bins on the BINARY32 value of the coordinate relative to the grid origin -- the same number the screening
 // copies (sorted32) hold -- so a kernel that has only the 8/16-byte screening copy of a point knows its cell, and the
 // partition build can carry binary32 records.  rel32 is monotone in x, hence so is the cell index; the cell width
-// includes the rounding of two such values (run(): cellw), so two points within eps of each other on an axis still
+// includes the rounding of two such values (grid_geometry: cellw), so two points within eps of each other on an axis still
 // land in the same or in adjacent cells.
 // (the factor is a power of two: exact, so the scaled value rounds exactly like the unscaled one would in a wider format)
 __device__ __forceinline__ float rel32(double x, double mn, double scale) { return (float)((x - mn) * scale); }
@@ -170,9 +184,11 @@ __device__ __forceinline__ void store_pt32(float* __restrict__ c, int64_t i, con
   }
 }
 
-// Where the binary64 coordinates of cell-ordered position p are: a cell-ordered copy (idx == NULL, the sort-based
-// build and the staged multi-GPU calls), or the CALLER's array through the point's index (the partition build carries
-// binary32 records only).  Read by the exact re-test of a pair the binary32 screen cannot decide -- a handful per
+// Where the binary64 coordinates of cell-ordered position p are: in the CALLER's array, at the point's index idx[p] (the
+// partition build carries binary32 records only, there is no cell-ordered binary64 copy).  idx is sord, the list
+// positions, which ARE the indices unless the caller passed d_ord; with d_ord it is b_cellof, the index array the build
+// then writes besides (GridBuildArgs::sidx).  idx == NULL would mean base is in cell order already: no caller does that.
+// Read by the exact re-test of a pair the binary32 screen cannot decide -- a handful per
 // million candidates on real-valued clouds -- so the gather costs nothing there; on inputs where many pairs sit exactly
 // on the threshold (lattices with eps on the lattice) it is the price of the lighter build.
 struct ExactSrc {
@@ -231,6 +247,6 @@ struct GridOutputArgs {
   int32_t* labels = nullptr;
   uint8_t* is_core = nullptr;
   uint8_t* is_classed = nullptr;
-  unsigned long long* counters = nullptr;  // [4..36): points not classed on entry (only with have_in_classed)
+  unsigned long long* counters = nullptr;  // the counter block: CNT_UNCLASSED slots += points not classed on entry (only with have_in_classed)
 };
 int vcp_grid_output_partition(vcp_ctx* ctx, const GridOutputArgs& a);

@@ -753,7 +753,7 @@ __global__ __launch_bounds__(OWT) void k_out_write(const uint2* __restrict__ rec
     if (threadIdx.x == 0) {
       unsigned t = 0;
       for (int k = 0; k < OWT / 64; k++) t += wc[k];
-      if (t) atomicAdd(&counters[4 + (blockIdx.x & 31)], (unsigned long long)t);
+      if (t) atomicAdd(&counters[CNT_UNCLASSED + (blockIdx.x & (CNT_SPREAD - 1))], (unsigned long long)t);
     }
   }
 }

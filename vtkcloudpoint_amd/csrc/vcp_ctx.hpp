@@ -32,7 +32,7 @@ struct vcp_ctx {
   hipDeviceProp_t prop;
   // pinned scratch for tiny readbacks (64 KB).  Who reads back where (byte offsets; a context runs one call at a time on
   // one stream, and every user has consumed its words before the call that wrote them returns or goes on):
-  //   [0, 1024)     the DBSCAN engine: bounds, counters, work sizes (dbscan.hip); the block partition's bounds (blockpart.hip);
+  //   [0, 1024)     the DBSCAN engine's EnginePinned: bounds, two totals, counters (dbscan.hip); the block partition's bounds (blockpart.hip);
   //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
   //                 nearest-neighbour grid's bounds (nngrid.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
