@@ -11,6 +11,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import centroid_ref as R  # noqa: E402  (the replay of the centroid kernels' summation tree)
 from oracle import binding as O  # noqa: E402  (test tooling: the oracle is the checker)
 from vtkcloudpoint_amd import _native as N  # noqa: E402
 
@@ -120,6 +122,11 @@ def tools_case():
     motor) on random clouds"""
     n = int(10 ** rng.uniform(0.5, 5.3))
     K = int(rng.integers(1, max(2, min(n, 3000) + 1)))
+    # few, large clusters (above 16384 members a cluster spans several chunks of the tree): a tenth of the cases, and the
+    # first one of every sweep, so that the bounded sweep always has one
+    if (rng.random() < 0.1) | (done.get("tools", 0) == 0):
+        K = int(rng.integers(1, 9))
+        n = max(n, 20000 * (K + 1))
     K = min(K, n)
     xyz = rng.uniform(-100, 100, (n, 3)) if rng.random() < 0.7 else rng.integers(-9, 9, (n, 3)).astype(np.float64)
     motor = rng.uniform(-10, 10, (n, 2))
@@ -130,6 +137,10 @@ def tools_case():
     full = oc > 0
     ok = ok and np.allclose(g3[full], o3[full], rtol=1e-12, atol=1e-9) and np.allclose(g2[full], o2[full], rtol=1e-12, atol=1e-10)
     ok = ok and np.isnan(g3[~full]).all()
+    t3, t2, tc = R.tree_centroids(xyz, motor, lab, K)  # bit for bit against the replay of the tree
+    ok = ok and np.array_equal(gc, tc) and np.array_equal(g3, t3, equal_nan=True) and np.array_equal(g2, t2, equal_nan=True)
+    if int(oc.max()) > R.CH:
+        done["tools_multichunk"] = done.get("tools_multichunk", 0) + 1
     grp = rng.integers(0, K + 1, n).astype(np.int32)  # 1..K, 0 = in no list
     grp[:K] = np.arange(1, K + 1)  # no empty list: clusList[i].li[0] throws in the C# (VCP_ERR_INDEX here, covered by the tests)
     cid = rng.integers(0, 3, n).astype(np.int32)
@@ -139,6 +150,8 @@ def tools_case():
     v3, vi = O.fixed_centroids(xyz, grp, cid, pc, K, ign)
     has = vi > 0
     ok = ok and np.array_equal(wi, vi) and np.allclose(w3[has], v3[has], rtol=1e-12, atol=1e-9)
+    u3, ui = R.tree_centroids_weighted(xyz, grp, cid, pc, K, ign)
+    ok = ok and np.array_equal(wi, ui) and np.array_equal(w3, u3, equal_nan=True)
     cen = np.round(rng.uniform(0, 30, (min(K, 2000), 2)) * 8) / 8
     ids = np.arange(1, len(cen) + 1, dtype=np.int32)
     thr = float(rng.choice([0.25, 0.5, 1.0]))
@@ -291,8 +304,9 @@ def run(budget=300.0, seed=12345, max_log_n=6.3, gpu_bound=None, device=0, quiet
         if (done["dbscan"] % 50) == 0:
             say("%.0f s: %d dbscan, %d block pipelines agree" % (time.time() - t0, done["dbscan"], done["blocks"]), flush=True)
     msg = ("OK: %d dbscan calls, %d block pipelines, %d nearest-neighbour / matching cases, %d calls of the dead class DB "
-           "bit-exact and %d centroid / merge / keyed-pipeline cases against the oracle (seed %d)"
-           % (done["dbscan"], done["blocks"], done.get("nn", 0), done.get("db", 0), done.get("tools", 0), seed))
+           "bit-exact and %d centroid / merge / keyed-pipeline cases (%d with a multi-chunk cluster) against the oracle "
+           "(seed %d)" % (done["dbscan"], done["blocks"], done.get("nn", 0), done.get("db", 0), done.get("tools", 0),
+                          done.get("tools_multichunk", 0), seed))
     print(msg, flush=True)
     if own:
         ctx.close()

@@ -5,11 +5,13 @@ BC/Tools.cs:162-195), BC/ICP.cs:18-285, FrmMain.cs:3572-3618 (matching).
 
 The clustering is the monolithic DBImproved.dbscan on (motor_x, motor_y) (BC/DBImproved.cs:91-114); the literal O(n^2)
 port cannot run at this size, the oracle's order-free formulation (proved equal to the literal one on small inputs,
-tests/test_oracle_dbscan.py) takes ~90 s.  Bars: labels / core flags / counters bit-exact, centroids 1e-12 relative,
+tests/test_oracle_dbscan.py) takes ~90 s.  Bars: labels / core flags / counters bit-exact, centroids 1e-12 relative to
+the oracle's sequential sums and bit for bit equal to the replay of the kernel's tree (tests/centroid_ref.py),
 ICP R, t, RMSE within 1e-5 (north_star), matching bit-exact."""
 import numpy as np
 import pytest
 
+import centroid_ref
 from vtkcloudpoint_amd import _native as N
 from vtkcloudpoint_amd import synth
 
@@ -37,6 +39,8 @@ def test_c5_50m_dbscan_centroids_icp_match(vcp_ctx, oracle):
     assert np.array_equal(gcnt, ocnt) and int(gcnt.min()) >= 1
     assert np.allclose(g3, o3, rtol=1e-12, atol=1e-12)
     assert np.allclose(g2, o2, rtol=1e-12, atol=1e-12)
+    t3, t2, tcnt = centroid_ref.tree_centroids(d["xyz"], d["motor"], g["labels"], K)
+    assert np.array_equal(g3, t3) and np.array_equal(g2, t2) and np.array_equal(gcnt, tcnt)
 
     # 3. ICP of the centroids (data) against a rotated + shifted copy (model = "truth"), ICP.go_hell_ICP's intended
     #    arithmetic; the first round's correspondences are already the right ones at this rotation

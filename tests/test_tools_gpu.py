@@ -3,11 +3,16 @@ centroid<->truth matching, through the C-ABI, vs the CPU oracle."""
 import numpy as np
 import pytest
 
+import centroid_ref as R
 from vtkcloudpoint_amd import _native as N
 from vtkcloudpoint_amd import synth
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-12  # fixed-order tree sum vs the C#'s sequential sum
+RTOL = 1e-12  # fixed-order tree sum vs the C#'s sequential sum; beside it, bit for bit vs the tree's replay
+
+
+def same(a, b):
+    return np.array_equal(a, b, equal_nan=True)
 
 
 def test_centroids_c1_and_1m(vcp_ctx, oracle):
@@ -18,6 +23,8 @@ def test_centroids_c1_and_1m(vcp_ctx, oracle):
         r3, r2, rc = oracle.centroids(d["xyz"], d["motor"], o["labels"], K)
         assert np.array_equal(cnt, rc)
         assert np.allclose(c3, r3, rtol=RTOL, atol=1e-12) and np.allclose(c2, r2, rtol=RTOL, atol=1e-12)
+        t3, t2, tc = R.tree_centroids(d["xyz"], d["motor"], o["labels"], K)
+        assert same(c3, t3) and same(c2, t2) and np.array_equal(cnt, tc)
         # run-to-run deterministic (fixed reduction tree)
         c3b, c2b, _ = vcp_ctx.centroids(d["xyz"], d["motor"], o["labels"], K)
         assert np.array_equal(c3, c3b) and np.array_equal(c2, c2b)
@@ -34,7 +41,14 @@ def test_centroids_edge_cases(vcp_ctx, oracle):
     r3, r2, rc = oracle.centroids(xyz, motor, lab, 9)
     assert np.array_equal(cnt, rc) and cnt[2] == 0 and cnt[8] == 0
     assert np.allclose(c3, r3, rtol=RTOL, equal_nan=True) and np.allclose(c2, r2, rtol=RTOL, equal_nan=True)
-    # a giant cluster spanning many chunks and all-noise input
+    t3, t2, _ = R.tree_centroids(xyz, motor, lab, 9)
+    assert same(c3, t3) and same(c2, t2)
+    # a giant cluster spanning many chunks (3 full ones and a part of a fourth) and all-noise input
+    big = 3 * R.CH + 1000
+    bxyz = rng.random((big, 3))
+    c3, _, cnt = vcp_ctx.centroids(bxyz, None, np.ones(big, np.int32), 1)
+    assert cnt[0] == big > 3 * R.CH and np.allclose(c3[0], bxyz.mean(0), rtol=1e-12)
+    assert same(c3, R.tree_centroids(bxyz, None, np.ones(big, np.int32), 1)[0])
     lab[:] = 1
     c3, _, cnt = vcp_ctx.centroids(xyz, None, lab, 1)
     assert cnt[0] == n and np.allclose(c3[0], xyz.mean(0), rtol=1e-12)
@@ -62,6 +76,8 @@ def test_merge_and_refresh(vcp_ctx, oracle):
         lg, kg, g3, g2, gc = vcp_ctx.refresh_by_dictionary(d["xyz"], d["motor"], o["labels"], K, mg)
         assert ko == kg and np.array_equal(lo, lg) and np.array_equal(oc, gc)
         assert np.allclose(o3, g3, rtol=RTOL, atol=1e-12) and np.allclose(o2, g2, rtol=RTOL, atol=1e-12)
+        tl, tk, t3, t2, tc = R.tree_refresh(d["xyz"], d["motor"], o["labels"], K, mg)
+        assert tk == kg and np.array_equal(tl, lg) and np.array_equal(tc, gc) and same(g3, t3) and same(g2, t2)
     assert co > 0  # the largest threshold really merges something
 
 
@@ -228,6 +244,8 @@ def test_fixed_points_centroid_weighted(vcp_ctx, oracle):
             o3, oi = oracle.fixed_centroids(xyz, group, c, pts, K, ignore)
             assert np.array_equal(gi, oi)
             assert np.allclose(g3, o3, rtol=RTOL, atol=1e-12)
+            t3, ti = R.tree_centroids_weighted(xyz, group, c, pts, K, ignore)
+            assert np.array_equal(gi, ti) and same(g3, t3)
     # unweighted limit: ptsCount 1 everywhere equals Tools.GetClusList's mean
     ones = np.ones(n, np.int32)
     g3, gi = vcp_ctx.centroids_weighted(xyz, group, None, ones, K, False)

@@ -6,7 +6,8 @@
 // members -> one workgroup each (thread-strided partial sums, wave shuffle tree, 4 waves in order), then
 // the chunk partials of a cluster are added in chunk order.  The partition depends only on the cluster
 // sizes, so results are run-to-run deterministic; they differ from the sequential sum in the last bits
-// (tests: 1e-12 relative).  Algorithmic bytes: 4 (label) + 24 (xyz) + 16 (motor) per point, read once.
+// (tests: bit for bit against a numpy replay of this tree, tests/centroid_ref.py; DESIGN.md section 13 has the bound
+// against the true mean and the inputs on which the two sums differ in kind).  Algorithmic bytes: 4 (label) + 24 (xyz) + 16 (motor) per point, read once.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -5,9 +5,10 @@
 // Here: one conversion pass, then a device hash table on the exact (tmpx, tmpy, tmpz) triple -- insert with
 // CAS + atomicMin (a slot ends up holding the smallest row index of its class), second pass keeps a row iff it
 // is that smallest index, i.e. the first occurrence, exactly what the sequential FindAll rule keeps.
-// Equality is the C#'s `==` on doubles (-0 == +0, NaN != NaN).  sin/cos are the device libm's: X,Y,Z agree with
-// the host's to a few ulp (tests: 1e-12 relative), duplicate decisions are bit-exact (identical inputs give
-// identical outputs on either side).
+// Equality is the C#'s `==` on doubles (-0 == +0, NaN != NaN).  sin/cos are the device libm's: tmpx, tmpy are held to
+// 2 L + 1 and tmpz to L + 0.5 units of 2^-52 of the true value at the binary64 angles (tests/test_import_accuracy_gpu.py,
+// DESIGN.md section 13 for L and the measured figures; the order of operations in the two angle expressions is part of
+// that contract), duplicate decisions are bit-exact (identical inputs give identical outputs on either side).
 // The duplicate test of the C# compares the STORED, direction-mapped p.X, p.Y with the unmapped tmpx, tmpy
 // (:1065); they coincide for the ImportPts defaults xdir = 2, ydir = 1 (ImportPts.cs:18-19).  For other
 // directions the C# test can only fire on mirrored points; that quirk is not rebuilt: VCP_ERR_UNSUPPORTED.
