@@ -333,7 +333,10 @@ int vcp_icp_dev(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d
                 double tol, int max_iter, int stop_rule, double R[9], double T[3], double* sse,
                 double* rmse, int32_t* iters);
 /* One correspondence pass (A10+A11): sums[16] = sum p[3], sum y[3], sum p y^T[9], SSE for
- * p = R data + T; nn [nd] may be NULL.  R,T NULL = identity. */
+ * p = R data + T; nn [nd] may be NULL.  R,T NULL = identity.
+ * The summation order -- and with it every bit of sums[] -- is fixed by (nm, nd, whether every model coordinate is
+ * finite) and by nothing else: not by the device, the context's history or nn being NULL.  The order is restated in
+ * tests/icp_sums_ref.py (a numpy replay the suite compares with bit for bit) and in DESIGN.md section 13. */
 int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
                  const double R[9], const double T[3], double sums[16], int32_t* nn);
 

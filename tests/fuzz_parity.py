@@ -6,6 +6,7 @@ shapes, far outliers, non-finite coordinates, every metric, isClassed inputs, cf
 usage: python tests/fuzz_parity.py [seconds] [seed]"""
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -13,6 +14,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import centroid_ref as R  # noqa: E402  (the replay of the centroid kernels' summation tree)
+import icp_sums_ref as IS  # noqa: E402  (the replay of the ICP moment sums' reduction tree)
 from oracle import binding as O  # noqa: E402  (test tooling: the oracle is the checker)
 from vtkcloudpoint_amd import _native as N  # noqa: E402
 
@@ -104,6 +106,16 @@ def nn_case():
     if not np.array_equal(nn, want):
         np.savez("gpurun_out/fuzz_fail_nn.npz", model=model, data=data)
         fail("MISMATCH nn nm=%d nd=%d kind=%d" % (nm, nd, kind))
+    # the 16 moment sums, bit for bit against the replay of their tree: IS.plan gives the path of a finite model, a
+    # model with a non-finite coordinate keeps the pairs path up to 512 points and takes the tiled one beyond
+    tree = IS.sums(model, data, None, None, want)
+    if not np.array_equal(sums, tree, equal_nan=True):
+        dump = os.path.join(tempfile.gettempdir(), "fuzz_fail_sums.npz")
+        np.savez(dump, model=model, data=data, sums=sums, tree=tree)
+        fail("MISMATCH sums nm=%d nd=%d kind=%d path=%s columns %s (inputs in %s)" % (
+            nm, nd, kind, IS.plan(nm, nd, np.isfinite(model).all())["path"],
+            np.flatnonzero(~((sums == tree) | (np.isnan(sums) & np.isnan(tree)))).tolist(), dump))
+    done["sums"] = done.get("sums", 0) + 1
     if np.isfinite(model).all():
         M = np.eye(4)
         M[:3, 3] = rng.normal(0, 0.1, 3)
@@ -303,10 +315,11 @@ def run(budget=300.0, seed=12345, max_log_n=6.3, gpu_bound=None, device=0, quiet
             done["blocks"] += 1
         if (done["dbscan"] % 50) == 0:
             say("%.0f s: %d dbscan, %d block pipelines agree" % (time.time() - t0, done["dbscan"], done["blocks"]), flush=True)
-    msg = ("OK: %d dbscan calls, %d block pipelines, %d nearest-neighbour / matching cases, %d calls of the dead class DB "
+    msg = ("OK: %d dbscan calls, %d block pipelines, %d nearest-neighbour / matching cases (%d sets of ICP moment sums "
+           "equal to the replay of their tree), %d calls of the dead class DB "
            "bit-exact and %d centroid / merge / keyed-pipeline cases (%d with a multi-chunk cluster) against the oracle "
-           "(seed %d)" % (done["dbscan"], done["blocks"], done.get("nn", 0), done.get("db", 0), done.get("tools", 0),
-                          done.get("tools_multichunk", 0), seed))
+           "(seed %d)" % (done["dbscan"], done["blocks"], done.get("nn", 0), done.get("sums", 0), done.get("db", 0),
+                          done.get("tools", 0), done.get("tools_multichunk", 0), seed))
     print(msg, flush=True)
     if own:
         ctx.close()

@@ -1,13 +1,33 @@
 """GPU parity: libvcp.so ICP (through the C-ABI) vs the CPU oracle.  Tolerance 1e-5 on R, t, RMSE
 (BASELINE.json north_star); nearest-neighbour indices are bit-exact."""
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
+import icp_sums_ref as S
+from test_centroid_replay_gpu import same
 from vtkcloudpoint_amd import _native as N
 from vtkcloudpoint_amd import synth
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
+
+
+def pinned(sums, ref, model, data, nn, R=None, T=None):
+    """What the rtol / atol lines beside it cannot say: the device's 16 sums are, bit for bit, the replay of the kernels'
+    reduction tree (tests/icp_sums_ref.py), and they differ from the oracle's sequential sums `ref` by at most the sum
+    of the two a-priori bounds (the tree's, and gamma_(nd - 1 + k) sum|t| of the sequential sum)."""
+    model, data = np.ascontiguousarray(model, np.float64), np.ascontiguousarray(data, np.float64)
+    pl = S.plan(len(model), len(data), np.isfinite(model).all())
+    t = S.terms(model, data, R, T, nn)
+    want = S.replay(t, len(data), pl)
+    assert same(sums, want), (np.flatnonzero(sums != want), sums, want)
+    sabs = S.abs_sums(t)
+    bt, bs = S.bound(pl, t, sabs=sabs), S.bound(pl, t, sequential=True, sabs=sabs)
+    for k in range(16):
+        assert abs(Fraction(float(sums[k])) - Fraction(float(ref[k]))) <= bt[k] + bs[k], (k, sums[k], ref[k])
+    return True
 
 
 def test_nn_and_sums_bit_exact_indices(vcp_ctx, oracle):
@@ -16,6 +36,7 @@ def test_nn_and_sums_bit_exact_indices(vcp_ctx, oracle):
     assert np.array_equal(nn, oracle.find_closest(d["model"], d["data"]))
     ref = oracle.icp_sums(d["model"], d["data"])
     assert np.allclose(sums, ref, rtol=1e-12, atol=1e-9)
+    assert pinned(sums, ref, d["model"], d["data"], nn)
     # with a transform: P = R data + T first (TransPoint), same op order as the C#
     R = synth.rotation_about((0, 1, 0), 3.0)
     T = np.array([0.1, 0.2, -0.3])
@@ -23,6 +44,8 @@ def test_nn_and_sums_bit_exact_indices(vcp_ctx, oracle):
     P = oracle.trans_point(d["data"], R, T)
     assert np.array_equal(nn, oracle.find_closest(d["model"], P))
     assert np.allclose(sums, oracle.icp_sums(d["model"], P), rtol=1e-12, atol=1e-9)
+    assert np.array_equal(P, S.transform(d["data"], R, T))   # the replay's TransPoint is the oracle's
+    assert pinned(sums, oracle.icp_sums(d["model"], P), d["model"], d["data"], nn, R, T)
 
 
 def test_nn_tie_lowest_index(vcp_ctx, oracle):
@@ -95,6 +118,7 @@ def test_large_model_goes_through_lds_tiles(vcp_ctx, oracle, nd):
     sums, nn = vcp_ctx.icp_sums(model, data)
     assert np.array_equal(nn, oracle.find_closest(model, data))
     assert np.allclose(sums, oracle.icp_sums(model, data), rtol=1e-12, atol=1e-6)
+    assert pinned(sums, oracle.icp_sums(model, data), model, data, nn)
     # K x K form of MainForm.ICP: centroids against a rotated + shifted copy
     cen = np.round(rng.uniform(0, 200.0, (2000, 3)) * 1024) / 1024
     truth = cen @ synth.rotation_about((1.0, 1.0, 1.0), 0.2).T + np.array([0.3, -0.2, 0.1])
@@ -117,6 +141,7 @@ def test_grid_nn_30k_x_30k_tie_heavy(vcp_ctx, oracle):
     sums, nn = vcp_ctx.icp_sums(model, data)
     assert np.array_equal(nn, oracle.find_closest(model, data))
     assert np.allclose(sums, oracle.icp_sums(model, data), rtol=1e-12, atol=1e-3)
+    assert pinned(sums, oracle.icp_sums(model, data), model, data, nn)
     for flat in (1, 2):  # planar (z constant), collinear (y and z constant)
         m2 = model[:5000].copy()
         m2[:, 3 - flat:] = 7.0

@@ -33,7 +33,7 @@
 namespace {
 
 constexpr int ITPB = 256;
-constexpr int ICP_MAX_BLOCKS = 1024;
+constexpr int ICP_MAX_BLOCKS = 1024;  // part of the sums' bits: tests/icp_sums_ref.py restates it (MAX_BLOCKS), change both
 constexpr int ICP_BATCH = 8;  // rounds enqueued per host synchronisation
 constexpr int ICPMS_MAX_POSES = 4096;
 
@@ -746,6 +746,7 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   const bool small = grid ? nd * nng::NNG <= (int64_t)64 * ICP_MAX_BLOCKS : small0;
   const int tb = small ? 64 : ITPB;
   const bool pairs = !grid && !tiled;  // scalar-cache models: two data points per lane (k_icp_pass_small)
+  // tb, nb and the path fix the order of the 16 sums bit for bit: restated as plan() in tests/icp_sums_ref.py, change both
   const int nb = (int)vcp_blocks(grid ? nd * nng::NNG : pairs ? (nd + 1) / 2 : nd, tb, ICP_MAX_BLOCKS);
   int ib = 1;
   while ((1 << ib) < (int)nm) ib++;
