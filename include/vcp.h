@@ -384,6 +384,50 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
                        int max_landmarks, double inlier_dist, double M_best[16], int32_t* best,
                        double* M_all, double* mean_dist, int32_t* inliers);
 
+/* -- gated ICP ------------------------------------------------------------------------------------
+ * Every loop above feeds every landmark into the round's 16 sums, however far its nearest target is; centroid lists
+ * hold false clusters (a wall beside the target field, clutter between targets) that pull every round.  The gated
+ * forms leave pairs beyond a per-round distance out of the sums (PCL's setMaxCorrespondenceDistance, Open3D's
+ * max_correspondence_distance; VTK's class has none).
+ *
+ * One round, state (R, T), gate g.  The landmark p = R d + T and its nearest target y are those of vcp_icp_sums: the
+ * same transform, the same NN rule, lowest index on ties.  With e = p - y,
+ *   dd = e0*e0 + e1*e1 + e2*e2     the SSE term: binary64, left to right, no contraction
+ *   the pair is DROPPED iff sqrt(dd) >= g (correctly rounded sqrt).  A NaN dd is kept and poisons the sums, as it
+ *   does ungated; with finite coordinates that do not overflow, g = +inf drops nothing.
+ * A dropped pair adds +0.0 to each of the 16 sums AT ITS OWN PLACE in vcp_icp_sums's summation order, which stays fixed
+ * by (nm, nd, whether every model coordinate is finite) and nothing else: tests/icp_sums_ref.py replays it with the
+ * dropped rows zeroed.  kept = the exact number of kept pairs.  The round's Horn step is the ungated one on (sums,
+ * kept): kept takes the place of nd, the eigenvector basis is carried from round to round as before.  A round with
+ * kept < min_pairs is STARVED: R, T and the basis stay as they are, the round still counts, and `starved` goes up by
+ * one.  mean_dist of a round = sqrt(sums[15] / kept), +inf when kept = 0.
+ *
+ * vcp_icp_sums_gated: one gated pass, the test handle on the kernels as vcp_icp_sums is.  Arguments as vcp_icp_sums;
+ * *kept (required) = the count; nn [nd] and keep [nd] (1 = kept, 0 = dropped) may be NULL.  gate NaN or <= 0:
+ * VCP_ERR_ARG, nothing written.  gate = +inf: sums bit-identical to vcp_icp_sums.
+ *
+ * vcp_icp_gated: vcp_icp_multistart with a gate schedule.  Everything not named here is vcp_icp_multistart's, word for
+ * word: the landmarks, the default poses and starts, exactly max_iter rounds, the composition, the inlier score over
+ * all ns source points (not gated: inlier_dist alone decides it), best = most inliers, then the smaller mean_dist,
+ * then the lower h.
+ *   gates [n_gates]  round r (1-based) uses gates[min(r, n_gates) - 1]: the last entry serves every later round
+ *   min_pairs        the fewest kept pairs a round acts on (3 determines a rigid motion of points in general position)
+ *   kept [n_poses]   the last round's count; starved [n_poses] the number of starved rounds.  Both may be NULL.
+ * n_gates < 1, min_pairs < 1, a gate NaN or <= 0: VCP_ERR_ARG.  A failed Horn solve in a round that is not starved:
+ * VCP_ERR_ARG, as in vcp_icp_multistart.  No output is written on an error.  The other errors and limits are
+ * vcp_icp_multistart's.  With every gate +inf, M_all, mean_dist, inliers and best equal vcp_icp_multistart's bit for
+ * bit, kept is the landmark count and starved 0.  A pose's bits do not depend on the other poses of the call.  The
+ * schedule is read on the device: all rounds are enqueued at once, one synchronisation at the end.
+ * Timing phases: icpg_rounds, icpg_score (csrc/icp.hip). */
+int vcp_icp_sums_gated(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
+                       const double R[9], const double T[3], double gate, double sums[16], int64_t* kept,
+                       int32_t* nn, uint8_t* keep);
+int vcp_icp_gated(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                  int32_t n_poses, const double* init_R, const double* init_T, int max_iter, int max_landmarks,
+                  const double* gates, int32_t n_gates, int32_t min_pairs, double inlier_dist, double M_best[16],
+                  int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
+                  int32_t* starved);
+
 /* -- minimal bounding circles ---------------------------------------------
  * Replaces Tools.getCircles (BC/Tools.cs:394-409) / Geometry.FindMinimalBoundingCircle
  * (BC/Geometry.cs:247-319; gift-wrap hull :122-208, circle through 2 or 3 hull points :260-312): for

@@ -32,6 +32,7 @@ SYMBOLS = [
     "vcp_blocks_build_dev", "vcp_blocks_finish_local_dev", "vcp_blocks_finish_zero_dev", "vcp_blocks_finish_zcoords_dev",
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
     "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
+    "vcp_icp_sums_gated", "vcp_icp_gated",
 ]
 
 
@@ -224,6 +225,22 @@ class Context:
         self._chk(lib().vcp_icp_sums(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
                                      C.c_int64(len(data)), _ptr(R), _ptr(T), _ptr(sums), _ptr(nn)))
         return sums, nn
+
+    def icp_sums_gated(self, model, data, gate, R=None, T=None, want_nn=True, want_keep=True):
+        """One gated pass (vcp_icp_sums_gated): pairs with sqrt(dd) >= gate add +0.0 at their place in icp_sums's
+        tree.  Returns (sums [16], kept, nn [nd] int32 or None, keep [nd] uint8 or None)."""
+        model = _f64(model, 3)
+        data = _f64(data, 3)
+        R = None if R is None else _f64(R).reshape(9)
+        T = None if T is None else _f64(T).reshape(3)
+        sums = np.zeros(16)
+        kept = C.c_int64(0)
+        nn = np.zeros(len(data), np.int32) if want_nn else None
+        keep = np.zeros(len(data), np.uint8) if want_keep else None
+        self._chk(lib().vcp_icp_sums_gated(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
+                                           C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums),
+                                           C.byref(kept), _ptr(nn), _ptr(keep)))
+        return sums, kept.value, nn, keep
 
     # -- centroids / merge / match -----------------------------------------------------------------
     def centroids(self, xyz, motor, labels, K):
@@ -571,6 +588,40 @@ class Context:
                                            int(max_iter), int(max_landmarks), C.c_double(inlier_dist), _ptr(M),
                                            C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl)))
         return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl)
+
+    def icp_gated(self, source, target, gates, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
+                  inlier_dist=np.inf):
+        """icp_multistart with a per-round gate on the correspondence distance (vcp_icp_gated): round r (1-based) leaves
+        pairs at gates[min(r, len(gates)) - 1] or farther out of its sums; a round that keeps fewer than min_pairs
+        pairs changes nothing and counts as starved.  poses, init_T, inlier_dist: as icp_multistart.  Returns its dict
+        plus kept [H] int64 (the last round's count) and starved [H] int32."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        gates = _f64(gates).reshape(-1)
+        if isinstance(poses, (int, np.integer)):
+            H, init_R = int(poses), None
+        else:
+            init_R = _f64(poses).reshape(-1, 9)
+            H = len(init_R)
+        if init_T is not None:
+            init_T = _f64(init_T, 3)
+            if len(init_T) != H:
+                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
+        n = max(H, 0)
+        M = np.zeros(16)
+        M_all = np.zeros((n, 16))
+        md = np.zeros(n)
+        inl = np.zeros(n, np.int32)
+        kept = np.zeros(n, np.int64)
+        starved = np.zeros(n, np.int32)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_icp_gated(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
+                                      C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter),
+                                      int(max_landmarks), _ptr(gates), C.c_int32(len(gates)), C.c_int32(min_pairs),
+                                      C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl),
+                                      _ptr(kept), _ptr(starved)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
+                    kept=kept, starved=starved)
 
     def import_convert(self, rows, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True):
         """MainForm.AddFolder per-row work: dict(xyz [n,3], state [n] (0 filtered / 1 kept / 2 duplicate), kept, duplicates)."""

@@ -8,7 +8,7 @@
 //   k_icp_step  fixed-order reduction of the partial rows (bitwise reproducible, no float atomics), then ONE
 //               thread solves Horn's closed form (the INTENDED arithmetic of :53-124), applies
 //               the stop rule (:149,:180) and composes R <- R1 R, T <- R1 T + T1 (:149-177) in the state.
-// The host enqueues rounds in batches of 8 and reads the 430-byte state back once per batch; kernels of rounds
+// The host enqueues rounds in batches of 8 and reads the 424-byte state back once per batch; kernels of rounds
 // after the stop see state.done and return at once.
 // Multi-start (vcp_icp_multistart): H independent states run side by side -- blockIdx.y of the pass selects the state
 // and its slice of partial rows, k_icp_step runs one workgroup per state, and each state's partition into workgroups and
@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "match.hpp"
@@ -45,8 +46,21 @@ struct IcpState {
   double sums[16];
   double cen[3], mmax;  // centre of the model's bounding box and its half extent: frame and scale of the screening
   double V[16];         // eigenvector basis of the last Horn solve (all zero = none yet)
-  int round, done, failed, pad;
+  int round, done, failed;
+  int starved;     // gated runs: rounds that kept fewer than min_pairs pairs (R, T, V untouched by them)
+  long long kept;  // gated runs: pairs the last pass kept
 };
+
+// What a gated pass reads beside the state (vcp.h, vcp_icp_gated): the schedule on the device (round r, 1-based, uses
+// gates[min(r, n_gates) - 1]; the state's round counter says which), one kept count per workgroup next to its partial
+// row, and optionally the per-point verdict.
+struct GateArgs {
+  const double* gates;
+  int n_gates;
+  uint32_t* pkept;  // [poses][workgroups]
+  uint8_t* keep;    // [nd] or NULL
+};
+struct NoGate {};
 
 
 // bounding box of the model -> centre and half extent in the nst states (single workgroup: models are small).  A model
@@ -121,14 +135,39 @@ struct StepArgs {
 };
 
 constexpr int MTILE = 1024;
-template <int TB, int NNMODE>
-__global__ __launch_bounds__(TB) void k_icp_pass(const double* __restrict__ model, const float4* __restrict__ model32,
-                                                int nm, const double* __restrict__ data, int64_t nd,
-                                                const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                int32_t* __restrict__ nn, NNGrid ng) {
+// The gate of the pass a gated kernel runs now, and a workgroup's kept count written next to its partial row (wave
+// shuffle, then the waves in order: integers, exact in any order).
+__device__ __forceinline__ double gate_now(const GateArgs& ga, const IcpState* st) {
+  return ga.gates[min(st->round + 1, ga.n_gates) - 1];
+}
+template <int TB>
+__device__ __forceinline__ void block_count(uint32_t c, uint32_t* __restrict__ out) {
+  __shared__ uint32_t sk[TB / 64];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+  if ((threadIdx.x & 63) == 0) sk[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < TB / 64; w++) t += sk[w];
+    *out = t;
+  }
+}
+
+// GATED (G = GateArgs): a pair whose distance sqrt(dd) is >= the round's gate adds +0.0 to each of the 16 rows at its
+// own place in the tree, which therefore stays the ungated one; dd is the SSE term.  A NaN dd compares false: kept.
+template <int TB, int NNMODE, class G>
+__device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, const float4* __restrict__ model32,
+                                              int nm, const double* __restrict__ data, int64_t nd,
+                                              const IcpState* __restrict__ st, double* __restrict__ partial,
+                                              int32_t* __restrict__ nn, const NNGrid& ng, const G& ga) {
+  constexpr bool GATED = std::is_same<G, GateArgs>::value;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * 16;
   if (st->done) return;
+  double gate = 0.0;
+  uint32_t nkept = 0;
+  if constexpr (GATED) gate = gate_now(ga, st);
   constexpr bool TILED = NNMODE == 1, GRID = NNMODE == 2;
   __shared__ float4 tile[TILED ? MTILE : 1];
   double R[9], T[3];
@@ -298,17 +337,50 @@ __global__ __launch_bounds__(TB) void k_icp_pass(const double* __restrict__ mode
     if (nn) nn[i] = order;
     const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
     const double y[3] = {y0, y1, y2};
+    if constexpr (GATED) {
+      const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
+      const double dd = e0 * e0 + e1 * e1 + e2 * e2;
+      const bool kp = !(sqrt(dd) >= gate);
+      if (ga.keep) ga.keep[i] = kp ? 1 : 0;
+      nkept += kp ? 1u : 0u;
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
-      s[r] += p[r];
-      s[3 + r] += y[r];
+      for (int r = 0; r < 3; r++) {
+        s[r] += kp ? p[r] : 0.0;
+        s[3 + r] += kp ? y[r] : 0.0;
 #pragma unroll
-      for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[r] * y[c];
+        for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[r] * y[c] : 0.0;
+      }
+      s[15] += kp ? dd : 0.0;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        s[r] += p[r];
+        s[3 + r] += y[r];
+#pragma unroll
+        for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[r] * y[c];
+      }
+      const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
+      s[15] += e0 * e0 + e1 * e1 + e2 * e2;
     }
-    const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
-    s[15] += e0 * e0 + e1 * e1 + e2 * e2;
   }
   block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
+  if constexpr (GATED) block_count<TB>(nkept, ga.pkept + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+template <int TB, int NNMODE>
+__global__ __launch_bounds__(TB) void k_icp_pass(const double* __restrict__ model, const float4* __restrict__ model32,
+                                                int nm, const double* __restrict__ data, int64_t nd,
+                                                const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                int32_t* __restrict__ nn, NNGrid ng) {
+  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, NoGate());
+}
+template <int TB, int NNMODE>
+__global__ __launch_bounds__(TB) void k_icp_pass_gated(const double* __restrict__ model,
+                                                      const float4* __restrict__ model32, int nm,
+                                                      const double* __restrict__ data, int64_t nd,
+                                                      const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                      int32_t* __restrict__ nn, NNGrid ng, GateArgs ga) {
+  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, ga);
 }
 
 // ---- small models (nm <= 512: MainForm's 100 truths, C3) ---------------------------------------------------
@@ -330,14 +402,18 @@ __device__ __forceinline__ float min_raw(float a, float b) {
   return r;
 }
 
-template <int TB>
-__global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict__ model, const float4* __restrict__ model32,
-                                                      int nm, const double* __restrict__ data, int64_t nd,
-                                                      const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                      int32_t* __restrict__ nn, uint32_t imask, double tolk) {
+template <int TB, class G>
+__device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ model, const float4* __restrict__ model32,
+                                                    int nm, const double* __restrict__ data, int64_t nd,
+                                                    const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                    int32_t* __restrict__ nn, uint32_t imask, double tolk, const G& ga) {
+  constexpr bool GATED = std::is_same<G, GateArgs>::value;  // as in icp_pass_body
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * 16;
   if (st->done) return;
+  double gate = 0.0;
+  uint32_t nkept = 0;
+  if constexpr (GATED) gate = gate_now(ga, st);
   double R[9], T[3];
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = st->R[k];
@@ -440,18 +516,52 @@ __global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict_
       if (nn) nn[idx[h]] = order;
       const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
       const double y[3] = {y0, y1, y2};
+      if constexpr (GATED) {
+        const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
+        const double dd = e0 * e0 + e1 * e1 + e2 * e2;
+        const bool kp = !(sqrt(dd) >= gate);
+        if (ga.keep) ga.keep[idx[h]] = kp ? 1 : 0;
+        nkept += kp ? 1u : 0u;
 #pragma unroll
-      for (int r = 0; r < 3; r++) {
-        s[r] += p[h][r];
-        s[3 + r] += y[r];
+        for (int r = 0; r < 3; r++) {
+          s[r] += kp ? p[h][r] : 0.0;
+          s[3 + r] += kp ? y[r] : 0.0;
 #pragma unroll
-        for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[h][r] * y[c];
+          for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[h][r] * y[c] : 0.0;
+        }
+        s[15] += kp ? dd : 0.0;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+          s[r] += p[h][r];
+          s[3 + r] += y[r];
+#pragma unroll
+          for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[h][r] * y[c];
+        }
+        const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
+        s[15] += e0 * e0 + e1 * e1 + e2 * e2;
       }
-      const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
-      s[15] += e0 * e0 + e1 * e1 + e2 * e2;
     }
   }
   block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
+  if constexpr (GATED) block_count<TB>(nkept, ga.pkept + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+template <int TB>
+__global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict__ model, const float4* __restrict__ model32,
+                                                      int nm, const double* __restrict__ data, int64_t nd,
+                                                      const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                      int32_t* __restrict__ nn, uint32_t imask, double tolk) {
+  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, NoGate());
+}
+template <int TB>
+__global__ __launch_bounds__(TB) void k_icp_pass_small_gated(const double* __restrict__ model,
+                                                            const float4* __restrict__ model32, int nm,
+                                                            const double* __restrict__ data, int64_t nd,
+                                                            const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                            int32_t* __restrict__ nn, uint32_t imask, double tolk,
+                                                            GateArgs ga) {
+  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
 }
 
 // ---- Horn's unit-quaternion closed form (host and device: same code, same rounding) -----------------
@@ -636,14 +746,32 @@ __host__ __device__ inline bool horn(const double s[16], long long nd, double R1
   return true;
 }
 
+// R <- R1 R, T <- R1 T + T1 in the state (BaseClass/ICP.cs:163-177)
+__device__ __forceinline__ void icp_compose(IcpState* __restrict__ st, const double R1[9], const double T1[3]) {
+  double tR[9], tT[3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double acc = 0.0;
+      for (int k = 0; k < 3; k++) acc += R1[3 * i + k] * st->R[3 * k + j];
+      tR[3 * i + j] = acc;
+    }
+  for (int i = 0; i < 3; i++) {
+    double acc = 0.0;
+    for (int k = 0; k < 3; k++) acc += R1[3 * i + k] * st->T[k];
+    tT[i] = acc + T1[i];
+  }
+  for (int k = 0; k < 9; k++) st->R[k] = tR[k];
+  for (int k = 0; k < 3; k++) st->T[k] = tT[k];
+}
+
 // What follows the pass: fixed-order reduction of the partial rows (thread t adds rows t, t+TB, ... in order, then a
 // fixed shuffle/LDS tree: bitwise reproducible, no float atomics), then thread 0 advances the ICP state by one round.
 // (Running this in the pass's last workgroup -- ticket + release fence per workgroup -- was built and measured at
 // 1 M x 100: 74 us per round against 51 us for the two launches; the Horn solve's registers also halve the pass's
 // occupancy.  It stays a launch of its own.)
 template <int TB>
-__device__ __forceinline__ void icp_step_body(const double* __restrict__ partial, int nb, IcpState* __restrict__ st,
-                                              const StepArgs& a) {
+__device__ __forceinline__ void icp_fold_rows(const double* __restrict__ partial, int nb, IcpState* __restrict__ st,
+                                              double* tot) {
   double s[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) s[k] = 0.0;
@@ -652,10 +780,16 @@ __device__ __forceinline__ void icp_step_body(const double* __restrict__ partial
     for (int k = 0; k < 16; k++)
       s[k] += partial[(size_t)b * 16 + k];
   }
-  __shared__ double tot[16];
   block_fold<TB>(s, FoldSum(), tot);
   if (threadIdx.x < 16) st->sums[threadIdx.x] = tot[threadIdx.x];
   __syncthreads();
+}
+
+template <int TB>
+__device__ __forceinline__ void icp_step_body(const double* __restrict__ partial, int nb, IcpState* __restrict__ st,
+                                              const StepArgs& a) {
+  __shared__ double tot[16];
+  icp_fold_rows<TB>(partial, nb, st, tot);
   if (threadIdx.x != 0) return;
   if (a.mode == MODE_SUMS_ONLY) {
     st->done = 1;
@@ -685,20 +819,7 @@ __device__ __forceinline__ void icp_step_body(const double* __restrict__ partial
       for (int k = 0; k < 9; k++) st->R[k] = R1[k];
       for (int k = 0; k < 3; k++) st->T[k] = T1[k];
     } else {  // :163-177  R <- R1 R, T <- R1 T + T1
-      double tR[9], tT[3];
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-          double acc = 0.0;
-          for (int k = 0; k < 3; k++) acc += R1[3 * i + k] * st->R[3 * k + j];
-          tR[3 * i + j] = acc;
-        }
-      for (int i = 0; i < 3; i++) {
-        double acc = 0.0;
-        for (int k = 0; k < 3; k++) acc += R1[3 * i + k] * st->T[k];
-        tT[i] = acc + T1[i];
-      }
-      for (int k = 0; k < 9; k++) st->R[k] = tR[k];
-      for (int k = 0; k < 3; k++) st->T[k] = tT[k];
+      icp_compose(st, R1, T1);
     }
   }
   if (!go || round >= a.max_iter) st->done = 1;
@@ -711,6 +832,58 @@ __global__ __launch_bounds__(ITPB) void k_icp_step(const double* __restrict__ pa
   partial += (size_t)blockIdx.x * nb * 16;
   if (st->done) return;
   icp_step_body<ITPB>(partial, nb, st, a);
+}
+
+// The step of a gated round (vcp.h, vcp_icp_gated): the same fold of the partial rows, the kept counts of the
+// workgroups added up (integers: exact), then Horn on (sums, kept) and the composition -- or, with fewer than
+// min_pairs pairs kept, nothing: R, T and the basis V stay, the round counts and `starved` goes up.  Always max_iter
+// rounds, as MODE_VTK.  sums_only: the pass alone (vcp_icp_sums_gated).
+struct GateStepArgs {
+  long long min_pairs;
+  int max_iter, sums_only;
+};
+__global__ __launch_bounds__(ITPB) void k_icp_step_gated(const double* __restrict__ partial,
+                                                        const uint32_t* __restrict__ pkept, int nb,
+                                                        IcpState* __restrict__ st, GateStepArgs a) {
+  st += blockIdx.x;
+  partial += (size_t)blockIdx.x * nb * 16;
+  pkept += (size_t)blockIdx.x * nb;
+  if (st->done) return;
+  __shared__ double tot[16];
+  __shared__ unsigned long long skept;
+  if (threadIdx.x == 0) skept = 0;
+  icp_fold_rows<ITPB>(partial, nb, st, tot);  // its barrier orders the store above before the adds below
+  unsigned long long c = 0;
+  for (int b = threadIdx.x; b < nb; b += ITPB) c += pkept[b];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+  if ((threadIdx.x & 63) == 0) atomicAdd(&skept, c);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const long long kept = (long long)skept;
+  st->kept = kept;
+  if (a.sums_only) {
+    st->done = 1;
+    return;
+  }
+  st->pre_d = st->d;
+  st->d = tot[15];
+  const int round = st->round + 1;
+  st->round = round;
+  if (kept < a.min_pairs) {
+    st->starved = st->starved + 1;
+  } else {
+    double S[16];
+    for (int k = 0; k < 16; k++) S[k] = tot[k];
+    double R1[9], T1[3];
+    if (!horn(S, kept, R1, T1, st->V)) {
+      st->failed = 1;
+      st->done = 1;
+      return;
+    }
+    icp_compose(st, R1, T1);
+  }
+  if (round >= a.max_iter) st->done = 1;
 }
 
 void identity(IcpState& s) {
@@ -726,9 +899,17 @@ IcpState* icp_states(vcp_ctx* ctx) { return ctx->b_icp_part.as<IcpState>(); }
 // independent states (nst > 1: vcp_icp_multistart, MODE_VTK), `out` receives them.  all_rounds: enqueue every round
 // and synchronise once (a fixed round count needs nothing back in between).  ng_out (may be NULL) receives the
 // model's grid; ng_out->rec == nullptr when the full scans serve the model.
+// gr (may be NULL): a gated run -- the gated passes and step, MODE_VTK's fixed round count or MODE_SUMS_ONLY; the
+// partition, and with it the tree of the sums, is the ungated one.
+struct GateRun {
+  const double* gates;  // host, [n_gates], validated by the caller
+  int n_gates;
+  long long min_pairs;
+  uint8_t* d_keep;  // [nd] or NULL
+};
 int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState* init,
             int nst, double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn, bool all_rounds,
-            NNGrid* ng_out) {
+            NNGrid* ng_out, const GateRun* gr = nullptr) {
   hipStream_t st = ctx->stream;
   // small data sets: one wave per workgroup so that they reach more CUs; large models: LDS tiles
   const bool small0 = nd <= (int64_t)64 * ICP_MAX_BLOCKS;
@@ -753,18 +934,32 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   const uint32_t imask = (1u << ib) - 1u;
   double tolk = 1.0;  // smallest power of two >= (54 + 9 * 2^ib) * 2^-24
   while (tolk * 0.5 >= (54.0 + 9.0 * (double)(1u << ib)) / 16777216.0) tolk *= 0.5;
-  // the nst states (icp_states), then [nst][nb][16] partial rows
+  // the nst states (icp_states), then [nst][nb][16] partial rows; a gated run: then the schedule and [nst][nb] counts
   const size_t st_bytes = icp_states_bytes(nst);
-  VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + (size_t)nst * nb * 16 * sizeof(double)));
+  const size_t part_bytes = (size_t)nst * nb * 16 * sizeof(double);
+  const size_t gate_bytes = gr ? (size_t)gr->n_gates * sizeof(double) + (size_t)nst * nb * sizeof(uint32_t) : 0;
+  VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + part_bytes + gate_bytes));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)nm * sizeof(float4) + 64));
   IcpState* d_st = icp_states(ctx);
   double* part = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes);
   const StepArgs sa{(long long)nd, tol, stop_rule, max_iter, mode};
   float4* model32 = ctx->b_aux0.as<float4>();
-  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 ? ctx->pinned : vcp_stage(ctx, (size_t)nst * sizeof(IcpState)));
+  // a gated run stages its schedule behind the states: the caller's array may be gone before the copy has run
+  const size_t h_bytes = (size_t)nst * sizeof(IcpState) + (gr ? (size_t)gr->n_gates * sizeof(double) : 0);
+  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr ? ctx->pinned : vcp_stage(ctx, h_bytes));
   if (!h_st) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
   std::memcpy(h_st, init, (size_t)nst * sizeof(IcpState));
   VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, (size_t)nst * sizeof(IcpState), hipMemcpyHostToDevice, st));
+  GateArgs ga{};
+  GateStepArgs gsa{};
+  if (gr) {
+    double* d_gates = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
+    ga = GateArgs{d_gates, gr->n_gates, reinterpret_cast<uint32_t*>(d_gates + gr->n_gates), gr->d_keep};
+    gsa = GateStepArgs{gr->min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
+    double* h_gates = reinterpret_cast<double*>(h_st + nst);
+    std::memcpy(h_gates, gr->gates, (size_t)gr->n_gates * sizeof(double));
+    VCP_HIP(ctx, hipMemcpyAsync(d_gates, h_gates, (size_t)gr->n_gates * sizeof(double), hipMemcpyHostToDevice, st));
+  }
   if (!grid) {  // the binary32 screening frame and copy serve the full scans only
     VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st, nst);
     VCP_LAUNCH(ctx, k_model32, dim3(vcp_blocks(nm, ITPB)), dim3(ITPB), 0, st, d_model, nm, d_st, model32);
@@ -778,21 +973,34 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   for (;;) {
     const int batch = mode == MODE_SUMS_ONLY ? 1 : std::min(all_rounds ? max_iter : ICP_BATCH, max_iter - launched);
     for (int b = 0; b < batch; b++) {
-#define VCP_PASS(TBV, TL) \
-  VCP_LAUNCH(ctx, (k_icp_pass<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd, d_st, part, \
-             d_nn, ng)
+#define VCP_PASS(TBV, TL)                                                                                               \
+  do {                                                                                                                  \
+    if (gr)                                                                                                             \
+      VCP_LAUNCH(ctx, (k_icp_pass_gated<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
+                 nd, d_st, part, d_nn, ng, ga);                                                                         \
+    else                                                                                                                \
+      VCP_LAUNCH(ctx, (k_icp_pass<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd,   \
+                 d_st, part, d_nn, ng);                                                                                 \
+  } while (0)
+#define VCP_PASS_SMALL(TBV)                                                                                             \
+  do {                                                                                                                  \
+    if (gr)                                                                                                             \
+      VCP_LAUNCH(ctx, k_icp_pass_small_gated<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
+                 nd, d_st, part, d_nn, imask, tolk, ga);                                                                \
+    else                                                                                                                \
+      VCP_LAUNCH(ctx, k_icp_pass_small<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd,   \
+                 d_st, part, d_nn, imask, tolk);                                                                        \
+  } while (0)
       if (small && grid) VCP_PASS(64, 2);
       else if (grid) VCP_PASS(ITPB, 2);
       else if (small && tiled) VCP_PASS(64, 1);
       else if (tiled) VCP_PASS(ITPB, 1);
-      else if (small)
-        VCP_LAUNCH(ctx, k_icp_pass_small<64>, dim3(nb, nst), dim3(64), 0, st, d_model, model32, (int)nm, d_data, nd, d_st,
-                        part, d_nn, imask, tolk);
-      else
-        VCP_LAUNCH(ctx, k_icp_pass_small<ITPB>, dim3(nb, nst), dim3(ITPB), 0, st, d_model, model32, (int)nm, d_data, nd,
-                        d_st, part, d_nn, imask, tolk);
+      else if (small) VCP_PASS_SMALL(64);
+      else VCP_PASS_SMALL(ITPB);
 #undef VCP_PASS
-      VCP_LAUNCH(ctx, k_icp_step, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, sa);
+#undef VCP_PASS_SMALL
+      if (gr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, gsa);
+      else VCP_LAUNCH(ctx, k_icp_step, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, sa);
     }
     launched += batch;
     VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, (size_t)nst * sizeof(IcpState), hipMemcpyDeviceToHost, st));
@@ -949,10 +1157,12 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
 
 // Multi-start form of vcp_icp_vtklike (vcp.h): the same landmarks, rounds and arithmetic per pose, from H starts at
 // once; the target's grid (or screening frame) is built once and serves every pose and the score.
-int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
-                       int32_t n_poses, const double* init_R, const double* init_T, int max_iter, int max_landmarks,
-                       double inlier_dist, double M_best[16], int32_t* best, double* M_all, double* mean_dist,
-                       int32_t* inliers) {
+// gr (NULL: vcp_icp_multistart): the gated form, vcp_icp_gated -- its schedule is checked here, next to the other
+// arguments, and kept / starved (each may be NULL) receive the states' counters.
+static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                              int32_t n_poses, const double* init_R, const double* init_T, int max_iter,
+                              int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all,
+                              double* mean_dist, int32_t* inliers, const GateRun* gr, int64_t* kept, int32_t* starved) {
   if (!ctx) return VCP_ERR_ARG;
   if (ns <= 0 || nt <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty source or target");
   if (max_iter < 1 || max_landmarks < 1 || !source || !target || !M_best || !best)
@@ -965,9 +1175,15 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
     if (!std::isfinite(init_R[k])) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite init_R");
   for (int64_t k = 0; k < (int64_t)n_poses * 3 && init_T; k++)
     if (!std::isfinite(init_T[k])) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite init_T");
+  if (gr) {
+    if (gr->n_gates < 1 || !gr->gates) return vcp_fail(ctx, VCP_ERR_ARG, "n_gates < 1");
+    if (gr->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
+    for (int k = 0; k < gr->n_gates; k++)
+      if (!(gr->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
+  }
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
-  vcp_phase(ctx, "icpms_rounds");
+  vcp_phase(ctx, gr ? "icpg_rounds" : "icpms_rounds");
   int64_t step = 1;
   if (ns > max_landmarks) step = ns / max_landmarks;
   const int64_t nb = ns / step;
@@ -1014,10 +1230,10 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
   VCP_HIP(ctx, hipStreamSynchronize(st));  // `a` is a local buffer
   NNGrid ng{};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init.data(), n_poses, 0.0,
-                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng));
+                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr));
   // score every pose over ALL source points with vcp_match's arithmetic, on the grid the rounds used (vcp_match bins
   // a target of more than 512 points too, and falls back to the full scan on the same condition)
-  vcp_phase(ctx, "icpms_score");
+  vcp_phase(ctx, gr ? "icpg_score" : "icpms_score");
   const double* d_src = step > 1 ? ctx->b_in3.as<double>() : ctx->b_in2.as<double>();  // step 1: the landmarks are all
   const IcpState* d_st = icp_states(ctx);
   uint32_t* d_cnt = ctx->b_out0.as<uint32_t>();
@@ -1033,10 +1249,15 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
   VCP_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_poses * 4, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipStreamSynchronize(st));
   VCP_TRY(vcp_phase_finish(ctx));
+  // RMS distance of the pairs the last round summed: all nb landmarks, or the kept ones of a gated run (none: +inf)
+  auto mean_of = [&](const IcpState& f) {
+    if (!gr) return std::sqrt(f.d / (double)nb);
+    return f.kept > 0 ? std::sqrt(f.d / (double)f.kept) : (double)INFINITY;
+  };
   // most inliers, then the smaller mean distance, then the lower index
   int b = 0;
   for (int h = 0; h < n_poses; h++) {
-    const double md = std::sqrt(fin[h].d / (double)nb), mb = std::sqrt(fin[b].d / (double)nb);
+    const double md = mean_of(fin[h]), mb = mean_of(fin[b]);
     if (h_cnt[h] > h_cnt[b] || (h_cnt[h] == h_cnt[b] && md < mb)) b = h;
     if (M_all) {
       double* M = M_all + 16 * (size_t)h;
@@ -1049,6 +1270,8 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
     }
     if (mean_dist) mean_dist[h] = md;
     if (inliers) inliers[h] = (int32_t)h_cnt[h];
+    if (kept) kept[h] = (int64_t)fin[h].kept;
+    if (starved) starved[h] = fin[h].starved;
   }
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) M_best[4 * r + c] = fin[b].R[3 * r + c];
@@ -1060,37 +1283,71 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
   return VCP_OK;
 }
 
+int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                       int32_t n_poses, const double* init_R, const double* init_T, int max_iter, int max_landmarks,
+                       double inlier_dist, double M_best[16], int32_t* best, double* M_all, double* mean_dist,
+                       int32_t* inliers) {
+  return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
+                            M_best, best, M_all, mean_dist, inliers, nullptr, nullptr, nullptr);
+}
+
+// vcp_icp_multistart with a per-round gate on the correspondence distance (vcp.h)
+int vcp_icp_gated(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                  const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* gates,
+                  int32_t n_gates, int32_t min_pairs, double inlier_dist, double M_best[16], int32_t* best,
+                  double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved) {
+  const GateRun gr{gates, n_gates, min_pairs, nullptr};
+  return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
+                            M_best, best, M_all, mean_dist, inliers, &gr, kept, starved);
+}
+
 // Host-side run of the Horn step the device executes per round (same source: horn() is __host__ __device__).
 int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v, double R1[9], double T1[3]) {
   if (!sums || !R1 || !T1 || nd <= 0 || (use_v && !V)) return VCP_ERR_ARG;
   return horn(sums, (long long)nd, R1, T1, use_v ? V : nullptr) ? 1 : 0;
 }
 
-int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
-                 const double T[3], double sums[16], int32_t* nn) {
+// gate (NULL: vcp_icp_sums): one gated pass, vcp_icp_sums_gated; kept and keep receive its verdicts
+static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
+                        const double T[3], double sums[16], int32_t* nn, const double* gate, int64_t* kept,
+                        uint8_t* keep) {
   if (!ctx) return VCP_ERR_ARG;
   if (nm <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty model");
   if (nd <= 0 || !model || !data || !sums) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
   if (nm >= 0x7FFFFFFFLL / 3) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "model too large");
+  if (gate && !(*gate > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gate must be > 0 (+inf allowed)");
+  if (gate && !kept) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
   VCP_TRY(vcp_ensure(ctx, ctx->b_in0, (size_t)nm * 24));
   VCP_TRY(vcp_ensure(ctx, ctx->b_in2, (size_t)nd * 24));
   VCP_TRY(vcp_ensure(ctx, ctx->b_out0, (size_t)nd * 4));
+  if (keep) VCP_TRY(vcp_ensure(ctx, ctx->b_out1, (size_t)nd));
   VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in0.p, model, (size_t)nm * 24, hipMemcpyHostToDevice, ctx->stream));
   VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in2.p, data, (size_t)nd * 24, hipMemcpyHostToDevice, ctx->stream));
   IcpState init, fin;
   identity(init);
   if (R) std::memcpy(init.R, R, sizeof(init.R));
   if (T) std::memcpy(init.T, T, sizeof(init.T));
+  const GateRun gr{gate, 1, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, &init, 1, 0.0, VCP_STOP_SSE_DELTA, 1,
-                  MODE_SUMS_ONLY, &fin, nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr));
+                  MODE_SUMS_ONLY, &fin, nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr, gate ? &gr : nullptr));
   std::memcpy(sums, fin.sums, sizeof(fin.sums));
-  if (nn) {
-    VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
-    VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if (gate) *kept = (int64_t)fin.kept;
+  if (nn) VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (keep) VCP_HIP(ctx, hipMemcpyAsync(keep, ctx->b_out1.p, (size_t)nd, hipMemcpyDeviceToHost, ctx->stream));
+  if (nn || keep) VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VCP_OK;
+}
+
+int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
+                 const double T[3], double sums[16], int32_t* nn) {
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, nullptr, nullptr, nullptr);
+}
+
+int vcp_icp_sums_gated(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
+                       const double T[3], double gate, double sums[16], int64_t* kept, int32_t* nn, uint8_t* keep) {
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep);
 }
 
 }  // extern "C"

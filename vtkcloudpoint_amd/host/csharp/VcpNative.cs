@@ -71,6 +71,16 @@ namespace vtkPointCloud
             long nt, int n_poses, double[] init_R, double[] init_T, int max_iter, int max_landmarks, double inlier_dist,
             double[] M_best, out int best, double[] M_all, double[] mean_dist, int[] inliers);
 
+        // gated ICP (vcp.h): a pair whose distance is >= the round's gate stays out of the sums.  One pass (the test
+        // handle; nn and keep may be null) and vcp_icp_multistart with a schedule: round r uses gates[min(r, n_gates) - 1];
+        // kept and starved may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_sums_gated(IntPtr ctx, double[] model, long nm, double[] data,
+            long nd, double[] R, double[] T, double gate, double[] sums, out long kept, int[] nn, byte[] keep);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_gated(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int n_poses, double[] init_R, double[] init_T, int max_iter, int max_landmarks, double[] gates,
+            int n_gates, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
+            double[] mean_dist, int[] inliers, long[] kept, int[] starved);
+
         // Tools.getCircles / Geometry.FindMinimalBoundingCircle (Tools.cs:394-409, Geometry.cs:247-319)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_mcc(IntPtr ctx, double[] xy, int[] labels, long[] order, long m, long n,
             int K, double[] centers, double[] radius, byte[] valid, int[] hull_n);

@@ -179,6 +179,44 @@ def multistart_icp(centers, truths, n_angles=36, mirror=False, init_T=None, max_
     return ctx.icp_multistart(src, tgt, poses, init_T, max_iter, max_landmarks, inlier_dist)
 
 
+def gate_schedule(start, end, rounds):
+    """`rounds` gates from `start` to `end` in geometric steps: the first entry is exactly `start`, the last exactly
+    `end`, and the list never rises (start >= end > 0).  rounds = 1 gives [end].  vcp_icp_gated holds the last gate for
+    every round beyond the schedule."""
+    start, end, rounds = float(start), float(end), int(rounds)
+    if rounds < 1:
+        raise ValueError("rounds < 1")
+    if not (end > 0.0 and start >= end):
+        raise ValueError("need start >= end > 0")
+    if rounds == 1:
+        return np.array([end])
+    if math.isinf(start):
+        g = np.full(rounds, start)
+    else:
+        la, lb = math.log(start), math.log(end)
+        g = np.array([math.exp(la + (lb - la) * (k / (rounds - 1.0))) for k in range(rounds)])
+    g[0], g[-1] = start, end
+    g = np.minimum.accumulate(np.clip(g, end, start))  # rounding may not undo the order
+    return g
+
+
+def gated_icp(centers, truths, gates, n_angles=1, mirror=False, init_T=None, max_iter=100, max_landmarks=200,
+              min_pairs=3, inlier_dist=np.inf, ctx=None):
+    """multistart_icp with a gate on the correspondence distance: round r leaves every centroid whose nearest truth is
+    gates[min(r, len(gates)) - 1] or farther away out of that round's fit, so false clusters beside or between the
+    targets stop pulling the pose once the gate has closed below their distance (gate_schedule makes a shrinking
+    schedule).  n_angles may also be an [H, 3, 3] array of start rotations.  Returns Context.icp_gated's dict (best, M,
+    M_all, mean_dist, inliers, kept, starved)."""
+    ctx = ctx or default_context()
+    src = _points(centers)
+    tgt = _points(truths)
+    if isinstance(n_angles, (int, np.integer)):
+        poses = rotations_about_z(n_angles, mirror) if mirror else int(n_angles)
+    else:
+        poses = np.asarray(n_angles, np.float64)
+    return ctx.icp_gated(src, tgt, gates, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
+
+
 def _points(p):
     if isinstance(p, np.ndarray):
         return p
