@@ -515,6 +515,48 @@ int vcp_match(vcp_ctx* ctx, const double* centers, int32_t K, const double* trut
               const double M[16], double max_dist, double* matched_xyz, uint8_t* is_matched,
               int32_t* nearest, double* nearest_dist, int32_t* count_matched);
 
+/* -- one-to-one matching ----------------------------------------------------------------------------
+ * vcp_match lets two centroids take the same truth (the C# does: nothing in FrmMain.cs:3588-3618 stops it), so matchedID
+ * and the exported (centroid, truth) list (:1696-1698) can hold one truth twice.  vcp_match_unique returns a pairing: no
+ * centroid and no truth appears in two pairs.  It has no counterpart in the reference; vcp_match is unchanged.
+ *   transform   m_j = M * (c_j, 1), row by row, left to right, no contraction: vcp_match's
+ *   distance    d(j,i) = sqrt(dx*dx + dy*dy + dz*dz), dx = truths[3i] - m_j[0] and so on: binary64, correctly rounded
+ *               sqrt, vcp_match's expression and operand order
+ *   candidates  E = { (j,i) : d(j,i) < max_dist }, a strict comparison.  A NaN distance is never a candidate and a +inf
+ *               distance neither, not even with max_dist = +inf: a centroid or truth with a non-finite coordinate pairs
+ *               with nobody
+ *   matching    walk E in ascending order of the key (d, j, i) -- equal distances go to the lower centroid index, then
+ *               to the lower truth index -- and accept a pair when neither end is taken yet.  This sequential greedy
+ *               walk is the specification (tests/match_unique_ref.py restates it in numpy; results are compared bit
+ *               for bit).  The device computes it by rounds of locally dominant pairs: in a round every pair that is
+ *               the minimum-key candidate of both of its ends, among the points still free, is accepted at once, until
+ *               a round accepts nothing.  The key order is strict and total, so both give the same pairing (DESIGN.md
+ *               section 15)
+ *   truth_of [K]      index of the paired truth, -1 when none
+ *   center_of [T]     the inverse, -1 when none: the unmatched-truth list the reference displays
+ *   pair_dist [K]     may be NULL: d of the pair, +inf when unpaired
+ *   matched_xyz [K*3] may be NULL: bit-identical to vcp_match's
+ *   *count_pairs      may be NULL: the number of pairs
+ *   *rounds           may be NULL: the number of rounds that accepted a pair; informative, <= min(K, T)
+ * Every truth vcp_match gives to some matched centroid is paired here; where vcp_match's nearest is injective on its
+ * matched centroids the two calls agree (truth_of[j] = nearest[j] where matched, -1 elsewhere, equal counts).
+ * K == 0 does nothing (center_of is filled with -1 when T > 0); K > 0 && T == 0: VCP_ERR_EMPTY; NULL M, truth_of or
+ * center_of: VCP_ERR_ARG.  max_dist NaN or <= 0 is no error: E is empty, zero pairs, VCP_OK (the C#'s plain `<`).
+ * Candidates come from a 3-D grid over the truths with a cell edge of max_dist or more (at most 2^22 cells), built per
+ * call in its own workspace.  max_dist = +inf, or a box that needs a cell edge beyond its extent, is one cell, that is
+ * all K * T pairs per round: slow and correct.  The worst case in rounds is a chain (each pair becomes dominant only when
+ * the one before it is gone): min(K, T) rounds of three small kernels each.
+ * Deterministic: two calls on the same input give identical bits, and the result does not depend on scheduling (only
+ * integer min-atomics decide it).  Timing phases: matchu_grid, matchu_rounds (csrc/match_unique.hip). */
+int vcp_match_unique(vcp_ctx* ctx, const double* centers, int32_t K, const double* truths, int32_t T,
+                     const double M[16], double max_dist, double* matched_xyz, int32_t* truth_of, int32_t* center_of,
+                     double* pair_dist, int32_t* count_pairs, int32_t* rounds);
+/* Same with device pointers (d_matched_xyz, d_pair_dist may be NULL), on the context's stream; M, count_pairs and rounds
+ * stay host pointers; returns when the result is in place. */
+int vcp_match_unique_dev(vcp_ctx* ctx, const double* d_centers, int32_t K, const double* d_truths, int32_t T,
+                         const double M[16], double max_dist, double* d_matched_xyz, int32_t* d_truth_of,
+                         int32_t* d_center_of, double* d_pair_dist, int32_t* count_pairs, int32_t* rounds);
+
 /* -- import conversion + duplicate removal ------------------------------------
  * Replaces the per-row work of MainForm.AddFolder for scan points (FrmMain.cs:1011-1090, typpe 1 / 2):
  * rows [n*3] = (motor_x, motor_y, Distance) as parsed from the tab-separated text (BC/FileMap.cs:16-33);

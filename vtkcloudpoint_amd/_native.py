@@ -32,7 +32,7 @@ SYMBOLS = [
     "vcp_blocks_build_dev", "vcp_blocks_finish_local_dev", "vcp_blocks_finish_zero_dev", "vcp_blocks_finish_zcoords_dev",
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
     "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
-    "vcp_icp_sums_gated", "vcp_icp_gated",
+    "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_match_unique", "vcp_match_unique_dev",
 ]
 
 
@@ -312,6 +312,36 @@ class Context:
                                   C.c_double(max_dist), _ptr(mxyz), _ptr(is_m), _ptr(nearest), _ptr(nd),
                                   C.byref(cnt)))
         return dict(matched_xyz=mxyz, is_matched=is_m, nearest=nearest, nearest_dist=nd, count=cnt.value)
+
+    def match_unique(self, centers, truths, M, max_dist):
+        """vcp_match_unique: the one-to-one pairing of the greedy walk over (d, j, i).  Returns dict(matched_xyz [K,3],
+        truth_of [K] (-1 = none), center_of [T] (-1 = none), pair_dist [K] (+inf = none), count, rounds)."""
+        centers = _f64(centers, 3)
+        truths = _f64(truths, 3)
+        M = _f64(M).reshape(16)
+        K, T = len(centers), len(truths)
+        mxyz = np.zeros((K, 3))
+        truth_of = np.full(K, -1, np.int32)
+        center_of = np.full(T, -1, np.int32)
+        pd = np.full(K, np.inf)
+        cnt, rounds = C.c_int32(0), C.c_int32(0)
+        self._chk(lib().vcp_match_unique(self._h, _ptr(centers), C.c_int32(K), _ptr(truths), C.c_int32(T), _ptr(M),
+                                         C.c_double(max_dist), _ptr(mxyz), _ptr(truth_of), _ptr(center_of), _ptr(pd),
+                                         C.byref(cnt), C.byref(rounds)))
+        return dict(matched_xyz=mxyz, truth_of=truth_of, center_of=center_of, pair_dist=pd, count=cnt.value,
+                    rounds=rounds.value)
+
+    def match_unique_dev(self, d_centers, K, d_truths, T, M, max_dist, d_truth_of, d_center_of, d_pair_dist=None,
+                         d_matched_xyz=None):
+        """Device-pointer form (ints from tensor.data_ptr()); M is a host array.  The arrays are written in place; returns
+        the same dict with the pointers passed in and count, rounds."""
+        M = _f64(M).reshape(16)
+        cnt, rounds = C.c_int32(0), C.c_int32(0)
+        self._chk(lib().vcp_match_unique_dev(self._h, _ptr(d_centers), C.c_int32(K), _ptr(d_truths), C.c_int32(T), _ptr(M),
+                                             C.c_double(max_dist), _ptr(d_matched_xyz), _ptr(d_truth_of),
+                                             _ptr(d_center_of), _ptr(d_pair_dist), C.byref(cnt), C.byref(rounds)))
+        return dict(matched_xyz=d_matched_xyz, truth_of=d_truth_of, center_of=d_center_of, pair_dist=d_pair_dist,
+                    count=cnt.value, rounds=rounds.value)
 
     # -- block-partitioned pipeline ------------------------------------------------------------------
     def dbscan_blocks(self, motor, eps, min_pts, pts_in_cell, small_max=3, key_xy=None):

@@ -34,9 +34,9 @@ struct vcp_ctx {
   // one stream, and every user has consumed its words before the call that wrote them returns or goes on):
   //   [0, 1024)     the DBSCAN engine's EnginePinned: bounds, two totals, counters (dbscan.hip); the block partition's bounds (blockpart.hip);
   //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
-  //                 nearest-neighbour grid's bounds (nngrid.hip)
+  //                 nearest-neighbour grid's bounds (nngrid.hip); at [0, 56) the truths' bounds of vcp_match_unique
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
-  //                 DB's counters (dbdead.hip, dbpairs.hip)
+  //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //   [2048, 2064)  DB pair by pair: next seed / frontier size (dbpairs.hip)
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
@@ -54,6 +54,9 @@ struct vcp_ctx {
   // cluster shapes and the cluster filter (shapes.hip): hull points per member slot, the host forms' rectangle / hull /
   // filter outputs, the filter's keep flags and their scan
   DevBuf b_sh_hull, b_sh_out, b_sh_flag;
+  // one-to-one matching (match_unique.hip): per-centroid state, per-truth state and the truths cell by cell, the round
+  // counters and the bounds, the cell starts of its own truth grid
+  DevBuf b_mu_cent, b_mu_truth, b_mu_misc, b_mu_cell;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

@@ -303,6 +303,34 @@ inline int RecorrectMatchingPtsByDistance(Context& c, std::vector<Point3D>& cent
   return cnt;
 }
 
+// RecorrectMatchingPtsByDistance as a one-to-one pairing (vcp.h: vcp_match_unique): a truth goes to one centroid only.
+// matchedID receives the paired truths in centroid order (no duplicates), unmatchedTruths the truths nobody took.
+inline int MatchOneToOne(Context& c, std::vector<Point3D>& centers, const std::vector<double>& truths, const double M[16],
+                         double matchDistance, std::vector<int32_t>* matchedID = nullptr,
+                         std::vector<int32_t>* unmatchedTruths = nullptr) {
+  const int32_t K = (int32_t)centers.size(), T = (int32_t)(truths.size() / 3);
+  std::vector<double> cen(3 * K), mx(3 * K);
+  std::vector<int32_t> truthOf(K > 0 ? K : 1, -1), centerOf(T > 0 ? T : 1, -1);
+  for (int32_t j = 0; j < K; j++) { cen[3 * j] = centers[j].tmp_X; cen[3 * j + 1] = centers[j].tmp_Y; cen[3 * j + 2] = centers[j].tmp_Z; }
+  int32_t cnt = 0, rounds = 0;
+  c.check(vcp_match_unique(c.get(), cen.data(), K, truths.data(), T, M, matchDistance, mx.data(), truthOf.data(),
+                           centerOf.data(), nullptr, &cnt, &rounds));
+  if (matchedID) matchedID->clear();
+  if (unmatchedTruths) unmatchedTruths->clear();
+  for (int32_t j = 0; j < K; j++) {
+    centers[j].matched_X = mx[3 * j]; centers[j].matched_Y = mx[3 * j + 1]; centers[j].matched_Z = mx[3 * j + 2];
+    centers[j].isMatched = truthOf[j] >= 0;
+    if (truthOf[j] >= 0) {
+      centers[j].matchNum = truthOf[j];
+      if (matchedID) matchedID->push_back(truthOf[j]);
+    }
+  }
+  if (unmatchedTruths)
+    for (int32_t i = 0; i < T; i++)
+      if (centerOf[i] < 0) unmatchedTruths->push_back(i);
+  return cnt;
+}
+
 // k-distance of every point for DBImproved with minPts = k (vcp.h: vcp_kdist): kd[i] <= eps exactly when point i is a
 // core point at eps.  L1 on (motor_x, motor_y) by default, X/Y/Z with VCP_L2_3D; knn (may be null) gets n*k indices.
 inline std::vector<double> k_distance(Context& c, const std::vector<Point3D*>& pts, int k, int metric = VCP_L1_2D,

@@ -79,6 +79,46 @@ namespace vtkPointCloud
             showMatchedLine(isShowUnmatchedCenterPts, isShowUnmatchedTruePts);
         }
 
+        // RecorrectMatchingPtsByDistance as a pairing: the loop above lets a false cluster beside a target take the same
+        // matchNum as the real one, so matchedID and the exported pair list (:1696-1698) hold that truth twice.  Here a
+        // truth goes to one centroid only (vcp_match_unique: nearest pairs first, ties to the lower centroid, then the
+        // lower truth index), so matchedID has no duplicates and unmatchedTruths is the complement the
+        // isShowUnmatchedTruePts display wants.  Call it in place of RecorrectMatchingPtsByDistance; nothing else changes.
+        public List<int> unmatchedTruths = new List<int>();
+
+        public void MatchOneToOne(double matchDistance, bool isShowUnmatchedCenterPts, bool isShowUnmatchedTruePts)
+        {
+            int K = centers.Count, T = (int)truePointCloud.GetNumberOfPoints();
+            matchedID = new List<int>();
+            unmatchedTruths = new List<int>();
+            int countMatched = 0, rounds = 0;
+            if (K > 0)
+            {
+                double[] c = new double[3 * K];
+                for (int j = 0; j < K; j++) { c[3 * j] = centers[j].tmp_X; c[3 * j + 1] = centers[j].tmp_Y; c[3 * j + 2] = centers[j].tmp_Z; }
+                gpuMatched = new double[3 * K];
+                int[] truthOf = new int[K], centerOf = new int[Math.Max(T, 1)];
+                using (VcpNative.Lease lease = VcpNative.Rent())
+                    VcpNative.Check(lease, VcpNative.vcp_match_unique(lease.Ctx, c, K, TruthArray(), T, Matrix16(M), matchDistance,
+                        gpuMatched, truthOf, centerOf, null, out countMatched, out rounds));
+                for (int j = 0; j < K; j++)
+                {
+                    centers[j].matched_X = gpuMatched[3 * j];
+                    centers[j].matched_Y = gpuMatched[3 * j + 1];
+                    centers[j].matched_Z = gpuMatched[3 * j + 2];
+                    centers[j].isMatched = truthOf[j] >= 0;
+                    if (truthOf[j] >= 0) { centers[j].matchNum = truthOf[j]; matchedID.Add(truthOf[j]); }
+                }
+                for (int i = 0; i < T; i++) if (centerOf[i] < 0) unmatchedTruths.Add(i);
+            }
+            else
+            {
+                for (int i = 0; i < T; i++) unmatchedTruths.Add(i);
+            }
+            this.toolStripStatusLabelCurrentPointCount.Text = "总共" + centers.Count + "个聚类质心，总共" + T + "个真值点，匹配" + countMatched + "个点";
+            showMatchedLine(isShowUnmatchedCenterPts, isShowUnmatchedTruePts);
+        }
+
         // FrmMain.cs:3437-3467: nearest truth within the radius per raw point (the LINQ query :3452-3456)
         private void refreshClusList()
         {

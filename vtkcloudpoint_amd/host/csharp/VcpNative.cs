@@ -53,6 +53,13 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_match(IntPtr ctx, double[] centers, int K, double[] truths, int T,
             double[] M, double max_dist, double[] matched_xyz, byte[] is_matched, int[] nearest, double[] nearest_dist,
             out int count_matched);
+        // the one-to-one pairing (no truth twice); matched_xyz and pair_dist may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_match_unique(IntPtr ctx, double[] centers, int K, double[] truths,
+            int T, double[] M, double max_dist, double[] matched_xyz, int[] truth_of, int[] center_of, double[] pair_dist,
+            out int count_pairs, out int rounds);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_match_unique_dev(IntPtr ctx, IntPtr d_centers, int K, IntPtr d_truths,
+            int T, double[] M, double max_dist, IntPtr d_matched_xyz, IntPtr d_truth_of, IntPtr d_center_of,
+            IntPtr d_pair_dist, out int count_pairs, out int rounds);
 
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_refresh_by_dictionary(IntPtr ctx, double[] xyz, double[] motor,
             int[] labels, long n, int K, int[] map_by_id, out int new_k, double[] c3, double[] c2, long[] counts);

@@ -240,6 +240,7 @@ class Matcher:
         self.M = np.asarray(M, np.float64).reshape(4, 4)
         self.ctx = ctx or default_context()
         self.matchedID = []
+        self.unmatchedTruths = []
 
     def RecorrectMatchingPtsByDistance(self, matchDistance):
         c = np.array([(p.tmp_X, p.tmp_Y, p.tmp_Z) for p in self.centers], np.float64).reshape(-1, 3)
@@ -251,4 +252,20 @@ class Matcher:
             if p.isMatched:
                 p.matchNum = int(r["nearest"][j])  # index into the truth cloud (:3611)
                 self.matchedID.append(p.matchNum)
+        return r["count"]
+
+    def MatchOneToOne(self, matchDistance):
+        """The same step as a pairing (vcp_match_unique): a truth goes to one centroid only -- nearest pairs first, ties
+        to the lower centroid, then the lower truth index -- so matchedID has no duplicates; unmatchedTruths lists the
+        truths nobody took (the isShowUnmatchedTruePts display)."""
+        c = np.array([(p.tmp_X, p.tmp_Y, p.tmp_Z) for p in self.centers], np.float64).reshape(-1, 3)
+        r = self.ctx.match_unique(c, self.truths, self.M, float(matchDistance))
+        self.matchedID = []
+        for j, p in enumerate(self.centers):
+            p.matched_X, p.matched_Y, p.matched_Z = (float(v) for v in r["matched_xyz"][j])
+            p.isMatched = bool(r["truth_of"][j] >= 0)
+            if p.isMatched:
+                p.matchNum = int(r["truth_of"][j])
+                self.matchedID.append(p.matchNum)
+        self.unmatchedTruths = [int(i) for i in np.flatnonzero(r["center_of"] < 0)]
         return r["count"]
