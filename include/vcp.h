@@ -428,6 +428,64 @@ int vcp_icp_gated(vcp_ctx* ctx, const double* source, int64_t ns, const double* 
                   int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
                   int32_t* starved);
 
+/* -- congruent-pair global registration ---------------------------------------------------------------
+ * Every ICP form above starts from T0 = mean(target) - R0 mean(source) unless told otherwise, which is only right when
+ * the scan covers the whole truth field; a scan that sees part of it starts wrong by a large translation from every
+ * rotation (the reference's README: ICP "generally relies on RANSAC", which it never wrote).  This call needs no start.
+ * Two source points (a base) laid on an ordered pair of targets of the same length give a rigid motion; every such
+ * motion is scored by its inliers and the best one per base is kept.  It has no counterpart in the reference.
+ * All arithmetic is binary64, every operation rounded on its own, sqrt and / correctly rounded.  The motion is planar: a
+ * rotation about z plus a translation (rotations_about_z; the reference feeds (tmp_X, tmp_Y, 0), Tools.cs:696-703).
+ *   base        base b is (a, b') = (bases[2b], bases[2b+1]), indices into source; one outside 0..ns-1: VCP_ERR_INDEX
+ *   flip        f = 0 always; with mirror != 0, f = 1 too: the source is read as (x, -y, z) throughout
+ *   lengths     u = b' - a in (x, y), Lu = sqrt(ux*ux + uy*uy); for ordered targets (i, j), i != j: v = t_j - t_i,
+ *               Lv = sqrt(vx*vx + vy*vy).  (b, f, i, j) is a HYPOTHESIS iff 0 < Lu < inf, 0 < Lv < inf and
+ *               fabs(Lv - Lu) <= len_tol.  Comparisons with NaN are false: NaN makes no hypothesis
+ *   pose        dot = ux*vx + uy*vy, crs = ux*vy - uy*vx, nrm = sqrt(dot*dot + crs*crs); the hypothesis is skipped (it
+ *               still counts in n_hyp) unless 0 < nrm < inf.  c = dot/nrm, s = crs/nrm.  Midpoints
+ *               ms = ((ax+bx)*0.5, (ay+by)*0.5, (az+bz)*0.5), mt likewise from t_i and t_j.
+ *               T = (mt.x - (c*ms.x - s*ms.y), mt.y - (s*ms.x + c*ms.y), mt.z - ms.z)
+ *               R = Rz(c,s) = [[c,-s,0],[s,c,0],[0,0,1]] for f = 0 and Rz(c,s) diag(1,-1,1) = [[c,s,0],[s,-c,0],[0,0,1]]
+ *               for f = 1 (a negation changes the sign bit only; u and ms under f = 1 are (ux, -uy) and (ms.x, -ms.y,
+ *               ms.z)).  M = the row-major 4x4 [R | T], last row 0 0 0 1, laid out like vcp_icp_multistart's
+ *   score       the landmarks are vcp_icp_vtklike's: every step-th source point, step = ns / max_landmarks when
+ *               ns > max_landmarks (ns / step of them).  Each is moved by M as vcp_match moves a centroid (row by row,
+ *               left to right, all four terms) and counts when SOME target has sqrt(dx*dx + dy*dy + dz*dz) <
+ *               inlier_dist, dx = target.x - moved.x and so on: vcp_match's expression and operand order, strict
+ *   per base    the hypothesis with the highest score wins, ties to the lowest (f, i, j) lexicographically:
+ *               score [n_bases], pick [n_bases*3] = (f, i, j), M_all [n_bases*16]; n_hyp [n_bases] = the exact number of
+ *               hypotheses of the base.  A base without a hypothesis that was scored: score -1, pick (0, -1, -1), a zero
+ *               M, inliers 0
+ *   inliers [n_bases]  the same count as the score taken over ALL ns source points under the base's winner; for
+ *               all-finite input inliers[b] == vcp_match(source, target, M_b, inlier_dist).count_matched
+ *   best        the base with the most inliers among those with score >= 0, ties to the higher score, then the lower b;
+ *               M_best = its matrix.  No such base: VCP_OK, *best = -1, M_best = the identity
+ * M_all, score, inliers, pick, n_hyp may each be NULL; M_best, best and bases are required.  VCP_ERR_ARG: a NULL required
+ * pointer, n_bases < 1, max_landmarks < 1, len_tol NaN or < 0, inlier_dist NaN or <= 0 (len_tol = 0, len_tol = +inf and
+ * inlier_dist = +inf are valid); VCP_ERR_EMPTY: ns < 2 or nt < 2; VCP_ERR_UNSUPPORTED: n_bases > 4096 (vcp_icp_gated's
+ * pose limit: the winners can be fed to it) or nt > 65 536 (the pair enumeration is quadratic in nt by design);
+ * VCP_ERR_TOO_LARGE: ns >= 2^31.  Nothing is written on an error.
+ * There is no list of hypotheses and no cap on their number: they are scored as they are found.  Deterministic: only
+ * integer comparisons and integer atomics decide anything, two calls give identical bits.  Timing phases: regp_grid
+ * (bases and the target grid), regp_search, regp_final (csrc/register.hip). */
+int vcp_register_pairs(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                       const int32_t* bases, int32_t n_bases, double len_tol, int mirror, int max_landmarks,
+                       double inlier_dist, double M_best[16], int32_t* best, double* M_all, int32_t* score,
+                       int32_t* inliers, int32_t* pick, int64_t* n_hyp);
+/* Same with device pointers for source, target, bases and the five per-base arrays, on the context's stream; M_best
+ * and best stay host pointers; returns when the result is in place. */
+int vcp_register_pairs_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, const double* d_target, int64_t nt,
+                           const int32_t* d_bases, int32_t n_bases, double len_tol, int mirror, int max_landmarks,
+                           double inlier_dist, double M_best[16], int32_t* best, double* d_M_all, int32_t* d_score,
+                           int32_t* d_inliers, int32_t* d_pick, int64_t* d_n_hyp);
+
+/* Self-test of the pose arithmetic of vcp_register_pairs, run on the HOST from the same source the device executes: the
+ * base (a, b'), the targets t_i, t_j and the flip f give Lu_Lv = (Lu, Lv) and, when the hypothesis is not skipped, M.
+ * Returns 1 (M written), 0 (skipped: nrm is not in (0, inf); M untouched) or VCP_ERR_ARG (a NULL pointer).  The length
+ * test against len_tol is the caller's.  Needs no device and no context. */
+int vcp_selftest_register_pose(const double a[3], const double b[3], const double ti[3], const double tj[3], int f,
+                               double Lu_Lv[2], double M[16]);
+
 /* -- minimal bounding circles ---------------------------------------------
  * Replaces Tools.getCircles (BC/Tools.cs:394-409) / Geometry.FindMinimalBoundingCircle
  * (BC/Geometry.cs:247-319; gift-wrap hull :122-208, circle through 2 or 3 hull points :260-312): for

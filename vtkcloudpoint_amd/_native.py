@@ -33,6 +33,7 @@ SYMBOLS = [
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
     "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
     "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_match_unique", "vcp_match_unique_dev",
+    "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose",
 ]
 
 
@@ -653,6 +654,42 @@ class Context:
         return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
                     kept=kept, starved=starved)
 
+    def register_pairs(self, source, target, bases, len_tol, inlier_dist, mirror=False, max_landmarks=200):
+        """vcp_register_pairs: a pose of source on target without a start.  Every base (two source indices) is laid on
+        every ordered pair of targets whose length matches its own within len_tol; each such pose is scored by the
+        landmarks it puts within inlier_dist of some target.  Returns dict(best (-1 = no hypothesis), M [4,4], M_all
+        [B,4,4], score [B] (-1 = none), inliers [B] (over all source points), pick [B,3] = (f, i, j), n_hyp [B])."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        bases = np.ascontiguousarray(bases, np.int32).reshape(-1, 2)
+        B = len(bases)
+        M = np.zeros(16)
+        M_all = np.zeros((B, 16))
+        score = np.zeros(B, np.int32)
+        inl = np.zeros(B, np.int32)
+        pick = np.zeros((B, 3), np.int32)
+        n_hyp = np.zeros(B, np.int64)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_register_pairs(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
+                                           C.c_int64(len(target)), _ptr(bases), C.c_int32(B), C.c_double(len_tol),
+                                           int(bool(mirror)), int(max_landmarks), C.c_double(inlier_dist), _ptr(M),
+                                           C.byref(best), _ptr(M_all), _ptr(score), _ptr(inl), _ptr(pick), _ptr(n_hyp)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(B, 4, 4), score=score, inliers=inl, pick=pick,
+                    n_hyp=n_hyp)
+
+    def register_pairs_dev(self, d_source, ns, d_target, nt, d_bases, n_bases, len_tol, inlier_dist, mirror=False,
+                           max_landmarks=200, d_M_all=None, d_score=None, d_inliers=None, d_pick=None, d_n_hyp=None):
+        """Device-pointer form (ints from tensor.data_ptr()); the per-base arrays are written in place and may be None.
+        Returns dict(best, M [4,4])."""
+        M = np.zeros(16)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_register_pairs_dev(self._h, _ptr(d_source), C.c_int64(ns), _ptr(d_target), C.c_int64(nt),
+                                               _ptr(d_bases), C.c_int32(n_bases), C.c_double(len_tol), int(bool(mirror)),
+                                               int(max_landmarks), C.c_double(inlier_dist), _ptr(M), C.byref(best),
+                                               _ptr(d_M_all), _ptr(d_score), _ptr(d_inliers), _ptr(d_pick),
+                                               _ptr(d_n_hyp)))
+        return dict(best=best.value, M=M.reshape(4, 4))
+
     def import_convert(self, rows, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True):
         """MainForm.AddFolder per-row work: dict(xyz [n,3], state [n] (0 filtered / 1 kept / 2 duplicate), kept, duplicates)."""
         rows = _f64(rows, 3)
@@ -664,6 +701,17 @@ class Context:
                                            int(xdir), int(ydir), int(dedupe), _ptr(xyz), _ptr(state), C.byref(kept),
                                            C.byref(dup)))
         return dict(xyz=xyz, state=state, kept=kept.value, duplicates=dup.value)
+
+
+def selftest_register_pose(a, b, ti, tj, f=0):
+    """vcp_selftest_register_pose: the pose arithmetic of vcp_register_pairs run on the host (no device).  Returns (Lu, Lv,
+    M [4,4] or None when the hypothesis is skipped)."""
+    a, b, ti, tj = (_f64(v).reshape(3) for v in (a, b, ti, tj))
+    L, M = np.zeros(2), np.zeros(16)
+    rc = lib().vcp_selftest_register_pose(_ptr(a), _ptr(b), _ptr(ti), _ptr(tj), int(f), _ptr(L), _ptr(M))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_register_pose")
+    return float(L[0]), float(L[1]), (M.reshape(4, 4) if rc == 1 else None)
 
 
 def blocks_share_plan(blockstart, world):

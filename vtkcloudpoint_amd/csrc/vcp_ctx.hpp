@@ -35,6 +35,7 @@ struct vcp_ctx {
   //   [0, 1024)     the DBSCAN engine's EnginePinned: bounds, two totals, counters (dbscan.hip); the block partition's bounds (blockpart.hip);
   //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
   //                 nearest-neighbour grid's bounds (nngrid.hip); at [0, 56) the truths' bounds of vcp_match_unique
+  //                 and the targets' bounds of vcp_register_pairs (mugrid.hpp)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //   [2048, 2064)  DB pair by pair: next seed / frontier size (dbpairs.hip)
@@ -57,6 +58,9 @@ struct vcp_ctx {
   // one-to-one matching (match_unique.hip): per-centroid state, per-truth state and the truths cell by cell, the round
   // counters and the bounds, the cell starts of its own truth grid
   DevBuf b_mu_cent, b_mu_truth, b_mu_misc, b_mu_cell;
+  // congruent-pair registration (register.hip): source, targets and bases of the host form; the targets cell by cell; the
+  // cell starts of its own target grid; the base table, the winners' words and the per-base results
+  DevBuf b_rg_in, b_rg_truth, b_rg_cell, b_rg_work;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

@@ -32,5 +32,22 @@ namespace vtkPointCloud
                 T[i, 0] = t[i];
             }
         }
+
+        // Global registration by congruent pairs (vcp.h: vcp_register_pairs; new, no counterpart in the reference): a pose
+        // of `source` on `target` without any start.  bases = pairs of source indices (2 per base); every base is laid on
+        // every ordered pair of targets of its own planar length within lenTol, and each such pose is scored by the source
+        // landmarks it puts within inlierDist of some target.  Returns the best base (-1: no base has a matching target
+        // pair, M16 is then the identity); M16 receives its row-major 4x4 matrix, inliers / score (may be null) the
+        // per-base counts.
+        public int RegisterPairs(List<Point3D> source, List<Point3D> target, int[] bases, double lenTol, bool mirror,
+            double inlierDist, double[] M16, int[] inliers, int[] score)
+        {
+            int best;
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_register_pairs(c.Ctx, Flatten(source), source.Count, Flatten(target),
+                target.Count, bases, bases.Length / 2, lenTol, mirror ? 1 : 0, 200, inlierDist, M16, out best, null, score,
+                inliers, null, null));
+            return best;
+        }
     }
 }

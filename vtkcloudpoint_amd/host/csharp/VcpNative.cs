@@ -88,6 +88,14 @@ namespace vtkPointCloud
             int n_gates, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
             double[] mean_dist, int[] inliers, long[] kept, int[] starved);
 
+        // congruent-pair global registration (no counterpart in the reference; bases = pairs of source indices)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_pairs(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int[] bases, int n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist,
+            double[] M_best, out int best, double[] M_all, int[] score, int[] inliers, int[] pick, long[] n_hyp);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_pairs_dev(IntPtr ctx, IntPtr d_source, long ns, IntPtr d_target,
+            long nt, IntPtr d_bases, int n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist,
+            double[] M_best, out int best, IntPtr d_M_all, IntPtr d_score, IntPtr d_inliers, IntPtr d_pick, IntPtr d_n_hyp);
+
         // Tools.getCircles / Geometry.FindMinimalBoundingCircle (Tools.cs:394-409, Geometry.cs:247-319)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_mcc(IntPtr ctx, double[] xy, int[] labels, long[] order, long m, long n,
             int K, double[] centers, double[] radius, byte[] valid, int[] hull_n);

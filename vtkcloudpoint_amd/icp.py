@@ -1,5 +1,5 @@
-"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start ICP for
-MainForm.ICP's centroid-to-truth matching."""
+"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start, gated and global
+(congruent-pair) ICP for MainForm.ICP's centroid-to-truth matching."""
 import math
 
 import numpy as np
@@ -215,6 +215,56 @@ def gated_icp(centers, truths, gates, n_angles=1, mirror=False, init_T=None, max
     else:
         poses = np.asarray(n_angles, np.float64)
     return ctx.icp_gated(src, tgt, gates, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
+
+
+def choose_bases(source, n_bases, min_len, max_len, seed=0):
+    """[n_bases, 2] int32 pairs of source indices for register_pairs: np.random.default_rng(seed).integers(0, ns, 2) is
+    drawn until n_bases pairs are accepted, a pair (a, b) being accepted when a != b and its planar length lies in
+    [min_len, max_len].  A short base fits many target pairs (slow, ambiguous), a long one may leave the overlap.
+    Raises ValueError after 1000 * n_bases draws."""
+    src = _points(source)
+    ns, n_bases = len(src), int(n_bases)
+    if ns < 2 or n_bases < 1:
+        raise ValueError("need two source points and n_bases >= 1")
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(1000 * n_bases):
+        a, b = (int(v) for v in rng.integers(0, ns, 2))
+        ux, uy = float(src[b, 0] - src[a, 0]), float(src[b, 1] - src[a, 1])
+        if a != b and min_len <= math.sqrt(ux * ux + uy * uy) <= max_len:
+            out.append((a, b))
+            if len(out) == n_bases:
+                return np.array(out, np.int32)
+    raise ValueError("%d of %d bases with a length in [%g, %g] after %d draws" % (len(out), n_bases, min_len, max_len,
+                                                                               1000 * n_bases))
+
+
+def register_pairs(centers, truths, bases, len_tol, inlier_dist, mirror=False, max_landmarks=200, ctx=None):
+    """A pose of the centroids on the truths without any start (vcp_register_pairs): each base (choose_bases) is laid on
+    every ordered pair of truths of its own length within len_tol, and the pose that puts the most landmarks within
+    inlier_dist of a truth is kept per base.  Works where the scan sees only part of the truth field, which the centroid
+    start of multistart_icp / gated_icp cannot.  Returns Context.register_pairs's dict (best, M, M_all, score, inliers,
+    pick, n_hyp)."""
+    ctx = ctx or default_context()
+    return ctx.register_pairs(_points(centers), _points(truths), bases, len_tol, inlier_dist, mirror, max_landmarks)
+
+
+def global_icp(centers, truths, bases, len_tol, inlier_dist, gates, mirror=False, max_iter=20, max_landmarks=200,
+               min_pairs=3, ctx=None):
+    """register_pairs, then ONE gated_icp call started from the pose of every base that found one (score >= 0).  Returns
+    gated_icp's dict (best indexes the started poses) plus registration = register_pairs's dict and bases_used = the base
+    of every started pose.  ValueError when no base has a hypothesis."""
+    ctx = ctx or default_context()
+    src, tgt = _points(centers), _points(truths)
+    reg = ctx.register_pairs(src, tgt, bases, len_tol, inlier_dist, mirror, max_landmarks)
+    used = np.flatnonzero(reg["score"] >= 0)
+    if len(used) == 0:
+        raise ValueError("no base has a target pair of its length within len_tol")
+    M = reg["M_all"][used]
+    out = ctx.icp_gated(src, tgt, gates, np.ascontiguousarray(M[:, :3, :3]), np.ascontiguousarray(M[:, :3, 3]), max_iter,
+                        max_landmarks, min_pairs, inlier_dist)
+    out.update(registration=reg, bases_used=used)
+    return out
 
 
 def _points(p):
