@@ -659,6 +659,55 @@ int vcp_kdist(vcp_ctx* ctx, const double* coords, int64_t n, int dim, int metric
 int vcp_kdist_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, int metric, int k, double* d_kdist,
                   int32_t* d_knn);
 
+/* -- eps tree -------------------------------------------------------------------------------------
+ * The knee of the k-distance graph knows nothing about the clusters the caller wants; a caller who knows the number of
+ * targets wants an eps at which vcp_dbscan finds about that many clusters.  For a fixed min_pts = k this call returns
+ * what vcp_dbscan decides at EVERY eps <= eps_max at once.  It has no counterpart in the reference.  All values are
+ * selections among binary64 numbers vcp_kdist defines: no new rounding.
+ *   d, kdist    d(i,j) and kdist[i] are vcp_kdist's (VCP_L1_2D, VCP_L2_2D, VCP_L2_3D; j = i included); a point with a
+ *               non-finite coordinate has kdist NaN and takes part in nothing
+ *   kdist       kdist_given == 0: kdist [n] is an output and may be NULL; it is computed by the code of vcp_kdist_dev.
+ *               kdist_given != 0: kdist is required and read as given; the caller vouches that it is vcp_kdist's for the
+ *               same coords, metric and k (suggest_eps has computed it already).  A call with kdist_given != 0 on an
+ *               earlier call's output gives identical bits
+ *   vertices    P = { i : kdist[i] <= eps_max }: the points that are core at some eps <= eps_max
+ *   edges       E = { (i,j) : i < j, both in P, d(i,j) <= eps_max }, w(i,j) = max(kdist[i], kdist[j], d(i,j)) (a
+ *               selection; the mutual-reachability distance): i and j are linked core points at eps iff w(i,j) <= eps.
+ *               Edges are ordered by the key (w, i, j), lexicographic: a strict total order
+ *   forest      the minimum spanning forest of (P, E) under that order is unique and equals the edges a Kruskal walk over
+ *               E in ascending key order accepts.  That sequential walk is the specification (tests/eps_tree_ref.py
+ *               restates it in numpy; results are compared bit for bit).  *n_merge = the number of accepted edges;
+ *               merge_w, merge_a, merge_b hold them in ascending key order, a < b indices into the caller's array; the
+ *               caller provides room for max(n - 1, 0) entries.  merge_a and merge_b: both or neither; merge_w and
+ *               n_merge are required.  The device computes the forest by Boruvka rounds
+ *   reach [n]   may be NULL: reach[i] = min over j in P (j = i included) with d(i,j) <= eps_max of max(kdist[j], d(i,j));
+ *               +inf when there is no such j, NaN for a non-finite point
+ * For all-finite input and every finite eps with 0 <= eps <= eps_max, r = vcp_dbscan(coords, eps, min_pts = k,
+ * cf_in = 0, in_classed = NULL) satisfies
+ *     sum(r.is_core)      == #{ kdist <= eps }
+ *     r.cf_out            == #{ kdist <= eps } - #{ merge_w <= eps }
+ *     #{ r.labels != 0 }  == #{ reach <= eps }
+ *     two core points of r share a label iff the forest edges with w <= eps connect them.
+ *   *rounds     may be NULL: the number of device rounds that accepted an edge; informative, <= floor(log2 |P|) and 0
+ *               when |P| < 2 (a tree that accepts an edge in round r has at least 2^(r-1) vertices, and so has the tree
+ *               it joins)
+ * Nothing is written on an error.  VCP_ERR_ARG: a NULL required pointer, merge_a without merge_b or the reverse,
+ * kdist_given with NULL kdist, dim not 2 or 3, VCP_L2_3D with dim 2, VCP_SIGNED_SUM_2D, k < 1, eps_max NaN, <= 0 or +inf;
+ * VCP_ERR_UNSUPPORTED: k > 64, an extent that overflows, as in vcp_kdist; VCP_ERR_TOO_LARGE: n >= 2^31.  n == 0:
+ * *n_merge = 0, VCP_OK.
+ * Candidates come from a uniform grid over the finite points with a cell edge of eps_max or more (at most 2^22 cells),
+ * built per call in its own workspace; an eps_max beyond the cloud's extent is one cell, that is all pairs per round: slow
+ * and correct.  Deterministic: only integer min-atomics decide anything, two calls give identical bits.  Timing phases:
+ * epst_kdist (absent when given), epst_grid, epst_rounds, epst_reach, epst_sort (csrc/eps_tree.hip). */
+int vcp_eps_tree(vcp_ctx* ctx, const double* coords, int64_t n, int dim, int metric, int k, double eps_max,
+                 int kdist_given, double* kdist, double* reach, int64_t* n_merge, double* merge_w, int32_t* merge_a,
+                 int32_t* merge_b, int32_t* rounds);
+/* Same with device pointers for coords, kdist, reach, merge_w, merge_a, merge_b, on the context's stream; n_merge and
+ * rounds stay host pointers; returns when the result is in place. */
+int vcp_eps_tree_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, int metric, int k, double eps_max,
+                     int kdist_given, double* d_kdist, double* d_reach, int64_t* n_merge, double* d_merge_w,
+                     int32_t* d_merge_a, int32_t* d_merge_b, int32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif

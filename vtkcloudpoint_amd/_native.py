@@ -33,7 +33,7 @@ SYMBOLS = [
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
     "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
     "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_match_unique", "vcp_match_unique_dev",
-    "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose",
+    "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
 ]
 
 
@@ -194,6 +194,44 @@ class Context:
         """Device-pointer form (ints from tensor.data_ptr()); d_knn may be None."""
         self._chk(lib().vcp_kdist_dev(self._h, _ptr(d_coords), C.c_int64(n), int(dim), int(metric), int(k),
                                       _ptr(d_kdist), _ptr(d_knn)))
+
+    # -- eps tree --------------------------------------------------------------------------------
+    def eps_tree(self, coords, k, eps_max, metric=L1_2D, kdist=None, want_edges=True):
+        """vcp_eps_tree: what dbscan(min_pts=k) decides at every eps <= eps_max.  kdist: an earlier kdist() / eps_tree()
+        result for the same coords, metric and k (read as given), or None (computed).  Returns dict(kdist [n], reach [n],
+        merge_w [m], merge_a [m], merge_b [m] (None without want_edges), rounds): the minimum spanning forest of the
+        mutual-reachability weights in ascending (w, a, b) order."""
+        coords = _f64(coords)
+        if coords.ndim != 2:
+            coords = coords.reshape(0, 2)
+        n, dim = coords.shape
+        given = kdist is not None
+        kd = np.array(kdist, np.float64).reshape(-1) if given else np.zeros(n, np.float64)
+        if given and len(kd) != n:
+            raise ValueError("kdist has %d entries for %d points" % (len(kd), n))
+        reach = np.zeros(n, np.float64)
+        cap = max(n - 1, 0)
+        mw = np.zeros(max(cap, 1), np.float64)
+        ma = np.zeros(max(cap, 1), np.int32) if want_edges else None
+        mb = np.zeros(max(cap, 1), np.int32) if want_edges else None
+        m, rounds = C.c_int64(0), C.c_int32(0)
+        self._chk(lib().vcp_eps_tree(self._h, _ptr(coords), C.c_int64(n), int(dim), int(metric), int(k),
+                                     C.c_double(eps_max), int(given), _ptr(kd), _ptr(reach), C.byref(m), _ptr(mw),
+                                     _ptr(ma), _ptr(mb), C.byref(rounds)))
+        m = m.value
+        return dict(kdist=kd, reach=reach, merge_w=mw[:m].copy(), merge_a=None if ma is None else ma[:m].copy(),
+                    merge_b=None if mb is None else mb[:m].copy(), rounds=rounds.value)
+
+    def eps_tree_dev(self, d_coords, n, dim, k, eps_max, d_merge_w, d_merge_a=None, d_merge_b=None, d_kdist=None,
+                     d_reach=None, kdist_given=False, metric=L1_2D):
+        """Device-pointer form (ints from tensor.data_ptr()); d_merge_* have room for max(n - 1, 0) entries, d_kdist
+        (read when kdist_given) and d_reach may be None.  Returns (n_merge, rounds)."""
+        m, rounds = C.c_int64(0), C.c_int32(0)
+        self._chk(lib().vcp_eps_tree_dev(self._h, _ptr(d_coords), C.c_int64(n), int(dim), int(metric), int(k),
+                                         C.c_double(eps_max), int(bool(kdist_given)), _ptr(d_kdist), _ptr(d_reach),
+                                         C.byref(m), _ptr(d_merge_w), _ptr(d_merge_a), _ptr(d_merge_b),
+                                         C.byref(rounds)))
+        return m.value, rounds.value
 
     # -- ICP -----------------------------------------------------------------------------------
     def icp(self, model, data, tol=1e-4, max_iter=100, stop_rule=STOP_SSE_DELTA):

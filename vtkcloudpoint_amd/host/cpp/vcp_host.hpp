@@ -365,4 +365,47 @@ inline std::vector<double> k_distance(Context& c, const std::vector<Point3D*>& p
   return kd;
 }
 
+// What DBImproved(minPts = k) decides at every eps <= epsMax, in one call (vcp.h: vcp_eps_tree): point i is core at eps
+// iff kdist[i] <= eps, carries a label iff reach[i] <= eps, and the cluster count is #{kdist <= eps} - #{mergeW <= eps}.
+// mergeW / mergeA / mergeB: the minimum spanning forest of the mutual-reachability weights in ascending (w, a, b) order.
+struct EpsTreeResult {
+  std::vector<double> kdist, reach, mergeW;
+  std::vector<int32_t> mergeA, mergeB;
+  double epsMax = 0.0;
+  int32_t rounds = 0;
+  // the cluster count vcp_dbscan(eps, minPts = k) reports, 0 <= eps <= epsMax
+  int64_t clustersAt(double eps) const {
+    int64_t c = 0;
+    for (double v : kdist) c += v <= eps;
+    for (double v : mergeW) c -= v <= eps;
+    return c;
+  }
+};
+inline EpsTreeResult EpsTree(Context& c, const std::vector<Point3D*>& pts, int k, double epsMax, int metric = VCP_L1_2D,
+                             const std::vector<double>* kdistGiven = nullptr) {
+  const int64_t n = (int64_t)pts.size();
+  const int dim = metric == VCP_L2_3D ? 3 : 2;
+  std::vector<double> xy(n * dim);
+  for (int64_t i = 0; i < n; i++) {
+    if (dim == 3) { xy[3 * i] = pts[i]->X; xy[3 * i + 1] = pts[i]->Y; xy[3 * i + 2] = pts[i]->Z; }
+    else { xy[2 * i] = pts[i]->motor_x; xy[2 * i + 1] = pts[i]->motor_y; }
+  }
+  EpsTreeResult r;
+  r.epsMax = epsMax;
+  r.kdist = kdistGiven ? *kdistGiven : std::vector<double>(n);
+  r.kdist.resize(n);
+  r.reach.resize(n);
+  const size_t cap = n > 1 ? (size_t)(n - 1) : 1;
+  r.mergeW.resize(cap);
+  r.mergeA.resize(cap);
+  r.mergeB.resize(cap);
+  int64_t m = 0;
+  c.check(vcp_eps_tree(c.get(), xy.data(), n, dim, metric, k, epsMax, kdistGiven ? 1 : 0, r.kdist.data(), r.reach.data(),
+                       &m, r.mergeW.data(), r.mergeA.data(), r.mergeB.data(), &r.rounds));
+  r.mergeW.resize((size_t)m);
+  r.mergeA.resize((size_t)m);
+  r.mergeB.resize((size_t)m);
+  return r;
+}
+
 }  // namespace vtkPointCloud

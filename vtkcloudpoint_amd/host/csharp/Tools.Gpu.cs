@@ -313,5 +313,56 @@ namespace vtkPointCloud
             }
             return v[best];
         }
+
+        // eps from the number of targets, not from a knee: the widest range [lo, hi) of eps <= epsMax on which
+        // DBImproved(eps, minPts) finds exactly `target` clusters (vcp.h: vcp_eps_tree; vtkcloudpoint_amd/epstree.py:
+        // eps_for_clusters).  clusters(eps) = #{kdist <= eps} - #{merge_w <= eps}; equal widths go to the lower lo; a
+        // range that reaches epsMax includes it.  null when the count never occurs.  L1 on motor_x / motor_y.
+        public static double[] EpsForClusters(List<Point3D> rawData, int minPts, double epsMax, int target)
+        {
+            int n = rawData.Count;
+            if (n == 0) return null;
+            double[] mot = new double[2 * n], kd = new double[n], mw = new double[Math.Max(n - 1, 1)];
+            for (int i = 0; i < n; i++) { mot[2 * i] = rawData[i].motor_x; mot[2 * i + 1] = rawData[i].motor_y; }
+            long m;
+            int rounds;
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_eps_tree(c.Ctx, mot, n, 2, VcpNative.VCP_L1_2D, minPts, epsMax, 0, kd, null,
+                    out m, mw, null, null, out rounds));
+            List<double> cores = new List<double>(n);
+            foreach (double d in kd) if (d <= epsMax) cores.Add(d);
+            cores.Sort();
+            // the breakpoints, ascending: 0, every k-distance and every merge weight (both lists are sorted)
+            List<double> br = new List<double>(cores.Count + (int)m + 1);
+            br.Add(0.0);
+            int a = 0, b = 0;
+            while (a < cores.Count || b < m)
+            {
+                double v = b >= m || (a < cores.Count && cores[a] <= mw[b]) ? cores[a++] : mw[b++];
+                if (v > br[br.Count - 1]) br.Add(v);
+            }
+            double[] bestIv = null;
+            double lo = 0.0;
+            bool open = false;
+            a = 0; b = 0;
+            for (int i = 0; i <= br.Count; i++)
+            {
+                bool ok = false;
+                if (i < br.Count)
+                {
+                    while (a < cores.Count && cores[a] <= br[i]) a++;
+                    while (b < m && mw[b] <= br[i]) b++;
+                    ok = a - b == target;
+                }
+                if (ok && !open) { lo = br[i]; open = true; }
+                if (!ok && open)
+                {
+                    double hi = i < br.Count ? br[i] : epsMax;
+                    if (bestIv == null || hi - lo > bestIv[1] - bestIv[0]) bestIv = new double[] { lo, hi };
+                    open = false;
+                }
+            }
+            return bestIv;
+        }
     }
 }

@@ -124,6 +124,12 @@ namespace vtkPointCloud
         // Clustering.Designer.cs:86,96); knn may be null
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_kdist(IntPtr ctx, double[] coords, long n, int dim, int metric,
             int k, double[] kdist, int[] knn);
+        // eps tree: what DBImproved(minPts = k) decides at every eps <= eps_max (vcp.h: vcp_eps_tree; no reference
+        // counterpart).  kdist: read when kdist_given != 0, else written (may be null); reach, merge_a / merge_b (both or
+        // neither) may be null; merge_w, merge_a, merge_b have room for max(n - 1, 0) entries
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_eps_tree(IntPtr ctx, double[] coords, long n, int dim, int metric,
+            int k, double eps_max, int kdist_given, double[] kdist, double[] reach, out long n_merge, double[] merge_w,
+            int[] merge_a, int[] merge_b, out int rounds);
 
         // ---- device-resident forms (IntPtr = device address): for hosts that keep the cloud on the GPU between
         // calls, and for the multi-GPU drivers (one process and one context per GPU) ----
@@ -144,6 +150,9 @@ namespace vtkPointCloud
             IntPtr d_filtered, IntPtr d_keep, IntPtr d_kept_idx, out int n_filtered, out long n_kept);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_kdist_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
             int k, IntPtr d_kdist, IntPtr d_knn);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_eps_tree_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
+            int k, double eps_max, int kdist_given, IntPtr d_kdist, IntPtr d_reach, out long n_merge, IntPtr d_merge_w,
+            IntPtr d_merge_a, IntPtr d_merge_b, out int rounds);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_dev(IntPtr ctx, IntPtr d_model, long nm, IntPtr d_data, long nd,
             double tol, int max_iter, int stop_rule, double[] R, double[] T, out double sse, out double rmse, out int iters);
         // block pipeline in stages (per-block step sharded over GPUs, distributed.py: sharded_blocks)
