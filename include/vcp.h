@@ -486,6 +486,44 @@ int vcp_register_pairs_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, con
 int vcp_selftest_register_pose(const double a[3], const double b[3], const double ti[3], const double tj[3], int f,
                                double Lu_Lv[2], double M[16]);
 
+/* -- scale-free registration by similarity pairs -------------------------------------------------------
+ * vcp_register_pairs assumes that source and targets are in one unit.  The reference brings a scan to the truths' unit by
+ * the ratio of the two bounding boxes (MainForm.showTruesAndCenters, FrmMain.cs:3030-3055), which is wrong for a scan that
+ * sees part of the field and moves with one false cluster at the edge.  This call lets the pair carry the scale: a base
+ * laid on an ordered pair of targets whose length is k times its own, scale_min <= k <= scale_max, is a planar similarity.
+ * Everything not named here is vcp_register_pairs's, word for word: bases, flip, Lu, Lv, the landmarks, the score (strict
+ * <), the per-base winner (highest score, ties to the lowest (f, i, j)), inliers over all ns, best, the limits, which
+ * outputs may be NULL, "nothing written on an error".  binary64, every operation rounded on its own.
+ *   hypothesis  k = Lv / Lu (one correctly rounded division).  (b, f, i, j) is a HYPOTHESIS iff 0 < Lu < inf,
+ *               0 < Lv < inf and scale_min <= k && k <= scale_max.  The division is the test: no product form, no squared
+ *               lengths.  Comparisons with NaN are false
+ *   pose        dot, crs, nrm, c, s, the midpoints and the sign handling under f = 1 are vcp_register_pairs's; skipped
+ *               (still counted in n_hyp) unless 0 < nrm < inf.  kc = k*c, ks = k*s.
+ *               T = (mt.x - (kc*ms.x - ks*ms.y), mt.y - (ks*ms.x + kc*ms.y), mt.z - k*ms.z)
+ *               R = [[kc,-ks,0],[ks,kc,0],[0,0,k]] for f = 0, [[kc,ks,0],[ks,-kc,0],[0,0,k]] for f = 1; M as before.
+ *               Where k == 1.0 exactly, M is vcp_register_pairs's bit for bit (1.0 * x is x, the sign of a zero included)
+ *   scale [n_bases]  (may be NULL) the winner's k; 0.0 for a base without a hypothesis that was scored
+ * VCP_ERR_ARG: scale_min NaN or <= 0; scale_max NaN, +inf or < scale_min (scale_min == scale_max is valid); the other
+ * errors are vcp_register_pairs's.  Timing phases: regs_grid, regs_search, regs_final (csrc/register.hip, DESIGN.md
+ * section 18). */
+int vcp_register_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                     const int32_t* bases, int32_t n_bases, double scale_min, double scale_max, int mirror,
+                     int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all, int32_t* score,
+                     int32_t* inliers, int32_t* pick, int64_t* n_hyp, double* scale);
+/* Same with device pointers for source, target, bases and the six per-base arrays, on the context's stream; M_best and
+ * best stay host pointers; returns when the result is in place. */
+int vcp_register_sim_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, const double* d_target, int64_t nt,
+                         const int32_t* d_bases, int32_t n_bases, double scale_min, double scale_max, int mirror,
+                         int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* d_M_all,
+                         int32_t* d_score, int32_t* d_inliers, int32_t* d_pick, int64_t* d_n_hyp, double* d_scale);
+
+/* Self-test of the pose arithmetic of vcp_register_sim, run on the HOST from the source the device executes:
+ * Lu_Lv_k = (Lu, Lv, k = Lv / Lu) and, when the hypothesis is not skipped, M.  Returns 1 (M written), 0 (skipped: nrm is
+ * not in (0, inf); M untouched) or VCP_ERR_ARG (a NULL pointer).  The test of k against the range is the caller's.  Needs
+ * no device and no context. */
+int vcp_selftest_register_sim_pose(const double a[3], const double b[3], const double ti[3], const double tj[3], int f,
+                                   double Lu_Lv_k[3], double M[16]);
+
 /* -- minimal bounding circles ---------------------------------------------
  * Replaces Tools.getCircles (BC/Tools.cs:394-409) / Geometry.FindMinimalBoundingCircle
  * (BC/Geometry.cs:247-319; gift-wrap hull :122-208, circle through 2 or 3 hull points :260-312): for

@@ -1,4 +1,4 @@
-// regp_host_emulation.cpp -- runs the SOURCE of k_regp_search (csrc/register.hip, copied into kernels.inc by
+// regp_host_emulation.cpp -- runs the SOURCE of k_regp_search and k_regs_search (csrc/register.hip, copied into kernels.inc by
 // tools/regp_host_emulation.py) on the host: 256 real threads per workgroup, one workgroup after the other, with
 // __syncthreads / __syncthreads_or / __ballot / __shfl built from std::barrier and the atomics from the compiler's
 // builtins.  It checks the queue, the barriers and the winner's word of the fused kernel where no GPU is at hand, and can
@@ -85,11 +85,14 @@ constexpr unsigned long long RG_LOW = (1ull << 33) - 1ull;
 #include "kernels.inc"
 
 int main(int argc, char** argv) {
-  // input file: int64 ns, nt, nb, step, mirror; double len_tol, inlier, h (cell edge; 0 = one cell); src, tgt, bases(int32)
+  // input file: int64 ns, nt, nb, step, mirror, sim; double len_tol, inlier, h (cell edge; 0 = one cell), scale_min,
+  // scale_max; src, tgt, bases(int32)
+  if (argc < 3) return 2;
   FILE* f = fopen(argv[1], "rb");
-  int64_t hd[5]; double pr[3];
-  if (fread(hd, 8, 5, f) != 5 || fread(pr, 8, 3, f) != 3) return 2;
-  const int64_t ns = hd[0], nt = hd[1], nb = hd[2], step = hd[3]; const int mirror = (int)hd[4];
+  if (!f) return 2;
+  int64_t hd[6]; double pr[5];
+  if (fread(hd, 8, 6, f) != 6 || fread(pr, 8, 5, f) != 5) return 2;
+  const int64_t ns = hd[0], nt = hd[1], nb = hd[2], step = hd[3]; const int mirror = (int)hd[4]; const bool sim = hd[5] != 0;
   std::vector<double> src(3 * ns), tgt(3 * nt); std::vector<int32_t> bases(2 * nb);
   if (fread(src.data(), 8, 3 * ns, f) != (size_t)(3 * ns) || fread(tgt.data(), 8, 3 * nt, f) != (size_t)(3 * nt) ||
       fread(bases.data(), 4, 2 * nb, f) != (size_t)(2 * nb)) return 2;
@@ -128,11 +131,11 @@ int main(int argc, char** argv) {
   for (int i = 0; i < nt; i++) if (cellof[i] != 0xFFFFFFFFu) { const uint32_t s = cellstart[cellof[i]] + cur[cellof[i]]++; for (int c = 0; c < 3; c++) sxyz[3 * s + c] = tgt[3 * i + c]; }
   RGScan q{g, cellstart.data(), sxyz.data(), pr[1]};
   std::vector<unsigned long long> key(nb, 0), nhyp(nb, 0);
-  RGSearch a{src.data(), step, (int)(ns / step), tgt.data(), (int)nt, RGTab{tab.data(), (int)nb}, sL.data(), ord.data(), (int)ord.size(), pr[0], mirror ? 2 : 1, q, key.data(), nhyp.data()};
+  RGSearch a{src.data(), step, (int)(ns / step), tgt.data(), (int)nt, RGTab{tab.data(), (int)nb}, sL.data(), ord.data(), (int)ord.size(), pr[0], pr[3], pr[4], mirror ? 2 : 1, q, key.data(), nhyp.data()};
   if (!ord.empty())
     for (unsigned blk = 0; blk < (unsigned)nt; blk++) {
       std::vector<std::thread> th;
-      for (unsigned t = 0; t < NT; t++) th.emplace_back([&, t, blk] { threadIdx = Dim{t, 0, 0}; blockIdx = Dim{blk, 0, 0}; k_regp_search(a); });
+      for (unsigned t = 0; t < NT; t++) th.emplace_back([&, t, blk] { threadIdx = Dim{t, 0, 0}; blockIdx = Dim{blk, 0, 0}; if (sim) k_regs_search(a); else k_regp_search(a); });
       for (auto& x : th) x.join();
     }
   FILE* o = fopen(argv[2], "wb");

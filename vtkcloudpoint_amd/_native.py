@@ -33,7 +33,8 @@ SYMBOLS = [
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
     "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
     "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_match_unique", "vcp_match_unique_dev",
-    "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
+    "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_register_sim",
+    "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
 ]
 
 
@@ -728,6 +729,44 @@ class Context:
                                                _ptr(d_n_hyp)))
         return dict(best=best.value, M=M.reshape(4, 4))
 
+    def register_sim(self, source, target, bases, scale_min, scale_max, inlier_dist, mirror=False, max_landmarks=200):
+        """vcp_register_sim: register_pairs where source and target differ by an unknown scale.  A base fits an ordered
+        pair of targets when k = Lv / Lu lies in [scale_min, scale_max]; the pose is the planar similarity with that k.
+        Returns register_pairs's dict plus scale [B] (the winner's k; 0.0 = none)."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        bases = np.ascontiguousarray(bases, np.int32).reshape(-1, 2)
+        B = len(bases)
+        M = np.zeros(16)
+        M_all = np.zeros((B, 16))
+        score = np.zeros(B, np.int32)
+        inl = np.zeros(B, np.int32)
+        pick = np.zeros((B, 3), np.int32)
+        n_hyp = np.zeros(B, np.int64)
+        scale = np.zeros(B)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_register_sim(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
+                                         C.c_int64(len(target)), _ptr(bases), C.c_int32(B), C.c_double(scale_min),
+                                         C.c_double(scale_max), int(bool(mirror)), int(max_landmarks),
+                                         C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(score),
+                                         _ptr(inl), _ptr(pick), _ptr(n_hyp), _ptr(scale)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(B, 4, 4), score=score, inliers=inl, pick=pick,
+                    n_hyp=n_hyp, scale=scale)
+
+    def register_sim_dev(self, d_source, ns, d_target, nt, d_bases, n_bases, scale_min, scale_max, inlier_dist,
+                         mirror=False, max_landmarks=200, d_M_all=None, d_score=None, d_inliers=None, d_pick=None,
+                         d_n_hyp=None, d_scale=None):
+        """Device-pointer form (ints from tensor.data_ptr()); the per-base arrays are written in place and may be None.
+        Returns dict(best, M [4,4])."""
+        M = np.zeros(16)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_register_sim_dev(self._h, _ptr(d_source), C.c_int64(ns), _ptr(d_target), C.c_int64(nt),
+                                             _ptr(d_bases), C.c_int32(n_bases), C.c_double(scale_min),
+                                             C.c_double(scale_max), int(bool(mirror)), int(max_landmarks),
+                                             C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(d_M_all), _ptr(d_score),
+                                             _ptr(d_inliers), _ptr(d_pick), _ptr(d_n_hyp), _ptr(d_scale)))
+        return dict(best=best.value, M=M.reshape(4, 4))
+
     def import_convert(self, rows, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True):
         """MainForm.AddFolder per-row work: dict(xyz [n,3], state [n] (0 filtered / 1 kept / 2 duplicate), kept, duplicates)."""
         rows = _f64(rows, 3)
@@ -750,6 +789,17 @@ def selftest_register_pose(a, b, ti, tj, f=0):
     if rc < 0:
         raise VcpError(rc, "vcp_selftest_register_pose")
     return float(L[0]), float(L[1]), (M.reshape(4, 4) if rc == 1 else None)
+
+
+def selftest_register_sim_pose(a, b, ti, tj, f=0):
+    """vcp_selftest_register_sim_pose: the pose arithmetic of vcp_register_sim run on the host (no device).  Returns (Lu,
+    Lv, k, M [4,4] or None when the hypothesis is skipped)."""
+    a, b, ti, tj = (_f64(v).reshape(3) for v in (a, b, ti, tj))
+    L, M = np.zeros(3), np.zeros(16)
+    rc = lib().vcp_selftest_register_sim_pose(_ptr(a), _ptr(b), _ptr(ti), _ptr(tj), int(f), _ptr(L), _ptr(M))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_register_sim_pose")
+    return float(L[0]), float(L[1]), float(L[2]), (M.reshape(4, 4) if rc == 1 else None)
 
 
 def blocks_share_plan(blockstart, world):

@@ -19,6 +19,14 @@
 //                  inliers over all ns source points
 // The score is an existence test over the 3 x 3 x 3 cells of mugrid.hpp's grid over the targets (cell edge >= inlier_dist
 // (1 + 2^-20)).  Only integer atomics decide anything: the result does not depend on scheduling.
+//
+// vcp_register_sim is the same call with a scale: a base fits a target pair when k = Lv / Lu lies in
+// [scale_min, scale_max], and the pose carries k (rg_sim_pose_of).  The search and the final kernel are one source for both
+// (rg_search<SIM>, rg_final<SIM>); what differs is the length test, the pose function and the scale that is written:
+//   k_regs_search  fl(Lv / Lu) does not rise as Lu rises (a correctly rounded division is monotone), so the passing bases
+//                  are again one run of sL: its start by binary search on Lv / sL[mid] <= scale_max, then walked while
+//                  Lv / sL[k] >= scale_min.  The exact division decides every place; there is no cheaper bracket
+//   k_regs_final   k_regp_final with the similarity pose; also writes the winner's k
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -100,6 +108,44 @@ __host__ __device__ inline bool rg_pose_of(const double r[6], int f, const doubl
   return true;
 }
 
+// The similarity pose: rg_pose_of's rotation and midpoints with k = Lv / Lu on the rotation block and on the moved source
+// midpoint; *scale = k.  False when the hypothesis is skipped (nrm).  With k == 1.0 every entry of M is rg_pose_of's bit for
+// bit (1.0 * x == x, sign of zero included).  Host and device run this source.
+__host__ __device__ inline bool rg_sim_pose_of(const double r[6], int f, const double* ti, const double* tj, double M[16],
+                                               double* scale) {
+  double ux = r[1], uy = r[2], msx = r[3], msy = r[4];
+  const double msz = r[5];
+  if (f) {
+    uy = -uy;
+    msy = -msy;
+  }
+  const double ix = ti[0], iy = ti[1], iz = ti[2], jx = tj[0], jy = tj[1], jz = tj[2];
+  const double vx = jx - ix, vy = jy - iy;
+  const double k = sqrt(vx * vx + vy * vy) / r[0];
+  *scale = k;
+  const double dot = ux * vx + uy * vy, crs = ux * vy - uy * vx;
+  const double nrm = sqrt(dot * dot + crs * crs);
+  if (!(nrm > 0.0 && nrm < INFINITY)) return false;
+  const double c = dot / nrm, s = crs / nrm;
+  const double kc = k * c, ks = k * s;
+  const double mtx = (ix + jx) * 0.5, mty = (iy + jy) * 0.5, mtz = (iz + jz) * 0.5;
+  M[0] = kc;
+  M[1] = f ? ks : -ks;
+  M[2] = 0.0;
+  M[3] = mtx - (kc * msx - ks * msy);
+  M[4] = ks;
+  M[5] = f ? -kc : kc;
+  M[6] = 0.0;
+  M[7] = mty - (ks * msx + kc * msy);
+  M[8] = 0.0;
+  M[9] = 0.0;
+  M[10] = k;
+  M[11] = mtz - k * msz;
+  M[12] = M[13] = M[14] = 0.0;
+  M[15] = 1.0;
+  return true;
+}
+
 __global__ __launch_bounds__(RT) void k_regp_bases(const double* __restrict__ src, int64_t ns,
                                                    const int32_t* __restrict__ bases, int nb, double* __restrict__ tab,
                                                    uint32_t* __restrict__ err) {
@@ -149,10 +195,12 @@ __device__ __forceinline__ bool rg_exists(const RGScan& q, const double* m) {
   return false;
 }
 
-// The pose of hypothesis (b, f, i, j) from the base table.
+// The pose of hypothesis (b, f, i, j) from the base table; SIM: the similarity pose and its scale.
+template <bool SIM>
 __device__ __forceinline__ bool rg_pose(const RGTab& tab, int b, int f, const double* __restrict__ tgt, int i, int j,
-                                        double M[16]) {
+                                        double M[16], double* scale) {
   const double r[6] = {tab.Lu(b), tab.ux(b), tab.uy(b), tab.msx(b), tab.msy(b), tab.msz(b)};
+  if (SIM) return rg_sim_pose_of(r, f, tgt + 3 * (size_t)i, tgt + 3 * (size_t)j, M, scale);
   return rg_pose_of(r, f, tgt + 3 * (size_t)i, tgt + 3 * (size_t)j, M);
 }
 
@@ -166,21 +214,23 @@ struct RGSearch {
   const double* sL;   // [nv] ascending
   const int32_t* sb;  // [nv] base of the sorted place
   int nv;
-  double len_tol;
-  int nf;  // 1, or 2 with the mirror images
+  double len_tol;               // the rigid search
+  double scale_min, scale_max;  // the similarity search
+  int nf;                       // 1, or 2 with the mirror images
   RGScan q;
   unsigned long long* key;   // [n_bases] the winners' words
   unsigned long long* nhyp;  // [n_bases]
 };
 
 // scores the n queued hypotheses of row i: wave w takes entries w, w + 4, ...
+template <bool SIM>
 __device__ __forceinline__ void rg_flush(const RGSearch& a, int i, const uint32_t* qe, uint32_t n) {
   const int lane = threadIdx.x & 63;
   for (uint32_t e = threadIdx.x >> 6; e < n; e += RT / 64) {
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)qe[e]);
     const int j = (int)(w & 0xFFFFu), f = (int)((w >> 16) & 1u), b = a.sb[w >> 17];
-    double M[16];
-    const bool ok = rg_pose(a.tab, b, f, a.tgt, i, j, M);
+    double M[16], sc;
+    const bool ok = rg_pose<SIM>(a.tab, b, f, a.tgt, i, j, M, &sc);
     uint32_t cnt = 0;
     if (ok) {
       for (int l0 = 0; l0 < a.nl; l0 += 64) {
@@ -206,13 +256,23 @@ __device__ __forceinline__ void rg_flush(const RGSearch& a, int i, const uint32_
   }
 }
 
-__global__ __launch_bounds__(RT) void k_regp_search(RGSearch a) {
-  __shared__ double sL[RG_MAX_BASES];
-  __shared__ uint32_t qe[RG_QCAP];
-  __shared__ uint32_t qn;
+// does the base at sorted place k fit a target pair of length Lv?  The header's test, on the operands it names.
+template <bool SIM>
+__device__ __forceinline__ bool rg_fits(const RGSearch& a, double Lv, const double* sL, int k) {
+  if (k >= a.nv) return false;
+  if (SIM) {
+    const double r = Lv / sL[k];
+    return a.scale_min <= r && r <= a.scale_max;
+  }
+  return fabs(Lv - sL[k]) <= a.len_tol;
+}
+
+// The search of one workgroup (target i = blockIdx.x); sL, qe and qn are the kernel's LDS.
+template <bool SIM>
+__device__ __forceinline__ void rg_search(const RGSearch& a, double* sL, uint32_t* qe, uint32_t* qn) {
   const int tid = threadIdx.x, lane = tid & 63;
   for (int k = tid; k < a.nv; k += RT) sL[k] = a.sL[k];
-  if (tid == 0) qn = 0;
+  if (tid == 0) *qn = 0;
   __syncthreads();
   const int i = blockIdx.x;
   const double ix = a.tgt[3 * (size_t)i], iy = a.tgt[3 * (size_t)i + 1];
@@ -225,16 +285,17 @@ __global__ __launch_bounds__(RT) void k_regp_search(RGSearch a) {
       const double vx = a.tgt[3 * (size_t)j] - ix, vy = a.tgt[3 * (size_t)j + 1] - iy;
       Lv = sqrt(vx * vx + vy * vy);
       if (Lv > 0.0 && Lv < INFINITY) {
-        int lo = 0, hi = a.nv;  // the first place with fl(Lv - Lu) <= len_tol; the difference falls as Lu rises
+        // the first place with fl(Lv - Lu) <= len_tol (SIM: fl(Lv / Lu) <= scale_max); both fall as Lu rises
+        int lo = 0, hi = a.nv;
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
-          if (Lv - sL[mid] <= a.len_tol)
+          if (SIM ? Lv / sL[mid] <= a.scale_max : Lv - sL[mid] <= a.len_tol)
             hi = mid;
           else
             lo = mid + 1;
         }
         k = lo;
-        live = k < a.nv && fabs(Lv - sL[k]) <= a.len_tol;
+        live = rg_fits<SIM>(a, Lv, sL, k);
       }
     }
     // a round: every lane that still has a hypothesis queues one; the queue is scored when the next round might not fit
@@ -243,7 +304,7 @@ __global__ __launch_bounds__(RT) void k_regp_search(RGSearch a) {
       if (bal) {  // wave-uniform
         const int leader = __ffsll((long long)bal) - 1;
         uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&qn, (uint32_t)__popcll(bal));
+        if (lane == leader) base = atomicAdd(qn, (uint32_t)__popcll(bal));
         base = (uint32_t)__shfl((int)base, leader, 64);
         if (live)
           qe[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)j | ((uint32_t)f << 16) | ((uint32_t)k << 17);
@@ -251,33 +312,45 @@ __global__ __launch_bounds__(RT) void k_regp_search(RGSearch a) {
       if (live && ++f == a.nf) {
         f = 0;
         k++;
-        live = k < a.nv && fabs(Lv - sL[k]) <= a.len_tol;
+        live = rg_fits<SIM>(a, Lv, sL, k);
       }
       __syncthreads();
-      const uint32_t n = qn;
+      const uint32_t n = *qn;
       if (n > RG_QCAP - RT) {  // workgroup-uniform
-        rg_flush(a, i, qe, n);
+        rg_flush<SIM>(a, i, qe, n);
         __syncthreads();
-        if (tid == 0) qn = 0;
+        if (tid == 0) *qn = 0;
       }
     }
   }
-  rg_flush(a, i, qe, qn);
+  rg_flush<SIM>(a, i, qe, *qn);
+}
+
+__global__ __launch_bounds__(RT) void k_regp_search(RGSearch a) {
+  __shared__ double sL[RG_MAX_BASES];
+  __shared__ uint32_t qe[RG_QCAP];
+  __shared__ uint32_t qn;
+  rg_search<false>(a, sL, qe, &qn);
+}
+
+__global__ __launch_bounds__(RT) void k_regs_search(RGSearch a) {
+  __shared__ double sL[RG_MAX_BASES];
+  __shared__ uint32_t qe[RG_QCAP];
+  __shared__ uint32_t qn;
+  rg_search<true>(a, sL, qe, &qn);
 }
 
 // grid (source points, bases)
-__global__ __launch_bounds__(RT) void k_regp_final(const double* __restrict__ src, int64_t ns,
-                                                   const double* __restrict__ tgt, RGTab tab,
-                                                   const unsigned long long* __restrict__ key, RGScan q,
-                                                   double* __restrict__ M_all, int32_t* __restrict__ score,
-                                                   int32_t* __restrict__ pick, uint32_t* __restrict__ inliers) {
-  __shared__ double sM[16];
-  __shared__ int has;
-  __shared__ uint32_t wc[RT / 64];
+template <bool SIM>
+__device__ __forceinline__ void rg_final(const double* __restrict__ src, int64_t ns, const double* __restrict__ tgt,
+                                         const RGTab& tab, const unsigned long long* __restrict__ key, const RGScan& q,
+                                         double* __restrict__ M_all, int32_t* __restrict__ score, int32_t* __restrict__ pick,
+                                         uint32_t* __restrict__ inliers, double* __restrict__ scale, double* sM, int* has,
+                                         uint32_t* wc) {
   const int b = blockIdx.y;
   if (threadIdx.x == 0) {
     const unsigned long long k = key[b];
-    double M[16];
+    double M[16], kw = 0.0;  // the winner's scale
     int sc = -1, f = 0, i = -1, j = -1;
     bool ok = false;
     if (k != 0ull) {
@@ -286,24 +359,26 @@ __global__ __launch_bounds__(RT) void k_regp_final(const double* __restrict__ sr
       f = (int)(pk >> 32);
       i = (int)((pk >> 16) & 0xFFFFull);
       j = (int)(pk & 0xFFFFull);
-      ok = rg_pose(tab, b, f, tgt, i, j, M);  // true: the word came from a pose that was scored
+      ok = rg_pose<SIM>(tab, b, f, tgt, i, j, M, &kw);  // true: the word came from a pose that was scored
     }
     if (!ok) {
       sc = -1, f = 0, i = -1, j = -1;
+      kw = 0.0;
       for (int t = 0; t < 16; t++) M[t] = 0.0;
     }
     for (int t = 0; t < 16; t++) sM[t] = M[t];
-    has = ok;
+    *has = ok;
     if (blockIdx.x == 0) {
       for (int t = 0; t < 16; t++) M_all[16 * (size_t)b + t] = M[t];
       score[b] = sc;
       pick[3 * b] = f;
       pick[3 * b + 1] = i;
       pick[3 * b + 2] = j;
+      if (SIM) scale[b] = kw;
     }
   }
   __syncthreads();
-  if (!has) return;
+  if (!*has) return;
   const int64_t p = (int64_t)blockIdx.x * RT + threadIdx.x;
   bool hit = false;
   if (p < ns) {
@@ -323,13 +398,48 @@ __global__ __launch_bounds__(RT) void k_regp_final(const double* __restrict__ sr
   }
 }
 
+__global__ __launch_bounds__(RT) void k_regp_final(const double* __restrict__ src, int64_t ns,
+                                                   const double* __restrict__ tgt, RGTab tab,
+                                                   const unsigned long long* __restrict__ key, RGScan q,
+                                                   double* __restrict__ M_all, int32_t* __restrict__ score,
+                                                   int32_t* __restrict__ pick, uint32_t* __restrict__ inliers) {
+  __shared__ double sM[16];
+  __shared__ int has;
+  __shared__ uint32_t wc[RT / 64];
+  rg_final<false>(src, ns, tgt, tab, key, q, M_all, score, pick, inliers, nullptr, sM, &has, wc);
+}
+
+__global__ __launch_bounds__(RT) void k_regs_final(const double* __restrict__ src, int64_t ns,
+                                                   const double* __restrict__ tgt, RGTab tab,
+                                                   const unsigned long long* __restrict__ key, RGScan q,
+                                                   double* __restrict__ M_all, int32_t* __restrict__ score,
+                                                   int32_t* __restrict__ pick, uint32_t* __restrict__ inliers,
+                                                   double* __restrict__ scale) {
+  __shared__ double sM[16];
+  __shared__ int has;
+  __shared__ uint32_t wc[RT / 64];
+  rg_final<true>(src, ns, tgt, tab, key, q, M_all, score, pick, inliers, scale, sM, &has, wc);
+}
+
+// what a target pair must satisfy to fit a base: |Lv - Lu| <= len_tol, or (sim) scale_min <= Lv / Lu <= scale_max
+struct RGFit {
+  bool sim;
+  double len_tol, scale_min, scale_max;
+};
+
 int rg_check(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, const int32_t* bases,
-             int32_t n_bases, double len_tol, int max_landmarks, double inlier_dist, const double* M_best,
+             int32_t n_bases, const RGFit& fit, int max_landmarks, double inlier_dist, const double* M_best,
              const int32_t* best) {
   if (!source || !target || !bases || !M_best || !best) return vcp_fail(ctx, VCP_ERR_ARG, "null argument");
   if (n_bases < 1) return vcp_fail(ctx, VCP_ERR_ARG, "n_bases < 1");
   if (max_landmarks < 1) return vcp_fail(ctx, VCP_ERR_ARG, "max_landmarks < 1");
-  if (!(len_tol >= 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "len_tol must be >= 0 (+inf allowed)");
+  if (fit.sim) {
+    if (!(fit.scale_min > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "scale_min must be > 0");
+    if (!(fit.scale_max >= fit.scale_min && fit.scale_max < INFINITY))
+      return vcp_fail(ctx, VCP_ERR_ARG, "scale_max must be finite and >= scale_min");
+  } else if (!(fit.len_tol >= 0.0)) {
+    return vcp_fail(ctx, VCP_ERR_ARG, "len_tol must be >= 0 (+inf allowed)");
+  }
   if (!(inlier_dist > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "inlier_dist must be > 0 (+inf allowed)");
   if (ns < 2 || nt < 2) return vcp_fail(ctx, VCP_ERR_EMPTY, "fewer than two source or target points");
   if (n_bases > RG_MAX_BASES) return vcp_fail(ctx, VCP_ERR_UNSUPPORTED, "n_bases > %d", RG_MAX_BASES);
@@ -341,27 +451,28 @@ int rg_check(vcp_ctx* ctx, const double* source, int64_t ns, const double* targe
 
 // the per-base results as they lie in b_rg_work and, read back, in the pinned stage
 struct RGLayout {
-  size_t o_M, o_nhyp, o_score, o_inl, o_pick, bytes;
-  explicit RGLayout(size_t nb) {
+  size_t o_M, o_nhyp, o_score, o_inl, o_pick, o_scale, bytes;
+  explicit RGLayout(size_t nb, bool sim = false) {
     o_M = 0;
     o_nhyp = o_M + nb * 128;
     o_score = o_nhyp + nb * 8;
     o_inl = o_score + nb * 4;
     o_pick = o_inl + nb * 4;
-    bytes = up16(o_pick + nb * 12);
+    o_scale = bytes = up16(o_pick + nb * 12);
+    if (sim) bytes = up16(o_scale + nb * 8);  // the winners' scales, vcp_register_sim only
   }
 };
 
 // The call on device pointers.  The per-base results stay in b_rg_work (at *res_dev) and are read back to *res_host,
 // laid out by RGLayout; M_best and best are filled.
 int rg_run(vcp_ctx* ctx, const double* d_src, int64_t ns, const double* d_tgt, int64_t nt, const int32_t* d_bases,
-           int32_t n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist, double M_best[16],
+           int32_t n_bases, const RGFit& fit, int mirror, int max_landmarks, double inlier_dist, double M_best[16],
            int32_t* best, const char** res_dev, const char** res_host) {
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
   hipStream_t st = ctx->stream;
   const size_t nb = (size_t)n_bases, tt = (size_t)nt;
-  const RGLayout L(nb);
+  const RGLayout L(nb, fit.sim);
   // b_rg_work: [results | base table 6 nb doubles | sL nb doubles | key nb words | sb nb int32 | error word]
   const size_t w_tab = L.bytes, w_sL = w_tab + nb * 48, w_key = w_sL + nb * 8, w_sb = w_key + nb * 8,
                w_err = up16(w_sb + nb * 4);
@@ -381,7 +492,7 @@ int rg_run(vcp_ctx* ctx, const double* d_src, int64_t ns, const double* d_tgt, i
   char* stage = static_cast<char*>(vcp_stage(ctx, s_err + 16));
   if (!stage) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of the per-base results");
 
-  vcp_phase(ctx, "regp_grid");
+  vcp_phase(ctx, fit.sim ? "regs_grid" : "regp_grid");
   VCP_HIP(ctx, hipMemsetAsync(dw, 0, w_err + 16, st));  // results, table, words and the error word
   VCP_LAUNCH(ctx, k_regp_bases, dim3(vcp_blocks(n_bases, RT)), dim3(RT), 0, st, d_src, ns, d_bases, n_bases, d_tab, d_err);
   VCP_HIP(ctx, hipMemcpyAsync(stage + s_Lu, d_tab, nb * 8, hipMemcpyDeviceToHost, st));
@@ -426,21 +537,30 @@ int rg_run(vcp_ctx* ctx, const double* d_src, int64_t ns, const double* d_tgt, i
     }
   }
 
-  vcp_phase(ctx, "regp_search");
+  vcp_phase(ctx, fit.sim ? "regs_search" : "regp_search");
   int64_t step = 1;
   if (ns > max_landmarks) step = ns / max_landmarks;
   const RGTab tab{d_tab, n_bases};
   unsigned long long* d_nhyp = reinterpret_cast<unsigned long long*>(dw + L.o_nhyp);
   if (nv > 0) {
-    const RGSearch a{d_src, step, (int)(ns / step), d_tgt, (int)nt, tab, d_sL, d_sb, nv, len_tol, mirror ? 2 : 1, q, d_key,
-                     d_nhyp};
-    VCP_LAUNCH(ctx, k_regp_search, dim3((unsigned)nt), dim3(RT), 0, st, a);
+    const RGSearch a{d_src, step, (int)(ns / step), d_tgt, (int)nt, tab, d_sL, d_sb, nv, fit.len_tol, fit.scale_min,
+                     fit.scale_max, mirror ? 2 : 1, q, d_key, d_nhyp};
+    if (fit.sim)
+      VCP_LAUNCH(ctx, k_regs_search, dim3((unsigned)nt), dim3(RT), 0, st, a);
+    else
+      VCP_LAUNCH(ctx, k_regp_search, dim3((unsigned)nt), dim3(RT), 0, st, a);
   }
 
-  vcp_phase(ctx, "regp_final");
-  VCP_LAUNCH(ctx, k_regp_final, dim3(vcp_blocks(ns, RT), (unsigned)n_bases), dim3(RT), 0, st, d_src, ns, d_tgt, tab, d_key,
-             q, reinterpret_cast<double*>(dw + L.o_M), reinterpret_cast<int32_t*>(dw + L.o_score),
-             reinterpret_cast<int32_t*>(dw + L.o_pick), reinterpret_cast<uint32_t*>(dw + L.o_inl));
+  vcp_phase(ctx, fit.sim ? "regs_final" : "regp_final");
+  if (fit.sim)
+    VCP_LAUNCH(ctx, k_regs_final, dim3(vcp_blocks(ns, RT), (unsigned)n_bases), dim3(RT), 0, st, d_src, ns, d_tgt, tab, d_key,
+               q, reinterpret_cast<double*>(dw + L.o_M), reinterpret_cast<int32_t*>(dw + L.o_score),
+               reinterpret_cast<int32_t*>(dw + L.o_pick), reinterpret_cast<uint32_t*>(dw + L.o_inl),
+               reinterpret_cast<double*>(dw + L.o_scale));
+  else
+    VCP_LAUNCH(ctx, k_regp_final, dim3(vcp_blocks(ns, RT), (unsigned)n_bases), dim3(RT), 0, st, d_src, ns, d_tgt, tab, d_key,
+               q, reinterpret_cast<double*>(dw + L.o_M), reinterpret_cast<int32_t*>(dw + L.o_score),
+               reinterpret_cast<int32_t*>(dw + L.o_pick), reinterpret_cast<uint32_t*>(dw + L.o_inl));
   VCP_HIP(ctx, hipMemcpyAsync(stage, dw, L.bytes, hipMemcpyDeviceToHost, st));
   VCP_TRY(vcp_phase_finish(ctx));
   VCP_HIP(ctx, hipStreamSynchronize(st));
@@ -479,37 +599,56 @@ int vcp_selftest_register_pose(const double a[3], const double b[3], const doubl
   return rg_pose_of(r, f != 0, ti, tj, M) ? 1 : 0;
 }
 
-int vcp_register_pairs_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, const double* d_target, int64_t nt,
-                           const int32_t* d_bases, int32_t n_bases, double len_tol, int mirror, int max_landmarks,
-                           double inlier_dist, double M_best[16], int32_t* best, double* d_M_all, int32_t* d_score,
-                           int32_t* d_inliers, int32_t* d_pick, int64_t* d_n_hyp) {
+int vcp_selftest_register_sim_pose(const double a[3], const double b[3], const double ti[3], const double tj[3], int f,
+                                   double Lu_Lv_k[3], double M[16]) {
+  if (!a || !b || !ti || !tj || !Lu_Lv_k || !M) return VCP_ERR_ARG;
+  double r[6], Ms[16], k;
+  rg_base(a, b, r);
+  const double vx = tj[0] - ti[0], vy = tj[1] - ti[1];
+  const bool ok = rg_sim_pose_of(r, f != 0, ti, tj, Ms, &k);
+  Lu_Lv_k[0] = r[0];
+  Lu_Lv_k[1] = sqrt(vx * vx + vy * vy);
+  Lu_Lv_k[2] = k;
+  if (ok) std::memcpy(M, Ms, sizeof(Ms));
+  return ok ? 1 : 0;
+}
+
+}  // extern "C"
+
+namespace {
+// The two entry points on device pointers (d_scale: vcp_register_sim_dev only).
+int rg_call_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, const double* d_target, int64_t nt, const int32_t* d_bases,
+                int32_t n_bases, const RGFit& fit, int mirror, int max_landmarks, double inlier_dist, double M_best[16],
+                int32_t* best, double* d_M_all, int32_t* d_score, int32_t* d_inliers, int32_t* d_pick, int64_t* d_n_hyp,
+                double* d_scale) {
   if (!ctx) return VCP_ERR_ARG;
-  VCP_TRY(rg_check(ctx, d_source, ns, d_target, nt, d_bases, n_bases, len_tol, max_landmarks, inlier_dist, M_best, best));
+  VCP_TRY(rg_check(ctx, d_source, ns, d_target, nt, d_bases, n_bases, fit, max_landmarks, inlier_dist, M_best, best));
   const char *rd = nullptr, *rh = nullptr;
   double Mb[16];
   int32_t bb = -1;
-  VCP_TRY(rg_run(ctx, d_source, ns, d_target, nt, d_bases, n_bases, len_tol, mirror, max_landmarks, inlier_dist, Mb, &bb,
-                 &rd, &rh));
+  VCP_TRY(rg_run(ctx, d_source, ns, d_target, nt, d_bases, n_bases, fit, mirror, max_landmarks, inlier_dist, Mb, &bb, &rd,
+                 &rh));
   const size_t nb = (size_t)n_bases;
-  const RGLayout L(nb);
+  const RGLayout L(nb, fit.sim);
   hipStream_t st = ctx->stream;
   if (d_M_all) VCP_HIP(ctx, hipMemcpyAsync(d_M_all, rd + L.o_M, nb * 128, hipMemcpyDeviceToDevice, st));
   if (d_score) VCP_HIP(ctx, hipMemcpyAsync(d_score, rd + L.o_score, nb * 4, hipMemcpyDeviceToDevice, st));
   if (d_inliers) VCP_HIP(ctx, hipMemcpyAsync(d_inliers, rd + L.o_inl, nb * 4, hipMemcpyDeviceToDevice, st));
   if (d_pick) VCP_HIP(ctx, hipMemcpyAsync(d_pick, rd + L.o_pick, nb * 12, hipMemcpyDeviceToDevice, st));
   if (d_n_hyp) VCP_HIP(ctx, hipMemcpyAsync(d_n_hyp, rd + L.o_nhyp, nb * 8, hipMemcpyDeviceToDevice, st));
+  if (fit.sim && d_scale) VCP_HIP(ctx, hipMemcpyAsync(d_scale, rd + L.o_scale, nb * 8, hipMemcpyDeviceToDevice, st));
   VCP_HIP(ctx, hipStreamSynchronize(st));
   std::memcpy(M_best, Mb, sizeof(Mb));
   *best = bb;
   return VCP_OK;
 }
 
-int vcp_register_pairs(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
-                       const int32_t* bases, int32_t n_bases, double len_tol, int mirror, int max_landmarks,
-                       double inlier_dist, double M_best[16], int32_t* best, double* M_all, int32_t* score,
-                       int32_t* inliers, int32_t* pick, int64_t* n_hyp) {
+// The two entry points on host pointers (scale: vcp_register_sim only).
+int rg_call(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, const int32_t* bases,
+            int32_t n_bases, const RGFit& fit, int mirror, int max_landmarks, double inlier_dist, double M_best[16],
+            int32_t* best, double* M_all, int32_t* score, int32_t* inliers, int32_t* pick, int64_t* n_hyp, double* scale) {
   if (!ctx) return VCP_ERR_ARG;
-  VCP_TRY(rg_check(ctx, source, ns, target, nt, bases, n_bases, len_tol, max_landmarks, inlier_dist, M_best, best));
+  VCP_TRY(rg_check(ctx, source, ns, target, nt, bases, n_bases, fit, max_landmarks, inlier_dist, M_best, best));
   VCP_TRY(vcp_bind(ctx));
   hipStream_t st = ctx->stream;
   // [source ns*24 | target nt*24 | bases n_bases*8]
@@ -523,17 +662,53 @@ int vcp_register_pairs(vcp_ctx* ctx, const double* source, int64_t ns, const dou
   double Mb[16];
   int32_t bb = -1;
   VCP_TRY(rg_run(ctx, reinterpret_cast<const double*>(din), ns, reinterpret_cast<const double*>(din + i_t), nt,
-                 reinterpret_cast<const int32_t*>(din + i_b), n_bases, len_tol, mirror, max_landmarks, inlier_dist, Mb, &bb,
-                 &rd, &rh));
-  const RGLayout L(nb);
+                 reinterpret_cast<const int32_t*>(din + i_b), n_bases, fit, mirror, max_landmarks, inlier_dist, Mb, &bb, &rd,
+                 &rh));
+  const RGLayout L(nb, fit.sim);
   if (M_all) std::memcpy(M_all, rh + L.o_M, nb * 128);
   if (score) std::memcpy(score, rh + L.o_score, nb * 4);
   if (inliers) std::memcpy(inliers, rh + L.o_inl, nb * 4);
   if (pick) std::memcpy(pick, rh + L.o_pick, nb * 12);
   if (n_hyp) std::memcpy(n_hyp, rh + L.o_nhyp, nb * 8);
+  if (fit.sim && scale) std::memcpy(scale, rh + L.o_scale, nb * 8);
   std::memcpy(M_best, Mb, sizeof(Mb));
   *best = bb;
   return VCP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int vcp_register_pairs_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, const double* d_target, int64_t nt,
+                           const int32_t* d_bases, int32_t n_bases, double len_tol, int mirror, int max_landmarks,
+                           double inlier_dist, double M_best[16], int32_t* best, double* d_M_all, int32_t* d_score,
+                           int32_t* d_inliers, int32_t* d_pick, int64_t* d_n_hyp) {
+  return rg_call_dev(ctx, d_source, ns, d_target, nt, d_bases, n_bases, RGFit{false, len_tol, 0.0, 0.0}, mirror,
+                     max_landmarks, inlier_dist, M_best, best, d_M_all, d_score, d_inliers, d_pick, d_n_hyp, nullptr);
+}
+
+int vcp_register_pairs(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                       const int32_t* bases, int32_t n_bases, double len_tol, int mirror, int max_landmarks,
+                       double inlier_dist, double M_best[16], int32_t* best, double* M_all, int32_t* score,
+                       int32_t* inliers, int32_t* pick, int64_t* n_hyp) {
+  return rg_call(ctx, source, ns, target, nt, bases, n_bases, RGFit{false, len_tol, 0.0, 0.0}, mirror, max_landmarks,
+                 inlier_dist, M_best, best, M_all, score, inliers, pick, n_hyp, nullptr);
+}
+
+int vcp_register_sim_dev(vcp_ctx* ctx, const double* d_source, int64_t ns, const double* d_target, int64_t nt,
+                         const int32_t* d_bases, int32_t n_bases, double scale_min, double scale_max, int mirror,
+                         int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* d_M_all,
+                         int32_t* d_score, int32_t* d_inliers, int32_t* d_pick, int64_t* d_n_hyp, double* d_scale) {
+  return rg_call_dev(ctx, d_source, ns, d_target, nt, d_bases, n_bases, RGFit{true, 0.0, scale_min, scale_max}, mirror,
+                     max_landmarks, inlier_dist, M_best, best, d_M_all, d_score, d_inliers, d_pick, d_n_hyp, d_scale);
+}
+
+int vcp_register_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                     const int32_t* bases, int32_t n_bases, double scale_min, double scale_max, int mirror,
+                     int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all, int32_t* score,
+                     int32_t* inliers, int32_t* pick, int64_t* n_hyp, double* scale) {
+  return rg_call(ctx, source, ns, target, nt, bases, n_bases, RGFit{true, 0.0, scale_min, scale_max}, mirror, max_landmarks,
+                 inlier_dist, M_best, best, M_all, score, inliers, pick, n_hyp, scale);
 }
 
 }  // extern "C"

@@ -163,6 +163,26 @@ class ICP {  // BaseClass/ICP.cs:8
                                 inliers ? inliers->data() : nullptr, nullptr, nullptr));
     return best;
   }
+  // RegisterPairs where source is not in the targets' unit (vcp.h: vcp_register_sim): a base fits a target pair whose length
+  // is k times its own, scaleMin <= k <= scaleMax; M16 is the planar similarity, scale (may be null) the per-base k.
+  int RegisterSimilarity(const std::vector<Point3D*>& source, const std::vector<Point3D*>& target,
+                         const std::vector<int32_t>& bases, double scaleMin, double scaleMax, bool mirror, double inlierDist,
+                         double M16[16], std::vector<int32_t>* inliers = nullptr, std::vector<int32_t>* score = nullptr,
+                         std::vector<double>* scale = nullptr) {
+    std::vector<double> s(3 * source.size()), t(3 * target.size());
+    for (size_t i = 0; i < source.size(); i++) { s[3 * i] = source[i]->X; s[3 * i + 1] = source[i]->Y; s[3 * i + 2] = source[i]->Z; }
+    for (size_t i = 0; i < target.size(); i++) { t[3 * i] = target[i]->X; t[3 * i + 1] = target[i]->Y; t[3 * i + 2] = target[i]->Z; }
+    const int32_t nb = (int32_t)(bases.size() / 2);
+    if (inliers) inliers->assign(nb, 0);
+    if (score) score->assign(nb, -1);
+    if (scale) scale->assign(nb, 0.0);
+    int32_t best = -1;
+    c_.check(vcp_register_sim(c_.get(), s.data(), (int64_t)source.size(), t.data(), (int64_t)target.size(), bases.data(), nb,
+                              scaleMin, scaleMax, mirror ? 1 : 0, 200, inlierDist, M16, &best, nullptr,
+                              score ? score->data() : nullptr, inliers ? inliers->data() : nullptr, nullptr, nullptr,
+                              scale ? scale->data() : nullptr));
+    return best;
+  }
   double last_sse = 0;
   int last_iters = 0;
 

@@ -49,5 +49,19 @@ namespace vtkPointCloud
                 inliers, null, null));
             return best;
         }
+
+        // RegisterPairs where `source` is not in the targets' unit (vcp.h: vcp_register_sim): a base fits an ordered pair
+        // of targets whose length is k times its own, scaleMin <= k <= scaleMax, and the pose in M16 is the planar
+        // similarity with that k.  scale (may be null) receives the winner's k per base, 0 where a base found nothing.
+        public int RegisterSimilarity(List<Point3D> source, List<Point3D> target, int[] bases, double scaleMin,
+            double scaleMax, bool mirror, double inlierDist, double[] M16, int[] inliers, int[] score, double[] scale)
+        {
+            int best;
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_register_sim(c.Ctx, Flatten(source), source.Count, Flatten(target),
+                target.Count, bases, bases.Length / 2, scaleMin, scaleMax, mirror ? 1 : 0, 200, inlierDist, M16, out best,
+                null, score, inliers, null, null, scale));
+            return best;
+        }
     }
 }

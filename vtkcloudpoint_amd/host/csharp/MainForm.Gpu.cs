@@ -119,6 +119,33 @@ namespace vtkPointCloud
             showMatchedLine(isShowUnmatchedCenterPts, isShowUnmatchedTruePts);
         }
 
+        // In place of the bounding-box factors of showTruesAndCenters (FrmMain.cs:3046-3055): the ratio of the two extents
+        // is the ratio of a window to the field when the scan sees part of the truths, and one false cluster at the edge
+        // moves it for every point.  Here the scale is the k of the best similarity a pair of centroids and a pair of
+        // truths agree on (vcp_register_sim), one factor for both axes.  bases = pairs of indices into centers.  Returns
+        // false, with scale and tmp_X / tmp_Y untouched, when no base found a pair in [scaleMin, scaleMax].
+        public bool ScaleCentersBySimilarity(int[] bases, double scaleMin, double scaleMax, bool mirror, double inlierDist)
+        {
+            int K = centers.Count, nb = bases.Length / 2;
+            if (K < 2 || nb < 1) return false;
+            double[] c = new double[3 * K];
+            for (int j = 0; j < K; j++) { c[3 * j] = centers[j].X; c[3 * j + 1] = centers[j].Y; c[3 * j + 2] = 0.0; }
+            double[] M16 = new double[16], k = new double[nb];
+            int best;
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_register_sim(lease.Ctx, c, K, TruthArray(), (int)truePointCloud.GetNumberOfPoints(),
+                    bases, nb, scaleMin, scaleMax, mirror ? 1 : 0, 200, inlierDist, M16, out best, null, null, null, null, null, k));
+            if (best < 0) return false;
+            scale[0] = k[best];
+            scale[1] = k[best];
+            foreach (Point3D p in centers)
+            {
+                p.tmp_X = p.X * scale[0];
+                p.tmp_Y = p.Y * scale[1];
+            }
+            return true;
+        }
+
         // FrmMain.cs:3437-3467: nearest truth within the radius per raw point (the LINQ query :3452-3456)
         private void refreshClusList()
         {

@@ -96,6 +96,17 @@ namespace vtkPointCloud
             long nt, IntPtr d_bases, int n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist,
             double[] M_best, out int best, IntPtr d_M_all, IntPtr d_score, IntPtr d_inliers, IntPtr d_pick, IntPtr d_n_hyp);
 
+        // scale-free registration by similarity pairs (vcp.h): vcp_register_pairs where a base fits a target pair whose
+        // length is k times its own, scale_min <= k <= scale_max; scale receives the winner's k per base (may be null)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_sim(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int[] bases, int n_bases, double scale_min, double scale_max, int mirror, int max_landmarks,
+            double inlier_dist, double[] M_best, out int best, double[] M_all, int[] score, int[] inliers, int[] pick,
+            long[] n_hyp, double[] scale);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_sim_dev(IntPtr ctx, IntPtr d_source, long ns, IntPtr d_target,
+            long nt, IntPtr d_bases, int n_bases, double scale_min, double scale_max, int mirror, int max_landmarks,
+            double inlier_dist, double[] M_best, out int best, IntPtr d_M_all, IntPtr d_score, IntPtr d_inliers, IntPtr d_pick,
+            IntPtr d_n_hyp, IntPtr d_scale);
+
         // Tools.getCircles / Geometry.FindMinimalBoundingCircle (Tools.cs:394-409, Geometry.cs:247-319)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_mcc(IntPtr ctx, double[] xy, int[] labels, long[] order, long m, long n,
             int K, double[] centers, double[] radius, byte[] valid, int[] hull_n);

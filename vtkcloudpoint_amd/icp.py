@@ -267,6 +267,82 @@ def global_icp(centers, truths, bases, len_tol, inlier_dist, gates, mirror=False
     return out
 
 
+def register_similarity(centers, truths, bases, scale_range, inlier_dist, mirror=False, max_landmarks=200, ctx=None):
+    """register_pairs for centroids whose unit is not the truths' (vcp_register_sim): a base fits an ordered pair of truths
+    whose length is k times its own, scale_range[0] <= k <= scale_range[1], and the pose is the planar similarity with
+    that k.  Returns Context.register_sim's dict: register_pairs's plus scale [B], the winner's k per base."""
+    ctx = ctx or default_context()
+    lo, hi = scale_range
+    return ctx.register_sim(_points(centers), _points(truths), bases, float(lo), float(hi), inlier_dist, mirror,
+                            max_landmarks)
+
+
+def bbox_scale_range(centers, truths, slack):
+    """(min(sx, sy) / slack, max(sx, sy) * slack) from the reference's two factors, sx = the truths' x extent over the
+    centroids' and sy likewise for y (MainForm.showTruesAndCenters, FrmMain.cs:3046-3055): a default prior for
+    register_similarity's scale_range, slack >= 1.  It is only right when the scan covers the whole truth field and holds
+    no false cluster at its edge: on a partial view the factors are the ratio of a window to the field, and a wide
+    explicit range must be given instead."""
+    src, tgt = _points(centers), _points(truths)
+    slack = float(slack)
+    if not slack >= 1.0:
+        raise ValueError("slack < 1")
+    s = [(float(tgt[:, c].max()) - float(tgt[:, c].min())) / (float(src[:, c].max()) - float(src[:, c].min()))
+         for c in (0, 1)]
+    return min(s) / slack, max(s) * slack
+
+
+def fit_scale(p, y):
+    """Horn's symmetric scale of paired rows, sqrt(sum |y - mean y|^2 / sum |p - mean p|^2): the k of the similarity
+    y ~ k R p + T that does not depend on the rotation."""
+    p, y = np.asarray(p, np.float64), np.asarray(y, np.float64)
+    if p.shape != y.shape or len(p) < 2:
+        raise ValueError("need two or more paired rows")
+    dp, dy = p - p.mean(axis=0), y - y.mean(axis=0)
+    return math.sqrt(float((dy * dy).sum()) / float((dp * dp).sum()))
+
+
+def _linear_scale(R):
+    """The scale of k times a rotation or reflection: sqrt(|det| of the planar block)."""
+    return math.sqrt(abs(float(R[0, 0] * R[1, 1] - R[0, 1] * R[1, 0])))
+
+
+def global_sim_icp(centers, truths, bases, scale_range, inlier_dist, gates, mirror=False, max_iter=20, max_landmarks=200,
+                   min_pairs=3, refine=True, ctx=None):
+    """global_icp where the centroids' unit is unknown: register_similarity, then ONE gated_icp call started from the
+    similarity of every base that found one (vcp_icp_gated takes init_R as given and composes proper rotations onto it,
+    so the scale rides through the rounds unchanged).  With refine, the best pose's one-to-one pairs at inlier_dist
+    (match_unique) give fit_scale's k', and a second gated_icp call starts from R (k' / k), T0 = mean(y) - R0 mean(p).
+    Returns gated_icp's dict (of the last call; best indexes its poses) plus registration = register_similarity's dict,
+    bases_used, scale = the returned pose's scale (sqrt |det| of its planar block) and scale_registration = the registered k
+    of the base whose start won the first call.  ValueError when
+    no base has a hypothesis."""
+    ctx = ctx or default_context()
+    src, tgt = _points(centers), _points(truths)
+    lo, hi = scale_range
+    reg = ctx.register_sim(src, tgt, bases, float(lo), float(hi), inlier_dist, mirror, max_landmarks)
+    used = np.flatnonzero(reg["score"] >= 0)
+    if len(used) == 0:
+        raise ValueError("no base has a target pair with a length ratio in scale_range")
+    M = reg["M_all"][used]
+    out = ctx.icp_gated(src, tgt, gates, np.ascontiguousarray(M[:, :3, :3]), np.ascontiguousarray(M[:, :3, 3]), max_iter,
+                        max_landmarks, min_pairs, inlier_dist)
+    scale_reg = float(reg["scale"][used[out["best"]]])
+    if refine:
+        Mb = out["M"]
+        mu = ctx.match_unique(src, tgt, Mb, inlier_dist)
+        got = np.flatnonzero(mu["truth_of"] >= 0)
+        if len(got) >= 2:
+            p, y = src[got], tgt[mu["truth_of"][got]]
+            k1 = fit_scale(p, y)
+            R0 = np.ascontiguousarray(Mb[:3, :3] * (k1 / _linear_scale(Mb[:3, :3])))
+            T0 = y.mean(axis=0) - R0 @ p.mean(axis=0)
+            out = ctx.icp_gated(src, tgt, gates, R0[None], np.ascontiguousarray(T0)[None], max_iter, max_landmarks,
+                                min_pairs, inlier_dist)
+    out.update(registration=reg, bases_used=used, scale=_linear_scale(out["M"][:3, :3]), scale_registration=scale_reg)
+    return out
+
+
 def _points(p):
     if isinstance(p, np.ndarray):
         return p
