@@ -531,7 +531,20 @@ int vcp_selftest_register_sim_pose(const double a[3], const double b[3], const d
  * xy [n*2] = (X,Y) for the 3-D view or (motor_x,motor_y) for the 2-D one; labels [n]; order [m] = the
  * list order the C# iterates (clusForMerge; NULL = 0..n-1, then m must equal n): "first in the list"
  * decides every tie.  centers [K*2], radius [K], valid [K] (0 = cluster skipped), hull_n [K] may be NULL.
- * Bit-identical to the C# arithmetic (binary64, no FMA contraction). */
+ * The C# arithmetic (binary64, no FMA contraction), bit for bit, wherever its circle encloses the cluster.  Two rules
+ * of this library's own stand behind it, for the two cases in which it does not; both are exact comparisons of the
+ * expression d(p) = (cx-p.x)*(cx-p.x) + (cy-p.y)*(cy-p.y), so host and device agree to the bit.  S is the hull, then
+ * the members rule 2 added, in that order (the search's loop order over S breaks its ties):
+ *   1. covering:  if no pair and no triple of S encloses S (points on a common circle up to rounding: every candidate
+ *      loses another point by an ulp, and the C# returns radius 0 around points[0]), the search over the pairs, then
+ *      the triples runs again and a candidate counts with max over S of d(p) from its centre instead of its own
+ *      radius^2; the smallest wins, the first on ties, and radius^2 is that maximum.
+ *   2. insertion: the gift wrap can close early on a cluster that is collinear up to rounding (the pseudo-angle to the
+ *      next point on the line falls an ulp below the sweep), and the hull then lacks true extreme points.  While a
+ *      member has d(p) strictly greater than every point of S (a NaN d(p) of a point of S: nothing is greater; of a
+ *      member: it is no candidate), the member with the largest d(p), the first in list order on ties, is appended to
+ *      S and the search runs again, rule 1 included.  More than 2048 points in S: VCP_ERR_TOO_LARGE.
+ * hull_n counts the wrap's hull: it can be incomplete for such clusters; the circle is not affected by that. */
 int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, const int64_t* order, int64_t m,
             int64_t n, int32_t K, double* centers, double* radius, uint8_t* valid, int32_t* hull_n);
 
@@ -548,7 +561,8 @@ int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, const int64_t
  * It is returned as indices into the caller's point array: hull_off [K+1] = prefix sums of the hull sizes
  * (hull_off[0] = 0; a cluster with valid != 1 contributes 0), hull_idx [hull_off[K]] (the caller provides room for m
  * entries).  Among points with equal coordinates the index is the one the C# picks: the first in list order that is
- * still in the list.
+ * still in the list.  hull_n, hull_off and hull_idx describe the wrap's hull: for a cluster collinear up to rounding
+ * it can lack extreme points (vcp_mcc, rule 2); the circle and the rectangle are not affected by that.
  *
  * Rectangle.  All arithmetic binary64, every operation rounded on its own, sqrt and / correctly rounded.  For hull
  * edge i, a = hull[i], b = hull[(i+1) % h]:
@@ -559,6 +573,8 @@ int vcp_mcc(vcp_ctx* ctx, const double* xy, const int32_t* labels, const int64_t
  * Minima and maxima are exact; one that is zero counts as +0; a NaN among the u, v makes the edge no candidate, and so
  * does an area that is not < +inf.  The rectangle of the cluster is that of the candidate with the smallest area_i,
  * the lowest i on ties (that a minimum-area enclosing rectangle has a side on a hull edge: Freeman & Shapira 1975).
+ * For a cluster on which vcp_mcc's rule 2 appended a member, "every hull point p" reads "every member p of the cluster
+ * other than (NaN, NaN)": the edges stay the wrap's, the extents span the members, so the rectangle contains them.
  *   rect_valid [K]   1 when valid == 1 and some edge is a candidate (for finite input that does not overflow:
  *                    valid == 1 && hull_n >= 2), else 0; then rect_len = 0, rect_edge = -1 and the four corners are
  *                    hull[0] (valid == 1) or (0, 0) (valid == 0: a cluster of <= 3 points has no hull)

@@ -243,18 +243,25 @@ def icp(model, data, tol=1e-4, max_iter=100, stop_rule=STOP_SSE_DELTA):
     return dict(R=R.reshape(3, 3), T=T, sse=sse.value, rmse=rmse.value, iters=it.value)
 
 
-def min_circle(pts):
+def min_circle_ex(pts, literal=False):
+    """dict(center, radius, hull, inserted): literal = the C# as it stands; otherwise with the insertion rule of
+    DESIGN.md section 12 (inserted = members it added; hull is the wrap's either way)."""
     pts = _f64(pts, 2)
     c = np.zeros(2)
     r = C.c_double(0)
-    hn = C.c_int32(0)
+    hn, ins = C.c_int32(0), C.c_int32(0)
     hull = np.zeros((len(pts), 2))
-    _chk(lib().orc_min_circle(_p(pts, C.c_double), C.c_int64(len(pts)), _p(c, C.c_double), C.byref(r),
-                              _p(hull, C.c_double), C.c_int64(len(pts)), C.byref(hn)))
-    return c, r.value, hull[: hn.value]
+    _chk(lib().orc_min_circle_ex(_p(pts, C.c_double), C.c_int64(len(pts)), int(literal), _p(c, C.c_double), C.byref(r),
+                                 _p(hull, C.c_double), C.c_int64(len(pts)), C.byref(hn), C.byref(ins)))
+    return dict(center=c, radius=r.value, hull=hull[: hn.value], inserted=ins.value)
 
 
-def get_circles(xy, labels, K, order=None):
+def min_circle(pts, literal=False):
+    g = min_circle_ex(pts, literal)
+    return g["center"], g["radius"], g["hull"]
+
+
+def get_circles(xy, labels, K, order=None, literal=False):
     xy = _f64(xy, 2)
     labels = np.ascontiguousarray(labels, np.int32)
     order = None if order is None else np.ascontiguousarray(order, np.int64)
@@ -263,10 +270,11 @@ def get_circles(xy, labels, K, order=None):
     radius = np.zeros(K)
     valid = np.zeros(K, np.uint8)
     hn = np.zeros(K, np.int32)
-    _chk(lib().orc_get_circles(_p(xy, C.c_double), _p(labels, C.c_int32), _p(order, C.c_int64), C.c_int64(m),
-                               C.c_int32(K), _p(centers, C.c_double), _p(radius, C.c_double), _p(valid, C.c_uint8),
-                               _p(hn, C.c_int32)))
-    return dict(centers=centers, radius=radius, valid=valid, hull_n=hn)
+    ins = np.zeros(K, np.int32)
+    _chk(lib().orc_get_circles_ex(_p(xy, C.c_double), _p(labels, C.c_int32), _p(order, C.c_int64), C.c_int64(m),
+                                  C.c_int32(K), int(literal), _p(centers, C.c_double), _p(radius, C.c_double),
+                                  _p(valid, C.c_uint8), _p(hn, C.c_int32), _p(ins, C.c_int32)))
+    return dict(centers=centers, radius=radius, valid=valid, hull_n=hn, inserted=ins)
 
 
 def import_convert(rows, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True, literal=False):

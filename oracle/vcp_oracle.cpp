@@ -1209,8 +1209,72 @@ void FindCircle(P2 a, P2 b, P2 c, P2* center, double* radius2) {
 }
 }  // namespace
 
-int orc_min_circle(const double* pts, int64_t cnt, double center[2], double* radius, double* hull_xy,
-                   int64_t hull_cap, int32_t* hull_n) {
+namespace {
+// :252-312 over the list S: pairs, then triples; the first smallest circle that encloses S.  r2 stays at
+// numeric_limits::max() and c at `fallback` when no candidate encloses.
+// cover != 0 (used only after the search above found nothing): a candidate counts with the
+// squared distance from its centre to the farthest point of S instead of its own radius^2, so every candidate whose
+// distances are numbers encloses S by construction; the smallest wins, the first in loop order on ties.
+struct Circle {
+  P2 c;
+  double r2;
+};
+bool Candidate(P2 tc, double tr2, const std::vector<P2>& hull, int i, int j, int k, int cover, double best, double* val) {
+  if (!cover) {
+    *val = tr2;
+    return tr2 < best && CircleEnclosesPoints(tc, tr2, hull, i, j, k);
+  }
+  double reach = -std::numeric_limits<double>::infinity();
+  for (const P2& s : hull) {
+    double dx = tc.x - s.x, dy = tc.y - s.y, d = dx * dx + dy * dy;
+    if (!(d == d)) return false;
+    if (d > reach) reach = d;
+  }
+  *val = reach;
+  return reach < best;
+}
+Circle SmallestCircle(const std::vector<P2>& hull, P2 fallback, int cover) {
+  P2 best_center = fallback;
+  double best_radius2 = std::numeric_limits<double>::max(), val;
+  const int h = (int)hull.size();
+  for (int i = 0; i < h - 1; i++)
+    for (int j = i + 1; j < h; j++) {
+      P2 tc{(hull[i].x + hull[j].x) / 2.0, (hull[i].y + hull[j].y) / 2.0};
+      double dx = tc.x - hull[i].x, dy = tc.y - hull[i].y;
+      double tr2 = dx * dx + dy * dy;
+      if (Candidate(tc, tr2, hull, i, j, -1, cover, best_radius2, &val)) {
+        best_center = tc;
+        best_radius2 = val;
+      }
+    }
+  for (int i = 0; i < h - 2; i++)
+    for (int j = i + 1; j < h - 1; j++)
+      for (int k = j + 1; k < h; k++) {
+        P2 tc;
+        double tr2;
+        FindCircle(hull[i], hull[j], hull[k], &tc, &tr2);
+        if (Candidate(tc, tr2, hull, i, j, k, cover, best_radius2, &val)) {
+          best_center = tc;
+          best_radius2 = val;
+        }
+      }
+  return Circle{best_center, best_radius2};
+}
+double Dist2(P2 c, double x, double y) {  // the form of CircleEnclosesPoints
+  double dx = c.x - x, dy = c.y - y;
+  return dx * dx + dy * dy;
+}
+}  // namespace
+
+// literal != 0: the C# as it stands.  Otherwise two rules of DESIGN.md section 12 follow the wrap.  Covering: when no
+// pair or triple of S (the wrap's hull, then the inserted members) encloses S -- points on a common circle up to
+// rounding -- the search runs again with cover = 1.  Insertion: while a member lies strictly farther from the centre
+// than every point of S, the farthest such member -- the first in the list on ties -- joins S and the search runs
+// again.  A NaN distance of a point of S never lets the rule fire; a NaN distance of a member never makes it a
+// candidate.
+int orc_min_circle_ex(const double* pts, int64_t cnt, int literal, double center[2], double* radius, double* hull_xy,
+                      int64_t hull_cap, int32_t* hull_n, int32_t* inserted) {
+  if (inserted) *inserted = 0;
   if (cnt <= 0) return ORC_ERR_EMPTY;  // points[0]
   // HullCull: keeps every point whose coordinates are not NaN (x <= 0 || x >= 0 || ...)
   std::vector<int64_t> rem;
@@ -1253,40 +1317,46 @@ int orc_min_circle(const double* pts, int64_t cnt, double center[2], double* rad
       hull_xy[2 * k] = hull[k].x;
       hull_xy[2 * k + 1] = hull[k].y;
     }
-  // :252-312
-  P2 best_center{pts[0], pts[1]};
-  double best_radius2 = std::numeric_limits<double>::max();
-  const int h = (int)hull.size();
-  for (int i = 0; i < h - 1; i++)
-    for (int j = i + 1; j < h; j++) {
-      P2 tc{(hull[i].x + hull[j].x) / 2.0, (hull[i].y + hull[j].y) / 2.0};
-      double dx = tc.x - hull[i].x, dy = tc.y - hull[i].y;
-      double tr2 = dx * dx + dy * dy;
-      if (tr2 < best_radius2 && CircleEnclosesPoints(tc, tr2, hull, i, j, -1)) {
-        best_center = tc;
-        best_radius2 = tr2;
+  Circle fit;
+  for (;;) {
+    fit = SmallestCircle(hull, P2{pts[0], pts[1]}, 0);
+    if (literal) break;
+    if (fit.r2 == std::numeric_limits<double>::max() && hull.size() > 2)  // rounding left no triple that encloses
+      fit = SmallestCircle(hull, P2{pts[0], pts[1]}, 1);
+    double reach = -std::numeric_limits<double>::infinity();  // the farthest point of S; +inf once one is NaN
+    for (const P2& s : hull) {
+      double d = Dist2(fit.c, s.x, s.y);
+      if (!(d == d))
+        reach = std::numeric_limits<double>::infinity();
+      else if (d > reach)
+        reach = d;
+    }
+    int64_t far = -1;
+    for (int64_t i = 0; i < cnt; i++) {
+      double d = Dist2(fit.c, pts[2 * i], pts[2 * i + 1]);
+      if (d > reach) {
+        reach = d;
+        far = i;
       }
     }
-  for (int i = 0; i < h - 2; i++)
-    for (int j = i + 1; j < h - 1; j++)
-      for (int k = j + 1; k < h; k++) {
-        P2 tc;
-        double tr2;
-        FindCircle(hull[i], hull[j], hull[k], &tc, &tr2);
-        if (tr2 < best_radius2 && CircleEnclosesPoints(tc, tr2, hull, i, j, k)) {
-          best_center = tc;
-          best_radius2 = tr2;
-        }
-      }
-  center[0] = best_center.x;
-  center[1] = best_center.y;
-  *radius = best_radius2 == std::numeric_limits<double>::max() ? 0.0 : std::sqrt(best_radius2);
+    if (far < 0) break;
+    hull.push_back(P2{pts[2 * far], pts[2 * far + 1]});
+    if (inserted) ++*inserted;
+  }
+  center[0] = fit.c.x;
+  center[1] = fit.c.y;
+  *radius = fit.r2 == std::numeric_limits<double>::max() ? 0.0 : std::sqrt(fit.r2);
   return ORC_OK;
 }
 
+int orc_min_circle(const double* pts, int64_t cnt, double center[2], double* radius, double* hull_xy,
+                   int64_t hull_cap, int32_t* hull_n) {
+  return orc_min_circle_ex(pts, cnt, 0, center, radius, hull_xy, hull_cap, hull_n, nullptr);
+}
+
 // Tools.getCircles (BC/Tools.cs:394-409): one circle per cluster with more than 3 points.
-int orc_get_circles(const double* xy, const int32_t* labels, const int64_t* order, int64_t m, int32_t K,
-                    double* centers, double* radius, uint8_t* valid, int32_t* hull_n) {
+int orc_get_circles_ex(const double* xy, const int32_t* labels, const int64_t* order, int64_t m, int32_t K, int literal,
+                       double* centers, double* radius, uint8_t* valid, int32_t* hull_n, int32_t* inserted) {
   if (m < 0 || K < 0) return ORC_ERR_ARG;
   std::vector<std::vector<double>> li(K);
   for (int64_t t = 0; t < m; t++) {
@@ -1303,15 +1373,22 @@ int orc_get_circles(const double* xy, const int32_t* labels, const int64_t* orde
     radius[k] = 0;
     centers[2 * k] = centers[2 * k + 1] = 0;
     if (hull_n) hull_n[k] = 0;
+    if (inserted) inserted[k] = 0;
     int64_t cnt = (int64_t)li[k].size() / 2;
     if (cnt <= 3) continue;  // :400
-    int32_t hn = 0;
-    int rc = orc_min_circle(li[k].data(), cnt, centers + 2 * k, radius + k, nullptr, 0, &hn);
+    int32_t hn = 0, ins = 0;
+    int rc = orc_min_circle_ex(li[k].data(), cnt, literal, centers + 2 * k, radius + k, nullptr, 0, &hn, &ins);
     if (rc) return rc;
     valid[k] = 1;
     if (hull_n) hull_n[k] = hn;
+    if (inserted) inserted[k] = ins;
   }
   return ORC_OK;
+}
+
+int orc_get_circles(const double* xy, const int32_t* labels, const int64_t* order, int64_t m, int32_t K,
+                    double* centers, double* radius, uint8_t* valid, int32_t* hull_n) {
+  return orc_get_circles_ex(xy, labels, order, m, K, 0, centers, radius, valid, hull_n, nullptr);
 }
 
 // Import conversion + duplicate removal: MainForm.AddFolder, FrmMain.cs:1011-1090, for the

@@ -163,12 +163,20 @@ int orc_icp(const double* model, int64_t nm, const double* data, int64_t nd, dou
             int32_t* iters);
 
 /* Geometry.FindMinimalBoundingCircle (BC/Geometry.cs:247-319) on `cnt` points (x,y) in list order: gift-wrap
- * hull, then the smallest enclosing circle through 2 or 3 hull points, first found on ties.  hull_xy may be NULL. */
+ * hull, then the smallest enclosing circle through 2 or 3 hull points, first found on ties; then the insertion rule
+ * (orc_min_circle_ex below).  hull_xy may be NULL. */
 int orc_min_circle(const double* pts, int64_t cnt, double center[2], double* radius, double* hull_xy,
                    int64_t hull_cap, int32_t* hull_n);
 /* Tools.getCircles (BC/Tools.cs:394-409): a circle for every cluster 1..K with more than 3 points (valid[k]). */
 int orc_get_circles(const double* xy, const int32_t* labels, const int64_t* order, int64_t m, int32_t K,
                     double* centers, double* radius, uint8_t* valid, int32_t* hull_n);
+/* The two above with a switch: literal != 0 is the C# as it stands; literal == 0 (what the two above compute) adds
+ * the insertion rule of DESIGN.md section 12 behind the wrap, for hulls that the wrap closed early.  inserted = how
+ * many members the rule added (per cluster; may be NULL).  hull_xy / hull_n describe the wrap's hull either way. */
+int orc_min_circle_ex(const double* pts, int64_t cnt, int literal, double center[2], double* radius, double* hull_xy,
+                      int64_t hull_cap, int32_t* hull_n, int32_t* inserted);
+int orc_get_circles_ex(const double* xy, const int32_t* labels, const int64_t* order, int64_t m, int32_t K, int literal,
+                       double* centers, double* radius, uint8_t* valid, int32_t* hull_n, int32_t* inserted);
 
 /* MainForm.AddFolder's conversion + duplicate removal for scan points (FrmMain.cs:1011-1090). */
 int orc_import_convert(const double* rows, int64_t n, double x_angle, double y_angle, int xdir, int ydir, int dedupe,

@@ -2,7 +2,8 @@
 through run() the bounded, fixed-seed form that tests/test_fuzz_gpu.py runs under `pytest -m gpu` (one pass, per-case
 GPU time bound).  libvcp (through the C-ABI) against the order-free CPU oracle on clouds no
 fixed test has -- sizes from one point to a few million, uniform / clustered / lattice / duplicate-heavy / collinear
-shapes, far outliers, non-finite coordinates, every metric, isClassed inputs, cf presets -- plus the block pipeline.
+shapes, far outliers, non-finite coordinates, every metric, isClassed inputs, cf presets -- plus the block pipeline,
+and the circle, hull and rectangle of the clusters every DBSCAN case finds.
 usage: python tests/fuzz_parity.py [seconds] [seed]"""
 import os
 import sys
@@ -15,10 +16,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import centroid_ref as R  # noqa: E402  (the replay of the centroid kernels' summation tree)
 import icp_sums_ref as IS  # noqa: E402  (the replay of the ICP moment sums' reduction tree)
+import shapes_ref as S  # noqa: E402  (the rectangle of include/vcp.h in numpy)
 from oracle import binding as O  # noqa: E402  (test tooling: the oracle is the checker)
 from vtkcloudpoint_amd import _native as N  # noqa: E402
 
 rng = None   # set by run()
+rng_shapes = None  # a stream of its own, so that the other cases of a seed stay what they were
 ctx = None
 done = {"dbscan": 0, "blocks": 0}
 QUIET = [False]
@@ -214,12 +217,72 @@ def db_case():
     done["db"] = done.get("db", 0) + 1
 
 
+SHAPES_MAX_N = 300000   # the oracle's wrap is O(members x hull) per cluster and its search cubic in the hull
+SHAPES_SAMPLE = 100     # clusters per case whose hull and rectangle are compared (the circle: every cluster)
+
+
+def shapes_case(c, labels, gpu_bound):
+    """vcp_mcc and vcp_cluster_shapes on the X,Y of a DBSCAN case and the labels it found: centre, radius, valid and
+    hull_n of every cluster against the oracle's circle, the hull and the rectangle of a sample of clusters against the
+    oracle's hull and the numpy restatement; an error of the oracle (a cluster without a finite point) must be the
+    library's error too"""
+    n = len(labels)
+    K = int(labels.max()) if n else 0
+    if K == 0 or n > SHAPES_MAX_N:
+        return
+    xy = np.ascontiguousarray(c[:, :2])
+    lab = np.ascontiguousarray(labels, np.int32)
+    try:
+        o = O.get_circles(xy, lab, K)
+    except O.OracleError as e:
+        for call in (ctx.mcc, ctx.cluster_shapes):
+            try:
+                call(xy, lab, K)
+                fail("MISSING ERROR shapes n=%d K=%d oracle code %d" % (n, K, e.code))
+            except N.VcpError as ge:
+                if ge.code not in (e.code, -5):
+                    fail("WRONG ERROR shapes n=%d K=%d oracle %d library %d" % (n, K, e.code, ge.code))
+        return
+    t1 = time.time()
+    try:
+        g = ctx.cluster_shapes(xy, lab, K)
+        m = ctx.mcc(xy, lab, K)
+    except N.VcpError as e:
+        if e.code == -5:  # a hull beyond 2048 points: the library's documented limit
+            return
+        raise
+    t2 = time.time()
+    if gpu_bound is not None and done.get("shapes", 0) > 0 and t2 - t1 > 2 * gpu_bound(n):  # (two calls)
+        fail("SLOW shapes n=%d K=%d: %.3f s on the GPU" % (n, K, t2 - t1))
+    same = lambda a, b: np.array_equal(a, b, equal_nan=True)
+    ok = all(same(g[k], o[k]) and same(m[k], o[k]) for k in ("centers", "radius", "valid", "hull_n"))
+    ok = ok and g["hull_off"][0] == 0 and same(np.diff(g["hull_off"]), np.where(o["valid"] == 1, o["hull_n"], 0))
+    if ok:
+        mem = S.members(lab, K)
+        live = np.flatnonzero(o["valid"] == 1)
+        for k in (live if len(live) <= SHAPES_SAMPLE else rng_shapes.choice(live, SHAPES_SAMPLE, replace=False)):
+            pts = xy[mem[k]]
+            f = O.min_circle_ex(pts)
+            r = S.rectangle(f["hull"], pts if f["inserted"] else None)
+            ok = ok and same(xy[g["hull_idx"][g["hull_off"][k]:g["hull_off"][k + 1]]], f["hull"]) \
+                and g["rect_valid"][k] == r["valid"] and g["rect_edge"][k] == r["edge"] \
+                and same(g["rect_len"][k], r["len"]) and same(g["rect_xy"][k], r["xy"])
+            if f["inserted"]:
+                done["shapes_inserted"] = done.get("shapes_inserted", 0) + 1
+    if not ok:
+        dump = os.path.join(tempfile.gettempdir(), "fuzz_fail_shapes.npz")
+        np.savez(dump, xy=xy, labels=lab)
+        fail("MISMATCH shapes n=%d K=%d kind=%d (inputs in %s)" % (n, K, KIND[0], dump))
+    done["shapes"] = done.get("shapes", 0) + 1
+
+
 def run(budget=300.0, seed=12345, max_log_n=6.3, gpu_bound=None, device=0, quiet=False, nn_log=4.6, with_db=True):
     """One sweep of `budget` seconds from `seed`.  max_log_n: log10 of the largest DBSCAN cloud; gpu_bound: optional
     function n -> seconds, the GPU time a DBSCAN call on n points may take (the sweep found two cliffs that way: eps = 0
     with far outliers, a cloud inside one eps-ball).  Raises Mismatch on the first disagreement."""
-    global rng, ctx
+    global rng, rng_shapes, ctx
     rng = np.random.default_rng(seed)
+    rng_shapes = np.random.default_rng([seed, 1])
     own = ctx is None
     if own:
         ctx = N.Context(device)
@@ -289,6 +352,7 @@ def run(budget=300.0, seed=12345, max_log_n=6.3, gpu_bound=None, device=0, quiet
                      cls=np.zeros(0) if cls is None else cls, lab0=np.zeros(0) if lab0 is None else lab0)
             fail("MISMATCH dbscan n=%d dim=%d metric=%d eps=%r mp=%d cf=%d cls=%s" % (n, dim, metric, eps, mp, cf, cls is not None))
         done["dbscan"] += 1
+        shapes_case(c, g["labels"], gpu_bound)
         if rng.random() < 0.3 and n >= 2 and np.isfinite(c).all():
             m2 = np.ascontiguousarray(c[:, :2])
             pic = int(rng.choice([1, 3, 20, 200, 5000]))
@@ -317,9 +381,11 @@ def run(budget=300.0, seed=12345, max_log_n=6.3, gpu_bound=None, device=0, quiet
             say("%.0f s: %d dbscan, %d block pipelines agree" % (time.time() - t0, done["dbscan"], done["blocks"]), flush=True)
     msg = ("OK: %d dbscan calls, %d block pipelines, %d nearest-neighbour / matching cases (%d sets of ICP moment sums "
            "equal to the replay of their tree), %d calls of the dead class DB "
-           "bit-exact and %d centroid / merge / keyed-pipeline cases (%d with a multi-chunk cluster) against the oracle "
+           "bit-exact, %d circle / hull / rectangle cases (the insertion rule fired on %d compared clusters) "
+           "and %d centroid / merge / keyed-pipeline cases (%d with a multi-chunk cluster) against the oracle "
            "(seed %d)" % (done["dbscan"], done["blocks"], done.get("nn", 0), done.get("sums", 0), done.get("db", 0),
-                          done.get("tools", 0), done.get("tools_multichunk", 0), seed))
+                          done.get("shapes", 0), done.get("shapes_inserted", 0), done.get("tools", 0),
+                          done.get("tools_multichunk", 0), seed))
     print(msg, flush=True)
     if own:
         ctx.close()

@@ -6,10 +6,16 @@ import numpy as np
 INF = np.inf
 
 
-def edge_boxes(hull):
-    """For every hull edge i: None when the edge is no candidate, else dict(area, U, V, L2, a, d, u0, u1, v0, v1)."""
+def edge_boxes(hull, members=None):
+    """For every hull edge i: None when the edge is no candidate, else dict(area, U, V, L2, a, d, u0, u1, v0, v1).
+    members: the extents are taken over these points instead of over the hull (a cluster on which the insertion rule
+    of the circle fired: the hull is incomplete); members with both coordinates NaN are left out, as HullCull does."""
     hull = np.ascontiguousarray(hull, np.float64).reshape(-1, 2)
     h = len(hull)
+    src = hull
+    if members is not None:
+        src = np.ascontiguousarray(members, np.float64).reshape(-1, 2)
+        src = src[~(np.isnan(src[:, 0]) & np.isnan(src[:, 1]))]
     out = []
     with np.errstate(all="ignore"):
         for i in range(h):
@@ -19,7 +25,7 @@ def edge_boxes(hull):
             if not (0 < L2 < INF):
                 out.append(None)
                 continue
-            rx, ry = hull[:, 0] - a[0], hull[:, 1] - a[1]
+            rx, ry = src[:, 0] - a[0], src[:, 1] - a[1]
             u = rx * dx + ry * dy
             v = ry * dx - rx * dy
             # exact extremes (NaN propagates); a zero extreme counts as +0
@@ -33,11 +39,11 @@ def edge_boxes(hull):
     return out
 
 
-def rectangle(hull):
+def rectangle(hull, members=None):
     """dict(valid, edge, len [2], xy [4, 2], areas) of the minimum-area bounding rectangle of a hull (the circle of
-    the cluster being valid): the smallest area_i, the lowest i on ties."""
+    the cluster being valid): the smallest area_i, the lowest i on ties.  members: see edge_boxes."""
     hull = np.ascontiguousarray(hull, np.float64).reshape(-1, 2)
-    boxes = edge_boxes(hull)
+    boxes = edge_boxes(hull, members)
     best = -1
     for i, e in enumerate(boxes):
         if e is not None and (best < 0 or e["area"] < boxes[best]["area"]):
@@ -85,15 +91,26 @@ def members(labels, K, order=None):
 
 
 def inside_rectangle(pts, xy, tol):
-    """Largest violation (<= 0 when inside) of the points against the rectangle with corners xy [4, 2], measured along
-    its two sides."""
+    """Largest violation (<= 0 when inside) of the points against the rectangle with corners xy [4, 2]: the distance
+    beyond the line of each of its four edges, measured along that edge's own normal.  (Measured along the neighbouring
+    side instead, a rectangle whose width is a few ulps of its corners has no usable direction: the rounding of the
+    corners turns that side anywhere.)  An edge of length zero bounds along the direction of the edge before it; without
+    an area the distance from the line counts on both sides."""
     pts = np.asarray(pts, np.float64).reshape(-1, 2)
-    c0, eu, ev = xy[0], xy[1] - xy[0], xy[3] - xy[0]
-    lu, lv = np.hypot(*eu), np.hypot(*ev)
+    q = np.asarray(xy, np.float64).reshape(4, 2)
+    e = np.roll(q, -1, axis=0) - q
+    l = np.hypot(e[:, 0], e[:, 1])
+    a, b, c = q[1] - q[0], q[2] - q[0], q[3] - q[0]  # twice the area, from differences of neighbouring corners
+    sgn = np.sign((a[0] * b[1] - a[1] * b[0]) + (b[0] * c[1] - b[1] * c[0]))
     worst = -INF
-    for e, l in ((eu, lu), (ev, lv)):
-        if l == 0:
-            continue
-        s = (pts - c0) @ (e / l)
-        worst = max(worst, float((-s).max()), float((s - l).max()))
+    for i in range(4):
+        r = pts - q[i]
+        if l[i] > 0:
+            d = (e[i, 0] * r[:, 1] - e[i, 1] * r[:, 0]) / l[i]  # > 0: to the left of the edge
+            d = -sgn * d if sgn else np.abs(d)
+        elif l[i - 1] > 0:
+            d = r @ e[i - 1] / l[i - 1]
+        else:
+            d = np.hypot(r[:, 0], r[:, 1])
+        worst = max(worst, float(d.max()))
     return worst - tol

@@ -1,6 +1,7 @@
 """The randomised GPU-vs-oracle parity sweep (tests/fuzz_parity.py) as ONE bounded, fixed-seed pass: every entry point
 (DBSCAN with all metrics / isClassed inputs / cf presets, the block pipeline and its keyed twin, nearest neighbour of
-ICP and of the matching, centroids, weighted centroids, centroid merge), bit-exact against the CPU oracle, with a bound
+ICP and of the matching, centroids, weighted centroids, centroid merge, the circle / hull / rectangle of the clusters
+that the DBSCAN cases find), bit-exact against the CPU oracle, with a bound
 on the GPU time of every DBSCAN call (the open-ended sweep found two performance cliffs in round 2: eps = 0 with far
 outliers, and a cloud that sits inside one eps-ball)."""
 import pytest
@@ -23,4 +24,5 @@ def test_bounded_fixed_seed_sweep(vcp_ctx, oracle):
         F.ctx = None
     assert done["dbscan"] >= 20 and done["blocks"] >= 3 and done.get("nn", 0) >= 3 and done.get("tools", 0) >= 1, done
     assert done.get("db", 0) >= 1, done
+    assert done.get("shapes", 0) >= 3, done  # vcp_mcc and vcp_cluster_shapes on the DBSCAN cases' labels
     assert done.get("tools_multichunk", 0) >= 1, done  # the centroid tree's chunk loop was compared with its replay

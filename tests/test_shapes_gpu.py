@@ -64,7 +64,8 @@ def _lattice_cloud():
 
 def _random_cloud():
     """Gaussian clusters of random anisotropy, uniformly filled boxes at random angles, clusters on the 2^-10 lattice
-    and on a 6 x 6 integer lattice (duplicates, collinear runs)."""
+    and on a 6 x 6 integer lattice (duplicates, collinear runs); behind them 16 lines that are collinear up to rounding
+    (centre + s * d in binary64), on which the reference's wrap can close early."""
     rng = np.random.default_rng(29)
     pts, lab, kinds = [], [], []
     for k in range(1, 161):
@@ -82,16 +83,27 @@ def _random_cloud():
         else:
             g = rng.integers(0, 6, (cnt, 2)).astype(float) + np.round(c)
         pts.append(g), lab.append(np.full(cnt, k)), kinds.append(kind)
+    near = np.random.default_rng(31)  # a stream of its own: the 160 clusters above stay what they were
+    for k in range(161, 177):
+        cnt = int(near.integers(5, 41))
+        th = near.uniform(0, 2 * math.pi)
+        d = np.array([math.cos(th), math.sin(th)]) * near.uniform(0.5, 3.0)
+        g = near.uniform(-500, 500, 2) * (k % 2) + near.uniform(-1, 1, (cnt, 1)) * d
+        pts.append(g), lab.append(np.full(cnt, k)), kinds.append("nearline")
     xy, lab = np.concatenate(pts), np.concatenate(lab).astype(np.int32)
     p = rng.permutation(len(lab))
-    return dict(xy=np.ascontiguousarray(xy[p]), labels=lab[p], order=None, K=160, kinds=kinds)
+    return dict(xy=np.ascontiguousarray(xy[p]), labels=lab[p], order=None, K=176, kinds=kinds)
 
 
 def _oracle_hulls(oracle, c):
-    """Per cluster: (member indices in list order, the oracle's hull or None for a cluster of <= 3 points)."""
+    """Per cluster: (member indices in list order, the oracle's hull or None for a cluster of <= 3 points).
+    c["inserted"][k]: how many members the circle's insertion rule added (the rectangle then spans the members)."""
     if "hulls" not in c:
-        c["hulls"] = [(idx, oracle.min_circle(c["xy"][idx])[2] if len(idx) > 3 else None)
-                      for idx in S.members(c["labels"], c["K"], c["order"])]
+        fits = [oracle.min_circle_ex(c["xy"][idx]) if len(idx) > 3 else None
+                for idx in S.members(c["labels"], c["K"], c["order"])]
+        c["hulls"] = [(idx, None if f is None else f["hull"])
+                      for idx, f in zip(S.members(c["labels"], c["K"], c["order"]), fits)]
+        c["inserted"] = [0 if f is None else f["inserted"] for f in fits]
     return c["hulls"]
 
 
@@ -102,7 +114,7 @@ def _shapes(vcp_ctx, c):
 
 
 def test_circle_unchanged(vcp_ctx, oracle, clouds):
-    for c in clouds:
+    for c in list(clouds) + [_lattice_cloud(), _random_cloud()]:
         got = _shapes(vcp_ctx, c)
         mcc = vcp_ctx.mcc(c["xy"], c["labels"], c["K"], c["order"])
         ref = oracle.get_circles(c["xy"], c["labels"], c["K"], c["order"])
@@ -143,7 +155,7 @@ def _check_rectangles(c, got, hulls):
             assert got["rect_valid"][k] == 0 and got["rect_edge"][k] == -1
             assert not got["rect_len"][k].any() and not got["rect_xy"][k].any()
             continue
-        r = S.rectangle(hull)
+        r = S.rectangle(hull, c["xy"][idx] if c["inserted"][k] else None)
         assert got["rect_valid"][k] == r["valid"] and got["rect_edge"][k] == r["edge"], k
         assert _same(got["rect_len"][k], r["len"]) and _same(got["rect_xy"][k], r["xy"]), k
         assert r["valid"] == (1 if len(hull) >= 2 else 0)

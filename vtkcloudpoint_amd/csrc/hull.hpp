@@ -14,6 +14,13 @@
 // an argmin over (value, list position), so the parallel reductions reproduce it exactly; the arithmetic is
 // binary64 without FMA contraction, sqrt and division correctly rounded: results are bit-identical to the oracle.
 //
+// Behind the reference's wrap and search stand two rules of this library's own, both made of
+// exact comparisons of the same expressions on host and device.  Covering: when rounding leaves no pair or triple
+// that encloses the hull (points on a common circle), the search runs again and a candidate counts with its distance
+// to the farthest hull point.  Insertion: when a member lies strictly farther from the centre than every hull point,
+// the wrap closed early (a cluster collinear up to rounding); the farthest such member joins the list and the search
+// runs again.  Both are rare; the common path pays one strided pass over the members and two block reductions.
+//
 // The rectangle is defined in include/vcp.h (no C# body stands behind it: Polygon.cs has no caller): hull edges over
 // the lanes, each lane walking the hull in LDS (every lane reads the same address: a broadcast), then one
 // (area, edge) lexicographic minimum.
@@ -111,25 +118,55 @@ __device__ __forceinline__ void find_circle(double2 a, double2 b, double2 c, dou
   *r2 = dx * dx + dy * dy;
 }
 
+// One candidate of the search: it replaces `mine` when it is smaller (earlier in the C#'s loop order on ties) and
+// encloses the list.  cover: its value is the squared distance to the farthest point of the list, not its radius^2.
+__device__ __forceinline__ void candidate(Best& mine, double cx, double cy, double tr2, unsigned long long seq,
+                                          const double2* hull, int h, int s1, int s2, int s3, bool cover) {
+  double val = tr2;
+  if (cover) {
+    val = -INFINITY;
+    for (int i = 0; i < h; i++) {
+      const double dx = cx - hull[i].x, dy = cy - hull[i].y, d = dx * dx + dy * dy;
+      if (!(d == d)) return;
+      val = d > val ? d : val;
+    }
+  }
+  if (!((val < mine.r2 || (val == mine.r2 && seq < mine.seq)) && val < DMAX)) return;
+  if (!cover && !encloses(cx, cy, tr2, hull, h, s1, s2, s3)) return;
+  mine.r2 = val;
+  mine.seq = seq;
+}
+
 // The bounding rectangle with one side on hull edge i (include/vcp.h, "cluster shapes"): extents of the hull in the
 // edge's frame, scaled by the squared edge length.  false = the edge is no candidate.
+// mem != null (a cluster on which the insertion rule fired: the hull is incomplete): the extents are taken over the
+// cnt members that HullCull keeps instead of over the hull.
 struct EdgeBox {
   double ax, ay, dx, dy, L2, u0, u1, v0, v1, area;
 };
-__device__ __forceinline__ bool edge_box(const double2* hull, int h, int i, EdgeBox* e) {
+__device__ __forceinline__ bool edge_box(const double2* hull, int h, int i, const double2* __restrict__ mem, uint32_t cnt,
+                                         EdgeBox* e) {
   const double2 a = hull[i], b = hull[i + 1 == h ? 0 : i + 1];
   const double dx = b.x - a.x, dy = b.y - a.y, L2 = dx * dx + dy * dy;
   if (!(L2 > 0 && L2 < INFINITY)) return false;
   double u0 = INFINITY, u1 = -INFINITY, v0 = INFINITY, v1 = -INFINITY;
   bool nan = false;
-  for (int j = 0; j < h; j++) {
-    const double rx = hull[j].x - a.x, ry = hull[j].y - a.y;
+  auto take = [&](const double2 p) {
+    const double rx = p.x - a.x, ry = p.y - a.y;
     const double u = rx * dx + ry * dy, v = ry * dx - rx * dy;
     nan |= !(u == u) || !(v == v);
     u0 = u < u0 ? u : u0;
     u1 = u > u1 ? u : u1;
     v0 = v < v0 ? v : v0;
     v1 = v > v1 ? v : v1;
+  };
+  if (!mem) {
+    for (int j = 0; j < h; j++) take(hull[j]);
+  } else {
+    for (uint32_t t = 0; t < cnt; t++) {
+      const double2 p = mem[t];
+      if (!(p.x != p.x && p.y != p.y)) take(p);
+    }
   }
   if (nan) return false;
   // a zero extreme is +0 whichever of -0 / +0 the hull point produced
@@ -280,69 +317,111 @@ __device__ __forceinline__ void cluster_fit(const double* __restrict__ cxy, cons
     }
     return;
   }
-  // Geometry.cs:260-312: pairs, then triples; the winner is the smallest (radius^2, loop position)
-  Best mine{DMAX, ~0ull};
-  const unsigned long long H = (unsigned long long)h;
-  for (int i = 0; i < h - 1; i++)
-    for (int j = i + 1 + tid; j < h; j += MT) {
-      const double tcx = (hull[i].x + hull[j].x) / 2.0, tcy = (hull[i].y + hull[j].y) / 2.0;
-      const double dx = tcx - hull[i].x, dy = tcy - hull[i].y;
-      const double tr2 = dx * dx + dy * dy;
-      const unsigned long long seq = (unsigned long long)i * H + (unsigned long long)j;
-      if ((tr2 < mine.r2 || (tr2 == mine.r2 && seq < mine.seq)) && tr2 < DMAX && encloses(tcx, tcy, tr2, hull, h, i, j, -1)) {
-        mine.r2 = tr2;
-        mine.seq = seq;
-      }
-    }
-  for (int i = 0; i < h - 2; i++)
-    for (int j = i + 1; j < h - 1; j++)
-      for (int kq = j + 1 + tid; kq < h; kq += MT) {
-        double tcx, tcy, tr2;
-        find_circle(hull[i], hull[j], hull[kq], &tcx, &tcy, &tr2);
-        const unsigned long long seq = H * H + ((unsigned long long)i * H + (unsigned long long)j) * H + (unsigned long long)kq;
-        if ((tr2 < mine.r2 || (tr2 == mine.r2 && seq < mine.seq)) && tr2 < DMAX && encloses(tcx, tcy, tr2, hull, h, i, j, kq)) {
-          mine.r2 = tr2;
-          mine.seq = seq;
-        }
-      }
-  // block reduction of (r2, seq)
-  Key bk{mine.r2, 0.0, 0};
-  // seq is 64-bit: reduce in two steps -- first the smallest r2, then the smallest seq among its holders
-  Key r2min = block_min(Key{mine.r2, 0.0, 0u}, smk);
+  // S = hull[0 .. hs): the wrap's hull, then the members that the insertion rule adds
+  int hs = h;
+  bool cover = false;  // the plain search found nothing: candidates count with their reach over S
+  bool fired = false;  // the insertion rule added a member
   __shared__ unsigned long long s_seq;
-  if (tid == 0) s_seq = ~0ull;
-  __syncthreads();
-  if (mine.r2 == r2min.a && mine.seq != ~0ull) atomicMin(&s_seq, mine.seq);
-  __syncthreads();
-  (void)bk;
-  if (tid == 0) {
-    double cx = pts[0].x, cy = pts[0].y, rad = 0;  // best_center = points[0] of the ORIGINAL list (:254-257)
-    const unsigned long long seq = s_seq;
-    if (seq != ~0ull && r2min.a < DMAX) {
-      if (seq < H * H) {
-        const int i = (int)(seq / H), j = (int)(seq % H);
-        cx = (hull[i].x + hull[j].x) / 2.0;
-        cy = (hull[i].y + hull[j].y) / 2.0;
-      } else {
-        const unsigned long long q = seq - H * H;
-        const int kq = (int)(q % H), j = (int)((q / H) % H), i = (int)(q / (H * H));
-        double r2;
-        find_circle(hull[i], hull[j], hull[kq], &cx, &cy, &r2);
+  __shared__ double s_fit[3];  // centre and radius of the current circle
+  for (;;) {
+    // Geometry.cs:260-312: pairs, then triples; the winner is the smallest (radius^2, loop position)
+    Best mine{DMAX, ~0ull};
+    const unsigned long long H = (unsigned long long)hs;
+    for (int i = 0; i < hs - 1; i++)
+      for (int j = i + 1 + tid; j < hs; j += MT) {
+        const double tcx = (hull[i].x + hull[j].x) / 2.0, tcy = (hull[i].y + hull[j].y) / 2.0;
+        const double dx = tcx - hull[i].x, dy = tcy - hull[i].y;
+        candidate(mine, tcx, tcy, dx * dx + dy * dy, (unsigned long long)i * H + (unsigned long long)j, hull, hs, i, j, -1,
+                  cover);
       }
-      rad = sqrt(r2min.a);
+    for (int i = 0; i < hs - 2; i++)
+      for (int j = i + 1; j < hs - 1; j++)
+        for (int kq = j + 1 + tid; kq < hs; kq += MT) {
+          double tcx, tcy, tr2;
+          find_circle(hull[i], hull[j], hull[kq], &tcx, &tcy, &tr2);
+          candidate(mine, tcx, tcy, tr2, H * H + ((unsigned long long)i * H + (unsigned long long)j) * H + (unsigned long long)kq,
+                    hull, hs, i, j, kq, cover);
+        }
+    // seq is 64-bit: reduce in two steps -- first the smallest r2, then the smallest seq among its holders
+    const Key r2min = block_min(Key{mine.r2, 0.0, 0u}, smk);
+    if (tid == 0) s_seq = ~0ull;
+    __syncthreads();
+    if (mine.r2 == r2min.a && mine.seq != ~0ull) atomicMin(&s_seq, mine.seq);
+    __syncthreads();
+    const unsigned long long seq = s_seq;
+    const bool found = seq != ~0ull && r2min.a < DMAX;
+    if (!found && !cover && hs > 2) {  // rounding left no triple that encloses: points on a common circle
+      cover = true;
+      continue;
     }
-    centers[2 * (k - 1)] = cx;
-    centers[2 * (k - 1) + 1] = cy;
-    radius[k - 1] = rad;
+    if (tid == 0) {
+      double cx = pts[0].x, cy = pts[0].y, rad = 0;  // best_center = points[0] of the ORIGINAL list (:254-257)
+      if (found) {
+        if (seq < H * H) {
+          const int i = (int)(seq / H), j = (int)(seq % H);
+          cx = (hull[i].x + hull[j].x) / 2.0;
+          cy = (hull[i].y + hull[j].y) / 2.0;
+        } else {
+          const unsigned long long q = seq - H * H;
+          const int kq = (int)(q % H), j = (int)((q / H) % H), i = (int)(q / (H * H));
+          double r2;
+          find_circle(hull[i], hull[j], hull[kq], &cx, &cy, &r2);
+        }
+        rad = sqrt(r2min.a);
+      }
+      s_fit[0] = cx, s_fit[1] = cy, s_fit[2] = rad;
+    }
+    __syncthreads();
+    // the insertion rule: a member strictly farther from the centre than every point of S joins S
+    const double cx = s_fit[0], cy = s_fit[1];
+    double reach = -INFINITY;  // the farthest point of S; +inf once a distance is NaN, so that nothing is farther
+    for (int i = tid; i < hs; i += MT) {
+      const double dx = cx - hull[i].x, dy = cy - hull[i].y, d = dx * dx + dy * dy;
+      reach = !(d == d) ? INFINITY : (d > reach ? d : reach);
+    }
+    Key far{INFINITY, 0.0, 0xFFFFFFFFu};  // (-distance^2, position): the farthest member, the first in the list on ties
+    for (uint32_t t = tid; t < cnt; t += MT) {
+      const double dx = cx - pts[t].x, dy = cy - pts[t].y, d = dx * dx + dy * dy;
+      if (d == d) {
+        Key c{-d, 0.0, t};
+        if (key_less(c, far)) far = c;
+      }
+    }
+    const Key rs = block_min(Key{-reach, 0.0, 0u}, smk);
+    far = block_min(far, smk);
+    if (!(far.p != 0xFFFFFFFFu && -far.a > -rs.a)) break;
+    if (hs >= HMAX) {
+      overflow = true;
+      break;
+    }
+    if (tid == 0) hull[hs] = pts[far.p];
+    hs++;
+    fired = true;
+    cover = false;
+    __syncthreads();
+  }
+  if (overflow) {
+    if (tid == 0) {
+      valid[k - 1] = 2;
+      if (hull_n) hull_n[k - 1] = h;
+    }
+    return;
+  }
+  if (tid == 0) {
+    centers[2 * (k - 1)] = s_fit[0];
+    centers[2 * (k - 1) + 1] = s_fit[1];
+    radius[k - 1] = s_fit[2];
     valid[k - 1] = 1;
     if (hull_n) hull_n[k - 1] = h;
   }
   if constexpr (SHAPES) {
     // the smallest (area, edge): one edge per lane and round, the hull walked out of LDS
+    // (the edges are the wrap's; where the insertion rule fired, their extents are taken over the members)
+    const double2* mem = fired ? pts : nullptr;
     Key rk{INFINITY, 0.0, 0xFFFFFFFFu};
     EdgeBox e;
     for (int i = tid; i < h; i += MT)
-      if (edge_box(hull, h, i, &e)) {
+      if (edge_box(hull, h, i, mem, cnt, &e)) {
         Key c{e.area, 0.0, (uint32_t)i};
         if (key_less(c, rk)) rk = c;
       }
@@ -351,7 +430,7 @@ __device__ __forceinline__ void cluster_fit(const double* __restrict__ cxy, cons
       if (rk.p == 0xFFFFFFFFu) {
         no_rectangle(so, k, hull[0].x, hull[0].y);
       } else {
-        edge_box(hull, h, (int)rk.p, &e);
+        edge_box(hull, h, (int)rk.p, mem, cnt, &e);
         if (so.rect_valid) so.rect_valid[k - 1] = 1;
         if (so.rect_edge) so.rect_edge[k - 1] = (int32_t)rk.p;
         if (so.rect_len) {
