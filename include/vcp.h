@@ -762,6 +762,50 @@ int vcp_eps_tree_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, i
                      int kdist_given, double* d_kdist, double* d_reach, int64_t* n_merge, double* d_merge_w,
                      int32_t* d_merge_a, int32_t* d_merge_b, int32_t* rounds);
 
+/* -- generalised DBSCAN: point weights and a range gate -----------------------------------------------
+ * vcp_dbscan decides what DBImproved decides: every row counts once, and two rows are neighbours whenever their
+ * coordinates are within eps.  This call generalises both (sample_weight of scikit-learn's DBSCAN, MinWeight of GDBSCAN,
+ * Sander et al. 1998; a neighbourhood predicate with a second test) and is otherwise the same algorithm.  It has no
+ * counterpart in the reference, whose answers are to drop duplicates (FrmMain.cs:1063-1068) and to cut one global band
+ * of Distance (Tools.FilterByDistance_ScanPoint, Tools.cs:416-431).
+ *   d(i,j)     vcp_kdist's binary64 expression for VCP_L1_2D, VCP_L2_2D, VCP_L2_3D (sums left to right, no FMA
+ *              contraction, correctly rounded sqrt); VCP_SIGNED_SUM_2D = VCP_ERR_ARG
+ *   N(i)       { j : d(i,j) <= eps and (aux == NULL or fabs(aux[i] - aux[j]) <= gate) }, both tests in binary64, j = i
+ *              included.  A row with a non-finite coordinate has an empty N and is in nobody's N; so has a row with a
+ *              non-finite aux[i] when aux is given.  eps NaN or < 0 makes every N empty (by the expression; not an error,
+ *              as in vcp_dbscan)
+ *   W(i)       the sum over j in N(i) of w[j], in int64; w[j] = weights[j], or 1 when weights == NULL.  Weights are
+ *              >= 0; a row of weight 0 adds nothing to any sum and is labelled like any other row
+ *   core[i]    <=> W(i) >= min_weight.  So min_weight <= 0 makes every row core, and a non-finite row then is a cluster
+ *              of its own, as in the literal C#
+ *   clusters   the connected components of the core points under j in N(i) (symmetric), numbered cf_in + 1,
+ *              cf_in + 2, ... by increasing smallest member index.  A non-core point with a core point in its N takes
+ *              the LARGEST such id (BC/DBImproved.cs:87); every other point gets 0.  *cf_out = cf_in + the number of
+ *              clusters
+ * With weights == NULL and aux == NULL this is vcp_dbscan(in_classed = NULL) with min_pts = min_weight.  With integer
+ * weights >= 1 it is vcp_dbscan on the cloud in which row j stands w[j] times, restricted to the first copies.
+ * coords [n*dim] point-major, dim 2 or 3 (the 2-D metrics read x, y; VCP_L2_3D needs dim 3); aux [n] or NULL;
+ * weights [n] or NULL; labels [n] out; is_core [n] and wsum [n] out, either may be NULL.  wsum, when given, is W(i)
+ * exactly for every row (0 for a row with an empty N); when it is NULL the count stops at min_weight.
+ * The result is a function of the input alone: two calls give identical bits, and so does a call after any other call
+ * on the same context (the workspace is sized and cleared per call; only integer atomics decide anything).
+ * Nothing is written on an error.  VCP_ERR_ARG: NULL ctx, NULL cf_out, NULL coords or labels with n > 0, n < 0, dim not
+ * 2 or 3, VCP_L2_3D with dim 2, VCP_SIGNED_SUM_2D, aux given and gate NaN or < 0 (+inf is allowed), any weight < 0
+ * (found on the device before any output is touched); VCP_ERR_TOO_LARGE: n >= 2^31; VCP_ERR_UNSUPPORTED: an extent
+ * that overflows binary64, as in vcp_kdist.  n == 0: *cf_out = cf_in, VCP_OK.
+ * Candidates come from a uniform grid over the finite rows on the coordinates only (aux is a filter, not an axis) with
+ * a cell edge of eps or more (at most 2^22 cells), built per call in its own workspace; an eps of 0 or beyond the
+ * cloud's extent is one cell, that is all pairs: slow and correct.  Timing phases: gdb_bounds, gdb_grid, gdb_count,
+ * gdb_union, gdb_label (csrc/gdbscan.hip). */
+int vcp_gdbscan(vcp_ctx* ctx, const double* coords, int64_t n, int dim, int metric, double eps, const double* aux,
+                double gate, const int32_t* weights, int64_t min_weight, int32_t cf_in, int32_t* labels,
+                uint8_t* is_core, int64_t* wsum, int32_t* cf_out);
+/* Same with device pointers for coords, aux, weights, labels, is_core, wsum, on the context's stream; cf_out stays a
+ * host pointer; returns when the result is in place. */
+int vcp_gdbscan_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, int metric, double eps,
+                    const double* d_aux, double gate, const int32_t* d_weights, int64_t min_weight, int32_t cf_in,
+                    int32_t* d_labels, uint8_t* d_is_core, int64_t* d_wsum, int32_t* cf_out);
+
 #ifdef __cplusplus
 }
 #endif

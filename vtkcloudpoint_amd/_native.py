@@ -35,6 +35,7 @@ SYMBOLS = [
     "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_match_unique", "vcp_match_unique_dev",
     "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_register_sim",
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
+    "vcp_gdbscan", "vcp_gdbscan_dev",
 ]
 
 
@@ -233,6 +234,46 @@ class Context:
                                          C.byref(m), _ptr(d_merge_w), _ptr(d_merge_a), _ptr(d_merge_b),
                                          C.byref(rounds)))
         return m.value, rounds.value
+
+    # -- generalised DBSCAN ----------------------------------------------------------------------
+    def gdbscan(self, coords, eps, min_weight, metric=L1_2D, weights=None, aux=None, gate=None, cf_in=0,
+                want_wsum=False):
+        """vcp_gdbscan: DBSCAN in which row j counts weights[j] times (None: once) and two rows are neighbours only when
+        their aux values are within gate as well (aux None: no second test).  Returns dict(labels, is_core, cf, wsum):
+        wsum [n] int64 = the weight of every row's neighbourhood with want_wsum, else None."""
+        coords = _f64(coords)
+        if coords.ndim != 2:
+            coords = coords.reshape(0, 2)
+        n, dim = coords.shape
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.int32).reshape(-1)
+            if len(weights) != n:
+                raise ValueError("weights has %d entries for %d points" % (len(weights), n))
+        if aux is not None:
+            if gate is None:
+                raise ValueError("aux needs a gate")
+            aux = _f64(aux).reshape(-1)
+            if len(aux) != n:
+                raise ValueError("aux has %d entries for %d points" % (len(aux), n))
+        labels = np.zeros(n, np.int32)
+        is_core = np.zeros(n, np.uint8)
+        wsum = np.zeros(n, np.int64) if want_wsum else None
+        cf = C.c_int32(0)
+        self._chk(lib().vcp_gdbscan(self._h, _ptr(coords), C.c_int64(n), int(dim), int(metric), C.c_double(eps),
+                                    _ptr(aux), C.c_double(0.0 if gate is None else gate), _ptr(weights),
+                                    C.c_int64(int(min_weight)), C.c_int32(cf_in), _ptr(labels), _ptr(is_core),
+                                    _ptr(wsum), C.byref(cf)))
+        return dict(labels=labels, is_core=is_core, cf=cf.value, wsum=wsum)
+
+    def gdbscan_dev(self, d_coords, n, dim, eps, min_weight, d_labels, metric=L1_2D, d_weights=None, d_aux=None,
+                    gate=0.0, cf_in=0, d_is_core=None, d_wsum=None):
+        """Device-pointer form (ints from tensor.data_ptr()): d_weights int32 [n], d_aux float64 [n], d_is_core uint8 [n]
+        and d_wsum int64 [n] may be None.  Returns cf."""
+        cf = C.c_int32(0)
+        self._chk(lib().vcp_gdbscan_dev(self._h, _ptr(d_coords), C.c_int64(n), int(dim), int(metric), C.c_double(eps),
+                                        _ptr(d_aux), C.c_double(gate), _ptr(d_weights), C.c_int64(int(min_weight)),
+                                        C.c_int32(cf_in), _ptr(d_labels), _ptr(d_is_core), _ptr(d_wsum), C.byref(cf)))
+        return cf.value
 
     # -- ICP -----------------------------------------------------------------------------------
     def icp(self, model, data, tol=1e-4, max_iter=100, stop_rule=STOP_SSE_DELTA):

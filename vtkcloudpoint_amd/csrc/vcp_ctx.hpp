@@ -35,10 +35,11 @@ struct vcp_ctx {
   //   [0, 1024)     the DBSCAN engine's EnginePinned: bounds, two totals, counters (dbscan.hip); the block partition's bounds (blockpart.hip);
   //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
   //                 nearest-neighbour grid's bounds (nngrid.hip); at [0, 56) the truths' bounds of vcp_match_unique
-  //                 and the targets' bounds of vcp_register_pairs (mugrid.hpp) and the cloud's of vcp_eps_tree (eps_tree.hip)
+  //                 and the targets' bounds of vcp_register_pairs (mugrid.hpp) and the cloud's of vcp_eps_tree (eps_tree.hip);
+  //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
-  //                 and of vcp_eps_tree (eps_tree.hip)
+  //                 and of vcp_eps_tree (eps_tree.hip); the cluster count of vcp_gdbscan (gdbscan.hip)
   //   [2048, 2064)  DB pair by pair: next seed / frontier size (dbpairs.hip)
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
@@ -66,6 +67,9 @@ struct vcp_ctx {
   // starts of its own grid; the records and per-slot state; the emitted edges and the sort's second set; the sort's
   // temporary storage
   DevBuf b_et_in, b_et_out, b_et_kd, b_et_misc, b_et_cell, b_et_work, b_et_edge, b_et_tmp;
+  // weighted / gated DBSCAN (gdbscan.hip): inputs and outputs of the host form; counters and bounds; the cell starts of
+  // its own grid; the records, the per-slot state and the ranks
+  DevBuf b_gd_in, b_gd_out, b_gd_misc, b_gd_cell, b_gd_work;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

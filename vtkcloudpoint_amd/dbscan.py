@@ -67,6 +67,38 @@ class DBImproved:
         self.clusterAmount = self.cf                # :112
         DBImproved.iritatorNum += r["evals"]
 
+    def dbscanGeneral(self, lst, e, minWeight, gate=None, usePtsCount=False):
+        """DBImproved.dbscan with the two generalisations of vcp_gdbscan (no counterpart in the C#): with usePtsCount a
+        point counts ptsCount times (the multiplicity the import keeps after removing duplicates), and with a gate two
+        points are neighbours only when their Distance values are within it as well.  A point is core when its
+        neighbourhood weighs minWeight or more.  Reads motor_x, motor_y (X, Y, Z under the L2_3D metric), Distance and
+        ptsCount; writes clusterId, isClassed, isKeyPoint and clusterAmount like dbscan.  Every point is taken as
+        unclassed on entry, and iritatorNum is left alone (the count of the O(n^2) C# has no meaning here)."""
+        n = len(lst)
+        if n == 0:
+            self.clusterAmount = self.cf
+            return
+        ctx = self._ctx or default_context()
+        weights = np.fromiter((p.ptsCount for p in lst), np.int32, n) if usePtsCount else None
+        aux = np.fromiter((p.Distance for p in lst), np.float64, n) if gate is not None else None
+        coords = self._coords(lst)
+        r = ctx.gdbscan(coords, float(e), int(minWeight), self.metric, weights, aux, gate, int(self.cf))
+        lab, core = r["labels"], r["is_core"]
+        # a point with an empty neighbourhood can only be its own seed, which expandCluster never marks classed
+        lonely = ~np.isfinite(coords).all(1) | (not float(e) >= 0.0)
+        if aux is not None:
+            lonely |= ~np.isfinite(aux)
+        for i, p in enumerate(lst):
+            if lab[i] != 0:
+                p.clusterId = int(lab[i])
+                if not lonely[i]:
+                    p.isClassed = True
+            if core[i]:
+                p.isKeyPoint = True
+        self.pointsAmount += n
+        self.cf = r["cf"]
+        self.clusterAmount = self.cf
+
 
 class DB:
     """BaseClass/DB.cs:9-116, the v1.0 class (dead in the reference: its only use is commented out at FrmMain.cs:38).

@@ -63,6 +63,38 @@ struct ClusObj {  // DataModel.cs:14-33
   bool visible = true;
 };
 
+namespace vcp {
+// vcp_gdbscan on a Point3D list: L1 on (motor_x, motor_y), weights = ptsCount with usePtsCount, aux = Distance with
+// gate >= 0.  hasNeighbourhood[i] is false for a point with a non-finite input and for every point when eps is NaN or < 0.
+struct GdbscanResult {
+  std::vector<int32_t> labels;
+  std::vector<uint8_t> isCore, hasNeighbourhood;
+  int32_t cf = 0;
+};
+inline GdbscanResult gdbscan(Context& c, const std::vector<Point3D*>& lst, double e, long long minWeight, double gate = -1.0,
+                             bool usePtsCount = false, int32_t cfIn = 0) {
+  const int64_t n = (int64_t)lst.size();
+  const bool gated = gate >= 0.0;
+  std::vector<double> xy(2 * n), aux(gated ? n : 0);
+  std::vector<int32_t> w(usePtsCount ? n : 0);
+  GdbscanResult r;
+  r.labels.resize(n);
+  r.isCore.resize(n);
+  r.hasNeighbourhood.resize(n);
+  for (int64_t i = 0; i < n; i++) {
+    xy[2 * i] = lst[i]->motor_x;
+    xy[2 * i + 1] = lst[i]->motor_y;
+    if (gated) aux[i] = lst[i]->Distance;
+    if (usePtsCount) w[i] = lst[i]->ptsCount;
+    r.hasNeighbourhood[i] = e >= 0.0 && std::isfinite(xy[2 * i]) && std::isfinite(xy[2 * i + 1]) &&
+                            (!gated || std::isfinite(aux[i]));
+  }
+  c.check(vcp_gdbscan(c.get(), xy.data(), n, 2, VCP_L1_2D, e, gated ? aux.data() : nullptr, gated ? gate : 0.0,
+                      usePtsCount ? w.data() : nullptr, minWeight, cfIn, r.labels.data(), r.isCore.data(), nullptr, &r.cf));
+  return r;
+}
+}  // namespace vcp
+
 class DBImproved {
  public:
   int clusterAmount = 0;                   // DBImproved.cs:10
@@ -107,6 +139,28 @@ class DBImproved {
     cf = cf_out;
     clusterAmount = cf;
     iritatorNum += ev;
+  }
+
+  // dbscan with the two generalisations of vcp_gdbscan (vcp.h; no counterpart in the C#): with usePtsCount a point counts
+  // ptsCount times, and with gate >= 0 two points are neighbours only when their Distance values are within it as well
+  // (gate < 0: no second test).  A point is core when its neighbourhood weighs minWeight or more.  Every point is taken as
+  // unclassed on entry; iritatorNum is left alone.
+  void dbscanGeneral(std::vector<Point3D*>& lst, double e, long long minWeight, double gate = -1.0,
+                     bool usePtsCount = false) {
+    const int64_t n = (int64_t)lst.size();
+    if (n == 0) {
+      clusterAmount = cf;
+      return;
+    }
+    const vcp::GdbscanResult r = vcp::gdbscan(c_, lst, e, minWeight, gate, usePtsCount, cf);
+    for (int64_t i = 0; i < n; i++) {
+      if (r.labels[i] != 0) lst[i]->clusterId = r.labels[i];
+      if (r.labels[i] != 0 && r.hasNeighbourhood[i]) lst[i]->isClassed = true;  // a seed with an empty list is never marked
+      if (r.isCore[i]) lst[i]->isKeyPoint = true;
+    }
+    pointsAmount += (int)n;
+    cf = r.cf;
+    clusterAmount = cf;
   }
 
  private:

@@ -142,6 +142,12 @@ namespace vtkPointCloud
             int k, double eps_max, int kdist_given, double[] kdist, double[] reach, out long n_merge, double[] merge_w,
             int[] merge_a, int[] merge_b, out int rounds);
 
+        // DBSCAN with point weights and a range gate (vcp.h: vcp_gdbscan; no reference counterpart).  aux (with gate),
+        // weights, is_core and wsum may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_gdbscan(IntPtr ctx, double[] coords, long n, int dim, int metric,
+            double eps, double[] aux, double gate, int[] weights, long min_weight, int cf_in, int[] labels, byte[] is_core,
+            long[] wsum, out int cf_out);
+
         // ---- device-resident forms (IntPtr = device address): for hosts that keep the cloud on the GPU between
         // calls, and for the multi-GPU drivers (one process and one context per GPU) ----
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_dev_alloc(IntPtr ctx, ulong bytes, out IntPtr dptr);
@@ -164,6 +170,9 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_eps_tree_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
             int k, double eps_max, int kdist_given, IntPtr d_kdist, IntPtr d_reach, out long n_merge, IntPtr d_merge_w,
             IntPtr d_merge_a, IntPtr d_merge_b, out int rounds);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_gdbscan_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
+            double eps, IntPtr d_aux, double gate, IntPtr d_weights, long min_weight, int cf_in, IntPtr d_labels, IntPtr d_is_core,
+            IntPtr d_wsum, out int cf_out);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_dev(IntPtr ctx, IntPtr d_model, long nm, IntPtr d_data, long nd,
             double tol, int max_iter, int stop_rule, double[] R, double[] T, out double sse, out double rmse, out int iters);
         // block pipeline in stages (per-block step sharded over GPUs, distributed.py: sharded_blocks)
