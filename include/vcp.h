@@ -428,6 +428,63 @@ int vcp_icp_gated(vcp_ctx* ctx, const double* source, int64_t ns, const double* 
                   int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
                   int32_t* starved);
 
+/* -- trimmed ICP -----------------------------------------------------------------------------------
+ * A gate is a distance: to set its schedule the caller has to know the start error, the centroid noise and the unit of
+ * the scan before a pose exists.  What the caller does know is a SHARE: with T truths, K centroids and `visible` the
+ * fraction of the truths the scan is expected to see, about min(1, visible T / K) of the centroids are real targets.
+ * Trimmed ICP (Chetverikov et al. 2002) takes that share: every round fits on the m pairs with the smallest distances
+ * and leaves the rest out.  It is unit-free (scaling every coordinate by a power of two scales the translation and
+ * changes nothing else) and cannot starve from a bad start the way a closed gate does.
+ *
+ * One round, state (R, T), keep count m with 1 <= m <= L, L the number of landmarks of the call (nd for the one-pass
+ * handle).
+ *   Pair and distance: vcp_icp_sums's.  p = R d + T, the nearest target y with the lowest index on ties, e = p - y,
+ *     dd = e0*e0 + e1*e1 + e2*e2    the SSE term: binary64, left to right, no contraction.
+ *   Key: landmark i (its position in the landmark list, 0-based) has the 96-bit key [K(dd) | i], K(dd) = the bit
+ *     pattern of dd as a uint64 when dd is not NaN, 0xFFFFFFFFFFFFFFFF when it is.  A non-NaN dd is >= +0, so the
+ *     unsigned order is the numeric order; +inf ranks before NaN, NaN ranks last.  Keys are distinct: equal distances go
+ *     to the lower landmark index.
+ *   Kept: the m pairs with the smallest keys.  Every other pair is DROPPED and adds +0.0 to each of the 16 sums AT ITS
+ *     OWN PLACE in vcp_icp_sums's summation order, which stays fixed by (nm, nd, whether every model coordinate is finite)
+ *     and nothing else.  A kept NaN poisons the sums as it does ungated; it is kept only when m reaches it.
+ *   thr: the dd of the kept pair with the largest key.  trim_dist = sqrt(thr), correctly rounded: the gate this round
+ *     was equivalent to.
+ *   Step: the gated step on (sums, kept = m): kept takes the place of nd, the basis is carried.  A round with
+ *     m < min_pairs is STARVED: R, T and the basis stay, the round still counts, `starved` goes up by one.
+ *     mean_dist = sqrt(sums[15] / kept).
+ *
+ * vcp_icp_sums_trimmed: one trimmed round's passes, the test handle as vcp_icp_sums_gated is.  *thr_dd (required) = thr;
+ * nn [nd] and keep [nd] (1 = kept, 0 = dropped) may be NULL.  m < 1 or m > nd: VCP_ERR_ARG, nothing written.  m = nd:
+ * sums bit-identical to vcp_icp_sums.  The key holds the landmark in 32 bits: nd >= 2^32 is VCP_ERR_TOO_LARGE.
+ *
+ * vcp_icp_trimmed: vcp_icp_multistart with a keep schedule.  Arguments as vcp_icp_gated, with keep [n_keep] in place of
+ * gates [n_gates] and one more optional output, trim_dist [n_poses], the last round's value (that of a starved round
+ * too: the select runs in every round).
+ *   keep [n_keep]   round r (1-based) uses f = keep[min(r, n_keep) - 1] and m = min(L, (int64_t)ceil(f * (double)L)):
+ *                   one multiplication, the ceiling is exact
+ * n_keep < 1, min_pairs < 1, an entry that is NaN, <= 0 or > 1: VCP_ERR_ARG.  A failed Horn solve in a round that is
+ * not starved: VCP_ERR_ARG.  No output is written on an error.  All other errors and limits are vcp_icp_multistart's.
+ * Everything not named here is vcp_icp_multistart's, word for word: the landmarks, the default poses and starts,
+ * exactly max_iter rounds, the composition, the inlier score over all ns source points (not trimmed), the choice of
+ * the best pose.  With every entry 1.0, M_all, mean_dist, inliers and best equal vcp_icp_multistart's bit for bit,
+ * kept = L and starved = 0.  A pose's bits do not depend on the other poses of the call.  The schedule is read on the
+ * device: all rounds are enqueued at once, one synchronisation at the end.  Deterministic: only integer comparisons
+ * and integer atomics decide the selection.  The select is a most-significant-digit radix select over the 96-bit keys,
+ * 8 bits a digit: up to VCP_ICPT_SELECT_WG_MAX landmarks one workgroup per pose holds the keys in LDS (one launch per
+ * round), beyond that a histogram kernel runs once per digit over many workgroups (13 launches per round, whatever
+ * the data).  Extra workspace: 12 bytes per (pose, landmark) -- the 8-byte K(dd) and the 4-byte index found -- and
+ * 12 480 bytes per pose for the larger form's prefixes and histograms; no new size limit beyond VCP_ERR_NOMEM.
+ * Timing phases: icpt_rounds, icpt_score (csrc/icp.hip). */
+#define VCP_ICPT_SELECT_WG_MAX 4096
+int vcp_icp_sums_trimmed(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
+                         const double R[9], const double T[3], int64_t m, double sums[16], double* thr_dd,
+                         int32_t* nn, uint8_t* keep);
+int vcp_icp_trimmed(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                    int32_t n_poses, const double* init_R, const double* init_T, int max_iter, int max_landmarks,
+                    const double* keep, int32_t n_keep, int32_t min_pairs, double inlier_dist, double M_best[16],
+                    int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
+                    int32_t* starved, double* trim_dist);
+
 /* -- congruent-pair global registration ---------------------------------------------------------------
  * Every ICP form above starts from T0 = mean(target) - R0 mean(source) unless told otherwise, which is only right when
  * the scan covers the whole truth field; a scan that sees part of it starts wrong by a large translation from every

@@ -32,7 +32,7 @@ SYMBOLS = [
     "vcp_blocks_build_dev", "vcp_blocks_finish_local_dev", "vcp_blocks_finish_zero_dev", "vcp_blocks_finish_zcoords_dev",
     "vcp_blocks_finish_pairs_dev", "vcp_scatter_pairs_dev", "vcp_kdist", "vcp_kdist_dev", "vcp_icp_multistart",
     "vcp_cluster_shapes", "vcp_cluster_shapes_dev", "vcp_cluster_filter", "vcp_cluster_filter_dev",
-    "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_match_unique", "vcp_match_unique_dev",
+    "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_icp_sums_trimmed", "vcp_icp_trimmed", "vcp_match_unique", "vcp_match_unique_dev",
     "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_register_sim",
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
     "vcp_gdbscan", "vcp_gdbscan_dev",
@@ -322,6 +322,23 @@ class Context:
                                            C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums),
                                            C.byref(kept), _ptr(nn), _ptr(keep)))
         return sums, kept.value, nn, keep
+
+    def icp_sums_trimmed(self, model, data, m, R=None, T=None, want_nn=True, want_keep=True):
+        """One trimmed round's passes (vcp_icp_sums_trimmed): the m pairs with the smallest keys [K(dd) | index] are
+        kept, the others add +0.0 at their place in icp_sums's tree.  Returns (sums [16], thr_dd = the dd of the kept
+        pair with the largest key, nn [nd] int32 or None, keep [nd] uint8 or None)."""
+        model = _f64(model, 3)
+        data = _f64(data, 3)
+        R = None if R is None else _f64(R).reshape(9)
+        T = None if T is None else _f64(T).reshape(3)
+        sums = np.zeros(16)
+        thr = C.c_double(0)
+        nn = np.zeros(len(data), np.int32) if want_nn else None
+        keep = np.zeros(len(data), np.uint8) if want_keep else None
+        self._chk(lib().vcp_icp_sums_trimmed(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
+                                             C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_int64(int(m)), _ptr(sums),
+                                             C.byref(thr), _ptr(nn), _ptr(keep)))
+        return sums, thr.value, nn, keep
 
     # -- centroids / merge / match -----------------------------------------------------------------
     def centroids(self, xyz, motor, labels, K):
@@ -733,6 +750,41 @@ class Context:
                                       _ptr(kept), _ptr(starved)))
         return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
                     kept=kept, starved=starved)
+
+    def icp_trimmed(self, source, target, keep, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
+                    inlier_dist=np.inf):
+        """icp_multistart with a per-round keep share (vcp_icp_trimmed): round r (1-based) fits on the
+        m = min(L, ceil(keep[min(r, len(keep)) - 1] * L)) of its L landmarks that lie closest to their nearest target;
+        a round with m < min_pairs changes nothing and counts as starved.  poses, init_T, inlier_dist: as
+        icp_multistart.  Returns icp_gated's dict plus trim_dist [H], the largest kept distance of the last round."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        keep = _f64(keep).reshape(-1)
+        if isinstance(poses, (int, np.integer)):
+            H, init_R = int(poses), None
+        else:
+            init_R = _f64(poses).reshape(-1, 9)
+            H = len(init_R)
+        if init_T is not None:
+            init_T = _f64(init_T, 3)
+            if len(init_T) != H:
+                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
+        n = max(H, 0)
+        M = np.zeros(16)
+        M_all = np.zeros((n, 16))
+        md = np.zeros(n)
+        inl = np.zeros(n, np.int32)
+        kept = np.zeros(n, np.int64)
+        starved = np.zeros(n, np.int32)
+        td = np.zeros(n)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_icp_trimmed(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
+                                        C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter),
+                                        int(max_landmarks), _ptr(keep), C.c_int32(len(keep)), C.c_int32(min_pairs),
+                                        C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(md),
+                                        _ptr(inl), _ptr(kept), _ptr(starved), _ptr(td)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
+                    kept=kept, starved=starved, trim_dist=td)
 
     def register_pairs(self, source, target, bases, len_tol, inlier_dist, mirror=False, max_landmarks=200):
         """vcp_register_pairs: a pose of source on target without a start.  Every base (two source indices) is laid on

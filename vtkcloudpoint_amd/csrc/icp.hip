@@ -62,6 +62,38 @@ struct GateArgs {
 };
 struct NoGate {};
 
+// Trimmed ICP (vcp.h, "trimmed ICP"): a round keeps the m landmarks with the smallest 96-bit keys [K(dd) | index].
+// Three steps per round and pose: a pass that runs the NN search and stores K(dd) and the index found (G = TrimDist),
+// a radix select of the rank-m key (k_icpt_select_wg, or k_icpt_hist x 12 + k_icpt_select_fin), and the sums pass
+// (G = TrimSum), which reads both back and keeps "key <= the selected one" where the gated pass tests the distance.
+struct TrimSel {
+  unsigned long long key;  // K(dd) of the kept pair with the largest key: thr's bit pattern (all ones: NaN)
+  uint32_t idx, pad;       // and its landmark
+};
+struct TrimArgs {
+  const double* share;  // the keep schedule on the device: round r (1-based) uses share[min(r, n_share) - 1]
+  int n_share;
+  long long m_fixed;  // > 0: the keep count itself (vcp_icp_sums_trimmed)
+  unsigned long long* key;  // [poses][L]
+  int32_t* nn;              // [poses][L]
+  TrimSel* sel;             // [poses]
+  uint32_t* pkept;          // [poses][workgroups]
+  uint8_t* keep;            // [L] or NULL
+};
+struct TrimDist {
+  TrimArgs a;
+};
+struct TrimSum {
+  TrimArgs a;
+};
+__device__ __forceinline__ uint8_t* keep_of(const GateArgs& g) { return g.keep; }
+__device__ __forceinline__ uint8_t* keep_of(const TrimSum& t) { return t.a.keep; }
+__device__ __forceinline__ uint32_t* pkept_of(const GateArgs& g) { return g.pkept; }
+__device__ __forceinline__ uint32_t* pkept_of(const TrimSum& t) { return t.a.pkept; }
+// K(dd): dd's bit pattern (dd >= +0, so the unsigned order is the numeric one, +inf last of the numbers), NaN above all
+__device__ __forceinline__ unsigned long long trim_key(double dd) {
+  return dd != dd ? ~0ull : (unsigned long long)__double_as_longlong(dd);
+}
 
 // bounding box of the model -> centre and half extent in the nst states (single workgroup: models are small).  A model
 // with non-finite coordinates gets an infinite scale: every data point is then resolved in binary64.
@@ -140,6 +172,14 @@ constexpr int MTILE = 1024;
 __device__ __forceinline__ double gate_now(const GateArgs& ga, const IcpState* st) {
   return ga.gates[min(st->round + 1, ga.n_gates) - 1];
 }
+// The keep count of the round a trimmed kernel runs now: min(L, ceil(f * L)), one multiplication; f in (0, 1] (checked
+// on the host), so the count lies in [1, L].
+__device__ __forceinline__ long long trim_m(const TrimArgs& a, const IcpState* st, long long L) {
+  if (a.m_fixed > 0) return a.m_fixed;
+  const double f = a.share[min(st->round + 1, a.n_share) - 1];
+  const long long m = (long long)ceil(f * (double)L);
+  return m < L ? m : L;
+}
 template <int TB>
 __device__ __forceinline__ void block_count(uint32_t c, uint32_t* __restrict__ out) {
   __shared__ uint32_t sk[TB / 64];
@@ -162,14 +202,29 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
                                               const IcpState* __restrict__ st, double* __restrict__ partial,
                                               int32_t* __restrict__ nn, const NNGrid& ng, const G& ga) {
   constexpr bool GATED = std::is_same<G, GateArgs>::value;
+  // TDIST: the search alone, K(dd) and the index stored per landmark; TSUM: no search, the stored index, and the sums
+  // of the landmarks whose key is <= the selected one
+  constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * 16;
   if (st->done) return;
   double gate = 0.0;
   uint32_t nkept = 0;
   if constexpr (GATED) gate = gate_now(ga, st);
+  unsigned long long* tkey = nullptr;
+  int32_t* tnn = nullptr;
+  unsigned long long thrk = 0;
+  uint32_t thri = 0;
+  if constexpr (TDIST || TSUM) {
+    tkey = ga.a.key + (size_t)blockIdx.y * (size_t)nd;
+    tnn = ga.a.nn + (size_t)blockIdx.y * (size_t)nd;
+  }
+  if constexpr (TSUM) {
+    thrk = ga.a.sel[blockIdx.y].key;
+    thri = ga.a.sel[blockIdx.y].idx;
+  }
   constexpr bool TILED = NNMODE == 1, GRID = NNMODE == 2;
-  __shared__ float4 tile[TILED ? MTILE : 1];
+  __shared__ float4 tile[TILED && !TSUM ? MTILE : 1];
   double R[9], T[3];
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = st->R[k];
@@ -204,7 +259,9 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
       p[r] = acc + T[r];
     }
     int order = 0;
-    if (GRID) {
+    if constexpr (TSUM) {
+      order = tnn[il];
+    } else if (GRID) {
       double bestv;
       nng::query<false>(ng, p, sub, order, bestv);
     } else {
@@ -337,11 +394,21 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
     if (nn) nn[i] = order;
     const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
     const double y[3] = {y0, y1, y2};
-    if constexpr (GATED) {
+    if constexpr (TDIST) {
+      const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
+      tkey[i] = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
+      tnn[i] = order;
+    } else if constexpr (GATED || TSUM) {
       const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
       const double dd = e0 * e0 + e1 * e1 + e2 * e2;
-      const bool kp = !(sqrt(dd) >= gate);
-      if (ga.keep) ga.keep[i] = kp ? 1 : 0;
+      bool kp;
+      if constexpr (GATED) {
+        kp = !(sqrt(dd) >= gate);
+      } else {
+        const unsigned long long k = tkey[i];
+        kp = k < thrk || (k == thrk && (uint32_t)i <= thri);
+      }
+      if (keep_of(ga)) keep_of(ga)[i] = kp ? 1 : 0;
       nkept += kp ? 1u : 0u;
 #pragma unroll
       for (int r = 0; r < 3; r++) {
@@ -363,8 +430,8 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
       s[15] += e0 * e0 + e1 * e1 + e2 * e2;
     }
   }
-  block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
-  if constexpr (GATED) block_count<TB>(nkept, ga.pkept + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
+  if constexpr (GATED || TSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 template <int TB, int NNMODE>
@@ -408,12 +475,25 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
                                                     int32_t* __restrict__ nn, uint32_t imask, double tolk, const G& ga) {
   constexpr bool GATED = std::is_same<G, GateArgs>::value;  // as in icp_pass_body
+  constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * 16;
   if (st->done) return;
   double gate = 0.0;
   uint32_t nkept = 0;
   if constexpr (GATED) gate = gate_now(ga, st);
+  unsigned long long* tkey = nullptr;
+  int32_t* tnn = nullptr;
+  unsigned long long thrk = 0;
+  uint32_t thri = 0;
+  if constexpr (TDIST || TSUM) {
+    tkey = ga.a.key + (size_t)blockIdx.y * (size_t)nd;
+    tnn = ga.a.nn + (size_t)blockIdx.y * (size_t)nd;
+  }
+  if constexpr (TSUM) {
+    thrk = ga.a.sel[blockIdx.y].key;
+    thri = ga.a.sel[blockIdx.y].idx;
+  }
   double R[9], T[3];
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = st->R[k];
@@ -454,8 +534,9 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       // 2^-149; overflow: inf scores): NaN = every candidate goes through the binary64 comparison
       tol2[h] = ((float)(S * S) < 1.0e37f && t2 >= 1.0e-30f) ? t2 : NAN;
     }
-    const f32x2 nq0 = {-q[0][0], -q[1][0]}, nq1 = {-q[0][1], -q[1][1]}, nq2 = {-q[0][2], -q[1][2]};
     float b1[2] = {INFINITY, INFINITY}, b2[2] = {INFINITY, INFINITY};
+    if constexpr (!TSUM) {
+    const f32x2 nq0 = {-q[0][0], -q[1][0]}, nq1 = {-q[0][1], -q[1][1]}, nq2 = {-q[0][2], -q[1][2]};
     // the mask lives in a VGPR so that (score & keep) | j is ONE v_and_or_b32 (a VOP3 reads one scalar operand: j)
     uint32_t keep;
     asm volatile("v_mov_b32 %0, %1" : "=v"(keep) : "s"(~imask));
@@ -487,10 +568,12 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
         b1[h] = min_raw(b1[h], ta);
       }
     }
+    }  // !TSUM
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       int order = (int)(__float_as_uint(b1[h]) & imask);
-      const bool amb = !(b2[h] > b1[h] + tol2[h]);
+      const bool amb = !TSUM && !(b2[h] > b1[h] + tol2[h]);
+      if constexpr (TSUM) order = tnn[live[h] ? idx[h] : nd - 1];
       if (amb) {
         // more than one candidate within the bound (or non-finite values): exact binary64 among the candidates, in
         // index order, strict `<` -- FindClosestPointSet's rule (lowest index among the exact minima)
@@ -516,11 +599,21 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       if (nn) nn[idx[h]] = order;
       const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
       const double y[3] = {y0, y1, y2};
-      if constexpr (GATED) {
+      if constexpr (TDIST) {
+        const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
+        tkey[idx[h]] = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
+        tnn[idx[h]] = order;
+      } else if constexpr (GATED || TSUM) {
         const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
         const double dd = e0 * e0 + e1 * e1 + e2 * e2;
-        const bool kp = !(sqrt(dd) >= gate);
-        if (ga.keep) ga.keep[idx[h]] = kp ? 1 : 0;
+        bool kp;
+        if constexpr (GATED) {
+          kp = !(sqrt(dd) >= gate);
+        } else {
+          const unsigned long long k = tkey[idx[h]];
+          kp = k < thrk || (k == thrk && (uint32_t)idx[h] <= thri);
+        }
+        if (keep_of(ga)) keep_of(ga)[idx[h]] = kp ? 1 : 0;
         nkept += kp ? 1u : 0u;
 #pragma unroll
         for (int r = 0; r < 3; r++) {
@@ -543,8 +636,8 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       }
     }
   }
-  block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
-  if constexpr (GATED) block_count<TB>(nkept, ga.pkept + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
+  if constexpr (GATED || TSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 template <int TB>
@@ -562,6 +655,164 @@ __global__ __launch_bounds__(TB) void k_icp_pass_small_gated(const double* __res
                                                             int32_t* __restrict__ nn, uint32_t imask, double tolk,
                                                             GateArgs ga) {
   icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
+}
+
+// The trimmed round's two passes (G = TrimDist, TrimSum): the same bodies, partition and fold.
+template <int TB, int NNMODE, class G>
+__global__ __launch_bounds__(TB) void k_icp_pass_trim(const double* __restrict__ model,
+                                                     const float4* __restrict__ model32, int nm,
+                                                     const double* __restrict__ data, int64_t nd,
+                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                     NNGrid ng, G ta) {
+  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nullptr, ng, ta);
+}
+template <int TB, class G>
+__global__ __launch_bounds__(TB) void k_icp_pass_small_trim(const double* __restrict__ model,
+                                                           const float4* __restrict__ model32, int nm,
+                                                           const double* __restrict__ data, int64_t nd,
+                                                           const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                           uint32_t imask, double tolk, G ta) {
+  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nullptr, imask, tolk, ta);
+}
+
+// ---- the select of a trimmed round ------------------------------------------------------------------------------
+// Rank m (1-based) over the L distinct 96-bit strings [K(dd) | landmark], most significant digit first, 8 bits a digit:
+// per digit a 256-bin histogram of the strings that agree with the digits chosen so far, then the bin the rank falls
+// into.  Only integer compares and integer atomics decide, so the result is the same in any order of execution.
+// Up to TRIM_SELECT_WG_MAX landmarks one workgroup per pose stages the keys in LDS and runs all twelve digits
+// (k_icpt_select_wg: one launch); beyond, k_icpt_hist runs once per digit over all workgroups with global histograms
+// and k_icpt_select_fin closes the round (13 launches, whatever the data).
+constexpr int TRIM_SELECT_WG_MAX = VCP_ICPT_SELECT_WG_MAX;  // 4096: 32 KB of keys in LDS
+constexpr int TRIM_DIGITS = 12;
+constexpr int TRIM_HIST_KEYS = 2048;    // keys per workgroup of k_icpt_hist, up to TRIM_HIST_BLOCKS workgroups per pose
+constexpr int TRIM_HIST_BLOCKS = 256;
+static_assert(ITPB == 256, "one thread per histogram bin");
+
+struct TrimPrefix {
+  uint32_t w0, w1, w2;  // the string's three words (K high, K low, landmark), the digits not chosen yet zero
+  uint32_t rank;  // the rank left among the strings that agree with them
+};
+__device__ __forceinline__ uint32_t trim_word(unsigned long long k, uint32_t i, int w) {
+  return w == 0 ? (uint32_t)(k >> 32) : w == 1 ? (uint32_t)k : i;
+}
+__device__ __forceinline__ uint32_t trim_digit(unsigned long long k, uint32_t i, int d) {
+  return (trim_word(k, i, d >> 2) >> (24 - 8 * (d & 3))) & 255u;
+}
+// whether (k, i) agrees with p in its first d digits
+__device__ __forceinline__ bool trim_match(unsigned long long k, uint32_t i, const TrimPrefix& p, int d) {
+  // per word: the mask of the bits that lie within the first d digits (named words: an index would go to scratch)
+  const int w = d >> 2, b = d & 3;
+  const uint32_t part = b ? ~0u << (32 - 8 * b) : 0u;
+  const uint32_t m0 = w > 0 ? ~0u : part, m1 = w > 1 ? ~0u : w == 1 ? part : 0u, m2 = w == 2 ? part : 0u;
+  return ((((uint32_t)(k >> 32) ^ p.w0) & m0) | (((uint32_t)k ^ p.w1) & m1) | ((i ^ p.w2) & m2)) == 0;
+}
+__device__ __forceinline__ void trim_push(TrimPrefix& p, int d, uint32_t g, uint32_t rank) {
+  const uint32_t add = g << (24 - 8 * (d & 3));
+  const int w = d >> 2;
+  p.w0 |= w == 0 ? add : 0u;
+  p.w1 |= w == 1 ? add : 0u;
+  p.w2 |= w == 2 ? add : 0u;
+  p.rank = rank;
+}
+// Thread t holds the count c of bin t; rank r, 1 <= r <= the total: the bin g with below(g) < r <= below(g) + c(g) and
+// the rank left in it, to every thread.  sh: 8 words of LDS, free again on return.
+__device__ __forceinline__ void trim_pick(uint32_t c, uint32_t r, uint32_t* sh, uint32_t& g, uint32_t& left) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t inc = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t v = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += v;
+  }
+  if (threadIdx.x == 0) {
+    sh[4] = 0;
+    sh[5] = 1;
+  }
+  if (lane == 63) sh[w] = inc;
+  __syncthreads();
+  for (int u = 0; u < w; u++) inc += sh[u];
+  const uint32_t exc = inc - c;
+  if (exc < r && r <= inc) {
+    sh[4] = threadIdx.x;
+    sh[5] = r - exc;
+  }
+  __syncthreads();
+  g = sh[4];
+  left = sh[5];
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(ITPB) void k_icpt_select_wg(const IcpState* __restrict__ st, TrimArgs a, int L) {
+  const int h = blockIdx.x;
+  st += h;
+  if (st->done) return;
+  __shared__ unsigned long long sk[TRIM_SELECT_WG_MAX];
+  __shared__ uint32_t hist[ITPB], sh[8];
+  const unsigned long long* key = a.key + (size_t)h * L;
+  for (int i = threadIdx.x; i < L; i += ITPB) sk[i] = key[i];
+  TrimPrefix p{0u, 0u, 0u, (uint32_t)trim_m(a, st, L)};
+  for (int d = 0; d < TRIM_DIGITS; d++) {
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < L; i += ITPB) {
+      const unsigned long long k = sk[i];
+      if (trim_match(k, (uint32_t)i, p, d)) atomicAdd(&hist[trim_digit(k, (uint32_t)i, d)], 1u);
+    }
+    __syncthreads();
+    uint32_t g, left;
+    trim_pick(hist[threadIdx.x], p.rank, sh, g, left);
+    trim_push(p, d, g, left);
+  }
+  if (threadIdx.x == 0) a.sel[h] = TrimSel{((unsigned long long)p.w0 << 32) | p.w1, p.w2, 0u};
+}
+
+// digit d of the multi-workgroup form: ghist [poses][12][256], zero on entry of a round; slot [poses][12], slot d = the
+// prefix and rank before digit d (written by workgroup 0 of this launch, read by the next)
+__global__ __launch_bounds__(ITPB) void k_icpt_hist(const IcpState* __restrict__ st, TrimArgs a, int64_t L,
+                                                   uint32_t* __restrict__ ghist, TrimPrefix* __restrict__ slot, int d) {
+  const int h = blockIdx.y;
+  st += h;
+  if (st->done) return;
+  __shared__ uint32_t hist[ITPB], sh[8];
+  ghist += (size_t)h * TRIM_DIGITS * ITPB;
+  slot += (size_t)h * TRIM_DIGITS;
+  TrimPrefix p{0u, 0u, 0u, 0u};
+  if (d == 0) {
+    p.rank = (uint32_t)trim_m(a, st, L);
+  } else {
+    p = slot[d - 1];
+    uint32_t g, left;
+    trim_pick(ghist[(d - 1) * ITPB + threadIdx.x], p.rank, sh, g, left);
+    trim_push(p, d - 1, g, left);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) slot[d] = p;
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned long long* key = a.key + (size_t)h * (size_t)L;
+  for (int64_t i = (int64_t)blockIdx.x * ITPB + threadIdx.x; i < L; i += (int64_t)gridDim.x * ITPB) {
+    const unsigned long long k = key[i];
+    if (trim_match(k, (uint32_t)i, p, d)) atomicAdd(&hist[trim_digit(k, (uint32_t)i, d)], 1u);
+  }
+  __syncthreads();
+  const uint32_t c = hist[threadIdx.x];
+  if (c) atomicAdd(&ghist[d * ITPB + threadIdx.x], c);
+}
+
+// the last digit's bin, the selected string into sel, and the histograms zero again for the next round
+__global__ __launch_bounds__(ITPB) void k_icpt_select_fin(const IcpState* __restrict__ st, TrimArgs a,
+                                                         uint32_t* __restrict__ ghist,
+                                                         const TrimPrefix* __restrict__ slot) {
+  const int h = blockIdx.x;
+  st += h;
+  if (st->done) return;
+  __shared__ uint32_t sh[8];
+  ghist += (size_t)h * TRIM_DIGITS * ITPB;
+  TrimPrefix p = slot[(size_t)h * TRIM_DIGITS + TRIM_DIGITS - 1];
+  uint32_t g, left;
+  trim_pick(ghist[(TRIM_DIGITS - 1) * ITPB + threadIdx.x], p.rank, sh, g, left);
+  trim_push(p, TRIM_DIGITS - 1, g, left);
+  if (threadIdx.x == 0) a.sel[h] = TrimSel{((unsigned long long)p.w0 << 32) | p.w1, p.w2, 0u};
+  for (int d = 0; d < TRIM_DIGITS; d++) ghist[d * ITPB + threadIdx.x] = 0;
 }
 
 // ---- Horn's unit-quaternion closed form (host and device: same code, same rounding) -----------------
@@ -907,9 +1158,24 @@ struct GateRun {
   long long min_pairs;
   uint8_t* d_keep;  // [nd] or NULL
 };
+// tr (may be NULL; never with gr): a trimmed run -- per round the distance pass, the select, the trimmed sums pass and
+// the gated step.  Its workspace is b_icpt: per (pose, landmark) 8 bytes of key and 4 of index, then per pose the
+// multi-workgroup select's 12 prefixes and 12 x 256 counters.
+struct TrimRun {
+  const double* share;  // host, [n_share], validated by the caller; NULL with m_fixed > 0
+  int n_share;
+  long long m_fixed;
+  long long min_pairs;
+  uint8_t* d_keep;   // [nd] or NULL
+  TrimSel* sel_out;  // host, [nst]: the last select of every pose
+};
+size_t icpt_keys_bytes(int nst, int64_t nd) { return ((size_t)nst * (size_t)nd * 12 + 255) & ~(size_t)255; }
+int32_t* icpt_nn(vcp_ctx* ctx, int nst, int64_t nd) {
+  return reinterpret_cast<int32_t*>(ctx->b_icpt.as<char>() + (size_t)nst * (size_t)nd * 8);
+}
 int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState* init,
             int nst, double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn, bool all_rounds,
-            NNGrid* ng_out, const GateRun* gr = nullptr) {
+            NNGrid* ng_out, const GateRun* gr = nullptr, const TrimRun* tr = nullptr) {
   hipStream_t st = ctx->stream;
   // small data sets: one wave per workgroup so that they reach more CUs; large models: LDS tiles
   const bool small0 = nd <= (int64_t)64 * ICP_MAX_BLOCKS;
@@ -937,16 +1203,25 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   // the nst states (icp_states), then [nst][nb][16] partial rows; a gated run: then the schedule and [nst][nb] counts
   const size_t st_bytes = icp_states_bytes(nst);
   const size_t part_bytes = (size_t)nst * nb * 16 * sizeof(double);
-  const size_t gate_bytes = gr ? (size_t)gr->n_gates * sizeof(double) + (size_t)nst * nb * sizeof(uint32_t) : 0;
+  const int n_sched = gr ? gr->n_gates : tr ? tr->n_share : 0;  // doubles staged behind the partial rows
+  const size_t cnt_bytes = ((size_t)nst * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
+  const size_t gate_bytes = gr   ? (size_t)n_sched * sizeof(double) + cnt_bytes
+                            : tr ? (size_t)n_sched * sizeof(double) + cnt_bytes + (size_t)nst * sizeof(TrimSel)
+                                 : 0;
   VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + part_bytes + gate_bytes));
+  const bool sel_wg = nd <= TRIM_SELECT_WG_MAX;
+  const size_t key_bytes = tr ? icpt_keys_bytes(nst, nd) : 0;
+  const size_t selws_bytes = (size_t)nst * TRIM_DIGITS * (sizeof(TrimPrefix) + ITPB * sizeof(uint32_t));
+  if (tr) VCP_TRY(vcp_ensure(ctx, ctx->b_icpt, key_bytes + selws_bytes));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)nm * sizeof(float4) + 64));
   IcpState* d_st = icp_states(ctx);
   double* part = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes);
   const StepArgs sa{(long long)nd, tol, stop_rule, max_iter, mode};
   float4* model32 = ctx->b_aux0.as<float4>();
   // a gated run stages its schedule behind the states: the caller's array may be gone before the copy has run
-  const size_t h_bytes = (size_t)nst * sizeof(IcpState) + (gr ? (size_t)gr->n_gates * sizeof(double) : 0);
-  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr ? ctx->pinned : vcp_stage(ctx, h_bytes));
+  const size_t h_bytes =
+      (size_t)nst * sizeof(IcpState) + (size_t)n_sched * sizeof(double) + (tr ? (size_t)nst * sizeof(TrimSel) : 0);
+  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr && !tr ? ctx->pinned : vcp_stage(ctx, h_bytes));
   if (!h_st) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
   std::memcpy(h_st, init, (size_t)nst * sizeof(IcpState));
   VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, (size_t)nst * sizeof(IcpState), hipMemcpyHostToDevice, st));
@@ -959,6 +1234,31 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     double* h_gates = reinterpret_cast<double*>(h_st + nst);
     std::memcpy(h_gates, gr->gates, (size_t)gr->n_gates * sizeof(double));
     VCP_HIP(ctx, hipMemcpyAsync(d_gates, h_gates, (size_t)gr->n_gates * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  TrimDist td{};
+  TrimSum ts{};
+  TrimPrefix* d_slot = nullptr;
+  uint32_t* d_ghist = nullptr;
+  TrimSel* h_sel = nullptr;
+  if (tr) {
+    double* d_share = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
+    uint32_t* pkept = reinterpret_cast<uint32_t*>(d_share + n_sched);
+    TrimSel* d_sel = reinterpret_cast<TrimSel*>(reinterpret_cast<char*>(pkept) + cnt_bytes);
+    td.a = TrimArgs{d_share, n_sched, tr->m_fixed, ctx->b_icpt.as<unsigned long long>(), icpt_nn(ctx, nst, nd),
+                    d_sel,   pkept,   tr->d_keep};
+    ts.a = td.a;
+    gsa = GateStepArgs{tr->min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
+    double* h_share = reinterpret_cast<double*>(h_st + nst);
+    h_sel = reinterpret_cast<TrimSel*>(h_share + n_sched);
+    if (n_sched) {
+      std::memcpy(h_share, tr->share, (size_t)n_sched * sizeof(double));
+      VCP_HIP(ctx, hipMemcpyAsync(d_share, h_share, (size_t)n_sched * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    // the selects' results are read back at the end; the multi-workgroup form's histograms start at zero
+    VCP_HIP(ctx, hipMemsetAsync(d_sel, 0, (size_t)nst * sizeof(TrimSel), st));
+    d_slot = reinterpret_cast<TrimPrefix*>(ctx->b_icpt.as<char>() + key_bytes);
+    d_ghist = reinterpret_cast<uint32_t*>(d_slot + (size_t)nst * TRIM_DIGITS);
+    if (!sel_wg) VCP_HIP(ctx, hipMemsetAsync(d_ghist, 0, (size_t)nst * TRIM_DIGITS * ITPB * sizeof(uint32_t), st));
   }
   if (!grid) {  // the binary32 screening frame and copy serve the full scans only
     VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st, nst);
@@ -975,7 +1275,14 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     for (int b = 0; b < batch; b++) {
 #define VCP_PASS(TBV, TL)                                                                                               \
   do {                                                                                                                  \
-    if (gr)                                                                                                             \
+    if (tr) {                                                                                                           \
+      if (phase == 0)                                                                                                   \
+        VCP_LAUNCH(ctx, (k_icp_pass_trim<TBV, TL, TrimDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,       \
+                   (int)nm, d_data, nd, d_st, part, ng, td);                                                            \
+      else                                                                                                              \
+        VCP_LAUNCH(ctx, (k_icp_pass_trim<TBV, TL, TrimSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,        \
+                   (int)nm, d_data, nd, d_st, part, ng, ts);                                                            \
+    } else if (gr)                                                                                                             \
       VCP_LAUNCH(ctx, (k_icp_pass_gated<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
                  nd, d_st, part, d_nn, ng, ga);                                                                         \
     else                                                                                                                \
@@ -984,30 +1291,52 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   } while (0)
 #define VCP_PASS_SMALL(TBV)                                                                                             \
   do {                                                                                                                  \
-    if (gr)                                                                                                             \
+    if (tr) {                                                                                                           \
+      if (phase == 0)                                                                                                   \
+        VCP_LAUNCH(ctx, (k_icp_pass_small_trim<TBV, TrimDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,     \
+                   (int)nm, d_data, nd, d_st, part, imask, tolk, td);                                                   \
+      else                                                                                                              \
+        VCP_LAUNCH(ctx, (k_icp_pass_small_trim<TBV, TrimSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,      \
+                   (int)nm, d_data, nd, d_st, part, imask, tolk, ts);                                                   \
+    } else if (gr)                                                                                                             \
       VCP_LAUNCH(ctx, k_icp_pass_small_gated<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
                  nd, d_st, part, d_nn, imask, tolk, ga);                                                                \
     else                                                                                                                \
       VCP_LAUNCH(ctx, k_icp_pass_small<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd,   \
                  d_st, part, d_nn, imask, tolk);                                                                        \
   } while (0)
-      if (small && grid) VCP_PASS(64, 2);
-      else if (grid) VCP_PASS(ITPB, 2);
-      else if (small && tiled) VCP_PASS(64, 1);
-      else if (tiled) VCP_PASS(ITPB, 1);
-      else if (small) VCP_PASS_SMALL(64);
-      else VCP_PASS_SMALL(ITPB);
+      // a trimmed round: the pass twice (distances, then sums) with the select between them
+      for (int phase = 0; phase < (tr ? 2 : 1); phase++) {
+        if (small && grid) VCP_PASS(64, 2);
+        else if (grid) VCP_PASS(ITPB, 2);
+        else if (small && tiled) VCP_PASS(64, 1);
+        else if (tiled) VCP_PASS(ITPB, 1);
+        else if (small) VCP_PASS_SMALL(64);
+        else VCP_PASS_SMALL(ITPB);
+        if (!tr || phase == 1) break;
+        if (sel_wg) {
+          VCP_LAUNCH(ctx, k_icpt_select_wg, dim3(nst), dim3(ITPB), 0, st, d_st, td.a, (int)nd);
+        } else {
+          const unsigned hb = vcp_blocks(nd, TRIM_HIST_KEYS, TRIM_HIST_BLOCKS);
+          for (int d = 0; d < TRIM_DIGITS; d++)
+            VCP_LAUNCH(ctx, k_icpt_hist, dim3(hb, nst), dim3(ITPB), 0, st, d_st, td.a, nd, d_ghist, d_slot, d);
+          VCP_LAUNCH(ctx, k_icpt_select_fin, dim3(nst), dim3(ITPB), 0, st, d_st, td.a, d_ghist, d_slot);
+        }
+      }
 #undef VCP_PASS
 #undef VCP_PASS_SMALL
-      if (gr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, gsa);
+      if (tr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, td.a.pkept, nb, d_st, gsa);
+      else if (gr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, gsa);
       else VCP_LAUNCH(ctx, k_icp_step, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, sa);
     }
     launched += batch;
     VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, (size_t)nst * sizeof(IcpState), hipMemcpyDeviceToHost, st));
+    if (tr) VCP_HIP(ctx, hipMemcpyAsync(h_sel, td.a.sel, (size_t)nst * sizeof(TrimSel), hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (all_done() || launched >= max_iter || mode == MODE_SUMS_ONLY) break;
   }
   std::memcpy(out, h_st, (size_t)nst * sizeof(IcpState));
+  if (tr) std::memcpy(tr->sel_out, h_sel, (size_t)nst * sizeof(TrimSel));
   for (int k = 0; k < nst; k++)
     if (out[k].failed) return vcp_fail(ctx, VCP_ERR_ARG, "Horn solve failed (non-finite sums)%s", nst > 1 ? " in a pose" : "");
   return VCP_OK;
@@ -1159,10 +1488,13 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
 // once; the target's grid (or screening frame) is built once and serves every pose and the score.
 // gr (NULL: vcp_icp_multistart): the gated form, vcp_icp_gated -- its schedule is checked here, next to the other
 // arguments, and kept / starved (each may be NULL) receive the states' counters.
+// tr (never with gr): the trimmed form, vcp_icp_trimmed -- likewise, and trim_dist (may be NULL) receives the root of
+// the last round's thr.
 static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
                               int32_t n_poses, const double* init_R, const double* init_T, int max_iter,
                               int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all,
-                              double* mean_dist, int32_t* inliers, const GateRun* gr, int64_t* kept, int32_t* starved) {
+                              double* mean_dist, int32_t* inliers, const GateRun* gr, int64_t* kept, int32_t* starved,
+                              const TrimRun* tr = nullptr, double* trim_dist = nullptr) {
   if (!ctx) return VCP_ERR_ARG;
   if (ns <= 0 || nt <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty source or target");
   if (max_iter < 1 || max_landmarks < 1 || !source || !target || !M_best || !best)
@@ -1181,9 +1513,15 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     for (int k = 0; k < gr->n_gates; k++)
       if (!(gr->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
   }
+  if (tr) {
+    if (tr->n_share < 1 || !tr->share) return vcp_fail(ctx, VCP_ERR_ARG, "n_keep < 1");
+    if (tr->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
+    for (int k = 0; k < tr->n_share; k++)
+      if (!(tr->share[k] > 0.0 && tr->share[k] <= 1.0)) return vcp_fail(ctx, VCP_ERR_ARG, "keep shares must be in (0, 1]");
+  }
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
-  vcp_phase(ctx, gr ? "icpg_rounds" : "icpms_rounds");
+  vcp_phase(ctx, tr ? "icpt_rounds" : gr ? "icpg_rounds" : "icpms_rounds");
   int64_t step = 1;
   if (ns > max_landmarks) step = ns / max_landmarks;
   const int64_t nb = ns / step;
@@ -1203,6 +1541,12 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     }
   }
   std::vector<IcpState> init((size_t)n_poses), fin((size_t)n_poses);
+  std::vector<TrimSel> sel(tr ? (size_t)n_poses : 0);
+  TrimRun trun{};
+  if (tr) {
+    trun = *tr;
+    trun.sel_out = sel.data();
+  }
   for (int h = 0; h < n_poses; h++) {
     IcpState& s = init[h];
     identity(s);
@@ -1230,10 +1574,10 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   VCP_HIP(ctx, hipStreamSynchronize(st));  // `a` is a local buffer
   NNGrid ng{};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init.data(), n_poses, 0.0,
-                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr));
+                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr, tr ? &trun : nullptr));
   // score every pose over ALL source points with vcp_match's arithmetic, on the grid the rounds used (vcp_match bins
   // a target of more than 512 points too, and falls back to the full scan on the same condition)
-  vcp_phase(ctx, gr ? "icpg_score" : "icpms_score");
+  vcp_phase(ctx, tr ? "icpt_score" : gr ? "icpg_score" : "icpms_score");
   const double* d_src = step > 1 ? ctx->b_in3.as<double>() : ctx->b_in2.as<double>();  // step 1: the landmarks are all
   const IcpState* d_st = icp_states(ctx);
   uint32_t* d_cnt = ctx->b_out0.as<uint32_t>();
@@ -1251,7 +1595,7 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   VCP_TRY(vcp_phase_finish(ctx));
   // RMS distance of the pairs the last round summed: all nb landmarks, or the kept ones of a gated run (none: +inf)
   auto mean_of = [&](const IcpState& f) {
-    if (!gr) return std::sqrt(f.d / (double)nb);
+    if (!gr && !tr) return std::sqrt(f.d / (double)nb);
     return f.kept > 0 ? std::sqrt(f.d / (double)f.kept) : (double)INFINITY;
   };
   // most inliers, then the smaller mean distance, then the lower index
@@ -1272,6 +1616,11 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     if (inliers) inliers[h] = (int32_t)h_cnt[h];
     if (kept) kept[h] = (int64_t)fin[h].kept;
     if (starved) starved[h] = fin[h].starved;
+    if (tr && trim_dist) {
+      double thr;
+      std::memcpy(&thr, &sel[h].key, sizeof(thr));
+      trim_dist[h] = std::sqrt(thr);
+    }
   }
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) M_best[4 * r + c] = fin[b].R[3 * r + c];
@@ -1301,6 +1650,17 @@ int vcp_icp_gated(vcp_ctx* ctx, const double* source, int64_t ns, const double* 
                             M_best, best, M_all, mean_dist, inliers, &gr, kept, starved);
 }
 
+// vcp_icp_multistart with a per-round keep share: every round fits on the closest pairs alone (vcp.h)
+int vcp_icp_trimmed(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                    const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* keep,
+                    int32_t n_keep, int32_t min_pairs, double inlier_dist, double M_best[16], int32_t* best,
+                    double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved,
+                    double* trim_dist) {
+  const TrimRun tr{keep, n_keep, 0, min_pairs, nullptr, nullptr};
+  return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
+                            M_best, best, M_all, mean_dist, inliers, nullptr, kept, starved, &tr, trim_dist);
+}
+
 // Host-side run of the Horn step the device executes per round (same source: horn() is __host__ __device__).
 int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v, double R1[9], double T1[3]) {
   if (!sums || !R1 || !T1 || nd <= 0 || (use_v && !V)) return VCP_ERR_ARG;
@@ -1308,15 +1668,19 @@ int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v
 }
 
 // gate (NULL: vcp_icp_sums): one gated pass, vcp_icp_sums_gated; kept and keep receive its verdicts
+// m (never with gate): one trimmed round's passes, vcp_icp_sums_trimmed; thr_dd and keep receive its verdicts
 static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                         const double T[3], double sums[16], int32_t* nn, const double* gate, int64_t* kept,
-                        uint8_t* keep) {
+                        uint8_t* keep, const int64_t* m = nullptr, double* thr_dd = nullptr) {
   if (!ctx) return VCP_ERR_ARG;
   if (nm <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty model");
   if (nd <= 0 || !model || !data || !sums) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
   if (nm >= 0x7FFFFFFFLL / 3) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "model too large");
   if (gate && !(*gate > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gate must be > 0 (+inf allowed)");
   if (gate && !kept) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
+  if (m && !thr_dd) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
+  if (m && (*m < 1 || *m > nd)) return vcp_fail(ctx, VCP_ERR_ARG, "m must be in [1, nd]");
+  if (m && nd > 0xFFFFFFFFLL) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "the key holds the landmark in 32 bits");
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
   VCP_TRY(vcp_ensure(ctx, ctx->b_in0, (size_t)nm * 24));
@@ -1330,11 +1694,19 @@ static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const dou
   if (R) std::memcpy(init.R, R, sizeof(init.R));
   if (T) std::memcpy(init.T, T, sizeof(init.T));
   const GateRun gr{gate, 1, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr};
+  TrimSel sel{};
+  const TrimRun tr{nullptr, 0, m ? (long long)*m : 0, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr, &sel};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, &init, 1, 0.0, VCP_STOP_SSE_DELTA, 1,
-                  MODE_SUMS_ONLY, &fin, nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr, gate ? &gr : nullptr));
+                  MODE_SUMS_ONLY, &fin, nn && !m ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr,
+                  gate ? &gr : nullptr, m ? &tr : nullptr));
   std::memcpy(sums, fin.sums, sizeof(fin.sums));
   if (gate) *kept = (int64_t)fin.kept;
-  if (nn) VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (m) {
+    std::memcpy(thr_dd, &sel.key, sizeof(double));
+    if (nn) VCP_HIP(ctx, hipMemcpyAsync(nn, icpt_nn(ctx, 1, nd), (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
+  } else if (nn) {
+    VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
   if (keep) VCP_HIP(ctx, hipMemcpyAsync(keep, ctx->b_out1.p, (size_t)nd, hipMemcpyDeviceToHost, ctx->stream));
   if (nn || keep) VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VCP_OK;
@@ -1348,6 +1720,12 @@ int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* da
 int vcp_icp_sums_gated(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                        const double T[3], double gate, double sums[16], int64_t* kept, int32_t* nn, uint8_t* keep) {
   return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep);
+}
+
+int vcp_icp_sums_trimmed(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
+                         const double R[9], const double T[3], int64_t m, double sums[16], double* thr_dd, int32_t* nn,
+                         uint8_t* keep) {
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, nullptr, nullptr, keep, &m, thr_dd);
 }
 
 }  // extern "C"

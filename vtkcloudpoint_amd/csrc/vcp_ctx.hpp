@@ -70,6 +70,9 @@ struct vcp_ctx {
   // weighted / gated DBSCAN (gdbscan.hip): inputs and outputs of the host form; counters and bounds; the cell starts of
   // its own grid; the records, the per-slot state and the ranks
   DevBuf b_gd_in, b_gd_out, b_gd_misc, b_gd_cell, b_gd_work;
+  // trimmed ICP (icp.hip): per (pose, landmark) the distance key and the index found, then the select's prefixes and
+  // histograms
+  DevBuf b_icpt;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

@@ -297,6 +297,54 @@ namespace vtkPointCloud
             ShowIcpSolution(SourcePolydata, TargetPolydata);
         }
 
+        // ICPMultiStart() where every round fits on a share of the centroids: the ceil(keepShare * count) of them that lie
+        // closest to their nearest truth, the others left out of that round.  keepShare is the share of the centroids
+        // expected to be real targets, min(1, visible * truths / centroids) -- known before any pose exists, and free of
+        // the scan's unit, where ICPGated's two distances are not.  M is set as by ICP().
+        void ICPTrimmed(int angles, bool mirror, double keepShare, double matchDistance)
+        {
+            ren = new vtk.vtkRenderer();
+            vtk.vtkPolyData SourcePolydata = Tools.ArrayList2PolyData(1, this.centers, this.trueScale, this.centroidScale,
+                this.scale, this.clock, this.clock_y, this.clock_x);
+            vtk.vtkPolyData TargetPolydata = new vtk.vtkPolyData();
+            TargetPolydata.SetPoints(truePointCloud);
+            TargetPolydata.SetVerts(truePointVertices);
+
+            int ns = centers.Count;
+            double[] src = new double[3 * Math.Max(ns, 1)];
+            for (int i = 0; i < ns; i++) { src[3 * i] = centers[i].tmp_X; src[3 * i + 1] = centers[i].tmp_Y; src[3 * i + 2] = 0.0; }
+            double[] tgt = TruthArray();
+            int poses = mirror ? 2 * angles : angles;
+            double[] initR = null;  // null: the library's Rz(h * 2 pi / angles)
+            if (mirror)
+            {
+                initR = new double[9 * poses];
+                for (int h = 0; h < angles; h++)
+                {
+                    double t = h * (2.0 * Math.PI / angles), c = Math.Cos(t), s = Math.Sin(t);
+                    double[] rz = { c, 0.0 - s, 0.0, s, c, 0.0, 0.0, 0.0, 1.0 };
+                    double[] rm = { c, s, 0.0, s, 0.0 - c, 0.0, 0.0, 0.0, 1.0 };  // Rz(t) * diag(1, -1, 1)
+                    Array.Copy(rz, 0, initR, 9 * h, 9);
+                    Array.Copy(rm, 0, initR, 9 * (angles + h), 9);
+                }
+            }
+            double[] keep = { keepShare };
+            double[] m16 = new double[16];
+            int[] inliers = new int[Math.Max(poses, 1)];
+            long[] kept = new long[Math.Max(poses, 1)];
+            int[] starved = new int[Math.Max(poses, 1)];
+            double[] trimDist = new double[Math.Max(poses, 1)];
+            int best;
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_icp_trimmed(lease.Ctx, src, ns, tgt, tgt.Length / 3, poses, initR, null,
+                    100, 200, keep, 1, 3, matchDistance, m16, out best, null, null, inliers, kept, starved, trimDist));
+            M = new vtk.vtkMatrix4x4();
+            for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) M.SetElement(r, c, m16[4 * r + c]);
+            Console.WriteLine("刚性变换矩阵为：" + M + " (start " + best + " of " + poses + ", " + inliers[best] + " / " + ns
+                + ", " + kept[best] + " kept within " + trimDist[best] + ", " + starved[best] + " starved rounds)");
+            ShowIcpSolution(SourcePolydata, TargetPolydata);
+        }
+
         // the display part of FrmMain.cs:863-906: the centroids moved by M next to the truths
         void ShowIcpSolution(vtk.vtkPolyData SourcePolydata, vtk.vtkPolyData TargetPolydata)
         {

@@ -88,6 +88,16 @@ namespace vtkPointCloud
             int n_gates, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
             double[] mean_dist, int[] inliers, long[] kept, int[] starved);
 
+        // trimmed ICP (vcp.h): every round fits on the m pairs with the smallest distances.  One round's passes (the test
+        // handle; nn and keep may be null) and vcp_icp_multistart with a schedule of keep shares: round r keeps
+        // ceil(keep[min(r, n_keep) - 1] * landmarks) pairs; kept, starved and trim_dist may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_sums_trimmed(IntPtr ctx, double[] model, long nm, double[] data,
+            long nd, double[] R, double[] T, long m, double[] sums, out double thr_dd, int[] nn, byte[] keep);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_trimmed(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int n_poses, double[] init_R, double[] init_T, int max_iter, int max_landmarks, double[] keep,
+            int n_keep, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
+            double[] mean_dist, int[] inliers, long[] kept, int[] starved, double[] trim_dist);
+
         // congruent-pair global registration (no counterpart in the reference; bases = pairs of source indices)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_pairs(IntPtr ctx, double[] source, long ns, double[] target,
             long nt, int[] bases, int n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist,

@@ -1,5 +1,5 @@
-"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start, gated and global
-(congruent-pair) ICP for MainForm.ICP's centroid-to-truth matching."""
+"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start, gated, trimmed and
+global (congruent-pair) ICP for MainForm.ICP's centroid-to-truth matching."""
 import math
 
 import numpy as np
@@ -217,6 +217,50 @@ def gated_icp(centers, truths, gates, n_angles=1, mirror=False, init_T=None, max
     return ctx.icp_gated(src, tgt, gates, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
 
 
+def trim_schedule(start, end, rounds):
+    """`rounds` keep shares that fall linearly from `start` to `end` (1 >= start >= end > 0): the first entry is exactly
+    `start`, the last exactly `end`, and the list never rises.  rounds = 1 gives [end].  vcp_icp_trimmed holds the last
+    share for every round beyond the schedule."""
+    start, end, rounds = float(start), float(end), int(rounds)
+    if rounds < 1:
+        raise ValueError("rounds < 1")
+    if not (end > 0.0 and start >= end and start <= 1.0):
+        raise ValueError("need 1 >= start >= end > 0")
+    if rounds == 1:
+        return np.array([end])
+    f = np.array([start + (end - start) * (k / (rounds - 1.0)) for k in range(rounds)])
+    f[0], f[-1] = start, end
+    return np.minimum.accumulate(np.clip(f, end, start))  # rounding may not undo the order
+
+
+def expected_share(n_centers, n_truths, visible=1.0):
+    """min(1, visible * n_truths / n_centers): the share of the centroids that are real targets when the scan sees the
+    fraction `visible` of the truths -- the keep share trimmed_icp is meant to be given."""
+    n_centers, n_truths, visible = int(n_centers), int(n_truths), float(visible)
+    if n_centers < 1 or n_truths < 1 or not (0.0 < visible <= 1.0):
+        raise ValueError("need n_centers >= 1, n_truths >= 1 and 0 < visible <= 1")
+    return min(1.0, visible * n_truths / n_centers)
+
+
+def trimmed_icp(centers, truths, keep, n_angles=1, mirror=False, init_T=None, max_iter=100, max_landmarks=200,
+                min_pairs=3, inlier_dist=np.inf, ctx=None):
+    """multistart_icp where every round fits on a share of the pairs: round r keeps the
+    ceil(keep[min(r, len(keep)) - 1] * L) of the L landmarks closest to their nearest truth and leaves the others out
+    of that round's fit (Chetverikov's trimmed ICP).  The share is what the caller knows before any pose exists
+    (expected_share), where gated_icp's distances need the start error, the noise and the unit; keep may be one number.
+    n_angles may also be an [H, 3, 3] array of start rotations.  Returns Context.icp_trimmed's dict (best, M, M_all,
+    mean_dist, inliers, kept, starved, trim_dist)."""
+    ctx = ctx or default_context()
+    src = _points(centers)
+    tgt = _points(truths)
+    if isinstance(n_angles, (int, np.integer)):
+        poses = rotations_about_z(n_angles, mirror) if mirror else int(n_angles)
+    else:
+        poses = np.asarray(n_angles, np.float64)
+    keep = np.atleast_1d(np.asarray(keep, np.float64))
+    return ctx.icp_trimmed(src, tgt, keep, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
+
+
 def choose_bases(source, n_bases, min_len, max_len, seed=0):
     """[n_bases, 2] int32 pairs of source indices for register_pairs: np.random.default_rng(seed).integers(0, ns, 2) is
     drawn until n_bases pairs are accepted, a pair (a, b) being accepted when a != b and its planar length lies in
@@ -250,10 +294,11 @@ def register_pairs(centers, truths, bases, len_tol, inlier_dist, mirror=False, m
 
 
 def global_icp(centers, truths, bases, len_tol, inlier_dist, gates, mirror=False, max_iter=20, max_landmarks=200,
-               min_pairs=3, ctx=None):
+               min_pairs=3, ctx=None, keep=None):
     """register_pairs, then ONE gated_icp call started from the pose of every base that found one (score >= 0).  Returns
     gated_icp's dict (best indexes the started poses) plus registration = register_pairs's dict and bases_used = the base
-    of every started pose.  ValueError when no base has a hypothesis."""
+    of every started pose.  ValueError when no base has a hypothesis.  keep (a share or a schedule of shares): the
+    polish is one trimmed_icp call instead (its dict, with trim_dist), and gates may be None."""
     ctx = ctx or default_context()
     src, tgt = _points(centers), _points(truths)
     reg = ctx.register_pairs(src, tgt, bases, len_tol, inlier_dist, mirror, max_landmarks)
@@ -261,8 +306,12 @@ def global_icp(centers, truths, bases, len_tol, inlier_dist, gates, mirror=False
     if len(used) == 0:
         raise ValueError("no base has a target pair of its length within len_tol")
     M = reg["M_all"][used]
-    out = ctx.icp_gated(src, tgt, gates, np.ascontiguousarray(M[:, :3, :3]), np.ascontiguousarray(M[:, :3, 3]), max_iter,
-                        max_landmarks, min_pairs, inlier_dist)
+    Rs, Ts = np.ascontiguousarray(M[:, :3, :3]), np.ascontiguousarray(M[:, :3, 3])
+    if keep is not None:
+        out = ctx.icp_trimmed(src, tgt, np.atleast_1d(np.asarray(keep, np.float64)), Rs, Ts, max_iter, max_landmarks,
+                              min_pairs, inlier_dist)
+    else:
+        out = ctx.icp_gated(src, tgt, gates, Rs, Ts, max_iter, max_landmarks, min_pairs, inlier_dist)
     out.update(registration=reg, bases_used=used)
     return out
 
