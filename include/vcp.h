@@ -840,7 +840,10 @@ int vcp_eps_tree_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, i
  *              the LARGEST such id (BC/DBImproved.cs:87); every other point gets 0.  *cf_out = cf_in + the number of
  *              clusters
  * With weights == NULL and aux == NULL this is vcp_dbscan(in_classed = NULL) with min_pts = min_weight.  With integer
- * weights >= 1 it is vcp_dbscan on the cloud in which row j stands w[j] times, restricted to the first copies.
+ * weights >= 1 it is vcp_dbscan on the cloud in which row j stands w[j] times, restricted to the first copies --
+ * wherever the copies of a row are neighbours of each other, that is for min_weight >= 1, or for eps >= 0 and rows
+ * without a non-finite coordinate.  (A row with an empty N is core only for min_weight <= 0; here it is one cluster
+ * whatever its weight, there every copy is a cluster of its own: the labels of the first copies agree, cf_out does not.)
  * coords [n*dim] point-major, dim 2 or 3 (the 2-D metrics read x, y; VCP_L2_3D needs dim 3); aux [n] or NULL;
  * weights [n] or NULL; labels [n] out; is_core [n] and wsum [n] out, either may be NULL.  wsum, when given, is W(i)
  * exactly for every row (0 for a row with an empty N); when it is NULL the count stops at min_weight.

@@ -211,6 +211,27 @@ def test_random_sweep(vcp_ctx, random_clouds, metric):
     _check(vcp_ctx, c, eps, mw, metric, weights=w, aux=aux, gate=0.5, cf_in=100)
 
 
+def test_expanded_cloud_where_a_row_is_not_its_own_neighbour(vcp_ctx):
+    """Found by tests/fuzz_queries.py (gdbscan, seed 10, case 144): one row of weight 3, eps = -5e-324 (the double below
+    a distance of 0), min_weight 0.  N is empty, the row is core by min_weight <= 0 and one cluster; in the expanded
+    cloud its three copies are no neighbours of each other and make three.  The device follows the definition (the
+    restatement); include/vcp.h now says where the two readings part: the first copies' labels agree, cf_out does not.
+    With min_weight >= 1, or eps >= 0 on finite rows, they are one reading."""
+    c = np.array([[2.0 ** 40, 2.0 ** 40], [2.0 ** 40 + 1.0, 2.0 ** 40], [np.nan, 0.0]])
+    w = np.array([3, 1, 2], np.int32)
+    for eps, mw, together in ((-5e-324, 0, False), (np.nan, -1, False), (0.0, 0, False), (-5e-324, 1, True),
+                              (0.0, 1, True), (1.0, 0, False), (1.0, 2, True)):
+        g, ref = _check(vcp_ctx, c, eps, mw, N.L1_2D, weights=w, cf_in=3)
+        d = vcp_ctx.dbscan(R.expand(c, w), eps, mw, N.L1_2D, 3)
+        assert np.array_equal(g["labels"], d["labels"][:3]) and np.array_equal(g["is_core"], d["is_core"][:3]), (eps, mw)
+        assert (g["cf"] == d["cf"]) == together, (eps, mw, g["cf"], d["cf"])
+    fin, wf = c[:2], w[:2]                                   # finite rows, eps >= 0: one reading for every min_weight
+    for eps, mw in ((0.0, 0), (0.0, -2), (1.0, 0), (1.0, 4), (1.0, 5)):
+        g, _ = _check(vcp_ctx, fin, eps, mw, N.L1_2D, weights=wf, cf_in=3)
+        d = vcp_ctx.dbscan(R.expand(fin, wf), eps, mw, N.L1_2D, 3)
+        assert R.same(g, dict(labels=d["labels"][:2], is_core=d["is_core"][:2], cf=d["cf"]), wsum=False) is None, (eps, mw)
+
+
 def test_context_history(vcp_ctx, random_clouds):
     s = random_clouds[N.L2_2D]
     c, w, aux, eps, mw = s["c"], s["w"], s["aux"], s["eps"], s["mw"]

@@ -202,6 +202,23 @@ def test_truth_grid_equals_brute_force(vcp_ctx, oracle):
         assert np.array_equal(o_ids, g_ids) and o_out == g_out
 
 
+def test_truth_grid_subnormal_radius_on_a_box_of_no_extent(vcp_ctx, oracle):
+    """Found by tests/fuzz_queries.py (assign_truths, seed 9, case 80): every truth at one place and a radius of
+    5e-324, the double above the distance 0 of a raw point that sits on them.  The cell edge stays subnormal (a box of
+    no extent needs no doubling), its reciprocal is +inf, and (p - x0) * inv_h = 0 * inf = NaN put that point outside
+    the grid: id 0 where d = 0 < radius gives the last truth's id.  The same with the smallest radii whose reciprocal is
+    still finite, and with a line of truths (extent in one axis only)."""
+    spot = np.array([-699896.66055029, -699955.7594064])
+    motor = np.array([spot + (7.8e-5, 7.2e-5), spot, spot - (1.2e-3, 7.9e-4), spot])
+    tids = np.arange(1, 13, dtype=np.int32)
+    for txy in (np.tile(spot, (12, 1)), np.c_[np.full(12, spot[0]), spot[1] + np.arange(12) * 0.5]):
+        for radius in (5e-324, 1e-310, 5.562684646268003e-309, np.nextafter(5.562684646268003e-309, 1.0), 2.3e-308):
+            o_ids, o_out = oracle.assign_truths(motor, txy, tids, radius)
+            g_ids, g_out = vcp_ctx.assign_truths(motor, txy, tids, radius)
+            assert o_ids[1] != 0 and o_ids[3] != 0 and o_out == 2
+            assert np.array_equal(o_ids, g_ids) and o_out == g_out, radius
+
+
 def test_import_conversion_and_duplicate_removal(vcp_ctx, oracle):
     """MainForm.AddFolder: Distance filter, spherical -> Cartesian, first-occurrence dedupe."""
     rng = np.random.default_rng(12)

@@ -161,9 +161,13 @@ bool build_truth_grid(const double* txy, const int32_t* tid, int32_t T, double r
   }
   const double dx = (x1 - x0) / h, dy = (y1 - y0) / h;
   if (!std::isfinite(h) || !std::isfinite(dx) || !std::isfinite(dy) || (dx + 1.0) * (dy + 1.0) > 4194304.0) return false;
+  // a subnormal radius over a box of no extent keeps its h, whose reciprocal overflows: 0 * inf = NaN would drop the
+  // raw point that sits ON a truth (d = 0 < radius) -> brute force, like every h the grid cannot hold
+  const double inv = 1.0 / h;
+  if (!std::isfinite(inv) || !(inv > 0.0)) return false;
   g->x0 = x0;
   g->y0 = y0;
-  g->inv_h = 1.0 / h;
+  g->inv_h = inv;
   g->Dx = (int)dx + 1;
   g->Dy = (int)dy + 1;
   const size_t nc = (size_t)g->Dx * g->Dy;
