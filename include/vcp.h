@@ -56,9 +56,20 @@ int vcp_create(int device_id, vcp_ctx** out);
 void vcp_destroy(vcp_ctx* ctx);
 const char* vcp_last_error(const vcp_ctx* ctx); /* ctx may be NULL: last create error      */
 int vcp_version(void);                           /* major*1000 + minor                      */
-/* Run on a caller-provided hipStream_t (NULL = the context's own stream). */
+/* Run on a caller-provided hipStream_t: from this call on every kernel, copy, memset and event of the context goes to
+ * hip_stream, the host-buffer entry points and vcp_h2d / vcp_d2h included.
+ *  - the inputs of a call must be ordered on that stream: work the caller queued on it before the call (a copy that
+ *    fills an input buffer, a kernel that produces it) is seen by the call; work on any other stream is not waited for;
+ *  - a call returns when its work on the stream is done, so everything queued on the stream before it is done too;
+ *  - the stream must outlive its use by the context: select another one (or NULL) or destroy the context first;
+ *  - NULL selects the context's own stream (created non-blocking by vcp_create), so the legacy null stream cannot be
+ *    selected.
+ * The workspace may grow during a call on any stream.  tests/test_stream_gpu.py holds every _dev entry point to this. */
 int vcp_set_stream(vcp_ctx* ctx, void* hip_stream);
-/* Pinned-free device allocation helpers for hosts without a HIP binding of their own. */
+/* Pinned-free device allocation helpers for hosts without a HIP binding of their own (the C# and C++ way of keeping a
+ * cloud resident): alloc, h2d, the _dev call, d2h, free.  bytes == 0 allocates a valid pointer vcp_dev_free accepts;
+ * the copies run on the context's stream and return when done (bytes == 0 copies nothing).  ctx == NULL, a NULL dptr /
+ * device pointer, or a NULL host pointer with bytes > 0: VCP_ERR_ARG. */
 int vcp_dev_alloc(vcp_ctx* ctx, uint64_t bytes, void** dptr);
 int vcp_dev_free(vcp_ctx* ctx, void* dptr);
 int vcp_h2d(vcp_ctx* ctx, void* dst_dev, const void* src_host, uint64_t bytes);
@@ -679,7 +690,8 @@ int vcp_cluster_filter_dev(vcp_ctx* ctx, const int32_t* d_labels, int64_t n, int
 /* -- matching ------------------------------------------------------------------------------
  * Replaces MainForm.calMatchedCoords (FrmMain.cs:3572-3587) + RecorrectMatchingPtsByDistance
  * (:3588-3618, getDisP :829-835): matched = M * (c,1); nearest truth by Euclidean distance
- * (strict <, lowest index on ties); is_matched iff distance < max_dist. */
+ * (strict <, lowest index on ties); is_matched iff distance < max_dist.  K == 0 does nothing; K > 0 && T == 0:
+ * VCP_ERR_EMPTY (the C# reads truePointCloud.GetPoint(0), :3598). */
 int vcp_match(vcp_ctx* ctx, const double* centers, int32_t K, const double* truths, int32_t T,
               const double M[16], double max_dist, double* matched_xyz, uint8_t* is_matched,
               int32_t* nearest, double* nearest_dist, int32_t* count_matched);

@@ -380,6 +380,7 @@ int vcp_dev_alloc(vcp_ctx* ctx, uint64_t bytes, void** dptr) {
 
 int vcp_dev_free(vcp_ctx* ctx, void* dptr) {
   if (!ctx) return VCP_ERR_ARG;
+  if (!dptr) return vcp_fail(ctx, VCP_ERR_ARG, "vcp_dev_free: null pointer");
   VCP_TRY(vcp_bind(ctx));
   VCP_HIP(ctx, hipFree(dptr));
   return VCP_OK;
@@ -387,6 +388,8 @@ int vcp_dev_free(vcp_ctx* ctx, void* dptr) {
 
 int vcp_h2d(vcp_ctx* ctx, void* dst, const void* src, uint64_t bytes) {
   if (!ctx) return VCP_ERR_ARG;
+  if (!dst || (!src && bytes)) return vcp_fail(ctx, VCP_ERR_ARG, "vcp_h2d: null pointer");
+  if (!bytes) return VCP_OK;
   VCP_TRY(vcp_bind(ctx));
   VCP_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -395,6 +398,8 @@ int vcp_h2d(vcp_ctx* ctx, void* dst, const void* src, uint64_t bytes) {
 
 int vcp_d2h(vcp_ctx* ctx, void* dst, const void* src, uint64_t bytes) {
   if (!ctx) return VCP_ERR_ARG;
+  if (!src || (!dst && bytes)) return vcp_fail(ctx, VCP_ERR_ARG, "vcp_d2h: null pointer");
+  if (!bytes) return VCP_OK;
   VCP_TRY(vcp_bind(ctx));
   VCP_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));

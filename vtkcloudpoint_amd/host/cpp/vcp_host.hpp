@@ -8,6 +8,7 @@
 //   Matrix     BaseClass/Matrix.cs (slice ICP uses)  ICP         BaseClass/ICP.cs:8-314
 //   Tools      BaseClass/Tools.cs:162-195, :580-621  MainFormPath FrmMain.cs:1214-1291,:1432-1544,:3572-3618
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <map>
@@ -327,19 +328,20 @@ struct Tools {
   // Tools.cs:70-74: the stable RemoveAll of every point whose clusterId is listed
   static void removeFilterPointFromClustering(Context& c, std::vector<Point3D*>& dataSet, const std::vector<int>& filterID) {
     if (filterID.empty() || dataSet.empty()) return;
-    int32_t K = 0;
-    for (int id : filterID) K = id > K ? id : K;
-    if (K <= 0) return;
-    // every listed id: a cluster of radius 1 against max_radius 0; the other ids are not valid, so never filtered
-    std::vector<double> rad(K, 0.0);
-    std::vector<uint8_t> valid(K, 0), filtered(K, 0);
-    for (int id : filterID)
-      if (id >= 1) rad[id - 1] = 1.0, valid[id - 1] = 1;
+    // the listed ids, each once, in ascending order: the r-th of them is cluster r + 1 of radius 1 against max_radius 0.
+    // Any int may be listed -- 0 (the noise points) and negative ids too, as List.Contains takes them -- and the
+    // arrays are as long as the list, not as its largest id
+    std::vector<int> ids(filterID);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const int32_t K = (int32_t)ids.size();
+    std::vector<double> rad(K, 1.0);
+    std::vector<uint8_t> valid(K, 1), filtered(K, 0);
     const int64_t n = (int64_t)dataSet.size();
     std::vector<int32_t> lab(n), kept(n);
     for (int64_t i = 0; i < n; i++) {
-      const int l = dataSet[i]->clusterId;
-      lab[i] = (l >= 1 && l <= K) ? l : 0;  // an id beyond the list is in nobody's filterID
+      const auto it = std::lower_bound(ids.begin(), ids.end(), dataSet[i]->clusterId);
+      lab[i] = (it != ids.end() && *it == dataSet[i]->clusterId) ? (int32_t)(it - ids.begin()) + 1 : 0;  // 0: in nobody's filterID
     }
     int32_t nf = 0;
     int64_t nk = 0;
@@ -424,7 +426,8 @@ inline int MatchOneToOne(Context& c, std::vector<Point3D>& centers, const std::v
 }
 
 // k-distance of every point for DBImproved with minPts = k (vcp.h: vcp_kdist): kd[i] <= eps exactly when point i is a
-// core point at eps.  L1 on (motor_x, motor_y) by default, X/Y/Z with VCP_L2_3D; knn (may be null) gets n*k indices.
+// core point at eps.  L1 on (motor_x, motor_y) by default, X/Y/Z with VCP_L2_3D; knn (may be null) gets n*k indices
+// (empty when the call throws).
 inline std::vector<double> k_distance(Context& c, const std::vector<Point3D*>& pts, int k, int metric = VCP_L1_2D,
                                       std::vector<int32_t>* knn = nullptr) {
   const int64_t n = (int64_t)pts.size();
@@ -435,7 +438,9 @@ inline std::vector<double> k_distance(Context& c, const std::vector<Point3D*>& p
     else { xy[2 * i] = pts[i]->motor_x; xy[2 * i + 1] = pts[i]->motor_y; }
   }
   if (knn) knn->assign(n * (k > 0 ? k : 0), -1);
-  c.check(vcp_kdist(c.get(), xy.data(), n, dim, metric, k, kd.data(), knn ? knn->data() : nullptr));
+  const int rc = vcp_kdist(c.get(), xy.data(), n, dim, metric, k, kd.data(), knn ? knn->data() : nullptr);
+  if (rc != VCP_OK && knn) knn->clear();  // a refused k leaves no n * k placeholders behind
+  c.check(rc);
   return kd;
 }
 

@@ -216,20 +216,24 @@ namespace vtkPointCloud
         }
 
         // Tools.removeFilterPointFromClustering, Tools.cs:70-74: the stable RemoveAll, with the membership test of
-        // filterID.Contains done once per cluster id on the GPU side of vcp_cluster_filter (labels beyond the largest
-        // filtered id are kept, like Contains would)
+        // filterID.Contains done once per listed id on the GPU side of vcp_cluster_filter.  Any int may be listed, 0 (the
+        // noise points) and negative ids too, as Contains takes them; the arrays are as long as the list, not as its largest id
         static public void removeFilterPointFromClustering(ref List<Point3D> dataSet, List<int> filterID)
         {
             if (filterID.Count == 0) return;
-            int n = dataSet.Count, K = 0;
-            foreach (int id in filterID) K = Math.Max(K, id);
-            if (n == 0 || K <= 0) return;
-            // every listed id becomes a cluster of radius 1 against max_radius 0; other ids are not valid, so never filtered
+            int n = dataSet.Count;
+            if (n == 0) return;
+            // the listed ids, each once, ascending: the r-th of them is cluster r + 1 of radius 1 against max_radius 0
+            List<int> ids = new List<int>(filterID);
+            ids.Sort();
+            int K = 0;
+            for (int r = 0; r < ids.Count; r++) if (r == 0 || ids[r] != ids[r - 1]) ids[K++] = ids[r];
+            ids.RemoveRange(K, ids.Count - K);
             double[] rad = new double[K];
             byte[] valid = new byte[K], filtered = new byte[K];
-            foreach (int id in filterID) if (id >= 1) { rad[id - 1] = 1.0; valid[id - 1] = 1; }
+            for (int r = 0; r < K; r++) { rad[r] = 1.0; valid[r] = 1; }
             int[] lab = new int[n], kept = new int[n];
-            for (int i = 0; i < n; i++) { int l = dataSet[i].clusterId; lab[i] = (l >= 1 && l <= K) ? l : 0; }
+            for (int i = 0; i < n; i++) { int r = ids.BinarySearch(dataSet[i].clusterId); lab[i] = r >= 0 ? r + 1 : 0; }
             int nf; long nk;
             using (VcpNative.Lease c = VcpNative.Rent())
                 VcpNative.Check(c, VcpNative.vcp_cluster_filter(c.Ctx, lab, n, K, rad, valid, null, null, 0.0, double.PositiveInfinity,
