@@ -496,6 +496,64 @@ int vcp_icp_trimmed(vcp_ctx* ctx, const double* source, int64_t ns, const double
                     int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
                     int32_t* starved, double* trim_dist);
 
+/* -- similarity ICP --------------------------------------------------------------------------------
+ * Every form above composes proper rotations onto the start: a start whose scale is off (centroids in another unit
+ * than the truths, vcp_register_sim's k from one pair per base) keeps that error, and an error of 2 % moves the edge of
+ * a 20 x 20 field by more than a closed gate of 0.1.  This form is the gated loop whose round fits rotation, translation
+ * and ONE isotropic scale (vtkLandmarkTransform's Similarity mode; Horn 1987, section 2.E, the symmetric scale).
+ * Everything is binary64, each operation rounded on its own, sqrt and / correctly rounded.
+ *
+ * Pass.  vcp_icp_sums_gated's, with two more columns.  For a kept pair, p = R d + T and y its nearest model point:
+ *   sums[16] += (p0*p0 + p1*p1) + p2*p2        sums[17] += (y0*y0 + y1*y1) + y2*y2
+ * A dropped pair adds +0.0 to both at its own place; a kept NaN poisons them.  Both go through the SAME summation tree
+ * as the sixteen, fixed by (nm, nd, whether every model coordinate is finite); sums[0..15] are bit-identical to
+ * vcp_icp_sums_gated's at the same gate.
+ *
+ * Step, on (sums [18], n = kept, c = the product of the factors applied so far, bounds ratio_min <= ratio_max).
+ *   R1, muP, muY: vcp_selftest_horn's on sums[0..15], basis handling included.  Where that fails, this fails.
+ *   N = (double)n;  vP = sums[16]/N - ((muP0*muP0 + muP1*muP1) + muP2*muP2);  vY likewise from sums[17] and muY.
+ *   The scale is DETERMINED iff 0 < vP < inf and 0 < vY < inf (comparisons with NaN are false).  Then
+ *     k = sqrt(vY / vP), t = c * k;
+ *     t < ratio_min: c_new = ratio_min, k_used = ratio_min / c;  t > ratio_max: c_new = ratio_max, k_used = ratio_max / c;
+ *     otherwise c_new = t, k_used = k.
+ *   Not determined (coincident points, every pair on one target, cancellation far from the origin): k_used = 1.0,
+ *     c_new = c.  Not fatal.
+ *   R1s[j] = k_used * R1[j];  T1[i] = muY[i] - (R1s[3i]*muP0 + R1s[3i+1]*muP1 + R1s[3i+2]*muP2).
+ *   Where k_used == 1.0, R1s and T1 are the rigid step's bit for bit.  The step is exactly invariant under a
+ *   power-of-two scaling of all coordinates (k_used, R1s and the return value bit-identical, T1 scaled) while nothing
+ *   leaves the normal range.  Accuracy of k: DESIGN.md section 22.
+ *
+ * vcp_icp_sums_sim: one pass, the test handle.  Arguments, drop rule, kept, nn, keep and errors are
+ * vcp_icp_sums_gated's; sums has 18 entries.  gate = +inf is the ungated pass.
+ *
+ * vcp_selftest_horn_sim: the step on the host, compiled from the source the device runs; needs no device.  Returns 1
+ * (scale determined), 2 (not determined), 0 (the Horn solve failed: nothing but V written, as vcp_selftest_horn) or
+ * VCP_ERR_ARG: a NULL pointer, n <= 0, use_v without V, c NaN or <= 0, ratio_min NaN or <= 0, ratio_max NaN, +inf or
+ * < ratio_min.
+ *
+ * vcp_icp_sim: vcp_icp_gated with that step.  Everything not named here is vcp_icp_gated's, word for word: the
+ * landmarks, the default poses and starts, exactly max_iter rounds, the starved rule, the composition R <- R1s R,
+ * T <- R1s T + T1, the score over all ns points, the choice of the best pose, no output on an error, a pose's bits
+ * independent of the other poses, all rounds enqueued at once with one synchronisation.
+ *   Every pose carries c, 1.0 at the start; a round that is not starved runs the step on (sums, kept, c).
+ *   ratio [n_poses]     (may be NULL) the final c: the nominal product of the applied factors.  The pose's actual scale is
+ *                       sqrt|det| of its planar block; it differs from c times the start's scale by roundings only.
+ *   unscaled [n_poses]  (may be NULL) the number of rounds whose scale was not determined.
+ * VCP_ERR_ARG also for ratio_min NaN or <= 0, ratio_max NaN, +inf or < ratio_min, and unless ratio_min <= 1 <= ratio_max.
+ * A failed Horn solve in a round that is not starved: VCP_ERR_ARG.  With ratio_min == ratio_max == 1.0 every factor is
+ * 1.0 / 1.0: M_all, mean_dist, inliers, best, kept and starved equal vcp_icp_gated's bit for bit and ratio is 1.0.
+ * Timing phases: icps_rounds, icps_score (csrc/icp.hip). */
+int vcp_icp_sums_sim(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
+                     const double R[9], const double T[3], double gate, double sums[18], int64_t* kept, int32_t* nn,
+                     uint8_t* keep);
+int vcp_selftest_horn_sim(const double sums[18], int64_t n, double V[16], int use_v, double c, double ratio_min,
+                          double ratio_max, double R1s[9], double T1[3], double* k_used, double* c_new);
+int vcp_icp_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* gates,
+                int32_t n_gates, int32_t min_pairs, double ratio_min, double ratio_max, double inlier_dist,
+                double M_best[16], int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
+                int32_t* starved, double* ratio, int32_t* unscaled);
+
 /* -- congruent-pair global registration ---------------------------------------------------------------
  * Every ICP form above starts from T0 = mean(target) - R0 mean(source) unless told otherwise, which is only right when
  * the scan covers the whole truth field; a scan that sees part of it starts wrong by a large translation from every

@@ -35,7 +35,7 @@ SYMBOLS = [
     "vcp_icp_sums_gated", "vcp_icp_gated", "vcp_icp_sums_trimmed", "vcp_icp_trimmed", "vcp_match_unique", "vcp_match_unique_dev",
     "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_register_sim",
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
-    "vcp_gdbscan", "vcp_gdbscan_dev",
+    "vcp_gdbscan", "vcp_gdbscan_dev", "vcp_icp_sums_sim", "vcp_selftest_horn_sim", "vcp_icp_sim",
 ]
 
 
@@ -321,6 +321,23 @@ class Context:
         self._chk(lib().vcp_icp_sums_gated(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
                                            C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums),
                                            C.byref(kept), _ptr(nn), _ptr(keep)))
+        return sums, kept.value, nn, keep
+
+    def icp_sums_sim(self, model, data, gate, R=None, T=None, want_nn=True, want_keep=True):
+        """One pass of the similarity form (vcp_icp_sums_sim): icp_sums_gated with sum |p|^2 at 16 and sum |y|^2 at 17
+        over the kept pairs, through the same tree.  Returns (sums [18], kept, nn [nd] int32 or None, keep [nd] uint8 or
+        None)."""
+        model = _f64(model, 3)
+        data = _f64(data, 3)
+        R = None if R is None else _f64(R).reshape(9)
+        T = None if T is None else _f64(T).reshape(3)
+        sums = np.zeros(18)
+        kept = C.c_int64(0)
+        nn = np.zeros(len(data), np.int32) if want_nn else None
+        keep = np.zeros(len(data), np.uint8) if want_keep else None
+        self._chk(lib().vcp_icp_sums_sim(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data), C.c_int64(len(data)),
+                                         _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums), C.byref(kept), _ptr(nn),
+                                         _ptr(keep)))
         return sums, kept.value, nn, keep
 
     def icp_sums_trimmed(self, model, data, m, R=None, T=None, want_nn=True, want_keep=True):
@@ -751,6 +768,43 @@ class Context:
         return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
                     kept=kept, starved=starved)
 
+    def icp_sim(self, source, target, gates, ratio_range, poses=1, init_T=None, max_iter=100, max_landmarks=200,
+                min_pairs=3, inlier_dist=np.inf):
+        """icp_gated whose rounds fit one isotropic scale beside the rotation and the translation (vcp_icp_sim).
+        ratio_range = (ratio_min, ratio_max), ratio_min <= 1 <= ratio_max: the bounds on the product of the scale
+        factors a pose applies to its start.  Returns icp_gated's dict plus ratio [H] (that product) and unscaled [H]
+        int32 (rounds whose scale the kept pairs did not determine)."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        gates = _f64(gates).reshape(-1)
+        rmin, rmax = (float(v) for v in ratio_range)
+        if isinstance(poses, (int, np.integer)):
+            H, init_R = int(poses), None
+        else:
+            init_R = _f64(poses).reshape(-1, 9)
+            H = len(init_R)
+        if init_T is not None:
+            init_T = _f64(init_T, 3)
+            if len(init_T) != H:
+                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
+        n = max(H, 0)
+        M = np.zeros(16)
+        M_all = np.zeros((n, 16))
+        md = np.zeros(n)
+        inl = np.zeros(n, np.int32)
+        kept = np.zeros(n, np.int64)
+        starved = np.zeros(n, np.int32)
+        ratio = np.zeros(n)
+        unscaled = np.zeros(n, np.int32)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_icp_sim(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target), C.c_int64(len(target)),
+                                    C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter), int(max_landmarks),
+                                    _ptr(gates), C.c_int32(len(gates)), C.c_int32(min_pairs), C.c_double(rmin),
+                                    C.c_double(rmax), C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all),
+                                    _ptr(md), _ptr(inl), _ptr(kept), _ptr(starved), _ptr(ratio), _ptr(unscaled)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
+                    kept=kept, starved=starved, ratio=ratio, unscaled=unscaled)
+
     def icp_trimmed(self, source, target, keep, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
                     inlier_dist=np.inf):
         """icp_multistart with a per-round keep share (vcp_icp_trimmed): round r (1-based) fits on the
@@ -871,6 +925,25 @@ class Context:
                                            int(xdir), int(ydir), int(dedupe), _ptr(xyz), _ptr(state), C.byref(kept),
                                            C.byref(dup)))
         return dict(xyz=xyz, state=state, kept=kept.value, duplicates=dup.value)
+
+
+def selftest_horn_sim(sums, n, c=1.0, ratio_range=(1.0, 1.0), V=None):
+    """vcp_selftest_horn_sim: one step of the similarity ICP on the host (no device), from the source the device runs.
+    V [16] (updated in place) is the carried eigenvector basis, None for a cold start.  Returns dict(rc = 1 (scale
+    determined), 2 (not determined) or 0 (the Horn solve failed: the other entries are None), R1s [9], T1 [3], k_used,
+    c_new)."""
+    sums = _f64(sums).reshape(18)
+    R1s, T1 = np.zeros(9), np.zeros(3)
+    ku, cn = C.c_double(0), C.c_double(0)
+    rmin, rmax = ratio_range
+    rc = lib().vcp_selftest_horn_sim(_ptr(sums), C.c_int64(int(n)), _ptr(V), C.c_int(0 if V is None else 1),
+                                     C.c_double(c), C.c_double(rmin), C.c_double(rmax), _ptr(R1s), _ptr(T1), C.byref(ku),
+                                     C.byref(cn))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_horn_sim")
+    if rc == 0:
+        return dict(rc=0, R1s=None, T1=None, k_used=None, c_new=None)
+    return dict(rc=rc, R1s=R1s, T1=T1, k_used=ku.value, c_new=cn.value)
 
 
 def selftest_register_pose(a, b, ti, tj, f=0):

@@ -61,6 +61,14 @@ struct GateArgs {
   uint8_t* keep;    // [nd] or NULL
 };
 struct NoGate {};
+// Similarity ICP (vcp.h, "similarity ICP"): the gated pass with two more columns, sum |p|^2 at 16 and sum |y|^2 at 17,
+// through the same tree.  A type of its own: the kernels of GateArgs stay the 16-wide ones they were.
+struct SimGate {
+  GateArgs g;
+};
+// columns of a pass's rows
+template <class G>
+constexpr int icp_ncol = std::is_same<G, SimGate>::value ? 18 : 16;
 
 // Trimmed ICP (vcp.h, "trimmed ICP"): a round keeps the m landmarks with the smallest 96-bit keys [K(dd) | index].
 // Three steps per round and pose: a pass that runs the NN search and stores K(dd) and the index found (G = TrimDist),
@@ -88,8 +96,10 @@ struct TrimSum {
 };
 __device__ __forceinline__ uint8_t* keep_of(const GateArgs& g) { return g.keep; }
 __device__ __forceinline__ uint8_t* keep_of(const TrimSum& t) { return t.a.keep; }
+__device__ __forceinline__ uint8_t* keep_of(const SimGate& s) { return s.g.keep; }
 __device__ __forceinline__ uint32_t* pkept_of(const GateArgs& g) { return g.pkept; }
 __device__ __forceinline__ uint32_t* pkept_of(const TrimSum& t) { return t.a.pkept; }
+__device__ __forceinline__ uint32_t* pkept_of(const SimGate& s) { return s.g.pkept; }
 // K(dd): dd's bit pattern (dd >= +0, so the unsigned order is the numeric one, +inf last of the numbers), NaN above all
 __device__ __forceinline__ unsigned long long trim_key(double dd) {
   return dd != dd ? ~0ull : (unsigned long long)__double_as_longlong(dd);
@@ -172,6 +182,7 @@ constexpr int MTILE = 1024;
 __device__ __forceinline__ double gate_now(const GateArgs& ga, const IcpState* st) {
   return ga.gates[min(st->round + 1, ga.n_gates) - 1];
 }
+__device__ __forceinline__ double gate_now(const SimGate& sg, const IcpState* st) { return gate_now(sg.g, st); }
 // The keep count of the round a trimmed kernel runs now: min(L, ceil(f * L)), one multiplication; f in (0, 1] (checked
 // on the host), so the count lies in [1, L].
 __device__ __forceinline__ long long trim_m(const TrimArgs& a, const IcpState* st, long long L) {
@@ -201,12 +212,14 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
                                               int nm, const double* __restrict__ data, int64_t nd,
                                               const IcpState* __restrict__ st, double* __restrict__ partial,
                                               int32_t* __restrict__ nn, const NNGrid& ng, const G& ga) {
-  constexpr bool GATED = std::is_same<G, GateArgs>::value;
+  constexpr bool SIM = std::is_same<G, SimGate>::value;  // GATED with the two columns of the scale
+  constexpr bool GATED = std::is_same<G, GateArgs>::value || SIM;
+  constexpr int NS = icp_ncol<G>;
   // TDIST: the search alone, K(dd) and the index stored per landmark; TSUM: no search, the stored index, and the sums
   // of the landmarks whose key is <= the selected one
   constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
-  partial += (size_t)blockIdx.y * gridDim.x * 16;
+  partial += (size_t)blockIdx.y * gridDim.x * NS;
   if (st->done) return;
   double gate = 0.0;
   uint32_t nkept = 0;
@@ -237,9 +250,9 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
   // 4.5 u S^2, three fused roundings 13.5 u S^2), so a model point can be the binary64 winner only if
   // score <= best score + 54 u S^2; 2^-17 S^2 = 128 u S^2 is used.  The bound is per data point.
   const double cen0 = st->cen[0], cen1 = st->cen[1], cen2 = st->cen[2], mmax = st->mmax;
-  double s[16];
+  double s[NS];
 #pragma unroll
-  for (int k = 0; k < 16; k++) s[k] = 0.0;
+  for (int k = 0; k < NS; k++) s[k] = 0.0;
   // GRID: nng::NNG consecutive lanes work one data point (they split the rows of its search block)
   constexpr int LPQ = GRID ? nng::NNG : 1;
   const int sub = GRID ? (int)(threadIdx.x & (LPQ - 1)) : 0;
@@ -418,6 +431,10 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
         for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[r] * y[c] : 0.0;
       }
       s[15] += kp ? dd : 0.0;
+      if constexpr (SIM) {
+        s[16] += kp ? (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2] : 0.0;
+        s[17] += kp ? (y0 * y0 + y1 * y1) + y2 * y2 : 0.0;
+      }
     } else {
 #pragma unroll
       for (int r = 0; r < 3; r++) {
@@ -430,7 +447,7 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
       s[15] += e0 * e0 + e1 * e1 + e2 * e2;
     }
   }
-  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
+  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
   if constexpr (GATED || TSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
@@ -447,6 +464,15 @@ __global__ __launch_bounds__(TB) void k_icp_pass_gated(const double* __restrict_
                                                       const double* __restrict__ data, int64_t nd,
                                                       const IcpState* __restrict__ st, double* __restrict__ partial,
                                                       int32_t* __restrict__ nn, NNGrid ng, GateArgs ga) {
+  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, ga);
+}
+
+template <int TB, int NNMODE>
+__global__ __launch_bounds__(TB) void k_icp_pass_sim(const double* __restrict__ model,
+                                                    const float4* __restrict__ model32, int nm,
+                                                    const double* __restrict__ data, int64_t nd,
+                                                    const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                    int32_t* __restrict__ nn, NNGrid ng, SimGate ga) {
   icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, ga);
 }
 
@@ -474,10 +500,12 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
                                                     int nm, const double* __restrict__ data, int64_t nd,
                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
                                                     int32_t* __restrict__ nn, uint32_t imask, double tolk, const G& ga) {
-  constexpr bool GATED = std::is_same<G, GateArgs>::value;  // as in icp_pass_body
+  constexpr bool SIM = std::is_same<G, SimGate>::value;  // as in icp_pass_body
+  constexpr bool GATED = std::is_same<G, GateArgs>::value || SIM;
+  constexpr int NS = icp_ncol<G>;
   constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
-  partial += (size_t)blockIdx.y * gridDim.x * 16;
+  partial += (size_t)blockIdx.y * gridDim.x * NS;
   if (st->done) return;
   double gate = 0.0;
   uint32_t nkept = 0;
@@ -500,9 +528,9 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
 #pragma unroll
   for (int k = 0; k < 3; k++) T[k] = st->T[k];
   const double cen0 = st->cen[0], cen1 = st->cen[1], cen2 = st->cen[2], mmax = st->mmax;
-  double s[16];
+  double s[NS];
 #pragma unroll
-  for (int k = 0; k < 16; k++) s[k] = 0.0;
+  for (int k = 0; k < NS; k++) s[k] = 0.0;
   const int64_t half = (nd + 1) >> 1;  // lane v works points v and v + half
   for (int64_t base = (int64_t)blockIdx.x * TB; base < half; base += (int64_t)gridDim.x * TB) {  // uniform trip count
     const int64_t v = base + threadIdx.x;
@@ -623,6 +651,10 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
           for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[h][r] * y[c] : 0.0;
         }
         s[15] += kp ? dd : 0.0;
+        if constexpr (SIM) {
+          s[16] += kp ? (p[h][0] * p[h][0] + p[h][1] * p[h][1]) + p[h][2] * p[h][2] : 0.0;
+          s[17] += kp ? (y0 * y0 + y1 * y1) + y2 * y2 : 0.0;
+        }
       } else {
 #pragma unroll
         for (int r = 0; r < 3; r++) {
@@ -636,7 +668,7 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       }
     }
   }
-  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * 16);
+  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
   if constexpr (GATED || TSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
@@ -654,6 +686,16 @@ __global__ __launch_bounds__(TB) void k_icp_pass_small_gated(const double* __res
                                                             const IcpState* __restrict__ st, double* __restrict__ partial,
                                                             int32_t* __restrict__ nn, uint32_t imask, double tolk,
                                                             GateArgs ga) {
+  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
+}
+
+template <int TB>
+__global__ __launch_bounds__(TB) void k_icp_pass_small_sim(const double* __restrict__ model,
+                                                          const float4* __restrict__ model32, int nm,
+                                                          const double* __restrict__ data, int64_t nd,
+                                                          const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                          int32_t* __restrict__ nn, uint32_t imask, double tolk,
+                                                          SimGate ga) {
   icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
 }
 
@@ -997,6 +1039,47 @@ __host__ __device__ inline bool horn(const double s[16], long long nd, double R1
   return true;
 }
 
+// The similarity step (vcp.h, "similarity ICP"): horn() on s[0..15] unchanged, then Horn's symmetric scale from the two
+// further columns, k = sqrt(vY / vP) with v = sum |x|^2 / N - |mu|^2, which does not depend on the rotation.  c is the
+// product of the factors applied so far; the new product c k is held in [ratio_min, ratio_max] by shortening this
+// round's factor.  Returns 0 (horn failed: nothing written), 1, or 2 (scale not determined: the rigid step, c stays).
+// Every operation is one binary64 rounding; where k_used is 1.0, R1s and T1 are horn()'s bit for bit (1.0 * x = x and
+// T1 is horn's expression).
+__host__ __device__ inline int horn_sim(const double s[18], long long n, double c, double ratio_min, double ratio_max,
+                                        double R1s[9], double T1[3], double* Vst, double* k_used, double* c_new) {
+  double R1[9], T1r[3];
+  if (!horn(s, n, R1, T1r, Vst)) return 0;
+  const double N = (double)n;
+  const double muP0 = s[0] / N, muP1 = s[1] / N, muP2 = s[2] / N;  // horn's means: the same divisions
+  const double muY0 = s[3] / N, muY1 = s[4] / N, muY2 = s[5] / N;
+  const double vP = s[16] / N - ((muP0 * muP0 + muP1 * muP1) + muP2 * muP2);
+  const double vY = s[17] / N - ((muY0 * muY0 + muY1 * muY1) + muY2 * muY2);
+  const double big = 1.7976931348623157e308;
+  const bool det = vP > 0.0 && vP <= big && vY > 0.0 && vY <= big;  // false for NaN
+  double ku = 1.0, cn = c;
+  if (det) {
+    const double k = sqrt(vY / vP), t = c * k;
+    if (t < ratio_min) {
+      cn = ratio_min;
+      ku = ratio_min / c;
+    } else if (t > ratio_max) {
+      cn = ratio_max;
+      ku = ratio_max / c;
+    } else {
+      cn = t;
+      ku = k;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 9; j++) R1s[j] = ku * R1[j];
+  const double muY[3] = {muY0, muY1, muY2};
+#pragma unroll
+  for (int i = 0; i < 3; i++) T1[i] = muY[i] - (R1s[3 * i] * muP0 + R1s[3 * i + 1] * muP1 + R1s[3 * i + 2] * muP2);
+  *k_used = ku;
+  *c_new = cn;
+  return det ? 1 : 2;
+}
+
 // R <- R1 R, T <- R1 T + T1 in the state (BaseClass/ICP.cs:163-177)
 __device__ __forceinline__ void icp_compose(IcpState* __restrict__ st, const double R1[9], const double T1[3]) {
   double tR[9], tT[3];
@@ -1020,16 +1103,17 @@ __device__ __forceinline__ void icp_compose(IcpState* __restrict__ st, const dou
 // (Running this in the pass's last workgroup -- ticket + release fence per workgroup -- was built and measured at
 // 1 M x 100: 74 us per round against 51 us for the two launches; the Horn solve's registers also halve the pass's
 // occupancy.  It stays a launch of its own.)
-template <int TB>
+// NS: columns of a row (18: the similarity pass; the state holds the first 16 all the same).
+template <int TB, int NS = 16>
 __device__ __forceinline__ void icp_fold_rows(const double* __restrict__ partial, int nb, IcpState* __restrict__ st,
                                               double* tot) {
-  double s[16];
+  double s[NS];
 #pragma unroll
-  for (int k = 0; k < 16; k++) s[k] = 0.0;
+  for (int k = 0; k < NS; k++) s[k] = 0.0;
   for (int b = threadIdx.x; b < nb; b += TB) {
 #pragma unroll
-    for (int k = 0; k < 16; k++)
-      s[k] += partial[(size_t)b * 16 + k];
+    for (int k = 0; k < NS; k++)
+      s[k] += partial[(size_t)b * NS + k];
   }
   block_fold<TB>(s, FoldSum(), tot);
   if (threadIdx.x < 16) st->sums[threadIdx.x] = tot[threadIdx.x];
@@ -1137,6 +1221,68 @@ __global__ __launch_bounds__(ITPB) void k_icp_step_gated(const double* __restric
   if (round >= a.max_iter) st->done = 1;
 }
 
+// The step of a similarity round (vcp.h, vcp_icp_sim): k_icp_step_gated over 18-wide rows, with horn_sim in horn's
+// place.  What the state has no room for lives in the pose's side record: the two further sums, the product c of the
+// factors applied and the count of rounds whose scale was not determined.
+struct SimSide {
+  double s16, s17;  // the last pass's sums[16], sums[17]
+  double c;
+  int unscaled, pad;
+};
+struct SimStepArgs {
+  double ratio_min, ratio_max;
+};
+__global__ __launch_bounds__(ITPB) void k_icp_step_sim(const double* __restrict__ partial,
+                                                      const uint32_t* __restrict__ pkept, int nb,
+                                                      IcpState* __restrict__ st, SimSide* __restrict__ side,
+                                                      GateStepArgs a, SimStepArgs sa) {
+  st += blockIdx.x;
+  side += blockIdx.x;
+  partial += (size_t)blockIdx.x * nb * 18;
+  pkept += (size_t)blockIdx.x * nb;
+  if (st->done) return;
+  __shared__ double tot[18];
+  __shared__ unsigned long long skept;
+  if (threadIdx.x == 0) skept = 0;
+  icp_fold_rows<ITPB, 18>(partial, nb, st, tot);  // its barrier orders the store above before the adds below
+  unsigned long long c = 0;
+  for (int b = threadIdx.x; b < nb; b += ITPB) c += pkept[b];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+  if ((threadIdx.x & 63) == 0) atomicAdd(&skept, c);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const long long kept = (long long)skept;
+  st->kept = kept;
+  side->s16 = tot[16];
+  side->s17 = tot[17];
+  if (a.sums_only) {
+    st->done = 1;
+    return;
+  }
+  st->pre_d = st->d;
+  st->d = tot[15];
+  const int round = st->round + 1;
+  st->round = round;
+  if (kept < a.min_pairs) {
+    st->starved = st->starved + 1;
+  } else {
+    double S[18];
+    for (int k = 0; k < 18; k++) S[k] = tot[k];
+    double R1s[9], T1[3], ku, cn;
+    const int rc = horn_sim(S, kept, side->c, sa.ratio_min, sa.ratio_max, R1s, T1, st->V, &ku, &cn);
+    if (rc == 0) {
+      st->failed = 1;
+      st->done = 1;
+      return;
+    }
+    side->c = cn;
+    if (rc == 2) side->unscaled = side->unscaled + 1;
+    icp_compose(st, R1s, T1);
+  }
+  if (round >= a.max_iter) st->done = 1;
+}
+
 void identity(IcpState& s) {
   std::memset(&s, 0, sizeof(s));
   s.R[0] = s.R[4] = s.R[8] = 1.0;
@@ -1158,6 +1304,12 @@ struct GateRun {
   long long min_pairs;
   uint8_t* d_keep;  // [nd] or NULL
 };
+// sr (may be NULL; only with gr): the gated run's similarity form -- 18-wide rows, the passes of SimGate and
+// k_icp_step_sim; the side records follow the kept counts on the device and the schedule in the staging area.
+struct SimRun {
+  double ratio_min, ratio_max;  // validated by the caller
+  SimSide* side_out;            // host, [nst]
+};
 // tr (may be NULL; never with gr): a trimmed run -- per round the distance pass, the select, the trimmed sums pass and
 // the gated step.  Its workspace is b_icpt: per (pose, landmark) 8 bytes of key and 4 of index, then per pose the
 // multi-workgroup select's 12 prefixes and 12 x 256 counters.
@@ -1175,7 +1327,7 @@ int32_t* icpt_nn(vcp_ctx* ctx, int nst, int64_t nd) {
 }
 int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState* init,
             int nst, double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn, bool all_rounds,
-            NNGrid* ng_out, const GateRun* gr = nullptr, const TrimRun* tr = nullptr) {
+            NNGrid* ng_out, const GateRun* gr = nullptr, const TrimRun* tr = nullptr, const SimRun* sr = nullptr) {
   hipStream_t st = ctx->stream;
   // small data sets: one wave per workgroup so that they reach more CUs; large models: LDS tiles
   const bool small0 = nd <= (int64_t)64 * ICP_MAX_BLOCKS;
@@ -1202,10 +1354,12 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   while (tolk * 0.5 >= (54.0 + 9.0 * (double)(1u << ib)) / 16777216.0) tolk *= 0.5;
   // the nst states (icp_states), then [nst][nb][16] partial rows; a gated run: then the schedule and [nst][nb] counts
   const size_t st_bytes = icp_states_bytes(nst);
-  const size_t part_bytes = (size_t)nst * nb * 16 * sizeof(double);
+  const int ncol = sr ? 18 : 16;
+  const size_t part_bytes = (size_t)nst * nb * ncol * sizeof(double);
   const int n_sched = gr ? gr->n_gates : tr ? tr->n_share : 0;  // doubles staged behind the partial rows
   const size_t cnt_bytes = ((size_t)nst * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
-  const size_t gate_bytes = gr   ? (size_t)n_sched * sizeof(double) + cnt_bytes
+  const size_t side_bytes = sr ? (size_t)nst * sizeof(SimSide) : 0;
+  const size_t gate_bytes = gr   ? (size_t)n_sched * sizeof(double) + cnt_bytes + side_bytes
                             : tr ? (size_t)n_sched * sizeof(double) + cnt_bytes + (size_t)nst * sizeof(TrimSel)
                                  : 0;
   VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + part_bytes + gate_bytes));
@@ -1220,13 +1374,17 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   float4* model32 = ctx->b_aux0.as<float4>();
   // a gated run stages its schedule behind the states: the caller's array may be gone before the copy has run
   const size_t h_bytes =
-      (size_t)nst * sizeof(IcpState) + (size_t)n_sched * sizeof(double) + (tr ? (size_t)nst * sizeof(TrimSel) : 0);
+      (size_t)nst * sizeof(IcpState) + (size_t)n_sched * sizeof(double) + (tr ? (size_t)nst * sizeof(TrimSel) : 0) +
+      (sr ? (size_t)nst * sizeof(SimSide) : 0);
   IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr && !tr ? ctx->pinned : vcp_stage(ctx, h_bytes));
   if (!h_st) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
   std::memcpy(h_st, init, (size_t)nst * sizeof(IcpState));
   VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, (size_t)nst * sizeof(IcpState), hipMemcpyHostToDevice, st));
   GateArgs ga{};
   GateStepArgs gsa{};
+  SimGate sga{};
+  SimStepArgs ssa{};
+  SimSide *d_side = nullptr, *h_side = nullptr;
   if (gr) {
     double* d_gates = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
     ga = GateArgs{d_gates, gr->n_gates, reinterpret_cast<uint32_t*>(d_gates + gr->n_gates), gr->d_keep};
@@ -1234,6 +1392,14 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     double* h_gates = reinterpret_cast<double*>(h_st + nst);
     std::memcpy(h_gates, gr->gates, (size_t)gr->n_gates * sizeof(double));
     VCP_HIP(ctx, hipMemcpyAsync(d_gates, h_gates, (size_t)gr->n_gates * sizeof(double), hipMemcpyHostToDevice, st));
+    if (sr) {  // every pose starts at c = 1, no round unscaled
+      sga.g = ga;
+      ssa = SimStepArgs{sr->ratio_min, sr->ratio_max};
+      d_side = reinterpret_cast<SimSide*>(reinterpret_cast<char*>(ga.pkept) + cnt_bytes);
+      h_side = reinterpret_cast<SimSide*>(h_gates + gr->n_gates);
+      for (int k = 0; k < nst; k++) h_side[k] = SimSide{0.0, 0.0, 1.0, 0, 0};
+      VCP_HIP(ctx, hipMemcpyAsync(d_side, h_side, (size_t)nst * sizeof(SimSide), hipMemcpyHostToDevice, st));
+    }
   }
   TrimDist td{};
   TrimSum ts{};
@@ -1282,7 +1448,10 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
       else                                                                                                              \
         VCP_LAUNCH(ctx, (k_icp_pass_trim<TBV, TL, TrimSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,        \
                    (int)nm, d_data, nd, d_st, part, ng, ts);                                                            \
-    } else if (gr)                                                                                                             \
+    } else if (sr)                                                                                                      \
+      VCP_LAUNCH(ctx, (k_icp_pass_sim<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data,   \
+                 nd, d_st, part, d_nn, ng, sga);                                                                        \
+    else if (gr)                                                                                                        \
       VCP_LAUNCH(ctx, (k_icp_pass_gated<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
                  nd, d_st, part, d_nn, ng, ga);                                                                         \
     else                                                                                                                \
@@ -1298,7 +1467,10 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
       else                                                                                                              \
         VCP_LAUNCH(ctx, (k_icp_pass_small_trim<TBV, TrimSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,      \
                    (int)nm, d_data, nd, d_st, part, imask, tolk, ts);                                                   \
-    } else if (gr)                                                                                                             \
+    } else if (sr)                                                                                                      \
+      VCP_LAUNCH(ctx, k_icp_pass_small_sim<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data,   \
+                 nd, d_st, part, d_nn, imask, tolk, sga);                                                               \
+    else if (gr)                                                                                                        \
       VCP_LAUNCH(ctx, k_icp_pass_small_gated<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
                  nd, d_st, part, d_nn, imask, tolk, ga);                                                                \
     else                                                                                                                \
@@ -1326,17 +1498,21 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
 #undef VCP_PASS
 #undef VCP_PASS_SMALL
       if (tr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, td.a.pkept, nb, d_st, gsa);
+      else if (sr)
+        VCP_LAUNCH(ctx, k_icp_step_sim, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, d_side, gsa, ssa);
       else if (gr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, gsa);
       else VCP_LAUNCH(ctx, k_icp_step, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, sa);
     }
     launched += batch;
     VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, (size_t)nst * sizeof(IcpState), hipMemcpyDeviceToHost, st));
     if (tr) VCP_HIP(ctx, hipMemcpyAsync(h_sel, td.a.sel, (size_t)nst * sizeof(TrimSel), hipMemcpyDeviceToHost, st));
+    if (sr) VCP_HIP(ctx, hipMemcpyAsync(h_side, d_side, (size_t)nst * sizeof(SimSide), hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (all_done() || launched >= max_iter || mode == MODE_SUMS_ONLY) break;
   }
   std::memcpy(out, h_st, (size_t)nst * sizeof(IcpState));
   if (tr) std::memcpy(tr->sel_out, h_sel, (size_t)nst * sizeof(TrimSel));
+  if (sr) std::memcpy(sr->side_out, h_side, (size_t)nst * sizeof(SimSide));
   for (int k = 0; k < nst; k++)
     if (out[k].failed) return vcp_fail(ctx, VCP_ERR_ARG, "Horn solve failed (non-finite sums)%s", nst > 1 ? " in a pose" : "");
   return VCP_OK;
@@ -1490,11 +1666,17 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
 // arguments, and kept / starved (each may be NULL) receive the states' counters.
 // tr (never with gr): the trimmed form, vcp_icp_trimmed -- likewise, and trim_dist (may be NULL) receives the root of
 // the last round's thr.
+// sr (only with gr): the similarity form, vcp_icp_sim -- its bounds are checked here, and ratio / unscaled (each may be
+// NULL) receive the side records' c and count.
+static bool sim_range_ok(double ratio_min, double ratio_max) {
+  return ratio_min > 0.0 && ratio_max >= ratio_min && ratio_max <= 1.7976931348623157e308;  // false for NaN
+}
 static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
                               int32_t n_poses, const double* init_R, const double* init_T, int max_iter,
                               int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all,
                               double* mean_dist, int32_t* inliers, const GateRun* gr, int64_t* kept, int32_t* starved,
-                              const TrimRun* tr = nullptr, double* trim_dist = nullptr) {
+                              const TrimRun* tr = nullptr, double* trim_dist = nullptr, const SimRun* sr = nullptr,
+                              double* ratio = nullptr, int32_t* unscaled = nullptr) {
   if (!ctx) return VCP_ERR_ARG;
   if (ns <= 0 || nt <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty source or target");
   if (max_iter < 1 || max_landmarks < 1 || !source || !target || !M_best || !best)
@@ -1513,6 +1695,12 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     for (int k = 0; k < gr->n_gates; k++)
       if (!(gr->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
   }
+  if (sr) {
+    if (!sim_range_ok(sr->ratio_min, sr->ratio_max))
+      return vcp_fail(ctx, VCP_ERR_ARG, "need 0 < ratio_min <= ratio_max < inf");
+    if (!(sr->ratio_min <= 1.0 && 1.0 <= sr->ratio_max))
+      return vcp_fail(ctx, VCP_ERR_ARG, "need ratio_min <= 1 <= ratio_max");
+  }
   if (tr) {
     if (tr->n_share < 1 || !tr->share) return vcp_fail(ctx, VCP_ERR_ARG, "n_keep < 1");
     if (tr->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
@@ -1521,7 +1709,7 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   }
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
-  vcp_phase(ctx, tr ? "icpt_rounds" : gr ? "icpg_rounds" : "icpms_rounds");
+  vcp_phase(ctx, tr ? "icpt_rounds" : sr ? "icps_rounds" : gr ? "icpg_rounds" : "icpms_rounds");
   int64_t step = 1;
   if (ns > max_landmarks) step = ns / max_landmarks;
   const int64_t nb = ns / step;
@@ -1546,6 +1734,12 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   if (tr) {
     trun = *tr;
     trun.sel_out = sel.data();
+  }
+  std::vector<SimSide> side(sr ? (size_t)n_poses : 0);
+  SimRun srun{};
+  if (sr) {
+    srun = *sr;
+    srun.side_out = side.data();
   }
   for (int h = 0; h < n_poses; h++) {
     IcpState& s = init[h];
@@ -1574,10 +1768,11 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   VCP_HIP(ctx, hipStreamSynchronize(st));  // `a` is a local buffer
   NNGrid ng{};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init.data(), n_poses, 0.0,
-                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr, tr ? &trun : nullptr));
+                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr, tr ? &trun : nullptr,
+                  sr ? &srun : nullptr));
   // score every pose over ALL source points with vcp_match's arithmetic, on the grid the rounds used (vcp_match bins
   // a target of more than 512 points too, and falls back to the full scan on the same condition)
-  vcp_phase(ctx, tr ? "icpt_score" : gr ? "icpg_score" : "icpms_score");
+  vcp_phase(ctx, tr ? "icpt_score" : sr ? "icps_score" : gr ? "icpg_score" : "icpms_score");
   const double* d_src = step > 1 ? ctx->b_in3.as<double>() : ctx->b_in2.as<double>();  // step 1: the landmarks are all
   const IcpState* d_st = icp_states(ctx);
   uint32_t* d_cnt = ctx->b_out0.as<uint32_t>();
@@ -1616,6 +1811,8 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     if (inliers) inliers[h] = (int32_t)h_cnt[h];
     if (kept) kept[h] = (int64_t)fin[h].kept;
     if (starved) starved[h] = fin[h].starved;
+    if (sr && ratio) ratio[h] = side[h].c;
+    if (sr && unscaled) unscaled[h] = side[h].unscaled;
     if (tr && trim_dist) {
       double thr;
       std::memcpy(&thr, &sel[h].key, sizeof(thr));
@@ -1661,17 +1858,38 @@ int vcp_icp_trimmed(vcp_ctx* ctx, const double* source, int64_t ns, const double
                             M_best, best, M_all, mean_dist, inliers, nullptr, kept, starved, &tr, trim_dist);
 }
 
+// vcp_icp_gated whose rounds fit one isotropic scale beside the rotation and the translation (vcp.h)
+int vcp_icp_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* gates,
+                int32_t n_gates, int32_t min_pairs, double ratio_min, double ratio_max, double inlier_dist,
+                double M_best[16], int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
+                int32_t* starved, double* ratio, int32_t* unscaled) {
+  const GateRun gr{gates, n_gates, min_pairs, nullptr};
+  const SimRun sr{ratio_min, ratio_max, nullptr};
+  return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
+                            M_best, best, M_all, mean_dist, inliers, &gr, kept, starved, nullptr, nullptr, &sr, ratio,
+                            unscaled);
+}
+
 // Host-side run of the Horn step the device executes per round (same source: horn() is __host__ __device__).
 int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v, double R1[9], double T1[3]) {
   if (!sums || !R1 || !T1 || nd <= 0 || (use_v && !V)) return VCP_ERR_ARG;
   return horn(sums, (long long)nd, R1, T1, use_v ? V : nullptr) ? 1 : 0;
 }
 
+// Host-side run of the similarity step (horn_sim is __host__ __device__ too).  Returns 0, 1 or 2 as horn_sim does.
+int vcp_selftest_horn_sim(const double sums[18], int64_t n, double V[16], int use_v, double c, double ratio_min,
+                          double ratio_max, double R1s[9], double T1[3], double* k_used, double* c_new) {
+  if (!sums || !R1s || !T1 || !k_used || !c_new || n <= 0 || (use_v && !V)) return VCP_ERR_ARG;
+  if (!(c > 0.0) || !sim_range_ok(ratio_min, ratio_max)) return VCP_ERR_ARG;
+  return horn_sim(sums, (long long)n, c, ratio_min, ratio_max, R1s, T1, use_v ? V : nullptr, k_used, c_new);
+}
+
 // gate (NULL: vcp_icp_sums): one gated pass, vcp_icp_sums_gated; kept and keep receive its verdicts
 // m (never with gate): one trimmed round's passes, vcp_icp_sums_trimmed; thr_dd and keep receive its verdicts
 static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                         const double T[3], double sums[16], int32_t* nn, const double* gate, int64_t* kept,
-                        uint8_t* keep, const int64_t* m = nullptr, double* thr_dd = nullptr) {
+                        uint8_t* keep, const int64_t* m = nullptr, double* thr_dd = nullptr, bool sim = false) {
   if (!ctx) return VCP_ERR_ARG;
   if (nm <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty model");
   if (nd <= 0 || !model || !data || !sums) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
@@ -1696,10 +1914,16 @@ static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const dou
   const GateRun gr{gate, 1, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr};
   TrimSel sel{};
   const TrimRun tr{nullptr, 0, m ? (long long)*m : 0, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr, &sel};
+  SimSide side{};
+  const SimRun sr{1.0, 1.0, &side};  // sim (only with gate): the 18-wide pass, sums [18]
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, &init, 1, 0.0, VCP_STOP_SSE_DELTA, 1,
                   MODE_SUMS_ONLY, &fin, nn && !m ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr,
-                  gate ? &gr : nullptr, m ? &tr : nullptr));
+                  gate ? &gr : nullptr, m ? &tr : nullptr, sim ? &sr : nullptr));
   std::memcpy(sums, fin.sums, sizeof(fin.sums));
+  if (sim) {
+    sums[16] = side.s16;
+    sums[17] = side.s17;
+  }
   if (gate) *kept = (int64_t)fin.kept;
   if (m) {
     std::memcpy(thr_dd, &sel.key, sizeof(double));
@@ -1720,6 +1944,11 @@ int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* da
 int vcp_icp_sums_gated(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                        const double T[3], double gate, double sums[16], int64_t* kept, int32_t* nn, uint8_t* keep) {
   return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep);
+}
+
+int vcp_icp_sums_sim(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
+                     const double T[3], double gate, double sums[18], int64_t* kept, int32_t* nn, uint8_t* keep) {
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep, nullptr, nullptr, true);
 }
 
 int vcp_icp_sums_trimmed(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,

@@ -345,6 +345,64 @@ namespace vtkPointCloud
             ShowIcpSolution(SourcePolydata, TargetPolydata);
         }
 
+        // ICPGated() for centroids whose unit is only roughly the truths' (vtkLandmarkTransform's Similarity mode, which
+        // ICP() switches off at FrmMain.cs:854 because showTruesAndCenters scaled by the bounding boxes first): every round
+        // also fits one isotropic scale from the centroids inside the gate.  The start is startScale times a rotation about
+        // z (the bounding-box factor, or RegisterSimilarity's k); the rounds may change the scale by a factor within
+        // [1 / maxRatio, maxRatio].  A start scale that is off by 2 % moves the edge of a 20 x 20 field by more than a
+        // closed gate of 0.1, and ICPGated() then keeps only the middle of the field.  M is set as by ICP().
+        void ICPSimilarity(int angles, double startScale, double maxRatio, double gateStart, double gateEnd, double matchDistance)
+        {
+            ren = new vtk.vtkRenderer();
+            vtk.vtkPolyData SourcePolydata = Tools.ArrayList2PolyData(1, this.centers, this.trueScale, this.centroidScale,
+                this.scale, this.clock, this.clock_y, this.clock_x);
+            vtk.vtkPolyData TargetPolydata = new vtk.vtkPolyData();
+            TargetPolydata.SetPoints(truePointCloud);
+            TargetPolydata.SetVerts(truePointVertices);
+
+            int ns = centers.Count;
+            double[] src = new double[3 * Math.Max(ns, 1)];
+            for (int i = 0; i < ns; i++) { src[3 * i] = centers[i].tmp_X; src[3 * i + 1] = centers[i].tmp_Y; src[3 * i + 2] = 0.0; }
+            double[] tgt = TruthArray();
+            int nt = tgt.Length / 3;
+            // means for the start translation T0 = mean(truths) - R0 mean(centroids), R0 = startScale Rz
+            double[] ms = new double[3], mt = new double[3];
+            for (int i = 0; i < ns; i++) for (int c = 0; c < 3; c++) ms[c] += src[3 * i + c];
+            for (int i = 0; i < nt; i++) for (int c = 0; c < 3; c++) mt[c] += tgt[3 * i + c];
+            for (int c = 0; c < 3; c++) { ms[c] /= Math.Max(ns, 1); mt[c] /= Math.Max(nt, 1); }
+            double[] initR = new double[9 * angles], initT = new double[3 * angles];
+            for (int h = 0; h < angles; h++)
+            {
+                double t = h * (2.0 * Math.PI / angles), c = startScale * Math.Cos(t), s = startScale * Math.Sin(t);
+                double[] r0 = { c, 0.0 - s, 0.0, s, c, 0.0, 0.0, 0.0, startScale };
+                Array.Copy(r0, 0, initR, 9 * h, 9);
+                for (int r = 0; r < 3; r++)
+                    initT[3 * h + r] = mt[r] - (r0[3 * r] * ms[0] + r0[3 * r + 1] * ms[1] + r0[3 * r + 2] * ms[2]);
+            }
+            const int steps = 10;
+            double[] gates = new double[steps];
+            for (int k = 0; k < steps; k++) gates[k] = gateStart * Math.Pow(gateEnd / gateStart, k / (steps - 1.0));
+            gates[0] = gateStart;
+            gates[steps - 1] = gateEnd;
+            double[] m16 = new double[16];
+            int[] inliers = new int[Math.Max(angles, 1)];
+            long[] kept = new long[Math.Max(angles, 1)];
+            int[] starved = new int[Math.Max(angles, 1)];
+            double[] ratio = new double[Math.Max(angles, 1)];
+            int[] unscaled = new int[Math.Max(angles, 1)];
+            int best;
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_icp_sim(lease.Ctx, src, ns, tgt, nt, angles, initR, initT, 100, 200, gates,
+                    steps, 3, 1.0 / maxRatio, maxRatio, matchDistance, m16, out best, null, null, inliers, kept, starved, ratio,
+                    unscaled));
+            M = new vtk.vtkMatrix4x4();
+            for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) M.SetElement(r, c, m16[4 * r + c]);
+            Console.WriteLine("相似变换矩阵为：" + M + " (start " + best + " of " + angles + ", " + inliers[best] + " / " + ns
+                + ", " + kept[best] + " inside the gate, scale " + startScale * ratio[best] + " = start x " + ratio[best] + ", "
+                + starved[best] + " starved and " + unscaled[best] + " unscaled rounds)");
+            ShowIcpSolution(SourcePolydata, TargetPolydata);
+        }
+
         // the display part of FrmMain.cs:863-906: the centroids moved by M next to the truths
         void ShowIcpSolution(vtk.vtkPolyData SourcePolydata, vtk.vtkPolyData TargetPolydata)
         {

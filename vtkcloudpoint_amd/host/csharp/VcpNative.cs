@@ -98,6 +98,20 @@ namespace vtkPointCloud
             int n_keep, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
             double[] mean_dist, int[] inliers, long[] kept, int[] starved, double[] trim_dist);
 
+        // similarity ICP (vcp.h): the gated loop whose rounds also fit one isotropic scale, the product of the factors held
+        // in [ratio_min, ratio_max] (ratio_min <= 1 <= ratio_max).  One pass (the test handle: vcp_icp_sums_gated with
+        // sums [18]; nn and keep may be null), the step on the host (returns 1, 2 = scale not determined, 0 = failed; V may
+        // be null with use_v = 0) and the loop; kept, starved, ratio and unscaled may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_sums_sim(IntPtr ctx, double[] model, long nm, double[] data,
+            long nd, double[] R, double[] T, double gate, double[] sums, out long kept, int[] nn, byte[] keep);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_selftest_horn_sim(double[] sums, long n, double[] V, int use_v, double c,
+            double ratio_min, double ratio_max, double[] R1s, double[] T1, out double k_used, out double c_new);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_sim(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int n_poses, double[] init_R, double[] init_T, int max_iter, int max_landmarks, double[] gates,
+            int n_gates, int min_pairs, double ratio_min, double ratio_max, double inlier_dist, double[] M_best,
+            out int best, double[] M_all, double[] mean_dist, int[] inliers, long[] kept, int[] starved, double[] ratio,
+            int[] unscaled);
+
         // congruent-pair global registration (no counterpart in the reference; bases = pairs of source indices)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_pairs(IntPtr ctx, double[] source, long ns, double[] target,
             long nt, int[] bases, int n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist,

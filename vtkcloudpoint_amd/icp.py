@@ -1,5 +1,5 @@
-"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start, gated, trimmed and
-global (congruent-pair) ICP for MainForm.ICP's centroid-to-truth matching."""
+"""Drop-in mirrors of BaseClass/ICP.cs and the slice of BaseClass/Matrix.cs it uses, and multi-start, gated, trimmed,
+similarity and global (congruent-pair) ICP for MainForm.ICP's centroid-to-truth matching."""
 import math
 
 import numpy as np
@@ -217,6 +217,24 @@ def gated_icp(centers, truths, gates, n_angles=1, mirror=False, init_T=None, max
     return ctx.icp_gated(src, tgt, gates, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
 
 
+def similarity_icp(centers, truths, gates, ratio_range, n_angles=1, mirror=False, init_T=None, max_iter=100,
+                   max_landmarks=200, min_pairs=3, inlier_dist=np.inf, ctx=None):
+    """gated_icp whose every round also fits one isotropic scale (vcp_icp_sim: Horn's symmetric scale of the kept pairs,
+    sqrt(spread of the truths / spread of the centroids)), for centroids whose unit is only roughly the truths': a start
+    scale that is off by 2 % moves the edge of a 20 x 20 field by more than a closed gate of 0.1, and the rigid loop then
+    keeps only the middle of the field.  ratio_range = (lo, hi), lo <= 1 <= hi, bounds the product of the factors a pose
+    applies to its start; (1, 1) is gated_icp bit for bit.  n_angles may also be an [H, 3, 3] array of start matrices
+    (rotations times the start scale).  Returns Context.icp_sim's dict (gated_icp's plus ratio, unscaled)."""
+    ctx = ctx or default_context()
+    src = _points(centers)
+    tgt = _points(truths)
+    if isinstance(n_angles, (int, np.integer)):
+        poses = rotations_about_z(n_angles, mirror) if mirror else int(n_angles)
+    else:
+        poses = np.asarray(n_angles, np.float64)
+    return ctx.icp_sim(src, tgt, gates, ratio_range, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
+
+
 def trim_schedule(start, end, rounds):
     """`rounds` keep shares that fall linearly from `start` to `end` (1 >= start >= end > 0): the first entry is exactly
     `start`, the last exactly `end`, and the list never rises.  rounds = 1 gives [end].  vcp_icp_trimmed holds the last
@@ -365,7 +383,7 @@ def global_sim_icp(centers, truths, bases, scale_range, inlier_dist, gates, mirr
     Returns gated_icp's dict (of the last call; best indexes its poses) plus registration = register_similarity's dict,
     bases_used, scale = the returned pose's scale (sqrt |det| of its planar block) and scale_registration = the registered k
     of the base whose start won the first call.  ValueError when
-    no base has a hypothesis."""
+    no base has a hypothesis.  global_similarity_icp is the form whose polish fits the scale on the device."""
     ctx = ctx or default_context()
     src, tgt = _points(centers), _points(truths)
     lo, hi = scale_range
@@ -389,6 +407,30 @@ def global_sim_icp(centers, truths, bases, scale_range, inlier_dist, gates, mirr
             out = ctx.icp_gated(src, tgt, gates, R0[None], np.ascontiguousarray(T0)[None], max_iter, max_landmarks,
                                 min_pairs, inlier_dist)
     out.update(registration=reg, bases_used=used, scale=_linear_scale(out["M"][:3, :3]), scale_registration=scale_reg)
+    return out
+
+
+def global_similarity_icp(centers, truths, bases, scale_range, inlier_dist, gates, ratio_range, mirror=False,
+                          max_iter=20, max_landmarks=200, min_pairs=3, ctx=None):
+    """global_sim_icp whose polish fits the scale itself: register_similarity, then ONE similarity_icp call
+    (vcp_icp_sim) started from the similarity of every base that found one, the product of each pose's scale factors
+    held in ratio_range = (lo, hi), lo <= 1 <= hi.  There is no host refit: the rounds do on the device what
+    global_sim_icp's match_unique / fit_scale / second-call alternation approximates.  Returns similarity_icp's dict
+    (best indexes the started poses; ratio, unscaled) plus registration, bases_used, scale = the returned pose's scale
+    (sqrt |det| of its planar block) and scale_registration, as global_sim_icp reports them.  ValueError when no base
+    has a hypothesis."""
+    ctx = ctx or default_context()
+    src, tgt = _points(centers), _points(truths)
+    lo, hi = scale_range
+    reg = ctx.register_sim(src, tgt, bases, float(lo), float(hi), inlier_dist, mirror, max_landmarks)
+    used = np.flatnonzero(reg["score"] >= 0)
+    if len(used) == 0:
+        raise ValueError("no base has a target pair with a length ratio in scale_range")
+    M = reg["M_all"][used]
+    out = ctx.icp_sim(src, tgt, gates, ratio_range, np.ascontiguousarray(M[:, :3, :3]), np.ascontiguousarray(M[:, :3, 3]),
+                      max_iter, max_landmarks, min_pairs, inlier_dist)
+    out.update(registration=reg, bases_used=used, scale=_linear_scale(out["M"][:3, :3]),
+               scale_registration=float(reg["scale"][used[out["best"]]]))
     return out
 
 
