@@ -554,6 +554,56 @@ int vcp_icp_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* ta
                 double M_best[16], int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
                 int32_t* starved, double* ratio, int32_t* unscaled);
 
+/* -- unique-correspondence ICP -----------------------------------------------------------------------
+ * Every loop above pairs each landmark with its nearest target on its own, so two centroids may fit against one truth.
+ * A target produces one centroid: where DBSCAN splits a target, or a reflection or an edge return makes a second
+ * cluster beside it, one of the two is a ghost.  A gate cannot remove it (it lies inside any gate that still admits the
+ * real centroids' start error) and a trim share does not know that its truth is taken.  This form lets every target
+ * take ONE landmark per round, the closest (Zinsser et al. 2003, "picky ICP"); vcp_match_unique does the same at the
+ * end of the pipeline.
+ *
+ * One round, state (R, T), gate g.
+ *   Pair and distance: vcp_icp_sums's.  p = R d + T, the nearest target y with the lowest index on ties, e = p - y,
+ *     dd = e0*e0 + e1*e1 + e2*e2    the SSE term: binary64, left to right, no contraction.
+ *   Key: the trimmed form's.  Landmark i (its position in the landmark list, 0-based) has the 96-bit key [K(dd) | i],
+ *     K(dd) = the bit pattern of dd as a uint64 when dd is not NaN, 0xFFFFFFFFFFFFFFFF when it is.
+ *   Winner: the WINNER of target j is the landmark with the smallest key among all landmarks whose nearest target is j.
+ *     The gate plays no part in this choice: a winner the gate drops does not hand its target to the next landmark.
+ *   Kept: a landmark is KEPT iff it is its target's winner and the gate does not drop it; the gate drops iff
+ *     sqrt(dd) >= g, as in vcp_icp_sums_gated.  A NaN dd wins only where every pair of that target is NaN; it is then
+ *     kept and poisons the sums, as it does ungated.  Every other pair adds +0.0 to each of the 16 sums AT ITS OWN PLACE
+ *     in vcp_icp_sums's summation order, which stays fixed by (nm, nd, whether every model coordinate is finite) and
+ *     nothing else.
+ *   kept = the number of kept pairs.  lost = the number of pairs that are not their target's winner, whatever the gate
+ *     says of them.
+ *   Step, starved rule, basis carry, composition, mean_dist (= sqrt(sums[15] / kept), +inf at kept = 0), score and the
+ *     choice of the best pose: vcp_icp_gated's, word for word.
+ *
+ * vcp_icp_sums_unique: one round's passes, the test handle as vcp_icp_sums_gated is.  Arguments as vcp_icp_sums_gated,
+ * then *lost (required).  keep [nd] (may be NULL): 2 = not the winner, 0 = winner dropped by the gate, 1 = kept.
+ * Errors are vcp_icp_sums_gated's; a NULL lost is VCP_ERR_ARG; the key holds the landmark in 32 bits: nd >= 2^32 is
+ * VCP_ERR_TOO_LARGE.  With gate = +inf and an nn that is injective on the data, sums are bit-identical to vcp_icp_sums.
+ *
+ * vcp_icp_unique: vcp_icp_gated with that rule.  Arguments as vcp_icp_gated, then lost [n_poses] (may be NULL), the
+ * last round's count.  Errors and limits are vcp_icp_gated's; no output is written on an error.  Where nn is injective
+ * on the landmarks in every round, M_all, mean_dist, inliers, best, kept and starved equal vcp_icp_gated's bit for bit
+ * and lost is 0.  Deterministic: only integer comparisons and integer atomics decide the selection (a 64-bit minimum of
+ * K(dd) per target, then a 32-bit minimum of the landmark among the ties); two calls give identical bits, and a pose's
+ * bits do not depend on the other poses of the call.  The schedule is read on the device: all rounds are enqueued at
+ * once, one synchronisation at the end.  Extra workspace: 12 bytes per (pose, landmark) and 12 bytes per
+ * (pose, target) -- the slot of that target, all ones between rounds: filled once per call, and after every round only
+ * the slots that round's landmarks touched are set back, so a round's cost does not grow with nt beyond the NN search.
+ * No new size limit beyond VCP_ERR_NOMEM.
+ * Timing phases: icpu_rounds, icpu_score (csrc/icp.hip). */
+int vcp_icp_sums_unique(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
+                        const double R[9], const double T[3], double gate, double sums[16], int64_t* kept,
+                        int32_t* nn, uint8_t* keep, int64_t* lost);
+int vcp_icp_unique(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
+                   int32_t n_poses, const double* init_R, const double* init_T, int max_iter, int max_landmarks,
+                   const double* gates, int32_t n_gates, int32_t min_pairs, double inlier_dist, double M_best[16],
+                   int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
+                   int32_t* starved, int64_t* lost);
+
 /* -- congruent-pair global registration ---------------------------------------------------------------
  * Every ICP form above starts from T0 = mean(target) - R0 mean(source) unless told otherwise, which is only right when
  * the scan covers the whole truth field; a scan that sees part of it starts wrong by a large translation from every

@@ -36,6 +36,7 @@ SYMBOLS = [
     "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_register_sim",
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
     "vcp_gdbscan", "vcp_gdbscan_dev", "vcp_icp_sums_sim", "vcp_selftest_horn_sim", "vcp_icp_sim",
+    "vcp_icp_sums_unique", "vcp_icp_unique",
 ]
 
 
@@ -356,6 +357,26 @@ class Context:
                                              C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_int64(int(m)), _ptr(sums),
                                              C.byref(thr), _ptr(nn), _ptr(keep)))
         return sums, thr.value, nn, keep
+
+    def icp_sums_unique(self, model, data, gate, R=None, T=None, want_nn=True, want_keep=True):
+        """One unique-correspondence round's passes (vcp_icp_sums_unique): of the pairs that share a nearest model point
+        only the one with the smallest key [K(dd) | index] may be kept, and it is kept unless sqrt(dd) >= gate; the
+        others add +0.0 at their place in icp_sums's tree.  Returns (sums [16], kept, lost = the pairs that are not
+        their model point's winner, nn [nd] int32 or None, keep [nd] uint8 or None: 1 kept, 0 winner dropped by the
+        gate, 2 not the winner)."""
+        model = _f64(model, 3)
+        data = _f64(data, 3)
+        R = None if R is None else _f64(R).reshape(9)
+        T = None if T is None else _f64(T).reshape(3)
+        sums = np.zeros(16)
+        kept = C.c_int64(0)
+        lost = C.c_int64(0)
+        nn = np.zeros(len(data), np.int32) if want_nn else None
+        keep = np.zeros(len(data), np.uint8) if want_keep else None
+        self._chk(lib().vcp_icp_sums_unique(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
+                                            C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums),
+                                            C.byref(kept), _ptr(nn), _ptr(keep), C.byref(lost)))
+        return sums, kept.value, lost.value, nn, keep
 
     # -- centroids / merge / match -----------------------------------------------------------------
     def centroids(self, xyz, motor, labels, K):
@@ -839,6 +860,41 @@ class Context:
                                         _ptr(inl), _ptr(kept), _ptr(starved), _ptr(td)))
         return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
                     kept=kept, starved=starved, trim_dist=td)
+
+    def icp_unique(self, source, target, gates, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
+                   inlier_dist=np.inf):
+        """icp_gated where a target takes one landmark per round (vcp_icp_unique): of the landmarks that share a
+        nearest target only the closest (ties: the lower index) may enter the round's sums, and the round's gate then
+        decides on it as in icp_gated.  Arguments as icp_gated.  Returns its dict plus lost [H] int64, the last round's
+        count of landmarks that were not their target's winner."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        gates = _f64(gates).reshape(-1)
+        if isinstance(poses, (int, np.integer)):
+            H, init_R = int(poses), None
+        else:
+            init_R = _f64(poses).reshape(-1, 9)
+            H = len(init_R)
+        if init_T is not None:
+            init_T = _f64(init_T, 3)
+            if len(init_T) != H:
+                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
+        n = max(H, 0)
+        M = np.zeros(16)
+        M_all = np.zeros((n, 16))
+        md = np.zeros(n)
+        inl = np.zeros(n, np.int32)
+        kept = np.zeros(n, np.int64)
+        starved = np.zeros(n, np.int32)
+        lost = np.zeros(n, np.int64)
+        best = C.c_int32(0)
+        self._chk(lib().vcp_icp_unique(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
+                                       C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter),
+                                       int(max_landmarks), _ptr(gates), C.c_int32(len(gates)), C.c_int32(min_pairs),
+                                       C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl),
+                                       _ptr(kept), _ptr(starved), _ptr(lost)))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
+                    kept=kept, starved=starved, lost=lost)
 
     def register_pairs(self, source, target, bases, len_tol, inlier_dist, mirror=False, max_landmarks=200):
         """vcp_register_pairs: a pose of source on target without a start.  Every base (two source indices) is laid on

@@ -94,12 +94,39 @@ struct TrimDist {
 struct TrimSum {
   TrimArgs a;
 };
+// Unique-correspondence ICP (vcp.h, "unique-correspondence ICP"): of the landmarks that share a nearest target, only the
+// one with the smallest 96-bit key [K(dd) | index] -- the target's WINNER -- may enter the sums; the gate then decides
+// on the winner as it does in the gated pass.  Three steps per round and pose: a pass that runs the NN search, stores
+// K(dd) and the index found and takes the 64-bit minimum of K(dd) in the slot of (pose, target) (G = UniqDist); the tie
+// pass k_icpu_tie, the 32-bit minimum of the landmark among those whose K equals the slot's; and the sums pass
+// (G = UniqSum), which keeps "my key and my index are the slot's, and the gate keeps me".  A slot is 12 bytes, two
+// arrays: skey [poses][nt] and sidx [poses][nt], all ones between rounds.
+struct UniqArgs {
+  const double* gates;  // the schedule on the device, as GateArgs'
+  int n_gates;
+  int nt;                    // targets: slots per pose
+  unsigned long long* key;   // [poses][L]
+  int32_t* nn;               // [poses][L]
+  unsigned long long* skey;  // [poses][nt]
+  uint32_t* sidx;            // [poses][nt]
+  uint32_t* pkept;           // [poses][workgroups]
+  uint32_t* plost;           // [poses][workgroups]: pairs that are not their target's winner
+  uint8_t* keep;             // [L] or NULL: 1 kept, 0 winner dropped by the gate, 2 not the winner
+};
+struct UniqDist {
+  UniqArgs a;
+};
+struct UniqSum {
+  UniqArgs a;
+};
 __device__ __forceinline__ uint8_t* keep_of(const GateArgs& g) { return g.keep; }
 __device__ __forceinline__ uint8_t* keep_of(const TrimSum& t) { return t.a.keep; }
 __device__ __forceinline__ uint8_t* keep_of(const SimGate& s) { return s.g.keep; }
+__device__ __forceinline__ uint8_t* keep_of(const UniqSum& u) { return u.a.keep; }
 __device__ __forceinline__ uint32_t* pkept_of(const GateArgs& g) { return g.pkept; }
 __device__ __forceinline__ uint32_t* pkept_of(const TrimSum& t) { return t.a.pkept; }
 __device__ __forceinline__ uint32_t* pkept_of(const SimGate& s) { return s.g.pkept; }
+__device__ __forceinline__ uint32_t* pkept_of(const UniqSum& u) { return u.a.pkept; }
 // K(dd): dd's bit pattern (dd >= +0, so the unsigned order is the numeric one, +inf last of the numbers), NaN above all
 __device__ __forceinline__ unsigned long long trim_key(double dd) {
   return dd != dd ? ~0ull : (unsigned long long)__double_as_longlong(dd);
@@ -183,6 +210,9 @@ __device__ __forceinline__ double gate_now(const GateArgs& ga, const IcpState* s
   return ga.gates[min(st->round + 1, ga.n_gates) - 1];
 }
 __device__ __forceinline__ double gate_now(const SimGate& sg, const IcpState* st) { return gate_now(sg.g, st); }
+__device__ __forceinline__ double gate_now(const UniqSum& us, const IcpState* st) {
+  return us.a.gates[min(st->round + 1, us.a.n_gates) - 1];
+}
 // The keep count of the round a trimmed kernel runs now: min(L, ceil(f * L)), one multiplication; f in (0, 1] (checked
 // on the host), so the count lies in [1, L].
 __device__ __forceinline__ long long trim_m(const TrimArgs& a, const IcpState* st, long long L) {
@@ -218,17 +248,21 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
   // TDIST: the search alone, K(dd) and the index stored per landmark; TSUM: no search, the stored index, and the sums
   // of the landmarks whose key is <= the selected one
   constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
+  // UDIST / USUM: the two passes of a unique-correspondence round; DIST / RSUM: what they share with the trimmed ones
+  // (DIST: the search alone, key and index stored; RSUM: no search, the stored index)
+  constexpr bool UDIST = std::is_same<G, UniqDist>::value, USUM = std::is_same<G, UniqSum>::value;
+  constexpr bool DIST = TDIST || UDIST, RSUM = TSUM || USUM;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * NS;
   if (st->done) return;
   double gate = 0.0;
-  uint32_t nkept = 0;
-  if constexpr (GATED) gate = gate_now(ga, st);
+  uint32_t nkept = 0, nlost = 0;
+  if constexpr (GATED || USUM) gate = gate_now(ga, st);
   unsigned long long* tkey = nullptr;
   int32_t* tnn = nullptr;
   unsigned long long thrk = 0;
   uint32_t thri = 0;
-  if constexpr (TDIST || TSUM) {
+  if constexpr (DIST || RSUM) {
     tkey = ga.a.key + (size_t)blockIdx.y * (size_t)nd;
     tnn = ga.a.nn + (size_t)blockIdx.y * (size_t)nd;
   }
@@ -237,7 +271,7 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
     thri = ga.a.sel[blockIdx.y].idx;
   }
   constexpr bool TILED = NNMODE == 1, GRID = NNMODE == 2;
-  __shared__ float4 tile[TILED && !TSUM ? MTILE : 1];
+  __shared__ float4 tile[TILED && !RSUM ? MTILE : 1];
   double R[9], T[3];
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = st->R[k];
@@ -272,7 +306,7 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
       p[r] = acc + T[r];
     }
     int order = 0;
-    if constexpr (TSUM) {
+    if constexpr (RSUM) {
       order = tnn[il];
     } else if (GRID) {
       double bestv;
@@ -407,21 +441,32 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
     if (nn) nn[i] = order;
     const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
     const double y[3] = {y0, y1, y2};
-    if constexpr (TDIST) {
+    if constexpr (DIST) {
       const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
-      tkey[i] = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
+      const unsigned long long k = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
+      tkey[i] = k;
       tnn[i] = order;
-    } else if constexpr (GATED || TSUM) {
+      if constexpr (UDIST) atomicMin(ga.a.skey + (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order, k);
+    } else if constexpr (GATED || RSUM) {
       const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
       const double dd = e0 * e0 + e1 * e1 + e2 * e2;
       bool kp;
+      uint8_t code;  // what keep[] receives
       if constexpr (GATED) {
         kp = !(sqrt(dd) >= gate);
+        code = kp ? 1 : 0;
+      } else if constexpr (USUM) {
+        const size_t sl = (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order;
+        const bool win = tkey[i] == ga.a.skey[sl] && (uint32_t)i == ga.a.sidx[sl];
+        kp = win && !(sqrt(dd) >= gate);
+        nlost += win ? 0u : 1u;
+        code = win ? (kp ? 1 : 0) : 2;
       } else {
         const unsigned long long k = tkey[i];
         kp = k < thrk || (k == thrk && (uint32_t)i <= thri);
+        code = kp ? 1 : 0;
       }
-      if (keep_of(ga)) keep_of(ga)[i] = kp ? 1 : 0;
+      if (keep_of(ga)) keep_of(ga)[i] = code;
       nkept += kp ? 1u : 0u;
 #pragma unroll
       for (int r = 0; r < 3; r++) {
@@ -447,8 +492,12 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
       s[15] += e0 * e0 + e1 * e1 + e2 * e2;
     }
   }
-  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
-  if constexpr (GATED || TSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (!DIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
+  if constexpr (GATED || RSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (USUM) {
+    __syncthreads();  // block_count's LDS words are free again
+    block_count<TB>(nlost, ga.a.plost + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  }
 }
 
 template <int TB, int NNMODE>
@@ -504,17 +553,21 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
   constexpr bool GATED = std::is_same<G, GateArgs>::value || SIM;
   constexpr int NS = icp_ncol<G>;
   constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
+  // UDIST / USUM: the two passes of a unique-correspondence round; DIST / RSUM: what they share with the trimmed ones
+  // (DIST: the search alone, key and index stored; RSUM: no search, the stored index)
+  constexpr bool UDIST = std::is_same<G, UniqDist>::value, USUM = std::is_same<G, UniqSum>::value;
+  constexpr bool DIST = TDIST || UDIST, RSUM = TSUM || USUM;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * NS;
   if (st->done) return;
   double gate = 0.0;
-  uint32_t nkept = 0;
-  if constexpr (GATED) gate = gate_now(ga, st);
+  uint32_t nkept = 0, nlost = 0;
+  if constexpr (GATED || USUM) gate = gate_now(ga, st);
   unsigned long long* tkey = nullptr;
   int32_t* tnn = nullptr;
   unsigned long long thrk = 0;
   uint32_t thri = 0;
-  if constexpr (TDIST || TSUM) {
+  if constexpr (DIST || RSUM) {
     tkey = ga.a.key + (size_t)blockIdx.y * (size_t)nd;
     tnn = ga.a.nn + (size_t)blockIdx.y * (size_t)nd;
   }
@@ -563,7 +616,7 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       tol2[h] = ((float)(S * S) < 1.0e37f && t2 >= 1.0e-30f) ? t2 : NAN;
     }
     float b1[2] = {INFINITY, INFINITY}, b2[2] = {INFINITY, INFINITY};
-    if constexpr (!TSUM) {
+    if constexpr (!RSUM) {
     const f32x2 nq0 = {-q[0][0], -q[1][0]}, nq1 = {-q[0][1], -q[1][1]}, nq2 = {-q[0][2], -q[1][2]};
     // the mask lives in a VGPR so that (score & keep) | j is ONE v_and_or_b32 (a VOP3 reads one scalar operand: j)
     uint32_t keep;
@@ -596,12 +649,12 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
         b1[h] = min_raw(b1[h], ta);
       }
     }
-    }  // !TSUM
+    }  // !RSUM
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       int order = (int)(__float_as_uint(b1[h]) & imask);
-      const bool amb = !TSUM && !(b2[h] > b1[h] + tol2[h]);
-      if constexpr (TSUM) order = tnn[live[h] ? idx[h] : nd - 1];
+      const bool amb = !RSUM && !(b2[h] > b1[h] + tol2[h]);
+      if constexpr (RSUM) order = tnn[live[h] ? idx[h] : nd - 1];
       if (amb) {
         // more than one candidate within the bound (or non-finite values): exact binary64 among the candidates, in
         // index order, strict `<` -- FindClosestPointSet's rule (lowest index among the exact minima)
@@ -627,21 +680,32 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       if (nn) nn[idx[h]] = order;
       const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
       const double y[3] = {y0, y1, y2};
-      if constexpr (TDIST) {
+      if constexpr (DIST) {
         const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
-        tkey[idx[h]] = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
+        const unsigned long long k = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
+        tkey[idx[h]] = k;
         tnn[idx[h]] = order;
-      } else if constexpr (GATED || TSUM) {
+        if constexpr (UDIST) atomicMin(ga.a.skey + (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order, k);
+      } else if constexpr (GATED || RSUM) {
         const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
         const double dd = e0 * e0 + e1 * e1 + e2 * e2;
         bool kp;
+        uint8_t code;  // what keep[] receives
         if constexpr (GATED) {
           kp = !(sqrt(dd) >= gate);
+          code = kp ? 1 : 0;
+        } else if constexpr (USUM) {
+          const size_t sl = (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order;
+          const bool win = tkey[idx[h]] == ga.a.skey[sl] && (uint32_t)idx[h] == ga.a.sidx[sl];
+          kp = win && !(sqrt(dd) >= gate);
+          nlost += win ? 0u : 1u;
+          code = win ? (kp ? 1 : 0) : 2;
         } else {
           const unsigned long long k = tkey[idx[h]];
           kp = k < thrk || (k == thrk && (uint32_t)idx[h] <= thri);
+          code = kp ? 1 : 0;
         }
-        if (keep_of(ga)) keep_of(ga)[idx[h]] = kp ? 1 : 0;
+        if (keep_of(ga)) keep_of(ga)[idx[h]] = code;
         nkept += kp ? 1u : 0u;
 #pragma unroll
         for (int r = 0; r < 3; r++) {
@@ -668,8 +732,12 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       }
     }
   }
-  if constexpr (!TDIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
-  if constexpr (GATED || TSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (!DIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
+  if constexpr (GATED || RSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (USUM) {
+    __syncthreads();  // block_count's LDS words are free again
+    block_count<TB>(nlost, ga.a.plost + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  }
 }
 
 template <int TB>
@@ -715,6 +783,62 @@ __global__ __launch_bounds__(TB) void k_icp_pass_small_trim(const double* __rest
                                                            const IcpState* __restrict__ st, double* __restrict__ partial,
                                                            uint32_t imask, double tolk, G ta) {
   icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nullptr, imask, tolk, ta);
+}
+
+// The unique-correspondence round's two passes (G = UniqDist, UniqSum): the same bodies, partition and fold.
+template <int TB, int NNMODE, class G>
+__global__ __launch_bounds__(TB) void k_icp_pass_uniq(const double* __restrict__ model,
+                                                     const float4* __restrict__ model32, int nm,
+                                                     const double* __restrict__ data, int64_t nd,
+                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                     NNGrid ng, G ua) {
+  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nullptr, ng, ua);
+}
+template <int TB, class G>
+__global__ __launch_bounds__(TB) void k_icp_pass_small_uniq(const double* __restrict__ model,
+                                                           const float4* __restrict__ model32, int nm,
+                                                           const double* __restrict__ data, int64_t nd,
+                                                           const IcpState* __restrict__ st, double* __restrict__ partial,
+                                                           uint32_t imask, double tolk, G ua) {
+  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nullptr, imask, tolk, ua);
+}
+
+// ---- the tie pass and the slot reset of a unique-correspondence round -----------------------------------------------
+// After the distance pass a slot's key is the smallest K(dd) among the landmarks on that target.  Every landmark whose
+// K equals it takes the minimum of its index in the slot's second word: the slot then names the smallest 96-bit key.
+// Integer atomics alone: the result is the same in any order of execution.  grid (workgroups over L, poses).
+__global__ __launch_bounds__(ITPB) void k_icpu_tie(const IcpState* __restrict__ st, UniqArgs a, int64_t L) {
+  const int h = blockIdx.y;
+  if (st[h].done) return;
+  const unsigned long long* key = a.key + (size_t)h * (size_t)L;
+  const int32_t* nn = a.nn + (size_t)h * (size_t)L;
+  const unsigned long long* skey = a.skey + (size_t)h * (size_t)a.nt;
+  uint32_t* sidx = a.sidx + (size_t)h * (size_t)a.nt;
+  for (int64_t i = (int64_t)blockIdx.x * ITPB + threadIdx.x; i < L; i += (int64_t)gridDim.x * ITPB) {
+    const int32_t j = nn[i];
+    if (key[i] == skey[j]) atomicMin(&sidx[j], (uint32_t)i);
+  }
+}
+// The slots a round's landmarks touched, all ones again: L stores per pose through the stored nn, whatever nt.  The
+// step of a round does it for up to UNIQ_RESET_STEP_MAX landmarks; beyond, k_icpu_reset runs between the sums pass and
+// the step over many workgroups (same grid as k_icpu_tie).
+constexpr int UNIQ_RESET_STEP_MAX = 4096;
+constexpr int UNIQ_TIE_KEYS = 2048;  // landmarks per workgroup of k_icpu_tie / k_icpu_reset, up to UNIQ_TIE_BLOCKS per pose
+constexpr int UNIQ_TIE_BLOCKS = 256;
+__device__ __forceinline__ void uniq_reset(const UniqArgs& a, int h, int64_t L, int64_t first, int64_t stride) {
+  const int32_t* nn = a.nn + (size_t)h * (size_t)L;
+  unsigned long long* skey = a.skey + (size_t)h * (size_t)a.nt;
+  uint32_t* sidx = a.sidx + (size_t)h * (size_t)a.nt;
+  for (int64_t i = first; i < L; i += stride) {
+    const int32_t j = nn[i];
+    skey[j] = ~0ull;
+    sidx[j] = ~0u;
+  }
+}
+__global__ __launch_bounds__(ITPB) void k_icpu_reset(const IcpState* __restrict__ st, UniqArgs a, int64_t L) {
+  const int h = blockIdx.y;
+  if (st[h].done) return;
+  uniq_reset(a, h, L, (int64_t)blockIdx.x * ITPB + threadIdx.x, (int64_t)gridDim.x * ITPB);
 }
 
 // ---- the select of a trimmed round ------------------------------------------------------------------------------
@@ -1221,6 +1345,69 @@ __global__ __launch_bounds__(ITPB) void k_icp_step_gated(const double* __restric
   if (round >= a.max_iter) st->done = 1;
 }
 
+// The step of a unique-correspondence round (vcp.h, vcp_icp_unique): k_icp_step_gated, word for word, on the sums
+// pass's rows and kept counts; beside it the lost counts of the workgroups added up into the pose's side record (the
+// state has no room for it), and -- reset_L > 0 -- the round's slots set back to all ones (uniq_reset).
+__global__ __launch_bounds__(ITPB) void k_icp_step_unique(const double* __restrict__ partial, int nb,
+                                                         IcpState* __restrict__ st, long long* __restrict__ lost,
+                                                         UniqArgs ua, long long reset_L, GateStepArgs a) {
+  const int h = blockIdx.x;
+  st += h;
+  partial += (size_t)h * nb * 16;
+  const uint32_t* pkept = ua.pkept + (size_t)h * nb;
+  const uint32_t* plost = ua.plost + (size_t)h * nb;
+  if (st->done) return;
+  __shared__ double tot[16];
+  __shared__ unsigned long long skept, slost;
+  if (threadIdx.x == 0) {
+    skept = 0;
+    slost = 0;
+  }
+  icp_fold_rows<ITPB>(partial, nb, st, tot);  // its barrier orders the stores above before the adds below
+  unsigned long long c = 0, l = 0;
+  for (int b = threadIdx.x; b < nb; b += ITPB) {
+    c += pkept[b];
+    l += plost[b];
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    c += __shfl_down(c, d, 64);
+    l += __shfl_down(l, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&skept, c);
+    atomicAdd(&slost, l);
+  }
+  if (reset_L > 0) uniq_reset(ua, h, reset_L, threadIdx.x, ITPB);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const long long kept = (long long)skept;
+  st->kept = kept;
+  lost[h] = (long long)slost;
+  if (a.sums_only) {
+    st->done = 1;
+    return;
+  }
+  st->pre_d = st->d;
+  st->d = tot[15];
+  const int round = st->round + 1;
+  st->round = round;
+  if (kept < a.min_pairs) {
+    st->starved = st->starved + 1;
+  } else {
+    double S[16];
+    for (int k = 0; k < 16; k++) S[k] = tot[k];
+    double R1[9], T1[3];
+    if (!horn(S, kept, R1, T1, st->V)) {
+      st->failed = 1;
+      st->done = 1;
+      return;
+    }
+    icp_compose(st, R1, T1);
+  }
+  if (round >= a.max_iter) st->done = 1;
+}
+
 // The step of a similarity round (vcp.h, vcp_icp_sim): k_icp_step_gated over 18-wide rows, with horn_sim in horn's
 // place.  What the state has no room for lives in the pose's side record: the two further sums, the product c of the
 // factors applied and the count of rounds whose scale was not determined.
@@ -1321,13 +1508,25 @@ struct TrimRun {
   uint8_t* d_keep;   // [nd] or NULL
   TrimSel* sel_out;  // host, [nst]: the last select of every pose
 };
+// ur (may be NULL; never with gr or tr): a unique-correspondence run -- per round the distance pass, the tie pass, the
+// sums pass and k_icp_step_unique.  Its workspace is b_icpt too: the trimmed run's 12 bytes per (pose, landmark), then
+// the slots, 8 bytes of key per (pose, target) and then 4 of index, all ones from one fill per call and from the reset
+// of every round.
+struct UniqRun {
+  const double* gates;  // host, [n_gates], validated by the caller
+  int n_gates;
+  long long min_pairs;
+  uint8_t* d_keep;      // [nd] or NULL
+  long long* lost_out;  // host, [nst]: the last round's count of every pose
+};
 size_t icpt_keys_bytes(int nst, int64_t nd) { return ((size_t)nst * (size_t)nd * 12 + 255) & ~(size_t)255; }
 int32_t* icpt_nn(vcp_ctx* ctx, int nst, int64_t nd) {
   return reinterpret_cast<int32_t*>(ctx->b_icpt.as<char>() + (size_t)nst * (size_t)nd * 8);
 }
 int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState* init,
             int nst, double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn, bool all_rounds,
-            NNGrid* ng_out, const GateRun* gr = nullptr, const TrimRun* tr = nullptr, const SimRun* sr = nullptr) {
+            NNGrid* ng_out, const GateRun* gr = nullptr, const TrimRun* tr = nullptr, const SimRun* sr = nullptr,
+            const UniqRun* ur = nullptr) {
   hipStream_t st = ctx->stream;
   // small data sets: one wave per workgroup so that they reach more CUs; large models: LDS tiles
   const bool small0 = nd <= (int64_t)64 * ICP_MAX_BLOCKS;
@@ -1356,17 +1555,20 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   const size_t st_bytes = icp_states_bytes(nst);
   const int ncol = sr ? 18 : 16;
   const size_t part_bytes = (size_t)nst * nb * ncol * sizeof(double);
-  const int n_sched = gr ? gr->n_gates : tr ? tr->n_share : 0;  // doubles staged behind the partial rows
+  const int n_sched = gr ? gr->n_gates : tr ? tr->n_share : ur ? ur->n_gates : 0;  // doubles staged behind the partial rows
   const size_t cnt_bytes = ((size_t)nst * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
   const size_t side_bytes = sr ? (size_t)nst * sizeof(SimSide) : 0;
   const size_t gate_bytes = gr   ? (size_t)n_sched * sizeof(double) + cnt_bytes + side_bytes
                             : tr ? (size_t)n_sched * sizeof(double) + cnt_bytes + (size_t)nst * sizeof(TrimSel)
+                            : ur ? (size_t)n_sched * sizeof(double) + 2 * cnt_bytes + (size_t)nst * sizeof(long long)
                                  : 0;
   VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + part_bytes + gate_bytes));
   const bool sel_wg = nd <= TRIM_SELECT_WG_MAX;
-  const size_t key_bytes = tr ? icpt_keys_bytes(nst, nd) : 0;
+  const size_t key_bytes = tr || ur ? icpt_keys_bytes(nst, nd) : 0;
   const size_t selws_bytes = (size_t)nst * TRIM_DIGITS * (sizeof(TrimPrefix) + ITPB * sizeof(uint32_t));
   if (tr) VCP_TRY(vcp_ensure(ctx, ctx->b_icpt, key_bytes + selws_bytes));
+  const size_t slot_n = ur ? (size_t)nst * (size_t)nm : 0;  // slots: one per (pose, target)
+  if (ur) VCP_TRY(vcp_ensure(ctx, ctx->b_icpt, key_bytes + slot_n * 12));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)nm * sizeof(float4) + 64));
   IcpState* d_st = icp_states(ctx);
   double* part = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes);
@@ -1375,8 +1577,8 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   // a gated run stages its schedule behind the states: the caller's array may be gone before the copy has run
   const size_t h_bytes =
       (size_t)nst * sizeof(IcpState) + (size_t)n_sched * sizeof(double) + (tr ? (size_t)nst * sizeof(TrimSel) : 0) +
-      (sr ? (size_t)nst * sizeof(SimSide) : 0);
-  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr && !tr ? ctx->pinned : vcp_stage(ctx, h_bytes));
+      (sr ? (size_t)nst * sizeof(SimSide) : 0) + (ur ? (size_t)nst * sizeof(long long) : 0);
+  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr && !tr && !ur ? ctx->pinned : vcp_stage(ctx, h_bytes));
   if (!h_st) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
   std::memcpy(h_st, init, (size_t)nst * sizeof(IcpState));
   VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, (size_t)nst * sizeof(IcpState), hipMemcpyHostToDevice, st));
@@ -1426,6 +1628,28 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     d_ghist = reinterpret_cast<uint32_t*>(d_slot + (size_t)nst * TRIM_DIGITS);
     if (!sel_wg) VCP_HIP(ctx, hipMemsetAsync(d_ghist, 0, (size_t)nst * TRIM_DIGITS * ITPB * sizeof(uint32_t), st));
   }
+  UniqDist ud{};
+  UniqSum us{};
+  long long *d_lost = nullptr, *h_lost = nullptr;
+  const bool reset_in_step = nd <= UNIQ_RESET_STEP_MAX;
+  if (ur) {
+    double* d_gates = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
+    uint32_t* pkept = reinterpret_cast<uint32_t*>(d_gates + n_sched);
+    uint32_t* plost = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(pkept) + cnt_bytes);
+    d_lost = reinterpret_cast<long long*>(reinterpret_cast<char*>(plost) + cnt_bytes);
+    unsigned long long* skey = reinterpret_cast<unsigned long long*>(ctx->b_icpt.as<char>() + key_bytes);
+    ud.a = UniqArgs{d_gates, n_sched, (int)nm, ctx->b_icpt.as<unsigned long long>(), icpt_nn(ctx, nst, nd), skey,
+                    reinterpret_cast<uint32_t*>(skey + slot_n), pkept, plost, ur->d_keep};
+    us.a = ud.a;
+    gsa = GateStepArgs{ur->min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
+    double* h_gates = reinterpret_cast<double*>(h_st + nst);
+    h_lost = reinterpret_cast<long long*>(h_gates + n_sched);
+    std::memcpy(h_gates, ur->gates, (size_t)n_sched * sizeof(double));
+    VCP_HIP(ctx, hipMemcpyAsync(d_gates, h_gates, (size_t)n_sched * sizeof(double), hipMemcpyHostToDevice, st));
+    // every slot all ones, once per call: the rounds set back what they touch
+    VCP_HIP(ctx, hipMemsetAsync(skey, 0xFF, slot_n * 12, st));
+    VCP_HIP(ctx, hipMemsetAsync(d_lost, 0, (size_t)nst * sizeof(long long), st));
+  }
   if (!grid) {  // the binary32 screening frame and copy serve the full scans only
     VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st, nst);
     VCP_LAUNCH(ctx, k_model32, dim3(vcp_blocks(nm, ITPB)), dim3(ITPB), 0, st, d_model, nm, d_st, model32);
@@ -1441,7 +1665,14 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     for (int b = 0; b < batch; b++) {
 #define VCP_PASS(TBV, TL)                                                                                               \
   do {                                                                                                                  \
-    if (tr) {                                                                                                           \
+    if (ur) {                                                                                                           \
+      if (phase == 0)                                                                                                   \
+        VCP_LAUNCH(ctx, (k_icp_pass_uniq<TBV, TL, UniqDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,       \
+                   (int)nm, d_data, nd, d_st, part, ng, ud);                                                            \
+      else                                                                                                              \
+        VCP_LAUNCH(ctx, (k_icp_pass_uniq<TBV, TL, UniqSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,        \
+                   (int)nm, d_data, nd, d_st, part, ng, us);                                                            \
+    } else if (tr) {                                                                                                    \
       if (phase == 0)                                                                                                   \
         VCP_LAUNCH(ctx, (k_icp_pass_trim<TBV, TL, TrimDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,       \
                    (int)nm, d_data, nd, d_st, part, ng, td);                                                            \
@@ -1460,7 +1691,14 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   } while (0)
 #define VCP_PASS_SMALL(TBV)                                                                                             \
   do {                                                                                                                  \
-    if (tr) {                                                                                                           \
+    if (ur) {                                                                                                           \
+      if (phase == 0)                                                                                                   \
+        VCP_LAUNCH(ctx, (k_icp_pass_small_uniq<TBV, UniqDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,     \
+                   (int)nm, d_data, nd, d_st, part, imask, tolk, ud);                                                   \
+      else                                                                                                              \
+        VCP_LAUNCH(ctx, (k_icp_pass_small_uniq<TBV, UniqSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,      \
+                   (int)nm, d_data, nd, d_st, part, imask, tolk, us);                                                   \
+    } else if (tr) {                                                                                                    \
       if (phase == 0)                                                                                                   \
         VCP_LAUNCH(ctx, (k_icp_pass_small_trim<TBV, TrimDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,     \
                    (int)nm, d_data, nd, d_st, part, imask, tolk, td);                                                   \
@@ -1477,16 +1715,20 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
       VCP_LAUNCH(ctx, k_icp_pass_small<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd,   \
                  d_st, part, d_nn, imask, tolk);                                                                        \
   } while (0)
-      // a trimmed round: the pass twice (distances, then sums) with the select between them
-      for (int phase = 0; phase < (tr ? 2 : 1); phase++) {
+      // a trimmed round: the pass twice (distances, then sums) with the select between them; a unique-correspondence
+      // round: likewise, with the tie pass between them
+      for (int phase = 0; phase < (tr || ur ? 2 : 1); phase++) {
         if (small && grid) VCP_PASS(64, 2);
         else if (grid) VCP_PASS(ITPB, 2);
         else if (small && tiled) VCP_PASS(64, 1);
         else if (tiled) VCP_PASS(ITPB, 1);
         else if (small) VCP_PASS_SMALL(64);
         else VCP_PASS_SMALL(ITPB);
-        if (!tr || phase == 1) break;
-        if (sel_wg) {
+        if ((!tr && !ur) || phase == 1) break;
+        if (ur) {
+          VCP_LAUNCH(ctx, k_icpu_tie, dim3(vcp_blocks(nd, UNIQ_TIE_KEYS, UNIQ_TIE_BLOCKS), nst), dim3(ITPB), 0, st, d_st,
+                     ud.a, nd);
+        } else if (sel_wg) {
           VCP_LAUNCH(ctx, k_icpt_select_wg, dim3(nst), dim3(ITPB), 0, st, d_st, td.a, (int)nd);
         } else {
           const unsigned hb = vcp_blocks(nd, TRIM_HIST_KEYS, TRIM_HIST_BLOCKS);
@@ -1497,7 +1739,14 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
       }
 #undef VCP_PASS
 #undef VCP_PASS_SMALL
-      if (tr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, td.a.pkept, nb, d_st, gsa);
+      if (ur) {  // sums only: one pass, nothing left to decide with the slots
+        const bool reset = mode != MODE_SUMS_ONLY;
+        if (reset && !reset_in_step)
+          VCP_LAUNCH(ctx, k_icpu_reset, dim3(vcp_blocks(nd, UNIQ_TIE_KEYS, UNIQ_TIE_BLOCKS), nst), dim3(ITPB), 0, st, d_st,
+                     ud.a, nd);
+        VCP_LAUNCH(ctx, k_icp_step_unique, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, d_lost, ud.a,
+                   (long long)(reset && reset_in_step ? nd : 0), gsa);
+      } else if (tr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, td.a.pkept, nb, d_st, gsa);
       else if (sr)
         VCP_LAUNCH(ctx, k_icp_step_sim, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, d_side, gsa, ssa);
       else if (gr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, gsa);
@@ -1507,12 +1756,14 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
     VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, (size_t)nst * sizeof(IcpState), hipMemcpyDeviceToHost, st));
     if (tr) VCP_HIP(ctx, hipMemcpyAsync(h_sel, td.a.sel, (size_t)nst * sizeof(TrimSel), hipMemcpyDeviceToHost, st));
     if (sr) VCP_HIP(ctx, hipMemcpyAsync(h_side, d_side, (size_t)nst * sizeof(SimSide), hipMemcpyDeviceToHost, st));
+    if (ur) VCP_HIP(ctx, hipMemcpyAsync(h_lost, d_lost, (size_t)nst * sizeof(long long), hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (all_done() || launched >= max_iter || mode == MODE_SUMS_ONLY) break;
   }
   std::memcpy(out, h_st, (size_t)nst * sizeof(IcpState));
   if (tr) std::memcpy(tr->sel_out, h_sel, (size_t)nst * sizeof(TrimSel));
   if (sr) std::memcpy(sr->side_out, h_side, (size_t)nst * sizeof(SimSide));
+  if (ur) std::memcpy(ur->lost_out, h_lost, (size_t)nst * sizeof(long long));
   for (int k = 0; k < nst; k++)
     if (out[k].failed) return vcp_fail(ctx, VCP_ERR_ARG, "Horn solve failed (non-finite sums)%s", nst > 1 ? " in a pose" : "");
   return VCP_OK;
@@ -1668,6 +1919,8 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
 // the last round's thr.
 // sr (only with gr): the similarity form, vcp_icp_sim -- its bounds are checked here, and ratio / unscaled (each may be
 // NULL) receive the side records' c and count.
+// ur (never with gr or tr): the unique-correspondence form, vcp_icp_unique -- its schedule is checked as gr's is, and
+// lost (may be NULL) receives the last round's count of pairs that were not their target's winner.
 static bool sim_range_ok(double ratio_min, double ratio_max) {
   return ratio_min > 0.0 && ratio_max >= ratio_min && ratio_max <= 1.7976931348623157e308;  // false for NaN
 }
@@ -1676,7 +1929,8 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
                               int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all,
                               double* mean_dist, int32_t* inliers, const GateRun* gr, int64_t* kept, int32_t* starved,
                               const TrimRun* tr = nullptr, double* trim_dist = nullptr, const SimRun* sr = nullptr,
-                              double* ratio = nullptr, int32_t* unscaled = nullptr) {
+                              double* ratio = nullptr, int32_t* unscaled = nullptr, const UniqRun* ur = nullptr,
+                              int64_t* lost = nullptr) {
   if (!ctx) return VCP_ERR_ARG;
   if (ns <= 0 || nt <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty source or target");
   if (max_iter < 1 || max_landmarks < 1 || !source || !target || !M_best || !best)
@@ -1695,6 +1949,12 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     for (int k = 0; k < gr->n_gates; k++)
       if (!(gr->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
   }
+  if (ur) {
+    if (ur->n_gates < 1 || !ur->gates) return vcp_fail(ctx, VCP_ERR_ARG, "n_gates < 1");
+    if (ur->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
+    for (int k = 0; k < ur->n_gates; k++)
+      if (!(ur->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
+  }
   if (sr) {
     if (!sim_range_ok(sr->ratio_min, sr->ratio_max))
       return vcp_fail(ctx, VCP_ERR_ARG, "need 0 < ratio_min <= ratio_max < inf");
@@ -1709,7 +1969,7 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   }
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
-  vcp_phase(ctx, tr ? "icpt_rounds" : sr ? "icps_rounds" : gr ? "icpg_rounds" : "icpms_rounds");
+  vcp_phase(ctx, ur ? "icpu_rounds" : tr ? "icpt_rounds" : sr ? "icps_rounds" : gr ? "icpg_rounds" : "icpms_rounds");
   int64_t step = 1;
   if (ns > max_landmarks) step = ns / max_landmarks;
   const int64_t nb = ns / step;
@@ -1741,6 +2001,12 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     srun = *sr;
     srun.side_out = side.data();
   }
+  std::vector<long long> nlost(ur ? (size_t)n_poses : 0);
+  UniqRun urun{};
+  if (ur) {
+    urun = *ur;
+    urun.lost_out = nlost.data();
+  }
   for (int h = 0; h < n_poses; h++) {
     IcpState& s = init[h];
     identity(s);
@@ -1769,10 +2035,10 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   NNGrid ng{};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init.data(), n_poses, 0.0,
                   VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr, tr ? &trun : nullptr,
-                  sr ? &srun : nullptr));
+                  sr ? &srun : nullptr, ur ? &urun : nullptr));
   // score every pose over ALL source points with vcp_match's arithmetic, on the grid the rounds used (vcp_match bins
   // a target of more than 512 points too, and falls back to the full scan on the same condition)
-  vcp_phase(ctx, tr ? "icpt_score" : sr ? "icps_score" : gr ? "icpg_score" : "icpms_score");
+  vcp_phase(ctx, ur ? "icpu_score" : tr ? "icpt_score" : sr ? "icps_score" : gr ? "icpg_score" : "icpms_score");
   const double* d_src = step > 1 ? ctx->b_in3.as<double>() : ctx->b_in2.as<double>();  // step 1: the landmarks are all
   const IcpState* d_st = icp_states(ctx);
   uint32_t* d_cnt = ctx->b_out0.as<uint32_t>();
@@ -1790,7 +2056,7 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   VCP_TRY(vcp_phase_finish(ctx));
   // RMS distance of the pairs the last round summed: all nb landmarks, or the kept ones of a gated run (none: +inf)
   auto mean_of = [&](const IcpState& f) {
-    if (!gr && !tr) return std::sqrt(f.d / (double)nb);
+    if (!gr && !tr && !ur) return std::sqrt(f.d / (double)nb);
     return f.kept > 0 ? std::sqrt(f.d / (double)f.kept) : (double)INFINITY;
   };
   // most inliers, then the smaller mean distance, then the lower index
@@ -1813,6 +2079,7 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     if (starved) starved[h] = fin[h].starved;
     if (sr && ratio) ratio[h] = side[h].c;
     if (sr && unscaled) unscaled[h] = side[h].unscaled;
+    if (ur && lost) lost[h] = (int64_t)nlost[h];
     if (tr && trim_dist) {
       double thr;
       std::memcpy(&thr, &sel[h].key, sizeof(thr));
@@ -1871,6 +2138,17 @@ int vcp_icp_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* ta
                             unscaled);
 }
 
+// vcp_icp_gated where, of the landmarks that share a nearest target, only the closest enters a round's sums (vcp.h)
+int vcp_icp_unique(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                   const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* gates,
+                   int32_t n_gates, int32_t min_pairs, double inlier_dist, double M_best[16], int32_t* best,
+                   double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved, int64_t* lost) {
+  const UniqRun ur{gates, n_gates, min_pairs, nullptr, nullptr};
+  return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
+                            M_best, best, M_all, mean_dist, inliers, nullptr, kept, starved, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, &ur, lost);
+}
+
 // Host-side run of the Horn step the device executes per round (same source: horn() is __host__ __device__).
 int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v, double R1[9], double T1[3]) {
   if (!sums || !R1 || !T1 || nd <= 0 || (use_v && !V)) return VCP_ERR_ARG;
@@ -1887,9 +2165,12 @@ int vcp_selftest_horn_sim(const double sums[18], int64_t n, double V[16], int us
 
 // gate (NULL: vcp_icp_sums): one gated pass, vcp_icp_sums_gated; kept and keep receive its verdicts
 // m (never with gate): one trimmed round's passes, vcp_icp_sums_trimmed; thr_dd and keep receive its verdicts
+// lost (only with gate): one unique-correspondence round's passes, vcp_icp_sums_unique; kept, lost and keep receive
+// its verdicts
 static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                         const double T[3], double sums[16], int32_t* nn, const double* gate, int64_t* kept,
-                        uint8_t* keep, const int64_t* m = nullptr, double* thr_dd = nullptr, bool sim = false) {
+                        uint8_t* keep, const int64_t* m = nullptr, double* thr_dd = nullptr, bool sim = false,
+                        int64_t* lost = nullptr) {
   if (!ctx) return VCP_ERR_ARG;
   if (nm <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty model");
   if (nd <= 0 || !model || !data || !sums) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
@@ -1898,7 +2179,8 @@ static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const dou
   if (gate && !kept) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
   if (m && !thr_dd) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
   if (m && (*m < 1 || *m > nd)) return vcp_fail(ctx, VCP_ERR_ARG, "m must be in [1, nd]");
-  if (m && nd > 0xFFFFFFFFLL) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "the key holds the landmark in 32 bits");
+  if ((m || lost) && nd > 0xFFFFFFFFLL)
+    return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "the key holds the landmark in 32 bits");
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
   VCP_TRY(vcp_ensure(ctx, ctx->b_in0, (size_t)nm * 24));
@@ -1916,17 +2198,21 @@ static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const dou
   const TrimRun tr{nullptr, 0, m ? (long long)*m : 0, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr, &sel};
   SimSide side{};
   const SimRun sr{1.0, 1.0, &side};  // sim (only with gate): the 18-wide pass, sums [18]
+  long long nlost = 0;
+  const UniqRun ur{gate, 1, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr, &nlost};
+  const bool stored_nn = m || lost;  // the rounds that keep the index found in their own workspace
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, &init, 1, 0.0, VCP_STOP_SSE_DELTA, 1,
-                  MODE_SUMS_ONLY, &fin, nn && !m ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr,
-                  gate ? &gr : nullptr, m ? &tr : nullptr, sim ? &sr : nullptr));
+                  MODE_SUMS_ONLY, &fin, nn && !stored_nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr,
+                  gate && !lost ? &gr : nullptr, m ? &tr : nullptr, sim ? &sr : nullptr, lost ? &ur : nullptr));
   std::memcpy(sums, fin.sums, sizeof(fin.sums));
   if (sim) {
     sums[16] = side.s16;
     sums[17] = side.s17;
   }
   if (gate) *kept = (int64_t)fin.kept;
-  if (m) {
-    std::memcpy(thr_dd, &sel.key, sizeof(double));
+  if (lost) *lost = (int64_t)nlost;
+  if (m) std::memcpy(thr_dd, &sel.key, sizeof(double));
+  if (stored_nn) {
     if (nn) VCP_HIP(ctx, hipMemcpyAsync(nn, icpt_nn(ctx, 1, nd), (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
   } else if (nn) {
     VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1949,6 +2235,13 @@ int vcp_icp_sums_gated(vcp_ctx* ctx, const double* model, int64_t nm, const doub
 int vcp_icp_sums_sim(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                      const double T[3], double gate, double sums[18], int64_t* kept, int32_t* nn, uint8_t* keep) {
   return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep, nullptr, nullptr, true);
+}
+
+int vcp_icp_sums_unique(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
+                        const double T[3], double gate, double sums[16], int64_t* kept, int32_t* nn, uint8_t* keep,
+                        int64_t* lost) {
+  if (ctx && !lost) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep, nullptr, nullptr, false, lost);
 }
 
 int vcp_icp_sums_trimmed(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,

@@ -71,7 +71,7 @@ struct vcp_ctx {
   // its own grid; the records, the per-slot state and the ranks
   DevBuf b_gd_in, b_gd_out, b_gd_misc, b_gd_cell, b_gd_work;
   // trimmed ICP (icp.hip): per (pose, landmark) the distance key and the index found, then the select's prefixes and
-  // histograms
+  // histograms; unique-correspondence ICP: the same keys and indices, then per (pose, target) the winner's slot
   DevBuf b_icpt;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)

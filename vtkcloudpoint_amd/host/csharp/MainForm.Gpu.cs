@@ -403,6 +403,59 @@ namespace vtkPointCloud
             ShowIcpSolution(SourcePolydata, TargetPolydata);
         }
 
+        // ICPGated() where a truth takes one centroid per round: of the centroids whose nearest truth is the same one, only
+        // the closest enters that round's fit.  A target makes one centroid; where DBSCAN split it, or a reflection or an
+        // edge return left a second cluster beside it, the second lies inside any gate that admits the real centroids and
+        // pulls ICPGated()'s pose by its offset times the ghosts' share.  M is set as by ICP().
+        void ICPUnique(int angles, bool mirror, double gateStart, double gateEnd, double matchDistance)
+        {
+            ren = new vtk.vtkRenderer();
+            vtk.vtkPolyData SourcePolydata = Tools.ArrayList2PolyData(1, this.centers, this.trueScale, this.centroidScale,
+                this.scale, this.clock, this.clock_y, this.clock_x);
+            vtk.vtkPolyData TargetPolydata = new vtk.vtkPolyData();
+            TargetPolydata.SetPoints(truePointCloud);
+            TargetPolydata.SetVerts(truePointVertices);
+
+            int ns = centers.Count;
+            double[] src = new double[3 * Math.Max(ns, 1)];
+            for (int i = 0; i < ns; i++) { src[3 * i] = centers[i].tmp_X; src[3 * i + 1] = centers[i].tmp_Y; src[3 * i + 2] = 0.0; }
+            double[] tgt = TruthArray();
+            int poses = mirror ? 2 * angles : angles;
+            double[] initR = null;  // null: the library's Rz(h * 2 pi / angles)
+            if (mirror)
+            {
+                initR = new double[9 * poses];
+                for (int h = 0; h < angles; h++)
+                {
+                    double t = h * (2.0 * Math.PI / angles), c = Math.Cos(t), s = Math.Sin(t);
+                    double[] rz = { c, 0.0 - s, 0.0, s, c, 0.0, 0.0, 0.0, 1.0 };
+                    double[] rm = { c, s, 0.0, s, 0.0 - c, 0.0, 0.0, 0.0, 1.0 };  // Rz(t) * diag(1, -1, 1)
+                    Array.Copy(rz, 0, initR, 9 * h, 9);
+                    Array.Copy(rm, 0, initR, 9 * (angles + h), 9);
+                }
+            }
+            const int steps = 10;
+            double[] gates = new double[steps];
+            for (int k = 0; k < steps; k++) gates[k] = gateStart * Math.Pow(gateEnd / gateStart, k / (steps - 1.0));
+            gates[0] = gateStart;
+            gates[steps - 1] = gateEnd;
+            double[] m16 = new double[16];
+            int[] inliers = new int[Math.Max(poses, 1)];
+            long[] kept = new long[Math.Max(poses, 1)];
+            int[] starved = new int[Math.Max(poses, 1)];
+            long[] lost = new long[Math.Max(poses, 1)];
+            int best;
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_icp_unique(lease.Ctx, src, ns, tgt, tgt.Length / 3, poses, initR, null,
+                    100, 200, gates, steps, 3, matchDistance, m16, out best, null, null, inliers, kept, starved, lost));
+            M = new vtk.vtkMatrix4x4();
+            for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) M.SetElement(r, c, m16[4 * r + c]);
+            Console.WriteLine("刚性变换矩阵为：" + M + " (start " + best + " of " + poses + ", " + inliers[best] + " / " + ns
+                + ", " + kept[best] + " kept, " + lost[best] + " lost their truth to a closer centroid, " + starved[best]
+                + " starved rounds)");
+            ShowIcpSolution(SourcePolydata, TargetPolydata);
+        }
+
         // the display part of FrmMain.cs:863-906: the centroids moved by M next to the truths
         void ShowIcpSolution(vtk.vtkPolyData SourcePolydata, vtk.vtkPolyData TargetPolydata)
         {

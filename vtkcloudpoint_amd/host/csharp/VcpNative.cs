@@ -98,6 +98,17 @@ namespace vtkPointCloud
             int n_keep, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
             double[] mean_dist, int[] inliers, long[] kept, int[] starved, double[] trim_dist);
 
+        // unique-correspondence ICP (vcp.h): of the landmarks that share a nearest target only the closest may enter a
+        // round's sums; the gate then decides on it.  One round's passes (the test handle; nn and keep may be null; keep:
+        // 1 kept, 0 winner dropped by the gate, 2 not the winner) and vcp_icp_gated with that rule; kept, starved and lost
+        // may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_sums_unique(IntPtr ctx, double[] model, long nm, double[] data,
+            long nd, double[] R, double[] T, double gate, double[] sums, out long kept, int[] nn, byte[] keep, out long lost);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_unique(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int n_poses, double[] init_R, double[] init_T, int max_iter, int max_landmarks, double[] gates,
+            int n_gates, int min_pairs, double inlier_dist, double[] M_best, out int best, double[] M_all,
+            double[] mean_dist, int[] inliers, long[] kept, int[] starved, long[] lost);
+
         // similarity ICP (vcp.h): the gated loop whose rounds also fit one isotropic scale, the product of the factors held
         // in [ratio_min, ratio_max] (ratio_min <= 1 <= ratio_max).  One pass (the test handle: vcp_icp_sums_gated with
         // sums [18]; nn and keep may be null), the step on the host (returns 1, 2 = scale not determined, 0 = failed; V may

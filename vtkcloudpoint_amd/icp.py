@@ -217,6 +217,24 @@ def gated_icp(centers, truths, gates, n_angles=1, mirror=False, init_T=None, max
     return ctx.icp_gated(src, tgt, gates, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
 
 
+def unique_icp(centers, truths, gates, n_angles=1, mirror=False, init_T=None, max_iter=100, max_landmarks=200,
+               min_pairs=3, inlier_dist=np.inf, ctx=None):
+    """gated_icp where a truth takes one centroid per round (vcp_icp_unique, "picky ICP"): of the centroids whose
+    nearest truth is the same one, only the closest enters that round's fit (ties: the lower index), and the round's
+    gate then decides on it as in gated_icp.  A target makes one centroid; a second cluster beside it (a split target, a
+    reflection, an edge return) lies inside any gate that admits the real centroids and pulls gated_icp's pose by its
+    offset times the ghosts' share of the pairs.  n_angles may also be an [H, 3, 3] array of start rotations.  Returns
+    Context.icp_unique's dict (gated_icp's plus lost, the last round's count of centroids that lost their truth)."""
+    ctx = ctx or default_context()
+    src = _points(centers)
+    tgt = _points(truths)
+    if isinstance(n_angles, (int, np.integer)):
+        poses = rotations_about_z(n_angles, mirror) if mirror else int(n_angles)
+    else:
+        poses = np.asarray(n_angles, np.float64)
+    return ctx.icp_unique(src, tgt, gates, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
+
+
 def similarity_icp(centers, truths, gates, ratio_range, n_angles=1, mirror=False, init_T=None, max_iter=100,
                    max_landmarks=200, min_pairs=3, inlier_dist=np.inf, ctx=None):
     """gated_icp whose every round also fits one isotropic scale (vcp_icp_sim: Horn's symmetric scale of the kept pairs,
@@ -330,6 +348,25 @@ def global_icp(centers, truths, bases, len_tol, inlier_dist, gates, mirror=False
                               min_pairs, inlier_dist)
     else:
         out = ctx.icp_gated(src, tgt, gates, Rs, Ts, max_iter, max_landmarks, min_pairs, inlier_dist)
+    out.update(registration=reg, bases_used=used)
+    return out
+
+
+def global_unique_icp(centers, truths, bases, len_tol, inlier_dist, gates, mirror=False, max_iter=20, max_landmarks=200,
+                      min_pairs=3, ctx=None):
+    """global_icp whose polish lets a truth take one centroid per round: register_pairs, then ONE unique_icp call
+    started from the pose of every base that found one (score >= 0).  Returns unique_icp's dict (best indexes the
+    started poses; lost) plus registration = register_pairs's dict and bases_used.  ValueError when no base has a
+    hypothesis."""
+    ctx = ctx or default_context()
+    src, tgt = _points(centers), _points(truths)
+    reg = ctx.register_pairs(src, tgt, bases, len_tol, inlier_dist, mirror, max_landmarks)
+    used = np.flatnonzero(reg["score"] >= 0)
+    if len(used) == 0:
+        raise ValueError("no base has a target pair of its length within len_tol")
+    M = reg["M_all"][used]
+    out = ctx.icp_unique(src, tgt, gates, np.ascontiguousarray(M[:, :3, :3]), np.ascontiguousarray(M[:, :3, 3]), max_iter,
+                         max_landmarks, min_pairs, inlier_dist)
     out.update(registration=reg, bases_used=used)
     return out
 
