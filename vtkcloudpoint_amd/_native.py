@@ -297,65 +297,53 @@ class Context:
                                     C.byref(sse), C.byref(rmse), C.byref(it)))
         return dict(R=R.reshape(3, 3), T=T, sse=sse.value, rmse=rmse.value, iters=it.value)
 
-    def icp_sums(self, model, data, R=None, T=None, want_nn=True):
+    def _icp_sums(self, fn, model, data, R, T, ncol, want_nn, want_keep, call):
+        """One call of a vcp_icp_sums* entry point fn.  call(head, sums, nn, keep) lays out fn's arguments: head is the
+        common leading ones, sums [ncol] / nn / keep the output arrays as C pointers (NULL where not wanted).  Returns
+        (sums, nn [nd] int32 or None, keep [nd] uint8 or None)."""
         model = _f64(model, 3)
         data = _f64(data, 3)
         R = None if R is None else _f64(R).reshape(9)
         T = None if T is None else _f64(T).reshape(3)
-        sums = np.zeros(16)
+        sums = np.zeros(ncol)
         nn = np.zeros(len(data), np.int32) if want_nn else None
-        self._chk(lib().vcp_icp_sums(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
-                                     C.c_int64(len(data)), _ptr(R), _ptr(T), _ptr(sums), _ptr(nn)))
+        keep = np.zeros(len(data), np.uint8) if want_keep else None
+        head = (self._h, _ptr(model), C.c_int64(len(model)), _ptr(data), C.c_int64(len(data)), _ptr(R), _ptr(T))
+        self._chk(fn(*call(head, _ptr(sums), _ptr(nn), _ptr(keep))))
+        return sums, nn, keep
+
+    def icp_sums(self, model, data, R=None, T=None, want_nn=True):
+        sums, nn, _ = self._icp_sums(lib().vcp_icp_sums, model, data, R, T, 16, want_nn, False,
+                                     lambda head, sums, nn, keep: head + (sums, nn))
         return sums, nn
 
     def icp_sums_gated(self, model, data, gate, R=None, T=None, want_nn=True, want_keep=True):
         """One gated pass (vcp_icp_sums_gated): pairs with sqrt(dd) >= gate add +0.0 at their place in icp_sums's
         tree.  Returns (sums [16], kept, nn [nd] int32 or None, keep [nd] uint8 or None)."""
-        model = _f64(model, 3)
-        data = _f64(data, 3)
-        R = None if R is None else _f64(R).reshape(9)
-        T = None if T is None else _f64(T).reshape(3)
-        sums = np.zeros(16)
         kept = C.c_int64(0)
-        nn = np.zeros(len(data), np.int32) if want_nn else None
-        keep = np.zeros(len(data), np.uint8) if want_keep else None
-        self._chk(lib().vcp_icp_sums_gated(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
-                                           C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums),
-                                           C.byref(kept), _ptr(nn), _ptr(keep)))
+        sums, nn, keep = self._icp_sums(
+            lib().vcp_icp_sums_gated, model, data, R, T, 16, want_nn, want_keep,
+            lambda head, sums, nn, keep: head + (C.c_double(gate), sums, C.byref(kept), nn, keep))
         return sums, kept.value, nn, keep
 
     def icp_sums_sim(self, model, data, gate, R=None, T=None, want_nn=True, want_keep=True):
         """One pass of the similarity form (vcp_icp_sums_sim): icp_sums_gated with sum |p|^2 at 16 and sum |y|^2 at 17
         over the kept pairs, through the same tree.  Returns (sums [18], kept, nn [nd] int32 or None, keep [nd] uint8 or
         None)."""
-        model = _f64(model, 3)
-        data = _f64(data, 3)
-        R = None if R is None else _f64(R).reshape(9)
-        T = None if T is None else _f64(T).reshape(3)
-        sums = np.zeros(18)
         kept = C.c_int64(0)
-        nn = np.zeros(len(data), np.int32) if want_nn else None
-        keep = np.zeros(len(data), np.uint8) if want_keep else None
-        self._chk(lib().vcp_icp_sums_sim(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data), C.c_int64(len(data)),
-                                         _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums), C.byref(kept), _ptr(nn),
-                                         _ptr(keep)))
+        sums, nn, keep = self._icp_sums(
+            lib().vcp_icp_sums_sim, model, data, R, T, 18, want_nn, want_keep,
+            lambda head, sums, nn, keep: head + (C.c_double(gate), sums, C.byref(kept), nn, keep))
         return sums, kept.value, nn, keep
 
     def icp_sums_trimmed(self, model, data, m, R=None, T=None, want_nn=True, want_keep=True):
         """One trimmed round's passes (vcp_icp_sums_trimmed): the m pairs with the smallest keys [K(dd) | index] are
         kept, the others add +0.0 at their place in icp_sums's tree.  Returns (sums [16], thr_dd = the dd of the kept
         pair with the largest key, nn [nd] int32 or None, keep [nd] uint8 or None)."""
-        model = _f64(model, 3)
-        data = _f64(data, 3)
-        R = None if R is None else _f64(R).reshape(9)
-        T = None if T is None else _f64(T).reshape(3)
-        sums = np.zeros(16)
         thr = C.c_double(0)
-        nn = np.zeros(len(data), np.int32) if want_nn else None
-        keep = np.zeros(len(data), np.uint8) if want_keep else None
-        self._chk(lib().vcp_icp_sums_trimmed(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
-                                             C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_int64(int(m)), _ptr(sums),
-                                             C.byref(thr), _ptr(nn), _ptr(keep)))
+        sums, nn, keep = self._icp_sums(
+            lib().vcp_icp_sums_trimmed, model, data, R, T, 16, want_nn, want_keep,
+            lambda head, sums, nn, keep: head + (C.c_int64(int(m)), sums, C.byref(thr), nn, keep))
         return sums, thr.value, nn, keep
 
     def icp_sums_unique(self, model, data, gate, R=None, T=None, want_nn=True, want_keep=True):
@@ -364,18 +352,11 @@ class Context:
         others add +0.0 at their place in icp_sums's tree.  Returns (sums [16], kept, lost = the pairs that are not
         their model point's winner, nn [nd] int32 or None, keep [nd] uint8 or None: 1 kept, 0 winner dropped by the
         gate, 2 not the winner)."""
-        model = _f64(model, 3)
-        data = _f64(data, 3)
-        R = None if R is None else _f64(R).reshape(9)
-        T = None if T is None else _f64(T).reshape(3)
-        sums = np.zeros(16)
         kept = C.c_int64(0)
         lost = C.c_int64(0)
-        nn = np.zeros(len(data), np.int32) if want_nn else None
-        keep = np.zeros(len(data), np.uint8) if want_keep else None
-        self._chk(lib().vcp_icp_sums_unique(self._h, _ptr(model), C.c_int64(len(model)), _ptr(data),
-                                            C.c_int64(len(data)), _ptr(R), _ptr(T), C.c_double(gate), _ptr(sums),
-                                            C.byref(kept), _ptr(nn), _ptr(keep), C.byref(lost)))
+        sums, nn, keep = self._icp_sums(
+            lib().vcp_icp_sums_unique, model, data, R, T, 16, want_nn, want_keep,
+            lambda head, sums, nn, keep: head + (C.c_double(gate), sums, C.byref(kept), nn, keep, C.byref(lost)))
         return sums, kept.value, lost.value, nn, keep
 
     # -- centroids / merge / match -----------------------------------------------------------------
@@ -726,14 +707,9 @@ class Context:
                                         int(start_by_centroids), _ptr(M), C.byref(md), C.byref(it)))
         return dict(M=M.reshape(4, 4), mean_dist=md.value, iters=it.value)
 
-    def icp_multistart(self, source, target, poses=36, init_T=None, max_iter=100, max_landmarks=200,
-                       inlier_dist=np.inf):
-        """icp_vtklike (centroid start) from H start rotations in one call, scored by inliers (vcp_icp_multistart).
-        poses: an int H (the library's Rz(h * 2 pi / H), h = 0 the identity) or an [H, 3, 3] array of start rotations;
-        init_T: None (T0 = target mean - R0 source mean) or [H, 3].  inliers[h] = vcp_match(source, target, M_all[h],
-        inlier_dist).count_matched.  Returns dict(best, M [4,4], M_all [H,4,4], mean_dist [H], inliers [H])."""
-        source = _f64(source, 3)
-        target = _f64(target, 3)
+    @staticmethod
+    def _icp_poses(poses, init_T):
+        """The pose arguments of the multi-start entry points -> (H, init_R [H, 9] or None, init_T [H, 3] or None)."""
         if isinstance(poses, (int, np.integer)):
             H, init_R = int(poses), None
         else:
@@ -743,17 +719,45 @@ class Context:
             init_T = _f64(init_T, 3)
             if len(init_T) != H:
                 raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
+        return H, init_R, init_T
+
+    def _icp_starts(self, fn, source, target, poses, init_T, max_iter, max_landmarks, form_args, inlier_dist, extra=()):
+        """One call of a multi-start entry point fn: the common arguments, form_args (arrays or C values) between
+        max_landmarks and inlier_dist, the common outputs, then one [H] array per (key, dtype) of extra.  Returns the
+        result dict."""
+        source = _f64(source, 3)
+        target = _f64(target, 3)
+        H, init_R, init_T = self._icp_poses(poses, init_T)
         n = max(H, 0)
         M = np.zeros(16)
         M_all = np.zeros((n, 16))
         md = np.zeros(n)
         inl = np.zeros(n, np.int32)
         best = C.c_int32(0)
-        self._chk(lib().vcp_icp_multistart(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
-                                           C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T),
-                                           int(max_iter), int(max_landmarks), C.c_double(inlier_dist), _ptr(M),
-                                           C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl)))
-        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl)
+        more = [(key, np.zeros(n, dtype)) for key, dtype in extra]
+        c_args = [_ptr(a) if isinstance(a, np.ndarray) else a for a in form_args]  # form_args keeps the arrays alive
+        self._chk(fn(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target), C.c_int64(len(target)), C.c_int32(H),
+                     _ptr(init_R), _ptr(init_T), int(max_iter), int(max_landmarks), *c_args, C.c_double(inlier_dist),
+                     _ptr(M), C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl), *[_ptr(a) for _, a in more]))
+        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
+                    **dict(more))
+
+    _ICP_COUNTED = (("kept", np.int64), ("starved", np.int32))  # what every counted form returns per pose
+
+    @staticmethod
+    def _icp_schedule(sched, min_pairs):
+        """A counted form's schedule (gates or keep shares) and min_pairs as form_args of _icp_starts."""
+        sched = _f64(sched).reshape(-1)
+        return sched, C.c_int32(len(sched)), C.c_int32(min_pairs)
+
+    def icp_multistart(self, source, target, poses=36, init_T=None, max_iter=100, max_landmarks=200,
+                       inlier_dist=np.inf):
+        """icp_vtklike (centroid start) from H start rotations in one call, scored by inliers (vcp_icp_multistart).
+        poses: an int H (the library's Rz(h * 2 pi / H), h = 0 the identity) or an [H, 3, 3] array of start rotations;
+        init_T: None (T0 = target mean - R0 source mean) or [H, 3].  inliers[h] = vcp_match(source, target, M_all[h],
+        inlier_dist).count_matched.  Returns dict(best, M [4,4], M_all [H,4,4], mean_dist [H], inliers [H])."""
+        return self._icp_starts(lib().vcp_icp_multistart, source, target, poses, init_T, max_iter, max_landmarks, (),
+                                inlier_dist)
 
     def icp_gated(self, source, target, gates, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
                   inlier_dist=np.inf):
@@ -761,33 +765,8 @@ class Context:
         pairs at gates[min(r, len(gates)) - 1] or farther out of its sums; a round that keeps fewer than min_pairs
         pairs changes nothing and counts as starved.  poses, init_T, inlier_dist: as icp_multistart.  Returns its dict
         plus kept [H] int64 (the last round's count) and starved [H] int32."""
-        source = _f64(source, 3)
-        target = _f64(target, 3)
-        gates = _f64(gates).reshape(-1)
-        if isinstance(poses, (int, np.integer)):
-            H, init_R = int(poses), None
-        else:
-            init_R = _f64(poses).reshape(-1, 9)
-            H = len(init_R)
-        if init_T is not None:
-            init_T = _f64(init_T, 3)
-            if len(init_T) != H:
-                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
-        n = max(H, 0)
-        M = np.zeros(16)
-        M_all = np.zeros((n, 16))
-        md = np.zeros(n)
-        inl = np.zeros(n, np.int32)
-        kept = np.zeros(n, np.int64)
-        starved = np.zeros(n, np.int32)
-        best = C.c_int32(0)
-        self._chk(lib().vcp_icp_gated(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
-                                      C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter),
-                                      int(max_landmarks), _ptr(gates), C.c_int32(len(gates)), C.c_int32(min_pairs),
-                                      C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl),
-                                      _ptr(kept), _ptr(starved)))
-        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
-                    kept=kept, starved=starved)
+        return self._icp_starts(lib().vcp_icp_gated, source, target, poses, init_T, max_iter, max_landmarks,
+                                self._icp_schedule(gates, min_pairs), inlier_dist, self._ICP_COUNTED)
 
     def icp_sim(self, source, target, gates, ratio_range, poses=1, init_T=None, max_iter=100, max_landmarks=200,
                 min_pairs=3, inlier_dist=np.inf):
@@ -795,36 +774,10 @@ class Context:
         ratio_range = (ratio_min, ratio_max), ratio_min <= 1 <= ratio_max: the bounds on the product of the scale
         factors a pose applies to its start.  Returns icp_gated's dict plus ratio [H] (that product) and unscaled [H]
         int32 (rounds whose scale the kept pairs did not determine)."""
-        source = _f64(source, 3)
-        target = _f64(target, 3)
-        gates = _f64(gates).reshape(-1)
         rmin, rmax = (float(v) for v in ratio_range)
-        if isinstance(poses, (int, np.integer)):
-            H, init_R = int(poses), None
-        else:
-            init_R = _f64(poses).reshape(-1, 9)
-            H = len(init_R)
-        if init_T is not None:
-            init_T = _f64(init_T, 3)
-            if len(init_T) != H:
-                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
-        n = max(H, 0)
-        M = np.zeros(16)
-        M_all = np.zeros((n, 16))
-        md = np.zeros(n)
-        inl = np.zeros(n, np.int32)
-        kept = np.zeros(n, np.int64)
-        starved = np.zeros(n, np.int32)
-        ratio = np.zeros(n)
-        unscaled = np.zeros(n, np.int32)
-        best = C.c_int32(0)
-        self._chk(lib().vcp_icp_sim(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target), C.c_int64(len(target)),
-                                    C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter), int(max_landmarks),
-                                    _ptr(gates), C.c_int32(len(gates)), C.c_int32(min_pairs), C.c_double(rmin),
-                                    C.c_double(rmax), C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all),
-                                    _ptr(md), _ptr(inl), _ptr(kept), _ptr(starved), _ptr(ratio), _ptr(unscaled)))
-        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
-                    kept=kept, starved=starved, ratio=ratio, unscaled=unscaled)
+        return self._icp_starts(lib().vcp_icp_sim, source, target, poses, init_T, max_iter, max_landmarks,
+                                self._icp_schedule(gates, min_pairs) + (C.c_double(rmin), C.c_double(rmax)), inlier_dist,
+                                self._ICP_COUNTED + (("ratio", np.float64), ("unscaled", np.int32)))
 
     def icp_trimmed(self, source, target, keep, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
                     inlier_dist=np.inf):
@@ -832,34 +785,9 @@ class Context:
         m = min(L, ceil(keep[min(r, len(keep)) - 1] * L)) of its L landmarks that lie closest to their nearest target;
         a round with m < min_pairs changes nothing and counts as starved.  poses, init_T, inlier_dist: as
         icp_multistart.  Returns icp_gated's dict plus trim_dist [H], the largest kept distance of the last round."""
-        source = _f64(source, 3)
-        target = _f64(target, 3)
-        keep = _f64(keep).reshape(-1)
-        if isinstance(poses, (int, np.integer)):
-            H, init_R = int(poses), None
-        else:
-            init_R = _f64(poses).reshape(-1, 9)
-            H = len(init_R)
-        if init_T is not None:
-            init_T = _f64(init_T, 3)
-            if len(init_T) != H:
-                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
-        n = max(H, 0)
-        M = np.zeros(16)
-        M_all = np.zeros((n, 16))
-        md = np.zeros(n)
-        inl = np.zeros(n, np.int32)
-        kept = np.zeros(n, np.int64)
-        starved = np.zeros(n, np.int32)
-        td = np.zeros(n)
-        best = C.c_int32(0)
-        self._chk(lib().vcp_icp_trimmed(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
-                                        C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter),
-                                        int(max_landmarks), _ptr(keep), C.c_int32(len(keep)), C.c_int32(min_pairs),
-                                        C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(md),
-                                        _ptr(inl), _ptr(kept), _ptr(starved), _ptr(td)))
-        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
-                    kept=kept, starved=starved, trim_dist=td)
+        return self._icp_starts(lib().vcp_icp_trimmed, source, target, poses, init_T, max_iter, max_landmarks,
+                                self._icp_schedule(keep, min_pairs), inlier_dist,
+                                self._ICP_COUNTED + (("trim_dist", np.float64),))
 
     def icp_unique(self, source, target, gates, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
                    inlier_dist=np.inf):
@@ -867,34 +795,9 @@ class Context:
         nearest target only the closest (ties: the lower index) may enter the round's sums, and the round's gate then
         decides on it as in icp_gated.  Arguments as icp_gated.  Returns its dict plus lost [H] int64, the last round's
         count of landmarks that were not their target's winner."""
-        source = _f64(source, 3)
-        target = _f64(target, 3)
-        gates = _f64(gates).reshape(-1)
-        if isinstance(poses, (int, np.integer)):
-            H, init_R = int(poses), None
-        else:
-            init_R = _f64(poses).reshape(-1, 9)
-            H = len(init_R)
-        if init_T is not None:
-            init_T = _f64(init_T, 3)
-            if len(init_T) != H:
-                raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
-        n = max(H, 0)
-        M = np.zeros(16)
-        M_all = np.zeros((n, 16))
-        md = np.zeros(n)
-        inl = np.zeros(n, np.int32)
-        kept = np.zeros(n, np.int64)
-        starved = np.zeros(n, np.int32)
-        lost = np.zeros(n, np.int64)
-        best = C.c_int32(0)
-        self._chk(lib().vcp_icp_unique(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target),
-                                       C.c_int64(len(target)), C.c_int32(H), _ptr(init_R), _ptr(init_T), int(max_iter),
-                                       int(max_landmarks), _ptr(gates), C.c_int32(len(gates)), C.c_int32(min_pairs),
-                                       C.c_double(inlier_dist), _ptr(M), C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl),
-                                       _ptr(kept), _ptr(starved), _ptr(lost)))
-        return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
-                    kept=kept, starved=starved, lost=lost)
+        return self._icp_starts(lib().vcp_icp_unique, source, target, poses, init_T, max_iter, max_landmarks,
+                                self._icp_schedule(gates, min_pairs), inlier_dist,
+                                self._ICP_COUNTED + (("lost", np.int64),))
 
     def register_pairs(self, source, target, bases, len_tol, inlier_dist, mirror=False, max_landmarks=200):
         """vcp_register_pairs: a pose of source on target without a start.  Every base (two source indices) is laid on

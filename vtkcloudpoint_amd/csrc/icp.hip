@@ -14,6 +14,13 @@
 // and its slice of partial rows, k_icp_step runs one workgroup per state, and each state's partition into workgroups and
 // reduction order are those of a single run, so every pose's bits are independent of the batch.  k_icpms_score then
 // counts, per pose, the source points vcp_match would call matched.
+// Forms (vcp.h: gated, similarity, trimmed, unique-correspondence ICP): a form is a POLICY type, the last argument of
+// the two pass kernels k_icp_pass<TB, NNMODE, G> and k_icp_pass_small<TB, G>.  The policy says at compile time whether
+// the pass searches, sums, stores keys, counts kept pairs; the bodies share one per-pair function (icp_pair: the keep
+// rule and the 16 or 18 accumulations, written once) and one epilogue.  The plain policy NoGate is empty.  The forms
+// that count their kept pairs share one step, k_icp_step_kept<F>, whose FORM type F holds what a form adds to it.  On
+// the host one IcpVariant names the form of a run, icp_layout() places everything a run keeps in the workspace, and
+// PassLaunch launches a pass on the path the run has chosen.  The Horn solve itself lives in horn.hpp.
 //
 // Nearest neighbour: the model index is wave-uniform, so model points come through the scalar cache, four per
 // trip.  Distances are first screened in binary32 (three FMAs per pair) with a rigorous rounding bound; only model points whose
@@ -23,9 +30,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 #include <vector>
 
+#include "horn.hpp"
 #include "match.hpp"
 #include "nngrid.hpp"
 #include "reduce.hpp"
@@ -51,29 +58,75 @@ struct IcpState {
   long long kept;  // gated runs: pairs the last pass kept
 };
 
-// What a gated pass reads beside the state (vcp.h, vcp_icp_gated): the schedule on the device (round r, 1-based, uses
-// gates[min(r, n_gates) - 1]; the state's round counter says which), one kept count per workgroup next to its partial
-// row, and optionally the per-point verdict.
+// ---- the policies of a pass --------------------------------------------------------------------------------------
+// Both pass kernels are compiled once per POLICY, the type of their last argument: it holds what that form of the pass
+// reads beside the state, and says at compile time what the pass does.
+//   SEARCH  it runs the NN search (false: it reads the index a distance pass stored)
+//   SUMS    it accumulates NS columns and folds them into the workgroup's partial row
+//   STORE   it stores K(dd) and the index found per landmark: store(view, i, order, K)
+//   COUNT   it decides per pair whether the pair enters the sums, keeps(view, i, order, dd, code, nlost), writes the
+//           verdict to keep[] (if not NULL) and the workgroup's count of kept pairs to pkept
+//   LOST    it also counts the pairs that are not their target's winner, into plost
+//   NS      columns of a row
+//   view(st, nd)  what the pass needs of its pose (blockIdx.y), read once before the loop
+// A dropped pair adds +0.0 to each row at its own place in the tree, which therefore stays the ungated one.
+struct PoseView {
+  double gate;              // this round's gate
+  unsigned long long* key;  // [L]: K(dd) per landmark of the pose
+  int32_t* nn;              // [L]: the index found
+  unsigned long long thrk;  // trimmed: the selected key
+  uint32_t thri;            // and its landmark
+  unsigned long long* skey;  // unique: [nt] the pose's slots
+  const uint32_t* sidx;
+};
+// round r (1-based) uses sched[min(r, n) - 1]; the state's round counter says which
+__device__ __forceinline__ double sched_now(const double* sched, int n, const IcpState* st) {
+  return sched[min(st->round + 1, n) - 1];
+}
+__device__ __forceinline__ PoseView stored_view(unsigned long long* key, int32_t* nn, int64_t nd) {
+  PoseView v{};
+  v.key = key + (size_t)blockIdx.y * (size_t)nd;
+  v.nn = nn + (size_t)blockIdx.y * (size_t)nd;
+  return v;
+}
+
+// The plain pass: every pair enters the sums, unconditionally.  Empty: the kernels' other arguments lie where they did.
+struct NoGate {
+  static constexpr bool SEARCH = true, SUMS = true, STORE = false, COUNT = false, LOST = false;
+  static constexpr int NS = 16;
+  __device__ __forceinline__ PoseView view(const IcpState*, int64_t) const { return PoseView{}; }
+};
+// The gated pass (vcp.h, vcp_icp_gated): the schedule on the device, one kept count per workgroup next to its partial
+// row, and optionally the per-point verdict.  A pair whose distance sqrt(dd) is >= the round's gate is dropped; dd is
+// the SSE term.  A NaN dd compares false: kept.
 struct GateArgs {
+  static constexpr bool SEARCH = true, SUMS = true, STORE = false, COUNT = true, LOST = false;
+  static constexpr int NS = 16;
   const double* gates;
   int n_gates;
   uint32_t* pkept;  // [poses][workgroups]
   uint8_t* keep;    // [nd] or NULL
+  __device__ __forceinline__ PoseView view(const IcpState* st, int64_t) const {
+    PoseView v{};
+    v.gate = sched_now(gates, n_gates, st);
+    return v;
+  }
+  __device__ __forceinline__ bool keeps(const PoseView& v, int64_t, int, double dd, uint8_t& code, uint32_t&) const {
+    const bool kp = !(sqrt(dd) >= v.gate);
+    code = kp ? 1 : 0;
+    return kp;
+  }
 };
-struct NoGate {};
 // Similarity ICP (vcp.h, "similarity ICP"): the gated pass with two more columns, sum |p|^2 at 16 and sum |y|^2 at 17,
 // through the same tree.  A type of its own: the kernels of GateArgs stay the 16-wide ones they were.
-struct SimGate {
-  GateArgs g;
+struct SimGate : GateArgs {
+  static constexpr int NS = 18;
 };
-// columns of a pass's rows
-template <class G>
-constexpr int icp_ncol = std::is_same<G, SimGate>::value ? 18 : 16;
 
 // Trimmed ICP (vcp.h, "trimmed ICP"): a round keeps the m landmarks with the smallest 96-bit keys [K(dd) | index].
-// Three steps per round and pose: a pass that runs the NN search and stores K(dd) and the index found (G = TrimDist),
-// a radix select of the rank-m key (k_icpt_select_wg, or k_icpt_hist x 12 + k_icpt_select_fin), and the sums pass
-// (G = TrimSum), which reads both back and keeps "key <= the selected one" where the gated pass tests the distance.
+// Three steps per round and pose: a pass that runs the NN search and stores K(dd) and the index found (TrimDist), a
+// radix select of the rank-m key (k_icpt_select_wg, or k_icpt_hist x 12 + k_icpt_select_fin), and the sums pass
+// (TrimSum), which reads both back and keeps "key <= the selected one" where the gated pass tests the distance.
 struct TrimSel {
   unsigned long long key;  // K(dd) of the kept pair with the largest key: thr's bit pattern (all ones: NaN)
   uint32_t idx, pad;       // and its landmark
@@ -88,18 +141,38 @@ struct TrimArgs {
   uint32_t* pkept;          // [poses][workgroups]
   uint8_t* keep;            // [L] or NULL
 };
-struct TrimDist {
-  TrimArgs a;
+struct TrimDist : TrimArgs {
+  static constexpr bool SEARCH = true, SUMS = false, STORE = true, COUNT = false, LOST = false;
+  static constexpr int NS = 16;
+  __device__ __forceinline__ PoseView view(const IcpState*, int64_t nd) const { return stored_view(key, nn, nd); }
+  __device__ __forceinline__ void store(const PoseView& v, int64_t i, int order, unsigned long long k) const {
+    v.key[i] = k;
+    v.nn[i] = order;
+  }
 };
-struct TrimSum {
-  TrimArgs a;
+struct TrimSum : TrimArgs {
+  static constexpr bool SEARCH = false, SUMS = true, STORE = false, COUNT = true, LOST = false;
+  static constexpr int NS = 16;
+  __device__ __forceinline__ PoseView view(const IcpState*, int64_t nd) const {
+    PoseView v = stored_view(key, nn, nd);
+    v.thrk = sel[blockIdx.y].key;
+    v.thri = sel[blockIdx.y].idx;
+    return v;
+  }
+  __device__ __forceinline__ bool keeps(const PoseView& v, int64_t i, int, double, uint8_t& code, uint32_t&) const {
+    const unsigned long long k = v.key[i];
+    const bool kp = k < v.thrk || (k == v.thrk && (uint32_t)i <= v.thri);
+    code = kp ? 1 : 0;
+    return kp;
+  }
 };
+
 // Unique-correspondence ICP (vcp.h, "unique-correspondence ICP"): of the landmarks that share a nearest target, only the
 // one with the smallest 96-bit key [K(dd) | index] -- the target's WINNER -- may enter the sums; the gate then decides
 // on the winner as it does in the gated pass.  Three steps per round and pose: a pass that runs the NN search, stores
-// K(dd) and the index found and takes the 64-bit minimum of K(dd) in the slot of (pose, target) (G = UniqDist); the tie
+// K(dd) and the index found and takes the 64-bit minimum of K(dd) in the slot of (pose, target) (UniqDist); the tie
 // pass k_icpu_tie, the 32-bit minimum of the landmark among those whose K equals the slot's; and the sums pass
-// (G = UniqSum), which keeps "my key and my index are the slot's, and the gate keeps me".  A slot is 12 bytes, two
+// (UniqSum), which keeps "my key and my index are the slot's, and the gate keeps me".  A slot is 12 bytes, two
 // arrays: skey [poses][nt] and sidx [poses][nt], all ones between rounds.
 struct UniqArgs {
   const double* gates;  // the schedule on the device, as GateArgs'
@@ -113,20 +186,39 @@ struct UniqArgs {
   uint32_t* plost;           // [poses][workgroups]: pairs that are not their target's winner
   uint8_t* keep;             // [L] or NULL: 1 kept, 0 winner dropped by the gate, 2 not the winner
 };
-struct UniqDist {
-  UniqArgs a;
+struct UniqDist : UniqArgs {
+  static constexpr bool SEARCH = true, SUMS = false, STORE = true, COUNT = false, LOST = false;
+  static constexpr int NS = 16;
+  __device__ __forceinline__ PoseView view(const IcpState*, int64_t nd) const {
+    PoseView v = stored_view(key, nn, nd);
+    v.skey = skey + (size_t)blockIdx.y * (size_t)nt;
+    return v;
+  }
+  __device__ __forceinline__ void store(const PoseView& v, int64_t i, int order, unsigned long long k) const {
+    v.key[i] = k;
+    v.nn[i] = order;
+    atomicMin(v.skey + (size_t)order, k);
+  }
 };
-struct UniqSum {
-  UniqArgs a;
+struct UniqSum : UniqArgs {
+  static constexpr bool SEARCH = false, SUMS = true, STORE = false, COUNT = true, LOST = true;
+  static constexpr int NS = 16;
+  __device__ __forceinline__ PoseView view(const IcpState* st, int64_t nd) const {
+    PoseView v = stored_view(key, nn, nd);
+    v.gate = sched_now(gates, n_gates, st);
+    v.skey = skey + (size_t)blockIdx.y * (size_t)nt;
+    v.sidx = sidx + (size_t)blockIdx.y * (size_t)nt;
+    return v;
+  }
+  __device__ __forceinline__ bool keeps(const PoseView& v, int64_t i, int order, double dd, uint8_t& code, uint32_t& nlost) const {
+    const bool win = v.key[i] == v.skey[order] && (uint32_t)i == v.sidx[order];
+    const bool kp = win && !(sqrt(dd) >= v.gate);
+    nlost += win ? 0u : 1u;
+    code = win ? (kp ? 1 : 0) : 2;
+    return kp;
+  }
 };
-__device__ __forceinline__ uint8_t* keep_of(const GateArgs& g) { return g.keep; }
-__device__ __forceinline__ uint8_t* keep_of(const TrimSum& t) { return t.a.keep; }
-__device__ __forceinline__ uint8_t* keep_of(const SimGate& s) { return s.g.keep; }
-__device__ __forceinline__ uint8_t* keep_of(const UniqSum& u) { return u.a.keep; }
-__device__ __forceinline__ uint32_t* pkept_of(const GateArgs& g) { return g.pkept; }
-__device__ __forceinline__ uint32_t* pkept_of(const TrimSum& t) { return t.a.pkept; }
-__device__ __forceinline__ uint32_t* pkept_of(const SimGate& s) { return s.g.pkept; }
-__device__ __forceinline__ uint32_t* pkept_of(const UniqSum& u) { return u.a.pkept; }
+
 // K(dd): dd's bit pattern (dd >= +0, so the unsigned order is the numeric one, +inf last of the numbers), NaN above all
 __device__ __forceinline__ unsigned long long trim_key(double dd) {
   return dd != dd ? ~0ull : (unsigned long long)__double_as_longlong(dd);
@@ -204,23 +296,16 @@ struct StepArgs {
 };
 
 constexpr int MTILE = 1024;
-// The gate of the pass a gated kernel runs now, and a workgroup's kept count written next to its partial row (wave
-// shuffle, then the waves in order: integers, exact in any order).
-__device__ __forceinline__ double gate_now(const GateArgs& ga, const IcpState* st) {
-  return ga.gates[min(st->round + 1, ga.n_gates) - 1];
-}
-__device__ __forceinline__ double gate_now(const SimGate& sg, const IcpState* st) { return gate_now(sg.g, st); }
-__device__ __forceinline__ double gate_now(const UniqSum& us, const IcpState* st) {
-  return us.a.gates[min(st->round + 1, us.a.n_gates) - 1];
-}
 // The keep count of the round a trimmed kernel runs now: min(L, ceil(f * L)), one multiplication; f in (0, 1] (checked
 // on the host), so the count lies in [1, L].
 __device__ __forceinline__ long long trim_m(const TrimArgs& a, const IcpState* st, long long L) {
   if (a.m_fixed > 0) return a.m_fixed;
-  const double f = a.share[min(st->round + 1, a.n_share) - 1];
+  const double f = sched_now(a.share, a.n_share, st);
   const long long m = (long long)ceil(f * (double)L);
   return m < L ? m : L;
 }
+// A workgroup's count written next to its partial row (wave shuffle, then the waves in order: integers, exact in any
+// order).
 template <int TB>
 __device__ __forceinline__ void block_count(uint32_t c, uint32_t* __restrict__ out) {
   __shared__ uint32_t sk[TB / 64];
@@ -235,43 +320,115 @@ __device__ __forceinline__ void block_count(uint32_t c, uint32_t* __restrict__ o
   }
 }
 
-// GATED (G = GateArgs): a pair whose distance sqrt(dd) is >= the round's gate adds +0.0 to each of the 16 rows at its
-// own place in the tree, which therefore stays the ungated one; dd is the SSE term.  A NaN dd compares false: kept.
+// ---- what the two pass bodies share: everything but the search --------------------------------------------------
+// TransPoint: r = R*p accumulated k ascending from 0 (Matrix.StupidMultiply), then + T
+__device__ __forceinline__ void trans_point(const double (&R)[9], const double (&T)[3], double d0, double d1, double d2,
+                                            double (&p)[3]) {
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    double acc = 0.0;
+    acc += R[3 * r] * d0;
+    acc += R[3 * r + 1] * d1;
+    acc += R[3 * r + 2] * d2;
+    p[r] = acc + T[r];
+  }
+}
+
+// More than one candidate within the bound `lim` of the screening (or non-finite values): exact binary64 among the
+// candidates, in index order, strict `<` -- FindClosestPointSet's rule (the C# seeds with model[0] and replaces on `<`,
+// so the lowest index among the exact minima wins; every exact minimum is a candidate by the bound)
+__device__ __forceinline__ int icp_exact_scan(const double* model, const float4* model32, int nm, float q0, float q1,
+                                              float q2, const double (&p)[3], float lim) {
+  int order = 0;
+  double best = INFINITY;
+  bool have = false;
+  for (int jj = 0; jj < nm; jj++) {
+    const float4 m4 = model32[jj];
+    const float sc = __builtin_fmaf(-q0, m4.x, __builtin_fmaf(-q1, m4.y, __builtin_fmaf(-q2, m4.z, m4.w)));
+    if (sc <= lim || !(sc == sc) || !(lim == lim)) {
+      const double e0 = p[0] - model[3 * jj], e1 = p[1] - model[3 * jj + 1], e2 = p[2] - model[3 * jj + 2];
+      const double dd = e0 * e0 + e1 * e1 + e2 * e2;
+      if (!have || dd < best) {
+        best = dd;
+        order = jj;
+        have = true;
+      }
+    }
+  }
+  return order;
+}
+
+// One pair (landmark i at p, model point `order`) under policy G: the key and index stored, or the pair decided and --
+// as far as kept -- added to the columns s.  Every column receives one addition per pair in either case (a dropped
+// pair's is +0.0 through a select, never a skipped statement: no sum can become -0.0).
+template <class G>
+__device__ __forceinline__ void icp_pair(const G& ga, const PoseView& v, int64_t i, int order, const double (&p)[3],
+                                         const double* model, double (&s)[G::NS], uint32_t& nkept, uint32_t& nlost) {
+  const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
+  const double y[3] = {y0, y1, y2};
+  if constexpr (G::STORE) {
+    const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
+    ga.store(v, i, order, trim_key(e0 * e0 + e1 * e1 + e2 * e2));
+  } else if constexpr (G::COUNT) {
+    const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
+    const double dd = e0 * e0 + e1 * e1 + e2 * e2;
+    uint8_t code;  // what keep[] receives
+    const bool kp = ga.keeps(v, i, order, dd, code, nlost);
+    if (ga.keep) ga.keep[i] = code;
+    nkept += kp ? 1u : 0u;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      s[r] += kp ? p[r] : 0.0;
+      s[3 + r] += kp ? y[r] : 0.0;
+#pragma unroll
+      for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[r] * y[c] : 0.0;
+    }
+    s[15] += kp ? dd : 0.0;
+    if constexpr (G::NS == 18) {
+      s[16] += kp ? (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2] : 0.0;
+      s[17] += kp ? (y0 * y0 + y1 * y1) + y2 * y2 : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      s[r] += p[r];
+      s[3 + r] += y[r];
+#pragma unroll
+      for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[r] * y[c];
+    }
+    const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
+    s[15] += e0 * e0 + e1 * e1 + e2 * e2;
+  }
+}
+
+// The end of a pass: the workgroup's partial row (pose's slice in `partial`) and its counts
+template <int TB, class G>
+__device__ __forceinline__ void icp_pass_finish(const G& ga, const double (&s)[G::NS], uint32_t nkept, uint32_t nlost,
+                                                double* partial) {
+  if constexpr (G::SUMS) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * G::NS);
+  if constexpr (G::COUNT) block_count<TB>(nkept, ga.pkept + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  if constexpr (G::LOST) {
+    __syncthreads();  // block_count's LDS words are free again
+    block_count<TB>(nlost, ga.plost + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+  }
+}
+
+// The two search bodies.  Each sits behind one __global__ template (k_icp_pass, k_icp_pass_small) that only forwards
+// its arguments: the `__restrict__` parameters of an inlined body give the loads and stores in it alias scopes of their
+// own, and the timed ungated kernels are scheduled with those.
 template <int TB, int NNMODE, class G>
 __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, const float4* __restrict__ model32,
                                               int nm, const double* __restrict__ data, int64_t nd,
                                               const IcpState* __restrict__ st, double* __restrict__ partial,
                                               int32_t* __restrict__ nn, const NNGrid& ng, const G& ga) {
-  constexpr bool SIM = std::is_same<G, SimGate>::value;  // GATED with the two columns of the scale
-  constexpr bool GATED = std::is_same<G, GateArgs>::value || SIM;
-  constexpr int NS = icp_ncol<G>;
-  // TDIST: the search alone, K(dd) and the index stored per landmark; TSUM: no search, the stored index, and the sums
-  // of the landmarks whose key is <= the selected one
-  constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
-  // UDIST / USUM: the two passes of a unique-correspondence round; DIST / RSUM: what they share with the trimmed ones
-  // (DIST: the search alone, key and index stored; RSUM: no search, the stored index)
-  constexpr bool UDIST = std::is_same<G, UniqDist>::value, USUM = std::is_same<G, UniqSum>::value;
-  constexpr bool DIST = TDIST || UDIST, RSUM = TSUM || USUM;
+  constexpr int NS = G::NS;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * NS;
   if (st->done) return;
-  double gate = 0.0;
+  const PoseView pv = ga.view(st, nd);
   uint32_t nkept = 0, nlost = 0;
-  if constexpr (GATED || USUM) gate = gate_now(ga, st);
-  unsigned long long* tkey = nullptr;
-  int32_t* tnn = nullptr;
-  unsigned long long thrk = 0;
-  uint32_t thri = 0;
-  if constexpr (DIST || RSUM) {
-    tkey = ga.a.key + (size_t)blockIdx.y * (size_t)nd;
-    tnn = ga.a.nn + (size_t)blockIdx.y * (size_t)nd;
-  }
-  if constexpr (TSUM) {
-    thrk = ga.a.sel[blockIdx.y].key;
-    thri = ga.a.sel[blockIdx.y].idx;
-  }
   constexpr bool TILED = NNMODE == 1, GRID = NNMODE == 2;
-  __shared__ float4 tile[TILED && !RSUM ? MTILE : 1];
+  __shared__ float4 tile[TILED && G::SEARCH ? MTILE : 1];
   double R[9], T[3];
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = st->R[k];
@@ -295,19 +452,11 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
     const bool live = i < nd;
     const int64_t il = live ? i : nd - 1;  // idle lanes of the last workgroup recompute the last point, unused
     const double d0 = data[3 * il], d1 = data[3 * il + 1], d2 = data[3 * il + 2];
-    // TransPoint: r = R*p accumulated k ascending from 0 (Matrix.StupidMultiply), then + T
     double p[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      double acc = 0.0;
-      acc += R[3 * r] * d0;
-      acc += R[3 * r + 1] * d1;
-      acc += R[3 * r + 2] * d2;
-      p[r] = acc + T[r];
-    }
+    trans_point(R, T, d0, d1, d2, p);
     int order = 0;
-    if constexpr (RSUM) {
-      order = tnn[il];
+    if constexpr (!G::SEARCH) {
+      order = pv.nn[il];
     } else if (GRID) {
       double bestv;
       nng::query<false>(ng, p, sub, order, bestv);
@@ -415,113 +564,24 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
         }
       }
     } else if (amb) {
-      // more than one candidate within the bound (or non-finite values): exact binary64 among the candidates, in
-      // index order, strict `<` -- FindClosestPointSet's rule (the C# seeds with model[0] and replaces on `<`, so
-      // the lowest index among the exact minima wins; every exact minimum is a candidate by the bound)
-      const float lim = b1 + tol2;
-      double best = INFINITY;
-      bool have = false;
-      order = 0;
-      for (int jj = 0; jj < nm; jj++) {
-        const float4 m4 = model32[jj];
-        const float sc = __builtin_fmaf(-q0, m4.x, __builtin_fmaf(-q1, m4.y, __builtin_fmaf(-q2, m4.z, m4.w)));
-        if (sc <= lim || !(sc == sc) || !(lim == lim)) {
-          const double e0 = p[0] - model[3 * jj], e1 = p[1] - model[3 * jj + 1], e2 = p[2] - model[3 * jj + 2];
-          const double dd = e0 * e0 + e1 * e1 + e2 * e2;
-          if (!have || dd < best) {
-            best = dd;
-            order = jj;
-            have = true;
-          }
-        }
-      }
+      order = icp_exact_scan(model, model32, nm, q0, q1, q2, p, b1 + tol2);
     }
     }  // !GRID
     if (!live || sub != 0) continue;  // one lane of the group carries the point into the sums
-    if (nn) nn[i] = order;
-    const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
-    const double y[3] = {y0, y1, y2};
-    if constexpr (DIST) {
-      const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
-      const unsigned long long k = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
-      tkey[i] = k;
-      tnn[i] = order;
-      if constexpr (UDIST) atomicMin(ga.a.skey + (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order, k);
-    } else if constexpr (GATED || RSUM) {
-      const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
-      const double dd = e0 * e0 + e1 * e1 + e2 * e2;
-      bool kp;
-      uint8_t code;  // what keep[] receives
-      if constexpr (GATED) {
-        kp = !(sqrt(dd) >= gate);
-        code = kp ? 1 : 0;
-      } else if constexpr (USUM) {
-        const size_t sl = (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order;
-        const bool win = tkey[i] == ga.a.skey[sl] && (uint32_t)i == ga.a.sidx[sl];
-        kp = win && !(sqrt(dd) >= gate);
-        nlost += win ? 0u : 1u;
-        code = win ? (kp ? 1 : 0) : 2;
-      } else {
-        const unsigned long long k = tkey[i];
-        kp = k < thrk || (k == thrk && (uint32_t)i <= thri);
-        code = kp ? 1 : 0;
-      }
-      if (keep_of(ga)) keep_of(ga)[i] = code;
-      nkept += kp ? 1u : 0u;
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        s[r] += kp ? p[r] : 0.0;
-        s[3 + r] += kp ? y[r] : 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[r] * y[c] : 0.0;
-      }
-      s[15] += kp ? dd : 0.0;
-      if constexpr (SIM) {
-        s[16] += kp ? (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2] : 0.0;
-        s[17] += kp ? (y0 * y0 + y1 * y1) + y2 * y2 : 0.0;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        s[r] += p[r];
-        s[3 + r] += y[r];
-#pragma unroll
-        for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[r] * y[c];
-      }
-      const double e0 = p[0] - y0, e1 = p[1] - y1, e2 = p[2] - y2;
-      s[15] += e0 * e0 + e1 * e1 + e2 * e2;
-    }
+    if constexpr (G::SEARCH && !G::STORE)  // the others keep the index in their own workspace: nn is NULL
+      if (nn) nn[i] = order;
+    icp_pair(ga, pv, i, order, p, model, s, nkept, nlost);
   }
-  if constexpr (!DIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
-  if constexpr (GATED || RSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
-  if constexpr (USUM) {
-    __syncthreads();  // block_count's LDS words are free again
-    block_count<TB>(nlost, ga.a.plost + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
-  }
+  icp_pass_finish<TB>(ga, s, nkept, nlost, partial);
 }
 
-template <int TB, int NNMODE>
+// The two pass kernels: the policy is the last argument; the trimmed and the unique passes get nn = nullptr (their
+// own workspace keeps the index found).
+template <int TB, int NNMODE, class G>
 __global__ __launch_bounds__(TB) void k_icp_pass(const double* __restrict__ model, const float4* __restrict__ model32,
                                                 int nm, const double* __restrict__ data, int64_t nd,
                                                 const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                int32_t* __restrict__ nn, NNGrid ng) {
-  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, NoGate());
-}
-template <int TB, int NNMODE>
-__global__ __launch_bounds__(TB) void k_icp_pass_gated(const double* __restrict__ model,
-                                                      const float4* __restrict__ model32, int nm,
-                                                      const double* __restrict__ data, int64_t nd,
-                                                      const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                      int32_t* __restrict__ nn, NNGrid ng, GateArgs ga) {
-  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, ga);
-}
-
-template <int TB, int NNMODE>
-__global__ __launch_bounds__(TB) void k_icp_pass_sim(const double* __restrict__ model,
-                                                    const float4* __restrict__ model32, int nm,
-                                                    const double* __restrict__ data, int64_t nd,
-                                                    const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                    int32_t* __restrict__ nn, NNGrid ng, SimGate ga) {
+                                                int32_t* __restrict__ nn, NNGrid ng, G ga) {
   icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nn, ng, ga);
 }
 
@@ -549,32 +609,12 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
                                                     int nm, const double* __restrict__ data, int64_t nd,
                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
                                                     int32_t* __restrict__ nn, uint32_t imask, double tolk, const G& ga) {
-  constexpr bool SIM = std::is_same<G, SimGate>::value;  // as in icp_pass_body
-  constexpr bool GATED = std::is_same<G, GateArgs>::value || SIM;
-  constexpr int NS = icp_ncol<G>;
-  constexpr bool TDIST = std::is_same<G, TrimDist>::value, TSUM = std::is_same<G, TrimSum>::value;
-  // UDIST / USUM: the two passes of a unique-correspondence round; DIST / RSUM: what they share with the trimmed ones
-  // (DIST: the search alone, key and index stored; RSUM: no search, the stored index)
-  constexpr bool UDIST = std::is_same<G, UniqDist>::value, USUM = std::is_same<G, UniqSum>::value;
-  constexpr bool DIST = TDIST || UDIST, RSUM = TSUM || USUM;
+  constexpr int NS = G::NS;
   st += blockIdx.y;  // the pose's state and partial rows (gridDim.y = 1 outside vcp_icp_multistart)
   partial += (size_t)blockIdx.y * gridDim.x * NS;
   if (st->done) return;
-  double gate = 0.0;
+  const PoseView pv = ga.view(st, nd);
   uint32_t nkept = 0, nlost = 0;
-  if constexpr (GATED || USUM) gate = gate_now(ga, st);
-  unsigned long long* tkey = nullptr;
-  int32_t* tnn = nullptr;
-  unsigned long long thrk = 0;
-  uint32_t thri = 0;
-  if constexpr (DIST || RSUM) {
-    tkey = ga.a.key + (size_t)blockIdx.y * (size_t)nd;
-    tnn = ga.a.nn + (size_t)blockIdx.y * (size_t)nd;
-  }
-  if constexpr (TSUM) {
-    thrk = ga.a.sel[blockIdx.y].key;
-    thri = ga.a.sel[blockIdx.y].idx;
-  }
   double R[9], T[3];
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = st->R[k];
@@ -595,15 +635,7 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
     for (int h = 0; h < 2; h++) {
       const int64_t il = live[h] ? idx[h] : nd - 1;  // idle slots recompute the last point, unused
       const double d0 = data[3 * il], d1 = data[3 * il + 1], d2 = data[3 * il + 2];
-      // TransPoint: r = R*p accumulated k ascending from 0 (Matrix.StupidMultiply), then + T
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        double acc = 0.0;
-        acc += R[3 * r] * d0;
-        acc += R[3 * r + 1] * d1;
-        acc += R[3 * r + 2] * d2;
-        p[h][r] = acc + T[r];
-      }
+      trans_point(R, T, d0, d1, d2, p[h]);
       const double pc0 = p[h][0] - cen0, pc1 = p[h][1] - cen1, pc2 = p[h][2] - cen2;
       q[h][0] = (float)pc0;
       q[h][1] = (float)pc1;
@@ -616,7 +648,7 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       tol2[h] = ((float)(S * S) < 1.0e37f && t2 >= 1.0e-30f) ? t2 : NAN;
     }
     float b1[2] = {INFINITY, INFINITY}, b2[2] = {INFINITY, INFINITY};
-    if constexpr (!RSUM) {
+    if constexpr (G::SEARCH) {
     const f32x2 nq0 = {-q[0][0], -q[1][0]}, nq1 = {-q[0][1], -q[1][1]}, nq2 = {-q[0][2], -q[1][2]};
     // the mask lives in a VGPR so that (score & keep) | j is ONE v_and_or_b32 (a VOP3 reads one scalar operand: j)
     uint32_t keep;
@@ -649,158 +681,28 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
         b1[h] = min_raw(b1[h], ta);
       }
     }
-    }  // !RSUM
+    }  // SEARCH
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       int order = (int)(__float_as_uint(b1[h]) & imask);
-      const bool amb = !RSUM && !(b2[h] > b1[h] + tol2[h]);
-      if constexpr (RSUM) order = tnn[live[h] ? idx[h] : nd - 1];
-      if (amb) {
-        // more than one candidate within the bound (or non-finite values): exact binary64 among the candidates, in
-        // index order, strict `<` -- FindClosestPointSet's rule (lowest index among the exact minima)
-        const float lim = b1[h] + tol2[h];
-        double best = INFINITY;
-        bool have = false;
-        order = 0;
-        for (int jj = 0; jj < nm; jj++) {
-          const float4 m4 = model32[jj];
-          const float sc = __builtin_fmaf(-q[h][0], m4.x, __builtin_fmaf(-q[h][1], m4.y, __builtin_fmaf(-q[h][2], m4.z, m4.w)));
-          if (sc <= lim || !(sc == sc) || !(lim == lim)) {
-            const double e0 = p[h][0] - model[3 * jj], e1 = p[h][1] - model[3 * jj + 1], e2 = p[h][2] - model[3 * jj + 2];
-            const double dd = e0 * e0 + e1 * e1 + e2 * e2;
-            if (!have || dd < best) {
-              best = dd;
-              order = jj;
-              have = true;
-            }
-          }
-        }
-      }
+      const bool amb = G::SEARCH && !(b2[h] > b1[h] + tol2[h]);
+      if constexpr (!G::SEARCH) order = pv.nn[live[h] ? idx[h] : nd - 1];
+      if (amb) order = icp_exact_scan(model, model32, nm, q[h][0], q[h][1], q[h][2], p[h], b1[h] + tol2[h]);
       if (!live[h]) continue;
-      if (nn) nn[idx[h]] = order;
-      const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
-      const double y[3] = {y0, y1, y2};
-      if constexpr (DIST) {
-        const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
-        const unsigned long long k = trim_key(e0 * e0 + e1 * e1 + e2 * e2);
-        tkey[idx[h]] = k;
-        tnn[idx[h]] = order;
-        if constexpr (UDIST) atomicMin(ga.a.skey + (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order, k);
-      } else if constexpr (GATED || RSUM) {
-        const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
-        const double dd = e0 * e0 + e1 * e1 + e2 * e2;
-        bool kp;
-        uint8_t code;  // what keep[] receives
-        if constexpr (GATED) {
-          kp = !(sqrt(dd) >= gate);
-          code = kp ? 1 : 0;
-        } else if constexpr (USUM) {
-          const size_t sl = (size_t)blockIdx.y * (size_t)ga.a.nt + (size_t)order;
-          const bool win = tkey[idx[h]] == ga.a.skey[sl] && (uint32_t)idx[h] == ga.a.sidx[sl];
-          kp = win && !(sqrt(dd) >= gate);
-          nlost += win ? 0u : 1u;
-          code = win ? (kp ? 1 : 0) : 2;
-        } else {
-          const unsigned long long k = tkey[idx[h]];
-          kp = k < thrk || (k == thrk && (uint32_t)idx[h] <= thri);
-          code = kp ? 1 : 0;
-        }
-        if (keep_of(ga)) keep_of(ga)[idx[h]] = code;
-        nkept += kp ? 1u : 0u;
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-          s[r] += kp ? p[h][r] : 0.0;
-          s[3 + r] += kp ? y[r] : 0.0;
-#pragma unroll
-          for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[h][r] * y[c] : 0.0;
-        }
-        s[15] += kp ? dd : 0.0;
-        if constexpr (SIM) {
-          s[16] += kp ? (p[h][0] * p[h][0] + p[h][1] * p[h][1]) + p[h][2] * p[h][2] : 0.0;
-          s[17] += kp ? (y0 * y0 + y1 * y1) + y2 * y2 : 0.0;
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-          s[r] += p[h][r];
-          s[3 + r] += y[r];
-#pragma unroll
-          for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += p[h][r] * y[c];
-        }
-        const double e0 = p[h][0] - y0, e1 = p[h][1] - y1, e2 = p[h][2] - y2;
-        s[15] += e0 * e0 + e1 * e1 + e2 * e2;
-      }
+      if constexpr (G::SEARCH && !G::STORE)  // the others keep the index in their own workspace: nn is NULL
+        if (nn) nn[idx[h]] = order;
+      icp_pair(ga, pv, idx[h], order, p[h], model, s, nkept, nlost);
     }
   }
-  if constexpr (!DIST) block_fold<TB>(s, FoldSum(), partial + (size_t)blockIdx.x * NS);
-  if constexpr (GATED || RSUM) block_count<TB>(nkept, pkept_of(ga) + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
-  if constexpr (USUM) {
-    __syncthreads();  // block_count's LDS words are free again
-    block_count<TB>(nlost, ga.a.plost + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
-  }
+  icp_pass_finish<TB>(ga, s, nkept, nlost, partial);
 }
 
-template <int TB>
+template <int TB, class G>
 __global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict__ model, const float4* __restrict__ model32,
                                                       int nm, const double* __restrict__ data, int64_t nd,
                                                       const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                      int32_t* __restrict__ nn, uint32_t imask, double tolk) {
-  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, NoGate());
-}
-template <int TB>
-__global__ __launch_bounds__(TB) void k_icp_pass_small_gated(const double* __restrict__ model,
-                                                            const float4* __restrict__ model32, int nm,
-                                                            const double* __restrict__ data, int64_t nd,
-                                                            const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                            int32_t* __restrict__ nn, uint32_t imask, double tolk,
-                                                            GateArgs ga) {
+                                                      int32_t* __restrict__ nn, uint32_t imask, double tolk, G ga) {
   icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
-}
-
-template <int TB>
-__global__ __launch_bounds__(TB) void k_icp_pass_small_sim(const double* __restrict__ model,
-                                                          const float4* __restrict__ model32, int nm,
-                                                          const double* __restrict__ data, int64_t nd,
-                                                          const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                          int32_t* __restrict__ nn, uint32_t imask, double tolk,
-                                                          SimGate ga) {
-  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
-}
-
-// The trimmed round's two passes (G = TrimDist, TrimSum): the same bodies, partition and fold.
-template <int TB, int NNMODE, class G>
-__global__ __launch_bounds__(TB) void k_icp_pass_trim(const double* __restrict__ model,
-                                                     const float4* __restrict__ model32, int nm,
-                                                     const double* __restrict__ data, int64_t nd,
-                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                     NNGrid ng, G ta) {
-  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nullptr, ng, ta);
-}
-template <int TB, class G>
-__global__ __launch_bounds__(TB) void k_icp_pass_small_trim(const double* __restrict__ model,
-                                                           const float4* __restrict__ model32, int nm,
-                                                           const double* __restrict__ data, int64_t nd,
-                                                           const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                           uint32_t imask, double tolk, G ta) {
-  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nullptr, imask, tolk, ta);
-}
-
-// The unique-correspondence round's two passes (G = UniqDist, UniqSum): the same bodies, partition and fold.
-template <int TB, int NNMODE, class G>
-__global__ __launch_bounds__(TB) void k_icp_pass_uniq(const double* __restrict__ model,
-                                                     const float4* __restrict__ model32, int nm,
-                                                     const double* __restrict__ data, int64_t nd,
-                                                     const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                     NNGrid ng, G ua) {
-  icp_pass_body<TB, NNMODE>(model, model32, nm, data, nd, st, partial, nullptr, ng, ua);
-}
-template <int TB, class G>
-__global__ __launch_bounds__(TB) void k_icp_pass_small_uniq(const double* __restrict__ model,
-                                                           const float4* __restrict__ model32, int nm,
-                                                           const double* __restrict__ data, int64_t nd,
-                                                           const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                           uint32_t imask, double tolk, G ua) {
-  icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nullptr, imask, tolk, ua);
 }
 
 // ---- the tie pass and the slot reset of a unique-correspondence round -----------------------------------------------
@@ -981,228 +883,6 @@ __global__ __launch_bounds__(ITPB) void k_icpt_select_fin(const IcpState* __rest
   for (int d = 0; d < TRIM_DIGITS; d++) ghist[d * ITPB + threadIdx.x] = 0;
 }
 
-// ---- Horn's unit-quaternion closed form (host and device: same code, same rounding) -----------------
-// cyclic Jacobi sweeps on a symmetric 4x4 (independent of the oracle's max-pivot variant).  Every index is a
-// compile-time constant after unrolling, so on the device A and V live in registers (dynamic indexing would put
-// them in scratch memory and make the single solving thread several times slower).
-template <int P, int Q>
-__host__ __device__ inline void jrot(double (&A)[4][4], double (&V)[4][4]) {
-  if (A[P][Q] == 0.0) return;
-  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * A[P][Q]);
-  const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const double akp = A[k][P], akq = A[k][Q];
-    A[k][P] = c * akp - s * akq;
-    A[k][Q] = s * akp + c * akq;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const double apk = A[P][k], aqk = A[Q][k];
-    A[P][k] = c * apk - s * aqk;
-    A[Q][k] = s * apk + c * aqk;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const double vkp = V[k][P], vkq = V[k][Q];
-    V[k][P] = c * vkp - s * vkq;
-    V[k][Q] = s * vkp + c * vkq;
-  }
-}
-
-// A = V0^T Q V0 and V = V0 on entry (V0 = identity for a cold start): on return the columns of V are eigenvectors of Q
-__host__ __device__ inline void jacobi4(double (&A)[4][4], double (&V)[4][4]) {
-  for (int sweep = 0; sweep < 60; sweep++) {
-    double off = 0.0, diag = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      diag += A[i][i] * A[i][i];
-#pragma unroll
-      for (int j = i + 1; j < 4; j++) off += A[i][j] * A[i][j];
-    }
-    if (off <= 1e-34 * (diag + off) || off == 0.0) break;
-    // three rounds of two rotations in DISJOINT planes: the angle of the second reads nothing the first one writes, so
-    // the two chains of divisions and square roots overlap in the single lane that runs this
-    jrot<0, 1>(A, V);
-    jrot<2, 3>(A, V);
-    jrot<0, 2>(A, V);
-    jrot<1, 3>(A, V);
-    jrot<0, 3>(A, V);
-    jrot<1, 2>(A, V);
-  }
-}
-
-// Vst [16]: the eigenvector basis of the previous round (row major), or NULL.  Consecutive rounds of an ICP solve
-// nearly the same 4x4 problem, so the sweeps start from the previous basis (A = V^T Q V is then almost diagonal: one
-// or two sweeps instead of six or seven -- the Jacobi chain is what bounds k_icp_step); the basis found is stored back.
-// A basis that is not finite or has drifted from orthonormal (first round, failed round) is replaced by the identity.
-__host__ __device__ inline bool horn(const double s[16], long long nd, double R1[9], double T1[3], double* Vst) {
-  const double N = (double)nd;
-  double Q[4][4], V[4][4];
-  if (Vst) {  // read first: on the device the loads then fly while the divisions below run
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) V[i][j] = Vst[4 * i + j];
-  }
-  double muP[3], muY[3], m[3][3];
-  for (int a = 0; a < 3; a++) {
-    muP[a] = s[a] / N;
-    muY[a] = s[3 + a] / N;
-  }
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) m[r][c] = s[6 + 3 * r + c] / N - muP[r] * muY[c];
-  const double tr = m[0][0] + m[1][1] + m[2][2];
-  const double delta[3] = {m[1][2] - m[2][1], m[2][0] - m[0][2], m[0][1] - m[1][0]};
-  Q[0][0] = tr;
-  for (int i = 0; i < 3; i++) {
-    Q[0][i + 1] = Q[i + 1][0] = delta[i];
-    for (int j = 0; j < 3; j++) Q[i + 1][j + 1] = m[i][j] + m[j][i] - (i == j ? tr : 0.0);
-  }
-  // Q goes into the sweeps divided by the power of two that brings its largest entry into [0.5, 1): jacobi4's stop test
-  // squares the entries, and beyond about 2^+-256 the squares overflow or flush to zero, which ended the sweeps before
-  // the first rotation with "solved".  The division is exact and R1 depends on the eigenvectors alone, so nothing
-  // changes where the squares were in range.  A non-finite entry (non-finite sums, or sums that overflow here) fails the
-  // solve: an infinite off-diagonal entry passed the same stop test.  Tested per entry: fmax would drop a NaN.  The
-  // verdict is returned at the end, not here: a branch at this point keeps the device compiler from issuing the loads
-  // of the basis early, and the failing case may take as long as it likes.
-  double rmax[4];  // per row of the upper triangle: four short chains instead of one of ten
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    rmax[i] = 0.0;
-#pragma unroll
-    for (int j = i; j < 4; j++) {
-      const double a = fabs(Q[i][j]);
-      finite = finite && (a <= 1.7976931348623157e308);  // false for NaN
-      rmax[i] = a > rmax[i] ? a : rmax[i];
-    }
-  }
-  const double m01 = rmax[0] > rmax[1] ? rmax[0] : rmax[1], m23 = rmax[2] > rmax[3] ? rmax[2] : rmax[3];
-  const double qmax = finite ? (m01 > m23 ? m01 : m23) : 0.0;
-  int e;  // 0 for qmax = 0 (coincident points, or a Q that fails anyway)
-  (void)frexp(qmax, &e);
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) Q[i][j] = ldexp(Q[i][j], -e);
-  bool warm = Vst != nullptr;
-  if (warm) {
-    bool ortho = true;  // | V^T V - I |_max <= 1e-9, tested per entry: fmax would drop a NaN
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = i; j < 4; j++) {
-        double d = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) d += V[k][i] * V[k][j];
-        ortho = ortho && (fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-9);  // false for NaN
-      }
-    warm = ortho;
-  }
-  if (warm) {
-    double QV[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        double d = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) d += Q[i][k] * V[k][j];
-        QV[i][j] = d;
-      }
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = i; j < 4; j++) {
-        double d = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) d += V[k][i] * QV[k][j];
-        Q[i][j] = d;
-        Q[j][i] = d;
-      }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
-  }
-  jacobi4(Q, V);
-  if (Vst) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) Vst[4 * i + j] = V[i][j];
-  }
-  // eigenvector of the largest eigenvalue, picked without dynamic indexing (first maximum wins)
-  double ev = Q[0][0];
-  double q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
-#pragma unroll
-  for (int i = 1; i < 4; i++)
-    if (Q[i][i] > ev) {
-      ev = Q[i][i];
-#pragma unroll
-      for (int k = 0; k < 4; k++) q[k] = V[k][i];
-    }
-  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  if (!finite || !(nrm > 0.0) || !(nrm <= 1.7976931348623157e308)) return false;
-  for (int i = 0; i < 4; i++) q[i] /= nrm;
-  // CalculateRotation, BaseClass/ICP.cs:274-285
-  R1[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3];
-  R1[1] = 2.0 * (q[1] * q[2] - q[0] * q[3]);
-  R1[2] = 2.0 * (q[1] * q[3] + q[0] * q[2]);
-  R1[3] = 2.0 * (q[1] * q[2] + q[0] * q[3]);
-  R1[4] = q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3];
-  R1[5] = 2.0 * (q[2] * q[3] - q[0] * q[1]);
-  R1[6] = 2.0 * (q[1] * q[3] - q[0] * q[2]);
-  R1[7] = 2.0 * (q[2] * q[3] + q[0] * q[1]);
-  R1[8] = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
-  for (int i = 0; i < 3; i++)
-    T1[i] = muY[i] - (R1[3 * i] * muP[0] + R1[3 * i + 1] * muP[1] + R1[3 * i + 2] * muP[2]);
-  return true;
-}
-
-// The similarity step (vcp.h, "similarity ICP"): horn() on s[0..15] unchanged, then Horn's symmetric scale from the two
-// further columns, k = sqrt(vY / vP) with v = sum |x|^2 / N - |mu|^2, which does not depend on the rotation.  c is the
-// product of the factors applied so far; the new product c k is held in [ratio_min, ratio_max] by shortening this
-// round's factor.  Returns 0 (horn failed: nothing written), 1, or 2 (scale not determined: the rigid step, c stays).
-// Every operation is one binary64 rounding; where k_used is 1.0, R1s and T1 are horn()'s bit for bit (1.0 * x = x and
-// T1 is horn's expression).
-__host__ __device__ inline int horn_sim(const double s[18], long long n, double c, double ratio_min, double ratio_max,
-                                        double R1s[9], double T1[3], double* Vst, double* k_used, double* c_new) {
-  double R1[9], T1r[3];
-  if (!horn(s, n, R1, T1r, Vst)) return 0;
-  const double N = (double)n;
-  const double muP0 = s[0] / N, muP1 = s[1] / N, muP2 = s[2] / N;  // horn's means: the same divisions
-  const double muY0 = s[3] / N, muY1 = s[4] / N, muY2 = s[5] / N;
-  const double vP = s[16] / N - ((muP0 * muP0 + muP1 * muP1) + muP2 * muP2);
-  const double vY = s[17] / N - ((muY0 * muY0 + muY1 * muY1) + muY2 * muY2);
-  const double big = 1.7976931348623157e308;
-  const bool det = vP > 0.0 && vP <= big && vY > 0.0 && vY <= big;  // false for NaN
-  double ku = 1.0, cn = c;
-  if (det) {
-    const double k = sqrt(vY / vP), t = c * k;
-    if (t < ratio_min) {
-      cn = ratio_min;
-      ku = ratio_min / c;
-    } else if (t > ratio_max) {
-      cn = ratio_max;
-      ku = ratio_max / c;
-    } else {
-      cn = t;
-      ku = k;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 9; j++) R1s[j] = ku * R1[j];
-  const double muY[3] = {muY0, muY1, muY2};
-#pragma unroll
-  for (int i = 0; i < 3; i++) T1[i] = muY[i] - (R1s[3 * i] * muP0 + R1s[3 * i + 1] * muP1 + R1s[3 * i + 2] * muP2);
-  *k_used = ku;
-  *c_new = cn;
-  return det ? 1 : 2;
-}
 
 // R <- R1 R, T <- R1 T + T1 in the state (BaseClass/ICP.cs:163-177)
 __device__ __forceinline__ void icp_compose(IcpState* __restrict__ st, const double R1[9], const double T1[3]) {
@@ -1293,156 +973,100 @@ __global__ __launch_bounds__(ITPB) void k_icp_step(const double* __restrict__ pa
   icp_step_body<ITPB>(partial, nb, st, a);
 }
 
-// The step of a gated round (vcp.h, vcp_icp_gated): the same fold of the partial rows, the kept counts of the
-// workgroups added up (integers: exact), then Horn on (sums, kept) and the composition -- or, with fewer than
-// min_pairs pairs kept, nothing: R, T and the basis V stay, the round counts and `starved` goes up.  Always max_iter
-// rounds, as MODE_VTK.  sums_only: the pass alone (vcp_icp_sums_gated).
+// The step of a round that counts its kept pairs (vcp.h, vcp_icp_gated and the forms built on it): the same fold of
+// the partial rows, the kept counts of the workgroups added up (integers: exact), then Horn on (sums, kept) and the
+// composition -- or, with fewer than min_pairs pairs kept, nothing: R, T and the basis V stay, the round counts and
+// `starved` goes up.  Always max_iter rounds, as MODE_VTK.  sums_only: the passes alone (vcp_icp_sums_gated, ...).
+// What a form adds to that sits in its FORM type F, the kernel's last argument:
+//   NS, LOST         columns of a row; whether the workgroups' lost counts (plost) are added up as well
+//   spread(h)        work for the whole workgroup before the totals are read
+//   record(h, tot, lost)  thread 0: what the state has no room for, into the pose's side record
+//   solve(...)       thread 0: horn(), or what stands in its place
 struct GateStepArgs {
   long long min_pairs;
   int max_iter, sums_only;
 };
-__global__ __launch_bounds__(ITPB) void k_icp_step_gated(const double* __restrict__ partial,
-                                                        const uint32_t* __restrict__ pkept, int nb,
-                                                        IcpState* __restrict__ st, GateStepArgs a) {
-  st += blockIdx.x;
-  partial += (size_t)blockIdx.x * nb * 16;
-  pkept += (size_t)blockIdx.x * nb;
-  if (st->done) return;
-  __shared__ double tot[16];
-  __shared__ unsigned long long skept;
-  if (threadIdx.x == 0) skept = 0;
-  icp_fold_rows<ITPB>(partial, nb, st, tot);  // its barrier orders the store above before the adds below
-  unsigned long long c = 0;
-  for (int b = threadIdx.x; b < nb; b += ITPB) c += pkept[b];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&skept, c);
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const long long kept = (long long)skept;
-  st->kept = kept;
-  if (a.sums_only) {
-    st->done = 1;
-    return;
+// gated and trimmed rounds: nothing beside the above
+struct KeptStep {
+  static constexpr int NS = 16;
+  static constexpr bool LOST = false;
+  const uint32_t* pkept;  // [poses][nb]
+  __device__ __forceinline__ void spread(int) const {}
+  __device__ __forceinline__ void record(int, const double*, long long) const {}
+  __device__ __forceinline__ bool solve(int, const double (&S)[16], long long kept, double R1[9], double T1[3], double* V) const {
+    return horn(S, kept, R1, T1, V);
   }
-  st->pre_d = st->d;
-  st->d = tot[15];
-  const int round = st->round + 1;
-  st->round = round;
-  if (kept < a.min_pairs) {
-    st->starved = st->starved + 1;
-  } else {
-    double S[16];
-    for (int k = 0; k < 16; k++) S[k] = tot[k];
-    double R1[9], T1[3];
-    if (!horn(S, kept, R1, T1, st->V)) {
-      st->failed = 1;
-      st->done = 1;
-      return;
-    }
-    icp_compose(st, R1, T1);
+};
+// unique-correspondence rounds: the lost counts added up into the pose's side record, and -- reset_L > 0 -- the
+// round's slots set back to all ones (uniq_reset)
+struct UniqStep : KeptStep {
+  static constexpr bool LOST = true;
+  const uint32_t* plost;  // [poses][nb]
+  long long* lost;        // [poses]
+  UniqArgs ua;
+  long long reset_L;
+  __device__ __forceinline__ void spread(int h) const {
+    if (reset_L > 0) uniq_reset(ua, h, reset_L, threadIdx.x, ITPB);
   }
-  if (round >= a.max_iter) st->done = 1;
-}
-
-// The step of a unique-correspondence round (vcp.h, vcp_icp_unique): k_icp_step_gated, word for word, on the sums
-// pass's rows and kept counts; beside it the lost counts of the workgroups added up into the pose's side record (the
-// state has no room for it), and -- reset_L > 0 -- the round's slots set back to all ones (uniq_reset).
-__global__ __launch_bounds__(ITPB) void k_icp_step_unique(const double* __restrict__ partial, int nb,
-                                                         IcpState* __restrict__ st, long long* __restrict__ lost,
-                                                         UniqArgs ua, long long reset_L, GateStepArgs a) {
-  const int h = blockIdx.x;
-  st += h;
-  partial += (size_t)h * nb * 16;
-  const uint32_t* pkept = ua.pkept + (size_t)h * nb;
-  const uint32_t* plost = ua.plost + (size_t)h * nb;
-  if (st->done) return;
-  __shared__ double tot[16];
-  __shared__ unsigned long long skept, slost;
-  if (threadIdx.x == 0) {
-    skept = 0;
-    slost = 0;
-  }
-  icp_fold_rows<ITPB>(partial, nb, st, tot);  // its barrier orders the stores above before the adds below
-  unsigned long long c = 0, l = 0;
-  for (int b = threadIdx.x; b < nb; b += ITPB) {
-    c += pkept[b];
-    l += plost[b];
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    c += __shfl_down(c, d, 64);
-    l += __shfl_down(l, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&skept, c);
-    atomicAdd(&slost, l);
-  }
-  if (reset_L > 0) uniq_reset(ua, h, reset_L, threadIdx.x, ITPB);
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const long long kept = (long long)skept;
-  st->kept = kept;
-  lost[h] = (long long)slost;
-  if (a.sums_only) {
-    st->done = 1;
-    return;
-  }
-  st->pre_d = st->d;
-  st->d = tot[15];
-  const int round = st->round + 1;
-  st->round = round;
-  if (kept < a.min_pairs) {
-    st->starved = st->starved + 1;
-  } else {
-    double S[16];
-    for (int k = 0; k < 16; k++) S[k] = tot[k];
-    double R1[9], T1[3];
-    if (!horn(S, kept, R1, T1, st->V)) {
-      st->failed = 1;
-      st->done = 1;
-      return;
-    }
-    icp_compose(st, R1, T1);
-  }
-  if (round >= a.max_iter) st->done = 1;
-}
-
-// The step of a similarity round (vcp.h, vcp_icp_sim): k_icp_step_gated over 18-wide rows, with horn_sim in horn's
-// place.  What the state has no room for lives in the pose's side record: the two further sums, the product c of the
-// factors applied and the count of rounds whose scale was not determined.
+  __device__ __forceinline__ void record(int h, const double*, long long nlost) const { lost[h] = nlost; }
+};
+// similarity rounds: 18-wide rows, horn_sim in horn's place; the side record holds the two further sums, the product c
+// of the factors applied and the count of rounds whose scale was not determined
 struct SimSide {
   double s16, s17;  // the last pass's sums[16], sums[17]
   double c;
   int unscaled, pad;
 };
-struct SimStepArgs {
+struct SimStep : KeptStep {
+  static constexpr int NS = 18;
+  SimSide* side;  // [poses]
   double ratio_min, ratio_max;
+  __device__ __forceinline__ void record(int h, const double* tot, long long) const {
+    side[h].s16 = tot[16];
+    side[h].s17 = tot[17];
+  }
+  __device__ __forceinline__ bool solve(int h, const double (&S)[18], long long kept, double R1s[9], double T1[3], double* V) const {
+    double ku, cn;
+    const int rc = horn_sim(S, kept, side[h].c, ratio_min, ratio_max, R1s, T1, V, &ku, &cn);
+    if (rc == 0) return false;
+    side[h].c = cn;
+    if (rc == 2) side[h].unscaled = side[h].unscaled + 1;
+    return true;
+  }
 };
-__global__ __launch_bounds__(ITPB) void k_icp_step_sim(const double* __restrict__ partial,
-                                                      const uint32_t* __restrict__ pkept, int nb,
-                                                      IcpState* __restrict__ st, SimSide* __restrict__ side,
-                                                      GateStepArgs a, SimStepArgs sa) {
-  st += blockIdx.x;
-  side += blockIdx.x;
-  partial += (size_t)blockIdx.x * nb * 18;
-  pkept += (size_t)blockIdx.x * nb;
-  if (st->done) return;
-  __shared__ double tot[18];
-  __shared__ unsigned long long skept;
-  if (threadIdx.x == 0) skept = 0;
-  icp_fold_rows<ITPB, 18>(partial, nb, st, tot);  // its barrier orders the store above before the adds below
+// this workgroup's share of nb counts, added into *total (LDS): integer shuffles and atomics, exact in any order
+__device__ __forceinline__ void step_total(const uint32_t* __restrict__ cnt, int nb, unsigned long long* total) {
   unsigned long long c = 0;
-  for (int b = threadIdx.x; b < nb; b += ITPB) c += pkept[b];
+  for (int b = threadIdx.x; b < nb; b += ITPB) c += cnt[b];
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&skept, c);
+  if ((threadIdx.x & 63) == 0) atomicAdd(total, c);
+}
+template <class F>
+__global__ __launch_bounds__(ITPB) void k_icp_step_kept(const double* __restrict__ partial, int nb,
+                                                       IcpState* __restrict__ st, GateStepArgs a, F f) {
+  constexpr int NS = F::NS;
+  const int h = blockIdx.x;
+  st += h;
+  partial += (size_t)h * nb * NS;
+  if (st->done) return;
+  __shared__ double tot[NS];
+  __shared__ unsigned long long skept, slost;
+  if (threadIdx.x == 0) {
+    skept = 0;
+    if constexpr (F::LOST) slost = 0;
+  }
+  icp_fold_rows<ITPB, NS>(partial, nb, st, tot);  // its barrier orders the stores above before the adds below
+  step_total(f.pkept + (size_t)h * nb, nb, &skept);
+  if constexpr (F::LOST) step_total(f.plost + (size_t)h * nb, nb, &slost);
+  f.spread(h);
   __syncthreads();
   if (threadIdx.x != 0) return;
   const long long kept = (long long)skept;
   st->kept = kept;
-  side->s16 = tot[16];
-  side->s17 = tot[17];
+  long long lost = 0;
+  if constexpr (F::LOST) lost = (long long)slost;
+  f.record(h, tot, lost);
   if (a.sums_only) {
     st->done = 1;
     return;
@@ -1454,18 +1078,15 @@ __global__ __launch_bounds__(ITPB) void k_icp_step_sim(const double* __restrict_
   if (kept < a.min_pairs) {
     st->starved = st->starved + 1;
   } else {
-    double S[18];
-    for (int k = 0; k < 18; k++) S[k] = tot[k];
-    double R1s[9], T1[3], ku, cn;
-    const int rc = horn_sim(S, kept, side->c, sa.ratio_min, sa.ratio_max, R1s, T1, st->V, &ku, &cn);
-    if (rc == 0) {
+    double S[NS];
+    for (int k = 0; k < NS; k++) S[k] = tot[k];
+    double R1[9], T1[3];
+    if (!f.solve(h, S, kept, R1, T1, st->V)) {
       st->failed = 1;
       st->done = 1;
       return;
     }
-    side->c = cn;
-    if (rc == 2) side->unscaled = side->unscaled + 1;
-    icp_compose(st, R1s, T1);
+    icp_compose(st, R1, T1);
   }
   if (round >= a.max_iter) st->done = 1;
 }
@@ -1479,54 +1100,115 @@ void identity(IcpState& s) {
 size_t icp_states_bytes(int nst) { return ((size_t)nst * sizeof(IcpState) + 255) & ~(size_t)255; }
 IcpState* icp_states(vcp_ctx* ctx) { return ctx->b_icp_part.as<IcpState>(); }
 
-// Runs rounds on device-resident model/data until the states say done.  `init` carries the starting R,T of nst
-// independent states (nst > 1: vcp_icp_multistart, MODE_VTK), `out` receives them.  all_rounds: enqueue every round
-// and synchronise once (a fixed round count needs nothing back in between).  ng_out (may be NULL) receives the
-// model's grid; ng_out->rec == nullptr when the full scans serve the model.
-// gr (may be NULL): a gated run -- the gated passes and step, MODE_VTK's fixed round count or MODE_SUMS_ONLY; the
-// partition, and with it the tree of the sums, is the ungated one.
-struct GateRun {
-  const double* gates;  // host, [n_gates], validated by the caller
-  int n_gates;
+// ---- the host side of a run --------------------------------------------------------------------------------------
+// The form of a run: which passes and which step a round is made of.  PLAIN (or no variant at all) is the reference /
+// VTK / sums-only round of k_icp_pass + k_icp_step; every other kind runs MODE_VTK's fixed round count or
+// MODE_SUMS_ONLY with the counted step, on the ungated partition -- and with it the ungated tree of the sums.
+//   GATED    the gated pass
+//   SIM      the gated pass over 18-wide rows, horn_sim in the step
+//   TRIMMED  per round the distance pass, the select, the trimmed sums pass
+//   UNIQUE   per round the distance pass, the tie pass, the sums pass, the slots' reset
+enum IcpKind { ICP_PLAIN = 0, ICP_GATED, ICP_SIM, ICP_TRIMMED, ICP_UNIQUE };
+struct IcpVariant {
+  IcpKind kind;
+  const double* sched;  // host, [n_sched], validated by the caller: the gates, or TRIMMED's keep shares (none: m_fixed)
+  int n_sched;
   long long min_pairs;
-  uint8_t* d_keep;  // [nd] or NULL
+  long long m_fixed;            // TRIMMED: > 0: the keep count itself (vcp_icp_sums_trimmed)
+  double ratio_min, ratio_max;  // SIM, validated by the caller
+  uint8_t* d_keep;              // [nd] or NULL
+  // host, [nst]: per pose what the state has no room for -- SimSide (SIM), TrimSel, the last select (TRIMMED), long long,
+  // the last round's lost count (UNIQUE)
+  void* side_out;
 };
-// sr (may be NULL; only with gr): the gated run's similarity form -- 18-wide rows, the passes of SimGate and
-// k_icp_step_sim; the side records follow the kept counts on the device and the schedule in the staging area.
-struct SimRun {
-  double ratio_min, ratio_max;  // validated by the caller
-  SimSide* side_out;            // host, [nst]
-};
-// tr (may be NULL; never with gr): a trimmed run -- per round the distance pass, the select, the trimmed sums pass and
-// the gated step.  Its workspace is b_icpt: per (pose, landmark) 8 bytes of key and 4 of index, then per pose the
-// multi-workgroup select's 12 prefixes and 12 x 256 counters.
-struct TrimRun {
-  const double* share;  // host, [n_share], validated by the caller; NULL with m_fixed > 0
-  int n_share;
-  long long m_fixed;
-  long long min_pairs;
-  uint8_t* d_keep;   // [nd] or NULL
-  TrimSel* sel_out;  // host, [nst]: the last select of every pose
-};
-// ur (may be NULL; never with gr or tr): a unique-correspondence run -- per round the distance pass, the tie pass, the
-// sums pass and k_icp_step_unique.  Its workspace is b_icpt too: the trimmed run's 12 bytes per (pose, landmark), then
-// the slots, 8 bytes of key per (pose, target) and then 4 of index, all ones from one fill per call and from the reset
-// of every round.
-struct UniqRun {
-  const double* gates;  // host, [n_gates], validated by the caller
-  int n_gates;
-  long long min_pairs;
-  uint8_t* d_keep;      // [nd] or NULL
-  long long* lost_out;  // host, [nst]: the last round's count of every pose
+size_t icp_side_size(IcpKind k) {
+  return k == ICP_SIM ? sizeof(SimSide) : k == ICP_TRIMMED ? sizeof(TrimSel) : k == ICP_UNIQUE ? sizeof(long long) : 0;
+}
+
+// Where everything of a run lies, in bytes from the start of its buffer.
+//   b_icp_part  the nst states (icp_states), from the next 256-byte boundary [nst][nb][16 or 18] partial rows; a
+//               counted run: then the schedule, [nst][nb] kept counts (UNIQUE: and as many lost counts), the side records
+//   b_icpt      TRIMMED and UNIQUE: per (pose, landmark) 8 bytes of key, then 4 of index; from the next 256-byte
+//               boundary TRIMMED's select workspace (per pose 12 prefixes, then 12 x 256 counters) or UNIQUE's slots
+//               (per (pose, target) 8 bytes of key, then 4 of index)
+//   staging     the states, the schedule, the side records
+struct IcpLayout {
+  size_t rows, sched, pkept, plost, side, part_bytes;
+  size_t nn, ws, ws_bytes, icpt_bytes;
+  size_t h_sched, h_side, h_bytes;
+  size_t side_bytes;
 };
 size_t icpt_keys_bytes(int nst, int64_t nd) { return ((size_t)nst * (size_t)nd * 12 + 255) & ~(size_t)255; }
 int32_t* icpt_nn(vcp_ctx* ctx, int nst, int64_t nd) {
   return reinterpret_cast<int32_t*>(ctx->b_icpt.as<char>() + (size_t)nst * (size_t)nd * 8);
 }
+IcpLayout icp_layout(const IcpVariant& v, int nst, int nb, int64_t nd, int64_t nm) {
+  IcpLayout l{};
+  const size_t cnt_bytes = v.kind == ICP_PLAIN ? 0 : ((size_t)nst * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
+  l.side_bytes = (size_t)nst * icp_side_size(v.kind);
+  l.rows = icp_states_bytes(nst);
+  l.sched = l.rows + (size_t)nst * nb * (v.kind == ICP_SIM ? 18 : 16) * sizeof(double);
+  l.pkept = l.sched + (size_t)v.n_sched * sizeof(double);
+  l.plost = l.pkept + cnt_bytes;
+  l.side = l.plost + (v.kind == ICP_UNIQUE ? cnt_bytes : 0);
+  l.part_bytes = l.side + l.side_bytes;
+  if (v.kind == ICP_TRIMMED || v.kind == ICP_UNIQUE) {
+    l.nn = (size_t)nst * (size_t)nd * 8;
+    l.ws = icpt_keys_bytes(nst, nd);
+    l.ws_bytes = v.kind == ICP_TRIMMED ? (size_t)nst * TRIM_DIGITS * (sizeof(TrimPrefix) + ITPB * sizeof(uint32_t))
+                                       : (size_t)nst * (size_t)nm * 12;
+    l.icpt_bytes = l.ws + l.ws_bytes;
+  }
+  l.h_sched = (size_t)nst * sizeof(IcpState);
+  l.h_side = l.h_sched + (size_t)v.n_sched * sizeof(double);
+  l.h_bytes = l.h_side + l.side_bytes;
+  return l;
+}
+
+// One pass of a run under policy G, on the path (pairs / grid / tiled) and workgroup size the run has chosen.
+struct PassLaunch {
+  vcp_ctx* ctx;
+  bool small, grid, tiled;
+  int nb, nst;
+  const double* model;
+  const float4* model32;
+  int nm;
+  const double* data;
+  int64_t nd;
+  IcpState* st;
+  double* part;
+  NNGrid ng;
+  uint32_t imask;
+  double tolk;
+  template <int TB, int NNMODE, class G>
+  int full(int32_t* nn, const G& g) const {
+    VCP_LAUNCH(ctx, (k_icp_pass<TB, NNMODE, G>), dim3(nb, nst), dim3(TB), 0, ctx->stream, model, model32, nm, data, nd,
+               st, part, nn, ng, g);
+    return VCP_OK;
+  }
+  template <int TB, class G>
+  int pairs(int32_t* nn, const G& g) const {
+    VCP_LAUNCH(ctx, (k_icp_pass_small<TB, G>), dim3(nb, nst), dim3(TB), 0, ctx->stream, model, model32, nm, data, nd,
+               st, part, nn, imask, tolk, g);
+    return VCP_OK;
+  }
+  template <class G>
+  int operator()(int32_t* nn, const G& g) const {
+    if (grid) return small ? full<64, 2>(nn, g) : full<ITPB, 2>(nn, g);
+    if (tiled) return small ? full<64, 1>(nn, g) : full<ITPB, 1>(nn, g);
+    return small ? pairs<64>(nn, g) : pairs<ITPB>(nn, g);
+  }
+};
+
+// Runs rounds on device-resident model/data until the states say done.  `init` carries the starting R,T of nst
+// independent states (nst > 1: vcp_icp_multistart, MODE_VTK), `out` receives them.  all_rounds: enqueue every round
+// and synchronise once (a fixed round count needs nothing back in between).  ng_out (may be NULL) receives the
+// model's grid; ng_out->rec == nullptr when the full scans serve the model.  var: NULL for a PLAIN run.
 int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_data, int64_t nd, const IcpState* init,
             int nst, double tol, int stop_rule, int max_iter, int mode, IcpState* out, int32_t* d_nn, bool all_rounds,
-            NNGrid* ng_out, const GateRun* gr = nullptr, const TrimRun* tr = nullptr, const SimRun* sr = nullptr,
-            const UniqRun* ur = nullptr) {
+            NNGrid* ng_out, const IcpVariant* var = nullptr) {
+  static const IcpVariant plain{};
+  const IcpVariant& v = var ? *var : plain;
   hipStream_t st = ctx->stream;
   // small data sets: one wave per workgroup so that they reach more CUs; large models: LDS tiles
   const bool small0 = nd <= (int64_t)64 * ICP_MAX_BLOCKS;
@@ -1551,109 +1233,65 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   const uint32_t imask = (1u << ib) - 1u;
   double tolk = 1.0;  // smallest power of two >= (54 + 9 * 2^ib) * 2^-24
   while (tolk * 0.5 >= (54.0 + 9.0 * (double)(1u << ib)) / 16777216.0) tolk *= 0.5;
-  // the nst states (icp_states), then [nst][nb][16] partial rows; a gated run: then the schedule and [nst][nb] counts
-  const size_t st_bytes = icp_states_bytes(nst);
-  const int ncol = sr ? 18 : 16;
-  const size_t part_bytes = (size_t)nst * nb * ncol * sizeof(double);
-  const int n_sched = gr ? gr->n_gates : tr ? tr->n_share : ur ? ur->n_gates : 0;  // doubles staged behind the partial rows
-  const size_t cnt_bytes = ((size_t)nst * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
-  const size_t side_bytes = sr ? (size_t)nst * sizeof(SimSide) : 0;
-  const size_t gate_bytes = gr   ? (size_t)n_sched * sizeof(double) + cnt_bytes + side_bytes
-                            : tr ? (size_t)n_sched * sizeof(double) + cnt_bytes + (size_t)nst * sizeof(TrimSel)
-                            : ur ? (size_t)n_sched * sizeof(double) + 2 * cnt_bytes + (size_t)nst * sizeof(long long)
-                                 : 0;
-  VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, st_bytes + part_bytes + gate_bytes));
-  const bool sel_wg = nd <= TRIM_SELECT_WG_MAX;
-  const size_t key_bytes = tr || ur ? icpt_keys_bytes(nst, nd) : 0;
-  const size_t selws_bytes = (size_t)nst * TRIM_DIGITS * (sizeof(TrimPrefix) + ITPB * sizeof(uint32_t));
-  if (tr) VCP_TRY(vcp_ensure(ctx, ctx->b_icpt, key_bytes + selws_bytes));
-  const size_t slot_n = ur ? (size_t)nst * (size_t)nm : 0;  // slots: one per (pose, target)
-  if (ur) VCP_TRY(vcp_ensure(ctx, ctx->b_icpt, key_bytes + slot_n * 12));
+  const IcpLayout lay = icp_layout(v, nst, nb, nd, nm);
+  VCP_TRY(vcp_ensure(ctx, ctx->b_icp_part, lay.part_bytes));
+  if (lay.icpt_bytes) VCP_TRY(vcp_ensure(ctx, ctx->b_icpt, lay.icpt_bytes));
   VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, (size_t)nm * sizeof(float4) + 64));
+  char* const dp = ctx->b_icp_part.as<char>();
+  char* const dt = lay.icpt_bytes ? ctx->b_icpt.as<char>() : nullptr;
   IcpState* d_st = icp_states(ctx);
-  double* part = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes);
-  const StepArgs sa{(long long)nd, tol, stop_rule, max_iter, mode};
-  float4* model32 = ctx->b_aux0.as<float4>();
-  // a gated run stages its schedule behind the states: the caller's array may be gone before the copy has run
-  const size_t h_bytes =
-      (size_t)nst * sizeof(IcpState) + (size_t)n_sched * sizeof(double) + (tr ? (size_t)nst * sizeof(TrimSel) : 0) +
-      (sr ? (size_t)nst * sizeof(SimSide) : 0) + (ur ? (size_t)nst * sizeof(long long) : 0);
-  IcpState* h_st = reinterpret_cast<IcpState*>(nst == 1 && !gr && !tr && !ur ? ctx->pinned : vcp_stage(ctx, h_bytes));
-  if (!h_st) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
+  double* part = reinterpret_cast<double*>(dp + lay.rows);
+  double* d_sched = reinterpret_cast<double*>(dp + lay.sched);
+  uint32_t* pkept = reinterpret_cast<uint32_t*>(dp + lay.pkept);
+  uint32_t* plost = reinterpret_cast<uint32_t*>(dp + lay.plost);
+  char* d_side = dp + lay.side;
+  unsigned long long* d_key = reinterpret_cast<unsigned long long*>(dt);
+  int32_t* d_knn = dt ? reinterpret_cast<int32_t*>(dt + lay.nn) : nullptr;
+  char* d_ws = dt ? dt + lay.ws : nullptr;
+  // a counted run stages its schedule behind the states: the caller's array may be gone before the copy has run
+  char* h_base = reinterpret_cast<char*>(nst == 1 && v.kind == ICP_PLAIN ? ctx->pinned : vcp_stage(ctx, lay.h_bytes));
+  if (!h_base) return vcp_fail(ctx, VCP_ERR_NOMEM, "pinned staging of %d ICP states", nst);
+  IcpState* h_st = reinterpret_cast<IcpState*>(h_base);
+  char* h_side = h_base + lay.h_side;
   std::memcpy(h_st, init, (size_t)nst * sizeof(IcpState));
   VCP_HIP(ctx, hipMemcpyAsync(d_st, h_st, (size_t)nst * sizeof(IcpState), hipMemcpyHostToDevice, st));
-  GateArgs ga{};
-  GateStepArgs gsa{};
-  SimGate sga{};
-  SimStepArgs ssa{};
-  SimSide *d_side = nullptr, *h_side = nullptr;
-  if (gr) {
-    double* d_gates = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
-    ga = GateArgs{d_gates, gr->n_gates, reinterpret_cast<uint32_t*>(d_gates + gr->n_gates), gr->d_keep};
-    gsa = GateStepArgs{gr->min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
-    double* h_gates = reinterpret_cast<double*>(h_st + nst);
-    std::memcpy(h_gates, gr->gates, (size_t)gr->n_gates * sizeof(double));
-    VCP_HIP(ctx, hipMemcpyAsync(d_gates, h_gates, (size_t)gr->n_gates * sizeof(double), hipMemcpyHostToDevice, st));
-    if (sr) {  // every pose starts at c = 1, no round unscaled
-      sga.g = ga;
-      ssa = SimStepArgs{sr->ratio_min, sr->ratio_max};
-      d_side = reinterpret_cast<SimSide*>(reinterpret_cast<char*>(ga.pkept) + cnt_bytes);
-      h_side = reinterpret_cast<SimSide*>(h_gates + gr->n_gates);
-      for (int k = 0; k < nst; k++) h_side[k] = SimSide{0.0, 0.0, 1.0, 0, 0};
-      VCP_HIP(ctx, hipMemcpyAsync(d_side, h_side, (size_t)nst * sizeof(SimSide), hipMemcpyHostToDevice, st));
-    }
+  if (v.n_sched) {
+    std::memcpy(h_base + lay.h_sched, v.sched, (size_t)v.n_sched * sizeof(double));
+    VCP_HIP(ctx, hipMemcpyAsync(d_sched, h_base + lay.h_sched, (size_t)v.n_sched * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  TrimDist td{};
-  TrimSum ts{};
-  TrimPrefix* d_slot = nullptr;
-  uint32_t* d_ghist = nullptr;
-  TrimSel* h_sel = nullptr;
-  if (tr) {
-    double* d_share = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
-    uint32_t* pkept = reinterpret_cast<uint32_t*>(d_share + n_sched);
-    TrimSel* d_sel = reinterpret_cast<TrimSel*>(reinterpret_cast<char*>(pkept) + cnt_bytes);
-    td.a = TrimArgs{d_share, n_sched, tr->m_fixed, ctx->b_icpt.as<unsigned long long>(), icpt_nn(ctx, nst, nd),
-                    d_sel,   pkept,   tr->d_keep};
-    ts.a = td.a;
-    gsa = GateStepArgs{tr->min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
-    double* h_share = reinterpret_cast<double*>(h_st + nst);
-    h_sel = reinterpret_cast<TrimSel*>(h_share + n_sched);
-    if (n_sched) {
-      std::memcpy(h_share, tr->share, (size_t)n_sched * sizeof(double));
-      VCP_HIP(ctx, hipMemcpyAsync(d_share, h_share, (size_t)n_sched * sizeof(double), hipMemcpyHostToDevice, st));
-    }
+  // what makes the call independent of the context's history
+  const bool sel_wg = nd <= TRIM_SELECT_WG_MAX;
+  TrimPrefix* d_slot = reinterpret_cast<TrimPrefix*>(d_ws);
+  uint32_t* d_ghist = v.kind == ICP_TRIMMED ? reinterpret_cast<uint32_t*>(d_slot + (size_t)nst * TRIM_DIGITS) : nullptr;
+  if (v.kind == ICP_SIM) {  // every pose starts at c = 1, no round unscaled
+    for (int k = 0; k < nst; k++) reinterpret_cast<SimSide*>(h_side)[k] = SimSide{0.0, 0.0, 1.0, 0, 0};
+    VCP_HIP(ctx, hipMemcpyAsync(d_side, h_side, lay.side_bytes, hipMemcpyHostToDevice, st));
+  } else if (v.kind == ICP_TRIMMED) {
     // the selects' results are read back at the end; the multi-workgroup form's histograms start at zero
-    VCP_HIP(ctx, hipMemsetAsync(d_sel, 0, (size_t)nst * sizeof(TrimSel), st));
-    d_slot = reinterpret_cast<TrimPrefix*>(ctx->b_icpt.as<char>() + key_bytes);
-    d_ghist = reinterpret_cast<uint32_t*>(d_slot + (size_t)nst * TRIM_DIGITS);
+    VCP_HIP(ctx, hipMemsetAsync(d_side, 0, lay.side_bytes, st));
     if (!sel_wg) VCP_HIP(ctx, hipMemsetAsync(d_ghist, 0, (size_t)nst * TRIM_DIGITS * ITPB * sizeof(uint32_t), st));
-  }
-  UniqDist ud{};
-  UniqSum us{};
-  long long *d_lost = nullptr, *h_lost = nullptr;
-  const bool reset_in_step = nd <= UNIQ_RESET_STEP_MAX;
-  if (ur) {
-    double* d_gates = reinterpret_cast<double*>(ctx->b_icp_part.as<char>() + st_bytes + part_bytes);
-    uint32_t* pkept = reinterpret_cast<uint32_t*>(d_gates + n_sched);
-    uint32_t* plost = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(pkept) + cnt_bytes);
-    d_lost = reinterpret_cast<long long*>(reinterpret_cast<char*>(plost) + cnt_bytes);
-    unsigned long long* skey = reinterpret_cast<unsigned long long*>(ctx->b_icpt.as<char>() + key_bytes);
-    ud.a = UniqArgs{d_gates, n_sched, (int)nm, ctx->b_icpt.as<unsigned long long>(), icpt_nn(ctx, nst, nd), skey,
-                    reinterpret_cast<uint32_t*>(skey + slot_n), pkept, plost, ur->d_keep};
-    us.a = ud.a;
-    gsa = GateStepArgs{ur->min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
-    double* h_gates = reinterpret_cast<double*>(h_st + nst);
-    h_lost = reinterpret_cast<long long*>(h_gates + n_sched);
-    std::memcpy(h_gates, ur->gates, (size_t)n_sched * sizeof(double));
-    VCP_HIP(ctx, hipMemcpyAsync(d_gates, h_gates, (size_t)n_sched * sizeof(double), hipMemcpyHostToDevice, st));
+  } else if (v.kind == ICP_UNIQUE) {
     // every slot all ones, once per call: the rounds set back what they touch
-    VCP_HIP(ctx, hipMemsetAsync(skey, 0xFF, slot_n * 12, st));
-    VCP_HIP(ctx, hipMemsetAsync(d_lost, 0, (size_t)nst * sizeof(long long), st));
+    VCP_HIP(ctx, hipMemsetAsync(d_ws, 0xFF, lay.ws_bytes, st));
+    VCP_HIP(ctx, hipMemsetAsync(d_side, 0, lay.side_bytes, st));
   }
+  const StepArgs sa{(long long)nd, tol, stop_rule, max_iter, mode};
+  const GateStepArgs gsa{v.min_pairs, max_iter, mode == MODE_SUMS_ONLY ? 1 : 0};
+  const GateArgs ga{d_sched, v.n_sched, pkept, v.d_keep};
+  const TrimArgs ta{d_sched, v.n_sched, v.m_fixed, d_key, d_knn, reinterpret_cast<TrimSel*>(d_side), pkept, v.d_keep};
+  unsigned long long* skey = reinterpret_cast<unsigned long long*>(d_ws);
+  const UniqArgs ua{d_sched, v.n_sched, (int)nm,
+                    d_key,   d_knn,     skey,
+                    v.kind == ICP_UNIQUE ? reinterpret_cast<uint32_t*>(skey + (size_t)nst * (size_t)nm) : nullptr,
+                    pkept,   plost,     v.d_keep};
+  const bool reset_in_step = nd <= UNIQ_RESET_STEP_MAX;
+  float4* model32 = ctx->b_aux0.as<float4>();
   if (!grid) {  // the binary32 screening frame and copy serve the full scans only
     VCP_LAUNCH(ctx, k_model_frame, dim3(1), dim3(ITPB), 0, st, d_model, nm, d_st, nst);
     VCP_LAUNCH(ctx, k_model32, dim3(vcp_blocks(nm, ITPB)), dim3(ITPB), 0, st, d_model, nm, d_st, model32);
   }
+  const PassLaunch pass{ctx, small, grid, tiled, nb, nst, d_model, model32, (int)nm, d_data, nd, d_st, part, ng, imask, tolk};
+  const dim3 one_per_pose(nst), threads(ITPB);
   auto all_done = [&]() {
     for (int k = 0; k < nst; k++)
       if (!h_st[k].done) return false;
@@ -1663,110 +1301,90 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   for (;;) {
     const int batch = mode == MODE_SUMS_ONLY ? 1 : std::min(all_rounds ? max_iter : ICP_BATCH, max_iter - launched);
     for (int b = 0; b < batch; b++) {
-#define VCP_PASS(TBV, TL)                                                                                               \
-  do {                                                                                                                  \
-    if (ur) {                                                                                                           \
-      if (phase == 0)                                                                                                   \
-        VCP_LAUNCH(ctx, (k_icp_pass_uniq<TBV, TL, UniqDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,       \
-                   (int)nm, d_data, nd, d_st, part, ng, ud);                                                            \
-      else                                                                                                              \
-        VCP_LAUNCH(ctx, (k_icp_pass_uniq<TBV, TL, UniqSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,        \
-                   (int)nm, d_data, nd, d_st, part, ng, us);                                                            \
-    } else if (tr) {                                                                                                    \
-      if (phase == 0)                                                                                                   \
-        VCP_LAUNCH(ctx, (k_icp_pass_trim<TBV, TL, TrimDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,       \
-                   (int)nm, d_data, nd, d_st, part, ng, td);                                                            \
-      else                                                                                                              \
-        VCP_LAUNCH(ctx, (k_icp_pass_trim<TBV, TL, TrimSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,        \
-                   (int)nm, d_data, nd, d_st, part, ng, ts);                                                            \
-    } else if (sr)                                                                                                      \
-      VCP_LAUNCH(ctx, (k_icp_pass_sim<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data,   \
-                 nd, d_st, part, d_nn, ng, sga);                                                                        \
-    else if (gr)                                                                                                        \
-      VCP_LAUNCH(ctx, (k_icp_pass_gated<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
-                 nd, d_st, part, d_nn, ng, ga);                                                                         \
-    else                                                                                                                \
-      VCP_LAUNCH(ctx, (k_icp_pass<TBV, TL>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd,   \
-                 d_st, part, d_nn, ng);                                                                                 \
-  } while (0)
-#define VCP_PASS_SMALL(TBV)                                                                                             \
-  do {                                                                                                                  \
-    if (ur) {                                                                                                           \
-      if (phase == 0)                                                                                                   \
-        VCP_LAUNCH(ctx, (k_icp_pass_small_uniq<TBV, UniqDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,     \
-                   (int)nm, d_data, nd, d_st, part, imask, tolk, ud);                                                   \
-      else                                                                                                              \
-        VCP_LAUNCH(ctx, (k_icp_pass_small_uniq<TBV, UniqSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,      \
-                   (int)nm, d_data, nd, d_st, part, imask, tolk, us);                                                   \
-    } else if (tr) {                                                                                                    \
-      if (phase == 0)                                                                                                   \
-        VCP_LAUNCH(ctx, (k_icp_pass_small_trim<TBV, TrimDist>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,     \
-                   (int)nm, d_data, nd, d_st, part, imask, tolk, td);                                                   \
-      else                                                                                                              \
-        VCP_LAUNCH(ctx, (k_icp_pass_small_trim<TBV, TrimSum>), dim3(nb, nst), dim3(TBV), 0, st, d_model, model32,      \
-                   (int)nm, d_data, nd, d_st, part, imask, tolk, ts);                                                   \
-    } else if (sr)                                                                                                      \
-      VCP_LAUNCH(ctx, k_icp_pass_small_sim<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data,   \
-                 nd, d_st, part, d_nn, imask, tolk, sga);                                                               \
-    else if (gr)                                                                                                        \
-      VCP_LAUNCH(ctx, k_icp_pass_small_gated<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, \
-                 nd, d_st, part, d_nn, imask, tolk, ga);                                                                \
-    else                                                                                                                \
-      VCP_LAUNCH(ctx, k_icp_pass_small<TBV>, dim3(nb, nst), dim3(TBV), 0, st, d_model, model32, (int)nm, d_data, nd,   \
-                 d_st, part, d_nn, imask, tolk);                                                                        \
-  } while (0)
-      // a trimmed round: the pass twice (distances, then sums) with the select between them; a unique-correspondence
-      // round: likewise, with the tie pass between them
-      for (int phase = 0; phase < (tr || ur ? 2 : 1); phase++) {
-        if (small && grid) VCP_PASS(64, 2);
-        else if (grid) VCP_PASS(ITPB, 2);
-        else if (small && tiled) VCP_PASS(64, 1);
-        else if (tiled) VCP_PASS(ITPB, 1);
-        else if (small) VCP_PASS_SMALL(64);
-        else VCP_PASS_SMALL(ITPB);
-        if ((!tr && !ur) || phase == 1) break;
-        if (ur) {
-          VCP_LAUNCH(ctx, k_icpu_tie, dim3(vcp_blocks(nd, UNIQ_TIE_KEYS, UNIQ_TIE_BLOCKS), nst), dim3(ITPB), 0, st, d_st,
-                     ud.a, nd);
-        } else if (sel_wg) {
-          VCP_LAUNCH(ctx, k_icpt_select_wg, dim3(nst), dim3(ITPB), 0, st, d_st, td.a, (int)nd);
-        } else {
-          const unsigned hb = vcp_blocks(nd, TRIM_HIST_KEYS, TRIM_HIST_BLOCKS);
-          for (int d = 0; d < TRIM_DIGITS; d++)
-            VCP_LAUNCH(ctx, k_icpt_hist, dim3(hb, nst), dim3(ITPB), 0, st, d_st, td.a, nd, d_ghist, d_slot, d);
-          VCP_LAUNCH(ctx, k_icpt_select_fin, dim3(nst), dim3(ITPB), 0, st, d_st, td.a, d_ghist, d_slot);
+      switch (v.kind) {
+        case ICP_PLAIN:
+          VCP_TRY(pass(d_nn, NoGate()));
+          VCP_LAUNCH(ctx, k_icp_step, one_per_pose, threads, 0, st, part, nb, d_st, sa);
+          break;
+        case ICP_GATED:
+          VCP_TRY(pass(d_nn, ga));
+          VCP_LAUNCH(ctx, k_icp_step_kept<KeptStep>, one_per_pose, threads, 0, st, part, nb, d_st, gsa, KeptStep{pkept});
+          break;
+        case ICP_SIM:
+          VCP_TRY(pass(d_nn, SimGate{ga}));
+          VCP_LAUNCH(ctx, k_icp_step_kept<SimStep>, one_per_pose, threads, 0, st, part, nb, d_st, gsa,
+                     (SimStep{{pkept}, reinterpret_cast<SimSide*>(d_side), v.ratio_min, v.ratio_max}));
+          break;
+        case ICP_TRIMMED:  // the pass twice (distances, then sums) with the select between them
+          VCP_TRY(pass(nullptr, TrimDist{ta}));
+          if (sel_wg) {
+            VCP_LAUNCH(ctx, k_icpt_select_wg, one_per_pose, threads, 0, st, d_st, ta, (int)nd);
+          } else {
+            const unsigned hb = vcp_blocks(nd, TRIM_HIST_KEYS, TRIM_HIST_BLOCKS);
+            for (int d = 0; d < TRIM_DIGITS; d++)
+              VCP_LAUNCH(ctx, k_icpt_hist, dim3(hb, nst), threads, 0, st, d_st, ta, nd, d_ghist, d_slot, d);
+            VCP_LAUNCH(ctx, k_icpt_select_fin, one_per_pose, threads, 0, st, d_st, ta, d_ghist, d_slot);
+          }
+          VCP_TRY(pass(nullptr, TrimSum{ta}));
+          VCP_LAUNCH(ctx, k_icp_step_kept<KeptStep>, one_per_pose, threads, 0, st, part, nb, d_st, gsa, KeptStep{pkept});
+          break;
+        case ICP_UNIQUE: {  // likewise, with the tie pass between them
+          const dim3 tie_grid(vcp_blocks(nd, UNIQ_TIE_KEYS, UNIQ_TIE_BLOCKS), nst);
+          VCP_TRY(pass(nullptr, UniqDist{ua}));
+          VCP_LAUNCH(ctx, k_icpu_tie, tie_grid, threads, 0, st, d_st, ua, nd);
+          VCP_TRY(pass(nullptr, UniqSum{ua}));
+          const bool reset = mode != MODE_SUMS_ONLY;  // sums only: one round, nothing left to decide with the slots
+          if (reset && !reset_in_step) VCP_LAUNCH(ctx, k_icpu_reset, tie_grid, threads, 0, st, d_st, ua, nd);
+          VCP_LAUNCH(ctx, k_icp_step_kept<UniqStep>, one_per_pose, threads, 0, st, part, nb, d_st, gsa,
+                     (UniqStep{{pkept}, plost, reinterpret_cast<long long*>(d_side), ua,
+                               (long long)(reset && reset_in_step ? nd : 0)}));
+          break;
         }
       }
-#undef VCP_PASS
-#undef VCP_PASS_SMALL
-      if (ur) {  // sums only: one pass, nothing left to decide with the slots
-        const bool reset = mode != MODE_SUMS_ONLY;
-        if (reset && !reset_in_step)
-          VCP_LAUNCH(ctx, k_icpu_reset, dim3(vcp_blocks(nd, UNIQ_TIE_KEYS, UNIQ_TIE_BLOCKS), nst), dim3(ITPB), 0, st, d_st,
-                     ud.a, nd);
-        VCP_LAUNCH(ctx, k_icp_step_unique, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, d_lost, ud.a,
-                   (long long)(reset && reset_in_step ? nd : 0), gsa);
-      } else if (tr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, td.a.pkept, nb, d_st, gsa);
-      else if (sr)
-        VCP_LAUNCH(ctx, k_icp_step_sim, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, d_side, gsa, ssa);
-      else if (gr) VCP_LAUNCH(ctx, k_icp_step_gated, dim3(nst), dim3(ITPB), 0, st, part, ga.pkept, nb, d_st, gsa);
-      else VCP_LAUNCH(ctx, k_icp_step, dim3(nst), dim3(ITPB), 0, st, part, nb, d_st, sa);
     }
     launched += batch;
     VCP_HIP(ctx, hipMemcpyAsync(h_st, d_st, (size_t)nst * sizeof(IcpState), hipMemcpyDeviceToHost, st));
-    if (tr) VCP_HIP(ctx, hipMemcpyAsync(h_sel, td.a.sel, (size_t)nst * sizeof(TrimSel), hipMemcpyDeviceToHost, st));
-    if (sr) VCP_HIP(ctx, hipMemcpyAsync(h_side, d_side, (size_t)nst * sizeof(SimSide), hipMemcpyDeviceToHost, st));
-    if (ur) VCP_HIP(ctx, hipMemcpyAsync(h_lost, d_lost, (size_t)nst * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (lay.side_bytes) VCP_HIP(ctx, hipMemcpyAsync(h_side, d_side, lay.side_bytes, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (all_done() || launched >= max_iter || mode == MODE_SUMS_ONLY) break;
   }
   std::memcpy(out, h_st, (size_t)nst * sizeof(IcpState));
-  if (tr) std::memcpy(tr->sel_out, h_sel, (size_t)nst * sizeof(TrimSel));
-  if (sr) std::memcpy(sr->side_out, h_side, (size_t)nst * sizeof(SimSide));
-  if (ur) std::memcpy(ur->lost_out, h_lost, (size_t)nst * sizeof(long long));
+  if (lay.side_bytes) std::memcpy(v.side_out, h_side, lay.side_bytes);
   for (int k = 0; k < nst; k++)
     if (out[k].failed) return vcp_fail(ctx, VCP_ERR_ARG, "Horn solve failed (non-finite sums)%s", nst > 1 ? " in a pose" : "");
   return VCP_OK;
+}
+
+// M = [R | T; 0 0 0 1], row major: a state as the VTK-like entry points return it
+__host__ __device__ inline void state_to_M(const IcpState& s, double M[16]) {
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) M[4 * r + c] = s.R[3 * r + c];
+    M[4 * r + 3] = s.T[r];
+  }
+  M[12] = M[13] = M[14] = 0;
+  M[15] = 1;
+}
+
+// The landmarks of the VTK-like entry points: every step-th source point, step = ns / max_landmarks when
+// ns > max_landmarks (vtkIterativeClosestPointTransform.h)
+std::vector<double> icp_landmarks(const double* source, int64_t ns, int max_landmarks, int64_t* step_o) {
+  int64_t step = 1;
+  if (ns > max_landmarks) step = ns / max_landmarks;
+  const int64_t nb = ns / step;
+  std::vector<double> a((size_t)3 * nb);
+  for (int64_t i = 0, j = 0; i < nb; i++, j += step)
+    for (int c = 0; c < 3; c++) a[3 * i + c] = source[3 * j + c];
+  *step_o = step;
+  return a;
+}
+// and the centroid of their centroid start: the sequential binary64 mean over ALL n points
+void icp_mean(const double* x, int64_t n, double m[3]) {
+  double s[3] = {0, 0, 0};
+  for (int64_t i = 0; i < n; i++)
+    for (int c = 0; c < 3; c++) s[c] += x[3 * i + c];
+  for (int c = 0; c < 3; c++) m[c] = s[c] / (double)n;
 }
 
 // Inlier score of vcp_icp_multistart: grid (source points [x NNG lanes], poses).  Per pose h, M_h = [R_h | T_h] from the
@@ -1782,12 +1400,7 @@ __global__ __launch_bounds__(ITPB) void k_icpms_score(const double* __restrict__
   const int64_t j = ((int64_t)blockIdx.x * ITPB + threadIdx.x) / LPQ;
   const int sub = (int)(threadIdx.x & (LPQ - 1));
   double M[16];  // what vcp_icp_vtklike returns as M
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) M[4 * r + c] = st[h].R[3 * r + c];
-    M[4 * r + 3] = st[h].T[r];
-  }
+  state_to_M(st[h], M);
   bool hit = false;
   if (j < ns) {  // uniform per NNG-lane group: the grid query's shuffles stay within live groups
     double m[3];
@@ -1877,21 +1490,16 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
   if (nt >= 0x7FFFFFFFLL / 3) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "target too large");
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
-  int64_t step = 1;
-  if (ns > max_landmarks) step = ns / max_landmarks;
+  int64_t step;
+  const std::vector<double> a = icp_landmarks(source, ns, max_landmarks, &step);
   const int64_t nb = ns / step;
-  std::vector<double> a((size_t)3 * nb);
-  for (int64_t i = 0, j = 0; i < nb; i++, j += step)
-    for (int c = 0; c < 3; c++) a[3 * i + c] = source[3 * j + c];
   IcpState init, fin;
   identity(init);
-  if (start_by_matching_centroids) {  // sequential binary64 means over ALL points of both sets
-    double cs[3] = {0, 0, 0}, ct[3] = {0, 0, 0};
-    for (int64_t i = 0; i < ns; i++)
-      for (int c = 0; c < 3; c++) cs[c] += source[3 * i + c];
-    for (int64_t i = 0; i < nt; i++)
-      for (int c = 0; c < 3; c++) ct[c] += target[3 * i + c];
-    for (int c = 0; c < 3; c++) init.T[c] = ct[c] / (double)nt - cs[c] / (double)ns;
+  if (start_by_matching_centroids) {
+    double ms[3], mt[3];
+    icp_mean(source, ns, ms);
+    icp_mean(target, nt, mt);
+    for (int c = 0; c < 3; c++) init.T[c] = mt[c] - ms[c];
   }
   VCP_TRY(vcp_ensure(ctx, ctx->b_in0, (size_t)nt * 24));
   VCP_TRY(vcp_ensure(ctx, ctx->b_in2, (size_t)nb * 24));
@@ -1900,12 +1508,7 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `a` is a local buffer
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, &init, 1, 0.0, VCP_STOP_SSE_DELTA,
                   max_iter, MODE_VTK, &fin, nullptr, false, nullptr));
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) M[4 * r + c] = fin.R[3 * r + c];
-    M[4 * r + 3] = fin.T[r];
-  }
-  M[12] = M[13] = M[14] = 0;
-  M[15] = 1;
+  state_to_M(fin, M);
   if (mean_dist) *mean_dist = std::sqrt(fin.d / (double)nb);
   if (iters_o) *iters_o = fin.round;
   return VCP_OK;
@@ -1913,24 +1516,31 @@ int vcp_icp_vtklike(vcp_ctx* ctx, const double* source, int64_t ns, const double
 
 // Multi-start form of vcp_icp_vtklike (vcp.h): the same landmarks, rounds and arithmetic per pose, from H starts at
 // once; the target's grid (or screening frame) is built once and serves every pose and the score.
-// gr (NULL: vcp_icp_multistart): the gated form, vcp_icp_gated -- its schedule is checked here, next to the other
-// arguments, and kept / starved (each may be NULL) receive the states' counters.
-// tr (never with gr): the trimmed form, vcp_icp_trimmed -- likewise, and trim_dist (may be NULL) receives the root of
-// the last round's thr.
-// sr (only with gr): the similarity form, vcp_icp_sim -- its bounds are checked here, and ratio / unscaled (each may be
-// NULL) receive the side records' c and count.
-// ur (never with gr or tr): the unique-correspondence form, vcp_icp_unique -- its schedule is checked as gr's is, and
-// lost (may be NULL) receives the last round's count of pairs that were not their target's winner.
+// var says which form runs (PLAIN: vcp_icp_multistart); its schedule and bounds are checked here, next to the other
+// arguments.  IcpOutputs: what the counted forms return per pose beside the common outputs; each may be NULL.
+struct IcpOutputs {
+  int64_t* kept;      // the states' counters
+  int32_t* starved;
+  double* trim_dist;  // TRIMMED: the root of the last round's thr
+  double* ratio;      // SIM: the side records' c
+  int32_t* unscaled;  //      and count
+  int64_t* lost;      // UNIQUE: the last round's count of pairs that were not their target's winner
+};
 static bool sim_range_ok(double ratio_min, double ratio_max) {
   return ratio_min > 0.0 && ratio_max >= ratio_min && ratio_max <= 1.7976931348623157e308;  // false for NaN
+}
+static const char* icp_phase(IcpKind k, bool score) {
+  static const char* const names[5][2] = {{"icpms_rounds", "icpms_score"},
+                                          {"icpg_rounds", "icpg_score"},
+                                          {"icps_rounds", "icps_score"},
+                                          {"icpt_rounds", "icpt_score"},
+                                          {"icpu_rounds", "icpu_score"}};
+  return names[k][score ? 1 : 0];
 }
 static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
                               int32_t n_poses, const double* init_R, const double* init_T, int max_iter,
                               int max_landmarks, double inlier_dist, double M_best[16], int32_t* best, double* M_all,
-                              double* mean_dist, int32_t* inliers, const GateRun* gr, int64_t* kept, int32_t* starved,
-                              const TrimRun* tr = nullptr, double* trim_dist = nullptr, const SimRun* sr = nullptr,
-                              double* ratio = nullptr, int32_t* unscaled = nullptr, const UniqRun* ur = nullptr,
-                              int64_t* lost = nullptr) {
+                              double* mean_dist, int32_t* inliers, IcpVariant var, const IcpOutputs& o) {
   if (!ctx) return VCP_ERR_ARG;
   if (ns <= 0 || nt <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty source or target");
   if (max_iter < 1 || max_landmarks < 1 || !source || !target || !M_best || !best)
@@ -1943,70 +1553,35 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     if (!std::isfinite(init_R[k])) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite init_R");
   for (int64_t k = 0; k < (int64_t)n_poses * 3 && init_T; k++)
     if (!std::isfinite(init_T[k])) return vcp_fail(ctx, VCP_ERR_ARG, "non-finite init_T");
-  if (gr) {
-    if (gr->n_gates < 1 || !gr->gates) return vcp_fail(ctx, VCP_ERR_ARG, "n_gates < 1");
-    if (gr->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
-    for (int k = 0; k < gr->n_gates; k++)
-      if (!(gr->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
+  const bool counted = var.kind != ICP_PLAIN, shares = var.kind == ICP_TRIMMED;
+  if (counted) {  // the schedule: gates > 0, or keep shares in (0, 1]
+    if (var.n_sched < 1 || !var.sched) return vcp_fail(ctx, VCP_ERR_ARG, shares ? "n_keep < 1" : "n_gates < 1");
+    if (var.min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
+    for (int k = 0; k < var.n_sched; k++)
+      if (!(var.sched[k] > 0.0) || (shares && !(var.sched[k] <= 1.0)))
+        return vcp_fail(ctx, VCP_ERR_ARG, shares ? "keep shares must be in (0, 1]" : "gates must be > 0 (+inf allowed)");
   }
-  if (ur) {
-    if (ur->n_gates < 1 || !ur->gates) return vcp_fail(ctx, VCP_ERR_ARG, "n_gates < 1");
-    if (ur->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
-    for (int k = 0; k < ur->n_gates; k++)
-      if (!(ur->gates[k] > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gates must be > 0 (+inf allowed)");
-  }
-  if (sr) {
-    if (!sim_range_ok(sr->ratio_min, sr->ratio_max))
+  if (var.kind == ICP_SIM) {
+    if (!sim_range_ok(var.ratio_min, var.ratio_max))
       return vcp_fail(ctx, VCP_ERR_ARG, "need 0 < ratio_min <= ratio_max < inf");
-    if (!(sr->ratio_min <= 1.0 && 1.0 <= sr->ratio_max))
+    if (!(var.ratio_min <= 1.0 && 1.0 <= var.ratio_max))
       return vcp_fail(ctx, VCP_ERR_ARG, "need ratio_min <= 1 <= ratio_max");
-  }
-  if (tr) {
-    if (tr->n_share < 1 || !tr->share) return vcp_fail(ctx, VCP_ERR_ARG, "n_keep < 1");
-    if (tr->min_pairs < 1) return vcp_fail(ctx, VCP_ERR_ARG, "min_pairs < 1");
-    for (int k = 0; k < tr->n_share; k++)
-      if (!(tr->share[k] > 0.0 && tr->share[k] <= 1.0)) return vcp_fail(ctx, VCP_ERR_ARG, "keep shares must be in (0, 1]");
   }
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
-  vcp_phase(ctx, ur ? "icpu_rounds" : tr ? "icpt_rounds" : sr ? "icps_rounds" : gr ? "icpg_rounds" : "icpms_rounds");
-  int64_t step = 1;
-  if (ns > max_landmarks) step = ns / max_landmarks;
+  vcp_phase(ctx, icp_phase(var.kind, false));
+  int64_t step;
+  const std::vector<double> a = icp_landmarks(source, ns, max_landmarks, &step);
   const int64_t nb = ns / step;
-  std::vector<double> a((size_t)3 * nb);
-  for (int64_t i = 0, j = 0; i < nb; i++, j += step)
-    for (int c = 0; c < 3; c++) a[3 * i + c] = source[3 * j + c];
   // source and target means exactly as vcp_icp_vtklike's centroid start computes them
   double ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
   if (!init_T) {
-    for (int64_t i = 0; i < ns; i++)
-      for (int c = 0; c < 3; c++) ms[c] += source[3 * i + c];
-    for (int64_t i = 0; i < nt; i++)
-      for (int c = 0; c < 3; c++) mt[c] += target[3 * i + c];
-    for (int c = 0; c < 3; c++) {
-      ms[c] = ms[c] / (double)ns;
-      mt[c] = mt[c] / (double)nt;
-    }
+    icp_mean(source, ns, ms);
+    icp_mean(target, nt, mt);
   }
   std::vector<IcpState> init((size_t)n_poses), fin((size_t)n_poses);
-  std::vector<TrimSel> sel(tr ? (size_t)n_poses : 0);
-  TrimRun trun{};
-  if (tr) {
-    trun = *tr;
-    trun.sel_out = sel.data();
-  }
-  std::vector<SimSide> side(sr ? (size_t)n_poses : 0);
-  SimRun srun{};
-  if (sr) {
-    srun = *sr;
-    srun.side_out = side.data();
-  }
-  std::vector<long long> nlost(ur ? (size_t)n_poses : 0);
-  UniqRun urun{};
-  if (ur) {
-    urun = *ur;
-    urun.lost_out = nlost.data();
-  }
+  std::vector<char> side((size_t)n_poses * icp_side_size(var.kind));
+  var.side_out = side.data();
   for (int h = 0; h < n_poses; h++) {
     IcpState& s = init[h];
     identity(s);
@@ -2034,11 +1609,10 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   VCP_HIP(ctx, hipStreamSynchronize(st));  // `a` is a local buffer
   NNGrid ng{};
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nt, ctx->b_in2.as<double>(), nb, init.data(), n_poses, 0.0,
-                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, gr, tr ? &trun : nullptr,
-                  sr ? &srun : nullptr, ur ? &urun : nullptr));
+                  VCP_STOP_SSE_DELTA, max_iter, MODE_VTK, fin.data(), nullptr, true, &ng, &var));
   // score every pose over ALL source points with vcp_match's arithmetic, on the grid the rounds used (vcp_match bins
   // a target of more than 512 points too, and falls back to the full scan on the same condition)
-  vcp_phase(ctx, ur ? "icpu_score" : tr ? "icpt_score" : sr ? "icps_score" : gr ? "icpg_score" : "icpms_score");
+  vcp_phase(ctx, icp_phase(var.kind, true));
   const double* d_src = step > 1 ? ctx->b_in3.as<double>() : ctx->b_in2.as<double>();  // step 1: the landmarks are all
   const IcpState* d_st = icp_states(ctx);
   uint32_t* d_cnt = ctx->b_out0.as<uint32_t>();
@@ -2054,46 +1628,46 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   VCP_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_poses * 4, hipMemcpyDeviceToHost, st));
   VCP_HIP(ctx, hipStreamSynchronize(st));
   VCP_TRY(vcp_phase_finish(ctx));
-  // RMS distance of the pairs the last round summed: all nb landmarks, or the kept ones of a gated run (none: +inf)
+  // RMS distance of the pairs the last round summed: all nb landmarks, or the kept ones of a counted run (none: +inf)
   auto mean_of = [&](const IcpState& f) {
-    if (!gr && !tr && !ur) return std::sqrt(f.d / (double)nb);
+    if (!counted) return std::sqrt(f.d / (double)nb);
     return f.kept > 0 ? std::sqrt(f.d / (double)f.kept) : (double)INFINITY;
   };
+  const SimSide* sim = reinterpret_cast<const SimSide*>(side.data());
+  const TrimSel* sel = reinterpret_cast<const TrimSel*>(side.data());
+  const long long* nlost = reinterpret_cast<const long long*>(side.data());
   // most inliers, then the smaller mean distance, then the lower index
   int b = 0;
   for (int h = 0; h < n_poses; h++) {
     const double md = mean_of(fin[h]), mb = mean_of(fin[b]);
     if (h_cnt[h] > h_cnt[b] || (h_cnt[h] == h_cnt[b] && md < mb)) b = h;
-    if (M_all) {
-      double* M = M_all + 16 * (size_t)h;
-      for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) M[4 * r + c] = fin[h].R[3 * r + c];
-        M[4 * r + 3] = fin[h].T[r];
-      }
-      M[12] = M[13] = M[14] = 0;
-      M[15] = 1;
-    }
+    if (M_all) state_to_M(fin[h], M_all + 16 * (size_t)h);
     if (mean_dist) mean_dist[h] = md;
     if (inliers) inliers[h] = (int32_t)h_cnt[h];
-    if (kept) kept[h] = (int64_t)fin[h].kept;
-    if (starved) starved[h] = fin[h].starved;
-    if (sr && ratio) ratio[h] = side[h].c;
-    if (sr && unscaled) unscaled[h] = side[h].unscaled;
-    if (ur && lost) lost[h] = (int64_t)nlost[h];
-    if (tr && trim_dist) {
+    if (o.kept) o.kept[h] = (int64_t)fin[h].kept;
+    if (o.starved) o.starved[h] = fin[h].starved;
+    if (var.kind == ICP_SIM && o.ratio) o.ratio[h] = sim[h].c;
+    if (var.kind == ICP_SIM && o.unscaled) o.unscaled[h] = sim[h].unscaled;
+    if (var.kind == ICP_UNIQUE && o.lost) o.lost[h] = (int64_t)nlost[h];
+    if (var.kind == ICP_TRIMMED && o.trim_dist) {
       double thr;
       std::memcpy(&thr, &sel[h].key, sizeof(thr));
-      trim_dist[h] = std::sqrt(thr);
+      o.trim_dist[h] = std::sqrt(thr);
     }
   }
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) M_best[4 * r + c] = fin[b].R[3 * r + c];
-    M_best[4 * r + 3] = fin[b].T[r];
-  }
-  M_best[12] = M_best[13] = M_best[14] = 0;
-  M_best[15] = 1;
+  state_to_M(fin[b], M_best);
   *best = b;
   return VCP_OK;
+}
+
+// A counted variant of the multi-start entry points: the schedule and min_pairs; what else a form needs is set by name.
+static IcpVariant icp_variant(IcpKind kind, const double* sched, int32_t n_sched, int32_t min_pairs) {
+  IcpVariant v{};
+  v.kind = kind;
+  v.sched = sched;
+  v.n_sched = n_sched;
+  v.min_pairs = min_pairs;
+  return v;
 }
 
 int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
@@ -2101,7 +1675,7 @@ int vcp_icp_multistart(vcp_ctx* ctx, const double* source, int64_t ns, const dou
                        double inlier_dist, double M_best[16], int32_t* best, double* M_all, double* mean_dist,
                        int32_t* inliers) {
   return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
-                            M_best, best, M_all, mean_dist, inliers, nullptr, nullptr, nullptr);
+                            M_best, best, M_all, mean_dist, inliers, IcpVariant{}, IcpOutputs{});
 }
 
 // vcp_icp_multistart with a per-round gate on the correspondence distance (vcp.h)
@@ -2109,9 +1683,11 @@ int vcp_icp_gated(vcp_ctx* ctx, const double* source, int64_t ns, const double* 
                   const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* gates,
                   int32_t n_gates, int32_t min_pairs, double inlier_dist, double M_best[16], int32_t* best,
                   double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved) {
-  const GateRun gr{gates, n_gates, min_pairs, nullptr};
+  IcpOutputs o{};
+  o.kept = kept;
+  o.starved = starved;
   return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
-                            M_best, best, M_all, mean_dist, inliers, &gr, kept, starved);
+                            M_best, best, M_all, mean_dist, inliers, icp_variant(ICP_GATED, gates, n_gates, min_pairs), o);
 }
 
 // vcp_icp_multistart with a per-round keep share: every round fits on the closest pairs alone (vcp.h)
@@ -2120,9 +1696,12 @@ int vcp_icp_trimmed(vcp_ctx* ctx, const double* source, int64_t ns, const double
                     int32_t n_keep, int32_t min_pairs, double inlier_dist, double M_best[16], int32_t* best,
                     double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved,
                     double* trim_dist) {
-  const TrimRun tr{keep, n_keep, 0, min_pairs, nullptr, nullptr};
+  IcpOutputs o{};
+  o.kept = kept;
+  o.starved = starved;
+  o.trim_dist = trim_dist;
   return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
-                            M_best, best, M_all, mean_dist, inliers, nullptr, kept, starved, &tr, trim_dist);
+                            M_best, best, M_all, mean_dist, inliers, icp_variant(ICP_TRIMMED, keep, n_keep, min_pairs), o);
 }
 
 // vcp_icp_gated whose rounds fit one isotropic scale beside the rotation and the translation (vcp.h)
@@ -2131,11 +1710,16 @@ int vcp_icp_sim(vcp_ctx* ctx, const double* source, int64_t ns, const double* ta
                 int32_t n_gates, int32_t min_pairs, double ratio_min, double ratio_max, double inlier_dist,
                 double M_best[16], int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
                 int32_t* starved, double* ratio, int32_t* unscaled) {
-  const GateRun gr{gates, n_gates, min_pairs, nullptr};
-  const SimRun sr{ratio_min, ratio_max, nullptr};
+  IcpVariant v = icp_variant(ICP_SIM, gates, n_gates, min_pairs);
+  v.ratio_min = ratio_min;
+  v.ratio_max = ratio_max;
+  IcpOutputs o{};
+  o.kept = kept;
+  o.starved = starved;
+  o.ratio = ratio;
+  o.unscaled = unscaled;
   return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
-                            M_best, best, M_all, mean_dist, inliers, &gr, kept, starved, nullptr, nullptr, &sr, ratio,
-                            unscaled);
+                            M_best, best, M_all, mean_dist, inliers, v, o);
 }
 
 // vcp_icp_gated where, of the landmarks that share a nearest target, only the closest enters a round's sums (vcp.h)
@@ -2143,10 +1727,12 @@ int vcp_icp_unique(vcp_ctx* ctx, const double* source, int64_t ns, const double*
                    const double* init_R, const double* init_T, int max_iter, int max_landmarks, const double* gates,
                    int32_t n_gates, int32_t min_pairs, double inlier_dist, double M_best[16], int32_t* best,
                    double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved, int64_t* lost) {
-  const UniqRun ur{gates, n_gates, min_pairs, nullptr, nullptr};
+  IcpOutputs o{};
+  o.kept = kept;
+  o.starved = starved;
+  o.lost = lost;
   return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
-                            M_best, best, M_all, mean_dist, inliers, nullptr, kept, starved, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, &ur, lost);
+                            M_best, best, M_all, mean_dist, inliers, icp_variant(ICP_UNIQUE, gates, n_gates, min_pairs), o);
 }
 
 // Host-side run of the Horn step the device executes per round (same source: horn() is __host__ __device__).
@@ -2163,91 +1749,114 @@ int vcp_selftest_horn_sim(const double sums[18], int64_t n, double V[16], int us
   return horn_sim(sums, (long long)n, c, ratio_min, ratio_max, R1s, T1, use_v ? V : nullptr, k_used, c_new);
 }
 
-// gate (NULL: vcp_icp_sums): one gated pass, vcp_icp_sums_gated; kept and keep receive its verdicts
-// m (never with gate): one trimmed round's passes, vcp_icp_sums_trimmed; thr_dd and keep receive its verdicts
-// lost (only with gate): one unique-correspondence round's passes, vcp_icp_sums_unique; kept, lost and keep receive
-// its verdicts
+// One round's passes from (R, T), behind vcp_icp_sums and its forms.  kind says which form; gate serves GATED, SIM (sums
+// [18]) and UNIQUE, m serves TRIMMED.  SumsOutputs: the verdicts a form returns beside the sums and nn.
+struct SumsOutputs {
+  int64_t* kept;   // GATED, SIM, UNIQUE
+  uint8_t* keep;   // all but PLAIN; may be NULL
+  double* thr_dd;  // TRIMMED
+  int64_t* lost;   // UNIQUE
+};
 static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
-                        const double T[3], double sums[16], int32_t* nn, const double* gate, int64_t* kept,
-                        uint8_t* keep, const int64_t* m = nullptr, double* thr_dd = nullptr, bool sim = false,
-                        int64_t* lost = nullptr) {
+                        const double T[3], double* sums, int32_t* nn, IcpKind kind, double gate, int64_t m,
+                        const SumsOutputs& o) {
+  const bool gated = kind == ICP_GATED || kind == ICP_SIM || kind == ICP_UNIQUE, trimmed = kind == ICP_TRIMMED;
+  const bool stored_nn = trimmed || kind == ICP_UNIQUE;  // the rounds that keep the index found in their own workspace
   if (!ctx) return VCP_ERR_ARG;
   if (nm <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty model");
   if (nd <= 0 || !model || !data || !sums) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
   if (nm >= 0x7FFFFFFFLL / 3) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "model too large");
-  if (gate && !(*gate > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gate must be > 0 (+inf allowed)");
-  if (gate && !kept) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
-  if (m && !thr_dd) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
-  if (m && (*m < 1 || *m > nd)) return vcp_fail(ctx, VCP_ERR_ARG, "m must be in [1, nd]");
-  if ((m || lost) && nd > 0xFFFFFFFFLL)
-    return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "the key holds the landmark in 32 bits");
+  if (gated && !(gate > 0.0)) return vcp_fail(ctx, VCP_ERR_ARG, "gate must be > 0 (+inf allowed)");
+  if (gated && !o.kept) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
+  if (trimmed && !o.thr_dd) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
+  if (trimmed && (m < 1 || m > nd)) return vcp_fail(ctx, VCP_ERR_ARG, "m must be in [1, nd]");
+  if (stored_nn && nd > 0xFFFFFFFFLL) return vcp_fail(ctx, VCP_ERR_TOO_LARGE, "the key holds the landmark in 32 bits");
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
   VCP_TRY(vcp_ensure(ctx, ctx->b_in0, (size_t)nm * 24));
   VCP_TRY(vcp_ensure(ctx, ctx->b_in2, (size_t)nd * 24));
   VCP_TRY(vcp_ensure(ctx, ctx->b_out0, (size_t)nd * 4));
-  if (keep) VCP_TRY(vcp_ensure(ctx, ctx->b_out1, (size_t)nd));
+  if (o.keep) VCP_TRY(vcp_ensure(ctx, ctx->b_out1, (size_t)nd));
   VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in0.p, model, (size_t)nm * 24, hipMemcpyHostToDevice, ctx->stream));
   VCP_HIP(ctx, hipMemcpyAsync(ctx->b_in2.p, data, (size_t)nd * 24, hipMemcpyHostToDevice, ctx->stream));
   IcpState init, fin;
   identity(init);
   if (R) std::memcpy(init.R, R, sizeof(init.R));
   if (T) std::memcpy(init.T, T, sizeof(init.T));
-  const GateRun gr{gate, 1, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr};
-  TrimSel sel{};
-  const TrimRun tr{nullptr, 0, m ? (long long)*m : 0, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr, &sel};
-  SimSide side{};
-  const SimRun sr{1.0, 1.0, &side};  // sim (only with gate): the 18-wide pass, sums [18]
-  long long nlost = 0;
-  const UniqRun ur{gate, 1, 1, keep ? ctx->b_out1.as<uint8_t>() : nullptr, &nlost};
-  const bool stored_nn = m || lost;  // the rounds that keep the index found in their own workspace
+  union {
+    SimSide sim;
+    TrimSel sel;
+    long long lost;
+  } side{};
+  IcpVariant v{};
+  v.kind = kind;
+  v.min_pairs = 1;
+  v.d_keep = o.keep ? ctx->b_out1.as<uint8_t>() : nullptr;
+  v.side_out = &side;
+  if (gated) {
+    v.sched = &gate;
+    v.n_sched = 1;
+  }
+  if (trimmed) v.m_fixed = (long long)m;
+  v.ratio_min = v.ratio_max = 1.0;
   VCP_TRY(icp_run(ctx, ctx->b_in0.as<double>(), nm, ctx->b_in2.as<double>(), nd, &init, 1, 0.0, VCP_STOP_SSE_DELTA, 1,
-                  MODE_SUMS_ONLY, &fin, nn && !stored_nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr,
-                  gate && !lost ? &gr : nullptr, m ? &tr : nullptr, sim ? &sr : nullptr, lost ? &ur : nullptr));
+                  MODE_SUMS_ONLY, &fin, nn && !stored_nn ? ctx->b_out0.as<int32_t>() : nullptr, false, nullptr, &v));
   std::memcpy(sums, fin.sums, sizeof(fin.sums));
-  if (sim) {
-    sums[16] = side.s16;
-    sums[17] = side.s17;
+  if (kind == ICP_SIM) {
+    sums[16] = side.sim.s16;
+    sums[17] = side.sim.s17;
   }
-  if (gate) *kept = (int64_t)fin.kept;
-  if (lost) *lost = (int64_t)nlost;
-  if (m) std::memcpy(thr_dd, &sel.key, sizeof(double));
-  if (stored_nn) {
-    if (nn) VCP_HIP(ctx, hipMemcpyAsync(nn, icpt_nn(ctx, 1, nd), (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
-  } else if (nn) {
-    VCP_HIP(ctx, hipMemcpyAsync(nn, ctx->b_out0.p, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (gated) *o.kept = (int64_t)fin.kept;
+  if (kind == ICP_UNIQUE) *o.lost = (int64_t)side.lost;
+  if (trimmed) std::memcpy(o.thr_dd, &side.sel.key, sizeof(double));
+  if (nn) {
+    const void* d_nn = stored_nn ? (const void*)icpt_nn(ctx, 1, nd) : ctx->b_out0.p;
+    VCP_HIP(ctx, hipMemcpyAsync(nn, d_nn, (size_t)nd * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
-  if (keep) VCP_HIP(ctx, hipMemcpyAsync(keep, ctx->b_out1.p, (size_t)nd, hipMemcpyDeviceToHost, ctx->stream));
-  if (nn || keep) VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (o.keep) VCP_HIP(ctx, hipMemcpyAsync(o.keep, ctx->b_out1.p, (size_t)nd, hipMemcpyDeviceToHost, ctx->stream));
+  if (nn || o.keep) VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VCP_OK;
 }
 
 int vcp_icp_sums(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                  const double T[3], double sums[16], int32_t* nn) {
-  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, nullptr, nullptr, nullptr);
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, ICP_PLAIN, 0.0, 0, SumsOutputs{});
 }
 
 int vcp_icp_sums_gated(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                        const double T[3], double gate, double sums[16], int64_t* kept, int32_t* nn, uint8_t* keep) {
-  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep);
+  SumsOutputs o{};
+  o.kept = kept;
+  o.keep = keep;
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, ICP_GATED, gate, 0, o);
 }
 
 int vcp_icp_sums_sim(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                      const double T[3], double gate, double sums[18], int64_t* kept, int32_t* nn, uint8_t* keep) {
-  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep, nullptr, nullptr, true);
+  SumsOutputs o{};
+  o.kept = kept;
+  o.keep = keep;
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, ICP_SIM, gate, 0, o);
 }
 
 int vcp_icp_sums_unique(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                         const double T[3], double gate, double sums[16], int64_t* kept, int32_t* nn, uint8_t* keep,
                         int64_t* lost) {
   if (ctx && !lost) return vcp_fail(ctx, VCP_ERR_ARG, "bad argument");
-  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, &gate, kept, keep, nullptr, nullptr, false, lost);
+  SumsOutputs o{};
+  o.kept = kept;
+  o.keep = keep;
+  o.lost = lost;
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, ICP_UNIQUE, gate, 0, o);
 }
 
 int vcp_icp_sums_trimmed(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
                          const double R[9], const double T[3], int64_t m, double sums[16], double* thr_dd, int32_t* nn,
                          uint8_t* keep) {
-  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, nullptr, nullptr, keep, &m, thr_dd);
+  SumsOutputs o{};
+  o.keep = keep;
+  o.thr_dd = thr_dd;
+  return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, ICP_TRIMMED, 0.0, m, o);
 }
 
 }  // extern "C"
