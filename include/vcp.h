@@ -604,6 +604,79 @@ int vcp_icp_unique(vcp_ctx* ctx, const double* source, int64_t ns, const double*
                    int32_t* best, double* M_all, double* mean_dist, int32_t* inliers, int64_t* kept,
                    int32_t* starved, int64_t* lost);
 
+/* -- anisotropic ICP --------------------------------------------------------------------------------
+ * The reference puts the centroids into the truths' unit with TWO factors, scale[0] for X and scale[1] for Y
+ * (FrmMain.cs:3046-3055: the motor's two axes do not have the same gain), taken from two bounding boxes, and only then
+ * runs the rigid loop.  The similarity form fits one factor for both.  This form is the gated loop whose round fits a
+ * rotation, a translation and one scale per axis: the pose sought is y = R diag(sx, sy, 1) d + t.  z keeps scale 1: the
+ * reference's input is planar (Tools.cs:696-703) and a free z-scale would be undetermined there.
+ * Every other form works in the transformed frame and composes a small step onto the pose; such a step cannot stay
+ * inside R diag(s).  So this form sums over the RAW landmark d, and its step SETS the pose.
+ * Everything is binary64, each operation rounded on its own, sums left to right as written, / correctly rounded.
+ *
+ * Pass.  The pose applied is A (any finite 3x3) and T: p = A d + T, by vcp_icp_sums's TransPoint.  The pair, the
+ * distance, dd, the drop rule, kept, nn and keep are vcp_icp_sums_gated's, word for word.  For a kept pair, y its
+ * nearest model point:
+ *   sums[r] += d_r        sums[3+r] += y_r        sums[6+3r+c] += d_r * y_c        sums[15] += dd (under A, T)
+ *   sums[16] += d0*d0     sums[17] += d1*d1
+ * A dropped pair adds +0.0 to each column at its own place; all 18 columns go through vcp_icp_sums_sim's tree, fixed by
+ * (nm, nd, whether every model coordinate is finite).  With A = identity, T = 0 and finite data sums[0..15] are
+ * vcp_icp_sums_gated's bit for bit (1*d + 0*... + 0 is d).
+ *
+ * Step, on (sums [18], n = kept, the carried basis V, the pose's rotation R, its scales s[2], bounds lo[2] <= hi[2]).
+ *   N = (double)n;  muD_a = sums[a]/N;  muY_b = sums[3+b]/N.
+ *   For a = 0, 1:
+ *     C_ab = sums[6+3a+b]/N - muD_a*muY_b  (b = 0..2);   D_a = sums[16+a]/N - muD_a*muD_a;
+ *     g_a = (R[a]*C_a0 + R[3+a]*C_a1) + R[6+a]*C_a2
+ *     -- the least-squares scale of axis a for the rotation R is g_a / D_a: the problem separates per axis.
+ *     The axis is DETERMINED iff 0 < D_a < inf and 0 < g_a < inf (comparisons with NaN are false).  Then
+ *     s'_a = g_a / D_a, clamped to [lo_a, hi_a].  Not determined (all kept d share that coordinate, cancellation far
+ *     from the origin, a rotation that has turned the axis round): s'_a = s_a.  Not fatal.
+ *   S' = sums[0..15] with S'[a] = s'_a * sums[a] and S'[6+3a+b] = s'_a * sums[6+3a+b] for a = 0, 1.
+ *   R_new, T_new: vcp_selftest_horn's R1, T1 on (S', n, V), basis handling included.  Where that fails, this fails.
+ *   A_new[3i+a] = R_new[3i+a] * s'_a for a = 0, 1;  A_new[3i+2] = R_new[3i+2].
+ *   The step SETS the pose: R <- R_new, s <- s', A <- A_new, T <- T_new; nothing is composed.
+ * One scale update and one Horn solve per round: block-coordinate descent interleaved with the re-pairing.  For a fixed
+ * kept set neither half-step raises sum |R S d + t - y|^2.  Two exact invariances, while nothing leaves the normal range:
+ * scaling every coordinate of data and model by 2^k leaves s', R_new and the return value bit-identical and scales
+ * T_new; scaling the data's x alone by 2^k, with s_0, lo_0, hi_0 scaled by 2^-k, leaves R_new, T_new, s'_1 and A_new
+ * applied to the scaled data bit-identical and scales s'_0 by 2^-k exactly.  Accuracy of s': DESIGN.md section 25.
+ *
+ * vcp_icp_sums_aniso: one pass, the test handle.  Arguments and errors are vcp_icp_sums_sim's, A in R's place.
+ *
+ * vcp_selftest_horn_aniso: the step on the host, compiled from the source the device runs; needs no device.
+ * *determined: bit a set = axis a was determined.  Returns 1, 0 (the Horn solve failed: nothing but V written) or
+ * VCP_ERR_ARG: a NULL pointer, n <= 0, use_v without V, a NaN or a value <= 0 in s, lo or hi, hi_a = +inf, hi_a < lo_a.
+ *
+ * vcp_icp_aniso: vcp_icp_gated with that pass and step.  Everything not named here is vcp_icp_gated's, word for word:
+ * the landmarks, the default poses, exactly max_iter rounds, the starved rule (pose, scales and basis stay), the score
+ * over all ns points, the choice of the best pose, no output on an error, a pose's bits independent of the other
+ * poses, all rounds enqueued at once with one synchronisation.
+ *   init_scale [n_poses*2]  (may be NULL: all 1.0) the start scales (sx, sy) of every pose
+ *   The start of a pose is R = init_R as given, s = init_scale, A[3i+a] = init_R[3i+a]*s_a (a = 0, 1), T = init_T;
+ *   where init_T is NULL, T is vcp_icp_gated's centroid start computed with A.  lo_a = ratio_min*init_s_a,
+ *   hi_a = ratio_max*init_s_a.  M_all and M_best hold [A | T].
+ *   scale [n_poses*2]     (may be NULL) the final (sx, sy)
+ *   unscaled [n_poses*2]  (may be NULL) per axis the number of rounds that did not determine it
+ * VCP_ERR_ARG also for an init_scale that is NaN, <= 0 or +inf, or whose bound lo_a is 0 or hi_a not finite, and for
+ * the ratios by vcp_icp_sim's rules (ratio_min <= 1 <= ratio_max).  A failed Horn solve in a round that is not starved:
+ * VCP_ERR_ARG.  With ratio_min == ratio_max == 1.0 the scales never move: the loop is then the rigid fit from A, and it
+ * equals vcp_icp_gated from the start A TO ROUNDING ONLY, not bit for bit -- this step sets the pose from sums over d
+ * where the gated one composes a step from sums over p.
+ * Timing phases: icpa_rounds, icpa_score (csrc/icp.hip). */
+int vcp_icp_sums_aniso(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd,
+                       const double A[9], const double T[3], double gate, double sums[18], int64_t* kept, int32_t* nn,
+                       uint8_t* keep);
+int vcp_selftest_horn_aniso(const double sums[18], int64_t n, double V[16], int use_v, const double R[9],
+                            const double s[2], const double lo[2], const double hi[2], double R_new[9],
+                            double T_new[3], double s_new[2], int32_t* determined);
+int vcp_icp_aniso(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                  const double* init_R, const double* init_T, const double* init_scale, int max_iter,
+                  int max_landmarks, const double* gates, int32_t n_gates, int32_t min_pairs, double ratio_min,
+                  double ratio_max, double inlier_dist, double M_best[16], int32_t* best, double* M_all,
+                  double* mean_dist, int32_t* inliers, int64_t* kept, int32_t* starved, double* scale,
+                  int32_t* unscaled);
+
 /* -- congruent-pair global registration ---------------------------------------------------------------
  * Every ICP form above starts from T0 = mean(target) - R0 mean(source) unless told otherwise, which is only right when
  * the scan covers the whole truth field; a scan that sees part of it starts wrong by a large translation from every

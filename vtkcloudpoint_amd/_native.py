@@ -36,7 +36,7 @@ SYMBOLS = [
     "vcp_register_pairs", "vcp_register_pairs_dev", "vcp_selftest_register_pose", "vcp_register_sim",
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
     "vcp_gdbscan", "vcp_gdbscan_dev", "vcp_icp_sums_sim", "vcp_selftest_horn_sim", "vcp_icp_sim",
-    "vcp_icp_sums_unique", "vcp_icp_unique",
+    "vcp_icp_sums_unique", "vcp_icp_unique", "vcp_icp_sums_aniso", "vcp_selftest_horn_aniso", "vcp_icp_aniso",
 ]
 
 
@@ -333,6 +333,16 @@ class Context:
         kept = C.c_int64(0)
         sums, nn, keep = self._icp_sums(
             lib().vcp_icp_sums_sim, model, data, R, T, 18, want_nn, want_keep,
+            lambda head, sums, nn, keep: head + (C.c_double(gate), sums, C.byref(kept), nn, keep))
+        return sums, kept.value, nn, keep
+
+    def icp_sums_aniso(self, model, data, gate, A=None, T=None, want_nn=True, want_keep=True):
+        """One pass of the anisotropic form (vcp_icp_sums_aniso): the pair, the distance and the gate are icp_sums_gated's
+        under the pose p = A d + T, but columns 0:3 and 6:15 sum the raw landmark d in p's place, 16 is sum d0*d0 and 17
+        sum d1*d1 over the kept pairs.  Returns (sums [18], kept, nn [nd] int32 or None, keep [nd] uint8 or None)."""
+        kept = C.c_int64(0)
+        sums, nn, keep = self._icp_sums(
+            lib().vcp_icp_sums_aniso, model, data, A, T, 18, want_nn, want_keep,
             lambda head, sums, nn, keep: head + (C.c_double(gate), sums, C.byref(kept), nn, keep))
         return sums, kept.value, nn, keep
 
@@ -721,10 +731,11 @@ class Context:
                 raise ValueError("init_T has %d rows for %d poses" % (len(init_T), H))
         return H, init_R, init_T
 
-    def _icp_starts(self, fn, source, target, poses, init_T, max_iter, max_landmarks, form_args, inlier_dist, extra=()):
+    def _icp_starts(self, fn, source, target, poses, init_T, max_iter, max_landmarks, form_args, inlier_dist, extra=(),
+                    start_args=()):
         """One call of a multi-start entry point fn: the common arguments, form_args (arrays or C values) between
-        max_landmarks and inlier_dist, the common outputs, then one [H] array per (key, dtype) of extra.  Returns the
-        result dict."""
+        max_landmarks and inlier_dist, the common outputs, then one [H] array per (key, dtype) of extra -- [H, cols] per
+        (key, dtype, cols).  start_args (arrays or None) go between init_T and max_iter.  Returns the result dict."""
         source = _f64(source, 3)
         target = _f64(target, 3)
         H, init_R, init_T = self._icp_poses(poses, init_T)
@@ -734,10 +745,11 @@ class Context:
         md = np.zeros(n)
         inl = np.zeros(n, np.int32)
         best = C.c_int32(0)
-        more = [(key, np.zeros(n, dtype)) for key, dtype in extra]
+        more = [(e[0], np.zeros((n,) + tuple(e[2:]), e[1])) for e in extra]
         c_args = [_ptr(a) if isinstance(a, np.ndarray) else a for a in form_args]  # form_args keeps the arrays alive
         self._chk(fn(self._h, _ptr(source), C.c_int64(len(source)), _ptr(target), C.c_int64(len(target)), C.c_int32(H),
-                     _ptr(init_R), _ptr(init_T), int(max_iter), int(max_landmarks), *c_args, C.c_double(inlier_dist),
+                     _ptr(init_R), _ptr(init_T), *[_ptr(a) for a in start_args], int(max_iter), int(max_landmarks),
+                     *c_args, C.c_double(inlier_dist),
                      _ptr(M), C.byref(best), _ptr(M_all), _ptr(md), _ptr(inl), *[_ptr(a) for _, a in more]))
         return dict(best=best.value, M=M.reshape(4, 4), M_all=M_all.reshape(n, 4, 4), mean_dist=md, inliers=inl,
                     **dict(more))
@@ -778,6 +790,24 @@ class Context:
         return self._icp_starts(lib().vcp_icp_sim, source, target, poses, init_T, max_iter, max_landmarks,
                                 self._icp_schedule(gates, min_pairs) + (C.c_double(rmin), C.c_double(rmax)), inlier_dist,
                                 self._ICP_COUNTED + (("ratio", np.float64), ("unscaled", np.int32)))
+
+    def icp_aniso(self, source, target, gates, ratio_range, poses=1, init_T=None, init_scale=None, max_iter=100,
+                  max_landmarks=200, min_pairs=3, inlier_dist=np.inf):
+        """icp_gated whose rounds fit one scale for x and one for y beside the rotation and the translation
+        (vcp_icp_aniso): the pose is y = R diag(sx, sy, 1) d + t.  init_scale: None (all 1.0) or [H, 2], the start scales
+        of every pose; ratio_range = (ratio_min, ratio_max), ratio_min <= 1 <= ratio_max, bounds every scale to that
+        multiple of its start.  M and M_all hold [R diag(sx, sy, 1) | t].  Returns icp_gated's dict plus scale [H, 2] and
+        unscaled [H, 2] int32 (per axis the rounds whose kept pairs did not determine it)."""
+        rmin, rmax = (float(v) for v in ratio_range)
+        H = poses if isinstance(poses, (int, np.integer)) else len(_f64(poses).reshape(-1, 9))
+        if init_scale is not None:
+            init_scale = _f64(init_scale, 2)
+            if len(init_scale) != H:
+                raise ValueError("init_scale has %d rows for %d poses" % (len(init_scale), H))
+        return self._icp_starts(lib().vcp_icp_aniso, source, target, poses, init_T, max_iter, max_landmarks,
+                                self._icp_schedule(gates, min_pairs) + (C.c_double(rmin), C.c_double(rmax)), inlier_dist,
+                                self._ICP_COUNTED + (("scale", np.float64, 2), ("unscaled", np.int32, 2)),
+                                start_args=(init_scale,))
 
     def icp_trimmed(self, source, target, keep, poses=1, init_T=None, max_iter=100, max_landmarks=200, min_pairs=3,
                     inlier_dist=np.inf):
@@ -903,6 +933,24 @@ def selftest_horn_sim(sums, n, c=1.0, ratio_range=(1.0, 1.0), V=None):
     if rc == 0:
         return dict(rc=0, R1s=None, T1=None, k_used=None, c_new=None)
     return dict(rc=rc, R1s=R1s, T1=T1, k_used=ku.value, c_new=cn.value)
+
+
+def selftest_horn_aniso(sums, n, R, s, lo, hi, V=None):
+    """vcp_selftest_horn_aniso: one step of the anisotropic ICP on the host (no device), from the source the device runs.
+    R [9] is the pose's current rotation, s [2] its scales, lo, hi [2] their bounds; V [16] (updated in place) the
+    carried eigenvector basis, None for a cold start.  Returns dict(rc = 1 or 0 (the Horn solve failed: the other entries
+    are None), R_new [9], T_new [3], s_new [2], determined = the bit mask of the axes the sums determined)."""
+    sums = _f64(sums).reshape(18)
+    R, s, lo, hi = _f64(R).reshape(9), _f64(s).reshape(2), _f64(lo).reshape(2), _f64(hi).reshape(2)
+    Rn, Tn, sn = np.zeros(9), np.zeros(3), np.zeros(2)
+    det = C.c_int32(0)
+    rc = lib().vcp_selftest_horn_aniso(_ptr(sums), C.c_int64(int(n)), _ptr(V), C.c_int(0 if V is None else 1), _ptr(R),
+                                       _ptr(s), _ptr(lo), _ptr(hi), _ptr(Rn), _ptr(Tn), _ptr(sn), C.byref(det))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_horn_aniso")
+    if rc == 0:
+        return dict(rc=0, R_new=None, T_new=None, s_new=None, determined=None)
+    return dict(rc=rc, R_new=Rn, T_new=Tn, s_new=sn, determined=det.value)
 
 
 def selftest_register_pose(a, b, ti, tj, f=0):

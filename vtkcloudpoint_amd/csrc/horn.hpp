@@ -1,6 +1,7 @@
 // horn.hpp -- Horn's unit-quaternion closed form, the solve of an ICP round (icp.hip): horn() for the rigid step,
-// horn_sim() for the similarity step.  Host and device: same code, same rounding (vcp_selftest_horn and
-// vcp_selftest_horn_sim run it on the host).  Internal linkage, as when it was part of icp.hip.
+// horn_sim() for the similarity step, horn_aniso() for the anisotropic one.  Host and device: same code, same rounding
+// (vcp_selftest_horn, vcp_selftest_horn_sim and vcp_selftest_horn_aniso run it on the host).  Internal linkage, as when
+// it was part of icp.hip.
 #pragma once
 #include <cmath>
 
@@ -226,6 +227,65 @@ __host__ __device__ inline int horn_sim(const double s[18], long long n, double 
   *k_used = ku;
   *c_new = cn;
   return det ? 1 : 2;
+}
+
+// The anisotropic step (vcp.h, "anisotropic ICP"): s[0..17] are sums over the RAW landmarks d (s[16] = sum d0^2,
+// s[17] = sum d1^2), and the pose sought is y = R diag(s0, s1, 1) d + t.  One half-step each of a block-coordinate
+// descent: per axis a = 0, 1 the least-squares scale for the current rotation R (the problem separates per axis: the
+// scale matrix is diagonal), held in [lo_a, hi_a]; then horn() on the sums with rows 0 and 1 of the d-side scaled.  An
+// axis whose scale the sums do not determine keeps sc[a]; bit a of *determined says which did.  Returns false where
+// horn() fails (nothing but the basis written).  An[9] = Rn diag(sn0, sn1, 1): what the pass applies.  Every operation
+// is one binary64 rounding.
+__host__ __device__ inline bool horn_aniso(const double (&s)[18], long long n, double* Vst, const double R[9],
+                                           const double sc[2], const double lo[2], const double hi[2], double Rn[9],
+                                           double Tn[3], double sn[2], double An[9], int* determined) {
+  const double N = (double)n;
+  const double muY[3] = {s[3] / N, s[4] / N, s[5] / N};
+  const double big = 1.7976931348623157e308;
+  double sa[2];
+  int det = 0;
+#pragma unroll
+  for (int a = 0; a < 2; a++) {
+    const double muD = s[a] / N;
+    const double C0 = s[6 + 3 * a] / N - muD * muY[0];
+    const double C1 = s[6 + 3 * a + 1] / N - muD * muY[1];
+    const double C2 = s[6 + 3 * a + 2] / N - muD * muY[2];
+    const double D = s[16 + a] / N - muD * muD;
+    const double g = (R[a] * C0 + R[3 + a] * C1) + R[6 + a] * C2;
+    const bool ok = D > 0.0 && D <= big && g > 0.0 && g <= big;  // false for NaN
+    double v = sc[a];
+    if (ok) {
+      v = g / D;
+      v = v < lo[a] ? lo[a] : v > hi[a] ? hi[a] : v;
+      det |= 1 << a;
+    }
+    sa[a] = v;
+  }
+  double S[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) S[k] = s[k];
+#pragma unroll
+  for (int a = 0; a < 2; a++) {
+    S[a] = sa[a] * s[a];
+#pragma unroll
+    for (int b = 0; b < 3; b++) S[6 + 3 * a + b] = sa[a] * s[6 + 3 * a + b];
+  }
+  double R1[9], T1[3];
+  if (!horn(S, n, R1, T1, Vst)) return false;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    Rn[3 * i] = R1[3 * i];
+    Rn[3 * i + 1] = R1[3 * i + 1];
+    Rn[3 * i + 2] = R1[3 * i + 2];
+    An[3 * i] = R1[3 * i] * sa[0];
+    An[3 * i + 1] = R1[3 * i + 1] * sa[1];
+    An[3 * i + 2] = R1[3 * i + 2];
+    Tn[i] = T1[i];
+  }
+  sn[0] = sa[0];
+  sn[1] = sa[1];
+  *determined = det;
+  return true;
 }
 
 }  // namespace

@@ -14,10 +14,11 @@
 // and its slice of partial rows, k_icp_step runs one workgroup per state, and each state's partition into workgroups and
 // reduction order are those of a single run, so every pose's bits are independent of the batch.  k_icpms_score then
 // counts, per pose, the source points vcp_match would call matched.
-// Forms (vcp.h: gated, similarity, trimmed, unique-correspondence ICP): a form is a POLICY type, the last argument of
-// the two pass kernels k_icp_pass<TB, NNMODE, G> and k_icp_pass_small<TB, G>.  The policy says at compile time whether
-// the pass searches, sums, stores keys, counts kept pairs; the bodies share one per-pair function (icp_pair: the keep
-// rule and the 16 or 18 accumulations, written once) and one epilogue.  The plain policy NoGate is empty.  The forms
+// Forms (vcp.h: gated, similarity, trimmed, unique-correspondence, anisotropic ICP): a form is a POLICY type, the last
+// argument of the two pass kernels k_icp_pass<TB, NNMODE, G> and k_icp_pass_small<TB, G>.  The policy says at compile
+// time whether the pass searches, sums, stores keys, counts kept pairs; the bodies share one per-pair function
+// (icp_pair: the keep rule and the 16 or 18 accumulations, written once, over p or -- the anisotropic form -- over the
+// raw landmark) and one epilogue.  The plain policy NoGate is empty.  The forms
 // that count their kept pairs share one step, k_icp_step_kept<F>, whose FORM type F holds what a form adds to it.  On
 // the host one IcpVariant names the form of a run, icp_layout() places everything a run keeps in the workspace, and
 // PassLaunch launches a pass on the path the run has chosen.  The Horn solve itself lives in horn.hpp.
@@ -68,6 +69,7 @@ struct IcpState {
 //           verdict to keep[] (if not NULL) and the workgroup's count of kept pairs to pkept
 //   LOST    it also counts the pairs that are not their target's winner, into plost
 //   NS      columns of a row
+//   RAW     (COUNT policies) the d-side columns (0..2, the rows of 6..14, 16, 17) sum the landmark d as read, not p
 //   view(st, nd)  what the pass needs of its pose (blockIdx.y), read once before the loop
 // A dropped pair adds +0.0 to each row at its own place in the tree, which therefore stays the ungated one.
 struct PoseView {
@@ -100,7 +102,7 @@ struct NoGate {
 // row, and optionally the per-point verdict.  A pair whose distance sqrt(dd) is >= the round's gate is dropped; dd is
 // the SSE term.  A NaN dd compares false: kept.
 struct GateArgs {
-  static constexpr bool SEARCH = true, SUMS = true, STORE = false, COUNT = true, LOST = false;
+  static constexpr bool SEARCH = true, SUMS = true, STORE = false, COUNT = true, LOST = false, RAW = false;
   static constexpr int NS = 16;
   const double* gates;
   int n_gates;
@@ -121,6 +123,13 @@ struct GateArgs {
 // through the same tree.  A type of its own: the kernels of GateArgs stay the 16-wide ones they were.
 struct SimGate : GateArgs {
   static constexpr int NS = 18;
+};
+// Anisotropic ICP (vcp.h, "anisotropic ICP"): the gated pass whose d-side columns sum the RAW landmark d where the
+// others sum p = A d + T (the pair, the distance and the gate stay p's), with sum d0^2 at 16 and sum d1^2 at 17.  Its
+// step sets the pose from those sums; it composes nothing.
+struct AnisoGate : GateArgs {
+  static constexpr int NS = 18;
+  static constexpr bool RAW = true;
 };
 
 // Trimmed ICP (vcp.h, "trimmed ICP"): a round keeps the m landmarks with the smallest 96-bit keys [K(dd) | index].
@@ -151,7 +160,7 @@ struct TrimDist : TrimArgs {
   }
 };
 struct TrimSum : TrimArgs {
-  static constexpr bool SEARCH = false, SUMS = true, STORE = false, COUNT = true, LOST = false;
+  static constexpr bool SEARCH = false, SUMS = true, STORE = false, COUNT = true, LOST = false, RAW = false;
   static constexpr int NS = 16;
   __device__ __forceinline__ PoseView view(const IcpState*, int64_t nd) const {
     PoseView v = stored_view(key, nn, nd);
@@ -201,7 +210,7 @@ struct UniqDist : UniqArgs {
   }
 };
 struct UniqSum : UniqArgs {
-  static constexpr bool SEARCH = false, SUMS = true, STORE = false, COUNT = true, LOST = true;
+  static constexpr bool SEARCH = false, SUMS = true, STORE = false, COUNT = true, LOST = true, RAW = false;
   static constexpr int NS = 16;
   __device__ __forceinline__ PoseView view(const IcpState* st, int64_t nd) const {
     PoseView v = stored_view(key, nn, nd);
@@ -358,12 +367,18 @@ __device__ __forceinline__ int icp_exact_scan(const double* model, const float4*
   return order;
 }
 
+template <bool RAW>
+__device__ __forceinline__ const double (&icp_side(const double (&p)[3], const double (&d)[3]))[3] {
+  if constexpr (RAW) return d;
+  else return p;
+}
 // One pair (landmark i at p, model point `order`) under policy G: the key and index stored, or the pair decided and --
 // as far as kept -- added to the columns s.  Every column receives one addition per pair in either case (a dropped
 // pair's is +0.0 through a select, never a skipped statement: no sum can become -0.0).
 template <class G>
 __device__ __forceinline__ void icp_pair(const G& ga, const PoseView& v, int64_t i, int order, const double (&p)[3],
-                                         const double* model, double (&s)[G::NS], uint32_t& nkept, uint32_t& nlost) {
+                                         const double* data, const double* model, double (&s)[G::NS],
+                                         uint32_t& nkept, uint32_t& nlost) {
   const double y0 = model[3 * order], y1 = model[3 * order + 1], y2 = model[3 * order + 2];
   const double y[3] = {y0, y1, y2};
   if constexpr (G::STORE) {
@@ -376,15 +391,29 @@ __device__ __forceinline__ void icp_pair(const G& ga, const PoseView& v, int64_t
     const bool kp = ga.keeps(v, i, order, dd, code, nlost);
     if (ga.keep) ga.keep[i] = code;
     nkept += kp ? 1u : 0u;
+    // What the d-side columns sum.  RAW: the landmark is read AGAIN, through a base pointer the compiler cannot see
+    // through (it stays in scalar registers) -- held from the first read the landmark would stay live across the search,
+    // the pass's register peak, at 6 VGPRs per point
+    double d[3];
+    if constexpr (G::RAW) {
+      const double* again = data;
+      asm volatile("" : "+s"(again) : "v"(dd));  // and not before dd is there: p's registers are free by then
+#pragma unroll
+      for (int r = 0; r < 3; r++) d[r] = again[3 * i + r];
+    }
+    const double(&x)[3] = icp_side<G::RAW>(p, d);
 #pragma unroll
     for (int r = 0; r < 3; r++) {
-      s[r] += kp ? p[r] : 0.0;
+      s[r] += kp ? x[r] : 0.0;
       s[3 + r] += kp ? y[r] : 0.0;
 #pragma unroll
-      for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? p[r] * y[c] : 0.0;
+      for (int c = 0; c < 3; c++) s[6 + 3 * r + c] += kp ? x[r] * y[c] : 0.0;
     }
     s[15] += kp ? dd : 0.0;
-    if constexpr (G::NS == 18) {
+    if constexpr (G::NS == 18 && G::RAW) {
+      s[16] += kp ? x[0] * x[0] : 0.0;
+      s[17] += kp ? x[1] * x[1] : 0.0;
+    } else if constexpr (G::NS == 18) {
       s[16] += kp ? (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2] : 0.0;
       s[17] += kp ? (y0 * y0 + y1 * y1) + y2 * y2 : 0.0;
     }
@@ -570,7 +599,7 @@ __device__ __forceinline__ void icp_pass_body(const double* __restrict__ model, 
     if (!live || sub != 0) continue;  // one lane of the group carries the point into the sums
     if constexpr (G::SEARCH && !G::STORE)  // the others keep the index in their own workspace: nn is NULL
       if (nn) nn[i] = order;
-    icp_pair(ga, pv, i, order, p, model, s, nkept, nlost);
+    icp_pair(ga, pv, i, order, p, data, model, s, nkept, nlost);
   }
   icp_pass_finish<TB>(ga, s, nkept, nlost, partial);
 }
@@ -691,17 +720,23 @@ __device__ __forceinline__ void icp_pass_small_body(const double* __restrict__ m
       if (!live[h]) continue;
       if constexpr (G::SEARCH && !G::STORE)  // the others keep the index in their own workspace: nn is NULL
         if (nn) nn[idx[h]] = order;
-      icp_pair(ga, pv, idx[h], order, p[h], model, s, nkept, nlost);
+      icp_pair(ga, pv, idx[h], order, p[h], data, model, s, nkept, nlost);
     }
   }
   icp_pass_finish<TB>(ga, s, nkept, nlost, partial);
 }
 
+// Waves per SIMD the pairs kernel of a policy is held to (0: no demand).  AnisoGate: the five of SimGate's kernel, 96
+// VGPRs -- left alone its schedule takes 97.
+template <class G>
+constexpr int PAIRS_WAVES = 0;
+template <>
+constexpr int PAIRS_WAVES<AnisoGate> = 5;
 template <int TB, class G>
-__global__ __launch_bounds__(TB) void k_icp_pass_small(const double* __restrict__ model, const float4* __restrict__ model32,
-                                                      int nm, const double* __restrict__ data, int64_t nd,
-                                                      const IcpState* __restrict__ st, double* __restrict__ partial,
-                                                      int32_t* __restrict__ nn, uint32_t imask, double tolk, G ga) {
+__global__ __launch_bounds__(TB, PAIRS_WAVES<G>) void k_icp_pass_small(
+    const double* __restrict__ model, const float4* __restrict__ model32, int nm, const double* __restrict__ data,
+    int64_t nd, const IcpState* __restrict__ st, double* __restrict__ partial, int32_t* __restrict__ nn, uint32_t imask,
+    double tolk, G ga) {
   icp_pass_small_body<TB>(model, model32, nm, data, nd, st, partial, nn, imask, tolk, ga);
 }
 
@@ -982,6 +1017,7 @@ __global__ __launch_bounds__(ITPB) void k_icp_step(const double* __restrict__ pa
 //   spread(h)        work for the whole workgroup before the totals are read
 //   record(h, tot, lost)  thread 0: what the state has no room for, into the pose's side record
 //   solve(...)       thread 0: horn(), or what stands in its place
+//   SETS             what solve() returns IS the new pose (R, T <- R1, T1); false: it is composed onto the pose
 struct GateStepArgs {
   long long min_pairs;
   int max_iter, sums_only;
@@ -989,7 +1025,7 @@ struct GateStepArgs {
 // gated and trimmed rounds: nothing beside the above
 struct KeptStep {
   static constexpr int NS = 16;
-  static constexpr bool LOST = false;
+  static constexpr bool LOST = false, SETS = false;
   const uint32_t* pkept;  // [poses][nb]
   __device__ __forceinline__ void spread(int) const {}
   __device__ __forceinline__ void record(int, const double*, long long) const {}
@@ -1031,6 +1067,41 @@ struct SimStep : KeptStep {
     if (rc == 0) return false;
     side[h].c = cn;
     if (rc == 2) side[h].unscaled = side[h].unscaled + 1;
+    return true;
+  }
+};
+// anisotropic rounds: 18-wide rows over the raw landmarks, horn_aniso in horn's place, and a step that SETS the pose --
+// a small step composed onto R diag(s) would leave that form.  The state's R holds A = R diag(s0, s1, 1), what the pass
+// and the score apply; the side record holds the rotation itself, the two scales, their bounds and per axis the count
+// of rounds that did not determine it.
+struct AnisoSide {
+  double s16, s17;  // the last pass's sums[16], sums[17]
+  double R[9];
+  double s[2], lo[2], hi[2];
+  int unscaled[2];
+};
+struct AnisoStep : KeptStep {
+  static constexpr int NS = 18;
+  static constexpr bool SETS = true;
+  AnisoSide* side;  // [poses]
+  __device__ __forceinline__ void record(int h, const double* tot, long long) const {
+    side[h].s16 = tot[16];
+    side[h].s17 = tot[17];
+  }
+  __device__ __forceinline__ bool solve(int h, const double (&S)[18], long long kept, double A1[9], double T1[3], double* V) const {
+    AnisoSide& sd = side[h];
+    double R0[9], Rn[9], sn[2];
+    const double s0[2] = {sd.s[0], sd.s[1]}, lo[2] = {sd.lo[0], sd.lo[1]}, hi[2] = {sd.hi[0], sd.hi[1]};
+#pragma unroll
+    for (int k = 0; k < 9; k++) R0[k] = sd.R[k];
+    int det;
+    if (!horn_aniso(S, kept, V, R0, s0, lo, hi, Rn, T1, sn, A1, &det)) return false;
+#pragma unroll
+    for (int k = 0; k < 9; k++) sd.R[k] = Rn[k];
+    sd.s[0] = sn[0];
+    sd.s[1] = sn[1];
+    sd.unscaled[0] = sd.unscaled[0] + ((det & 1) ? 0 : 1);
+    sd.unscaled[1] = sd.unscaled[1] + ((det & 2) ? 0 : 1);
     return true;
   }
 };
@@ -1086,7 +1157,12 @@ __global__ __launch_bounds__(ITPB) void k_icp_step_kept(const double* __restrict
       st->done = 1;
       return;
     }
-    icp_compose(st, R1, T1);
+    if constexpr (F::SETS) {
+      for (int k = 0; k < 9; k++) st->R[k] = R1[k];
+      for (int k = 0; k < 3; k++) st->T[k] = T1[k];
+    } else {
+      icp_compose(st, R1, T1);
+    }
   }
   if (round >= a.max_iter) st->done = 1;
 }
@@ -1108,21 +1184,28 @@ IcpState* icp_states(vcp_ctx* ctx) { return ctx->b_icp_part.as<IcpState>(); }
 //   SIM      the gated pass over 18-wide rows, horn_sim in the step
 //   TRIMMED  per round the distance pass, the select, the trimmed sums pass
 //   UNIQUE   per round the distance pass, the tie pass, the sums pass, the slots' reset
-enum IcpKind { ICP_PLAIN = 0, ICP_GATED, ICP_SIM, ICP_TRIMMED, ICP_UNIQUE };
+//   ANISO    the gated pass over 18-wide rows of the raw landmarks, horn_aniso in the step, which sets the pose
+enum IcpKind { ICP_PLAIN = 0, ICP_GATED, ICP_SIM, ICP_TRIMMED, ICP_UNIQUE, ICP_ANISO };
 struct IcpVariant {
   IcpKind kind;
   const double* sched;  // host, [n_sched], validated by the caller: the gates, or TRIMMED's keep shares (none: m_fixed)
   int n_sched;
   long long min_pairs;
   long long m_fixed;            // TRIMMED: > 0: the keep count itself (vcp_icp_sums_trimmed)
-  double ratio_min, ratio_max;  // SIM, validated by the caller
+  double ratio_min, ratio_max;  // SIM, ANISO, validated by the caller
+  const double* init_scale;     // ANISO: host, [poses][2] or NULL (all 1.0)
   uint8_t* d_keep;              // [nd] or NULL
   // host, [nst]: per pose what the state has no room for -- SimSide (SIM), TrimSel, the last select (TRIMMED), long long,
-  // the last round's lost count (UNIQUE)
+  // the last round's lost count (UNIQUE), AnisoSide (ANISO)
   void* side_out;
+  const void* side_in;  // host, [nst] or NULL (all zero): ANISO's side records at the start
 };
 size_t icp_side_size(IcpKind k) {
-  return k == ICP_SIM ? sizeof(SimSide) : k == ICP_TRIMMED ? sizeof(TrimSel) : k == ICP_UNIQUE ? sizeof(long long) : 0;
+  return k == ICP_SIM       ? sizeof(SimSide)
+         : k == ICP_TRIMMED ? sizeof(TrimSel)
+         : k == ICP_UNIQUE  ? sizeof(long long)
+         : k == ICP_ANISO   ? sizeof(AnisoSide)
+                            : 0;
 }
 
 // Where everything of a run lies, in bytes from the start of its buffer.
@@ -1147,7 +1230,7 @@ IcpLayout icp_layout(const IcpVariant& v, int nst, int nb, int64_t nd, int64_t n
   const size_t cnt_bytes = v.kind == ICP_PLAIN ? 0 : ((size_t)nst * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
   l.side_bytes = (size_t)nst * icp_side_size(v.kind);
   l.rows = icp_states_bytes(nst);
-  l.sched = l.rows + (size_t)nst * nb * (v.kind == ICP_SIM ? 18 : 16) * sizeof(double);
+  l.sched = l.rows + (size_t)nst * nb * (v.kind == ICP_SIM || v.kind == ICP_ANISO ? 18 : 16) * sizeof(double);
   l.pkept = l.sched + (size_t)v.n_sched * sizeof(double);
   l.plost = l.pkept + cnt_bytes;
   l.side = l.plost + (v.kind == ICP_UNIQUE ? cnt_bytes : 0);
@@ -1266,6 +1349,10 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
   if (v.kind == ICP_SIM) {  // every pose starts at c = 1, no round unscaled
     for (int k = 0; k < nst; k++) reinterpret_cast<SimSide*>(h_side)[k] = SimSide{0.0, 0.0, 1.0, 0, 0};
     VCP_HIP(ctx, hipMemcpyAsync(d_side, h_side, lay.side_bytes, hipMemcpyHostToDevice, st));
+  } else if (v.kind == ICP_ANISO) {  // the caller's records: rotation, scales and bounds of every pose
+    if (v.side_in) std::memcpy(h_side, v.side_in, lay.side_bytes);
+    else std::memset(h_side, 0, lay.side_bytes);
+    VCP_HIP(ctx, hipMemcpyAsync(d_side, h_side, lay.side_bytes, hipMemcpyHostToDevice, st));
   } else if (v.kind == ICP_TRIMMED) {
     // the selects' results are read back at the end; the multi-workgroup form's histograms start at zero
     VCP_HIP(ctx, hipMemsetAsync(d_side, 0, lay.side_bytes, st));
@@ -1314,6 +1401,11 @@ int icp_run(vcp_ctx* ctx, const double* d_model, int64_t nm, const double* d_dat
           VCP_TRY(pass(d_nn, SimGate{ga}));
           VCP_LAUNCH(ctx, k_icp_step_kept<SimStep>, one_per_pose, threads, 0, st, part, nb, d_st, gsa,
                      (SimStep{{pkept}, reinterpret_cast<SimSide*>(d_side), v.ratio_min, v.ratio_max}));
+          break;
+        case ICP_ANISO:
+          VCP_TRY(pass(d_nn, AnisoGate{ga}));
+          VCP_LAUNCH(ctx, k_icp_step_kept<AnisoStep>, one_per_pose, threads, 0, st, part, nb, d_st, gsa,
+                     (AnisoStep{{pkept}, reinterpret_cast<AnisoSide*>(d_side)}));
           break;
         case ICP_TRIMMED:  // the pass twice (distances, then sums) with the select between them
           VCP_TRY(pass(nullptr, TrimDist{ta}));
@@ -1525,16 +1617,19 @@ struct IcpOutputs {
   double* ratio;      // SIM: the side records' c
   int32_t* unscaled;  //      and count
   int64_t* lost;      // UNIQUE: the last round's count of pairs that were not their target's winner
+  double* scale;       // ANISO: [poses][2] the side records' s
+  int32_t* unscaled2;  //        [poses][2] and counts
 };
 static bool sim_range_ok(double ratio_min, double ratio_max) {
   return ratio_min > 0.0 && ratio_max >= ratio_min && ratio_max <= 1.7976931348623157e308;  // false for NaN
 }
 static const char* icp_phase(IcpKind k, bool score) {
-  static const char* const names[5][2] = {{"icpms_rounds", "icpms_score"},
+  static const char* const names[6][2] = {{"icpms_rounds", "icpms_score"},
                                           {"icpg_rounds", "icpg_score"},
                                           {"icps_rounds", "icps_score"},
                                           {"icpt_rounds", "icpt_score"},
-                                          {"icpu_rounds", "icpu_score"}};
+                                          {"icpu_rounds", "icpu_score"},
+                                          {"icpa_rounds", "icpa_score"}};
   return names[k][score ? 1 : 0];
 }
 static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt,
@@ -1561,11 +1656,16 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
       if (!(var.sched[k] > 0.0) || (shares && !(var.sched[k] <= 1.0)))
         return vcp_fail(ctx, VCP_ERR_ARG, shares ? "keep shares must be in (0, 1]" : "gates must be > 0 (+inf allowed)");
   }
-  if (var.kind == ICP_SIM) {
+  if (var.kind == ICP_SIM || var.kind == ICP_ANISO) {
     if (!sim_range_ok(var.ratio_min, var.ratio_max))
       return vcp_fail(ctx, VCP_ERR_ARG, "need 0 < ratio_min <= ratio_max < inf");
     if (!(var.ratio_min <= 1.0 && 1.0 <= var.ratio_max))
       return vcp_fail(ctx, VCP_ERR_ARG, "need ratio_min <= 1 <= ratio_max");
+  }
+  for (int64_t k = 0; k < (int64_t)n_poses * 2 && var.kind == ICP_ANISO && var.init_scale; k++) {
+    const double s0 = var.init_scale[k];
+    if (!(s0 > 0.0) || !sim_range_ok(var.ratio_min * s0, var.ratio_max * s0))  // false for NaN
+      return vcp_fail(ctx, VCP_ERR_ARG, "init_scale must be > 0 and finite, and so must its bounds");
   }
   VCP_TRY(vcp_bind(ctx));
   vcp_phase_reset(ctx);
@@ -1582,6 +1682,8 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   std::vector<IcpState> init((size_t)n_poses), fin((size_t)n_poses);
   std::vector<char> side((size_t)n_poses * icp_side_size(var.kind));
   var.side_out = side.data();
+  std::vector<AnisoSide> aside(var.kind == ICP_ANISO ? (size_t)n_poses : 0);
+  if (var.kind == ICP_ANISO) var.side_in = aside.data();
   for (int h = 0; h < n_poses; h++) {
     IcpState& s = init[h];
     identity(s);
@@ -1591,6 +1693,17 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
       const double th = (double)h * (2.0 * M_PI / (double)n_poses), c = std::cos(th), sn = std::sin(th);
       const double R0[9] = {c, 0.0 - sn, 0.0, sn, c, 0.0, 0.0, 0.0, 1.0};
       std::memcpy(s.R, R0, sizeof(s.R));
+    }
+    if (var.kind == ICP_ANISO) {  // the record keeps the rotation; the state gets A = R diag(s0, s1, 1)
+      AnisoSide& sd = aside[h];
+      sd = AnisoSide{};
+      std::memcpy(sd.R, s.R, sizeof(sd.R));
+      for (int a = 0; a < 2; a++) {
+        sd.s[a] = var.init_scale ? var.init_scale[2 * (size_t)h + a] : 1.0;
+        sd.lo[a] = var.ratio_min * sd.s[a];
+        sd.hi[a] = var.ratio_max * sd.s[a];
+        for (int i = 0; i < 3; i++) s.R[3 * i + a] = sd.R[3 * i + a] * sd.s[a];
+      }
     }
     if (init_T) {
       std::memcpy(s.T, init_T + 3 * (size_t)h, sizeof(s.T));
@@ -1636,6 +1749,7 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
   const SimSide* sim = reinterpret_cast<const SimSide*>(side.data());
   const TrimSel* sel = reinterpret_cast<const TrimSel*>(side.data());
   const long long* nlost = reinterpret_cast<const long long*>(side.data());
+  const AnisoSide* ani = reinterpret_cast<const AnisoSide*>(side.data());
   // most inliers, then the smaller mean distance, then the lower index
   int b = 0;
   for (int h = 0; h < n_poses; h++) {
@@ -1649,6 +1763,10 @@ static int icp_multistart_run(vcp_ctx* ctx, const double* source, int64_t ns, co
     if (var.kind == ICP_SIM && o.ratio) o.ratio[h] = sim[h].c;
     if (var.kind == ICP_SIM && o.unscaled) o.unscaled[h] = sim[h].unscaled;
     if (var.kind == ICP_UNIQUE && o.lost) o.lost[h] = (int64_t)nlost[h];
+    for (int a = 0; a < 2 && var.kind == ICP_ANISO; a++) {
+      if (o.scale) o.scale[2 * (size_t)h + a] = ani[h].s[a];
+      if (o.unscaled2) o.unscaled2[2 * (size_t)h + a] = ani[h].unscaled[a];
+    }
     if (var.kind == ICP_TRIMMED && o.trim_dist) {
       double thr;
       std::memcpy(&thr, &sel[h].key, sizeof(thr));
@@ -1735,6 +1853,25 @@ int vcp_icp_unique(vcp_ctx* ctx, const double* source, int64_t ns, const double*
                             M_best, best, M_all, mean_dist, inliers, icp_variant(ICP_UNIQUE, gates, n_gates, min_pairs), o);
 }
 
+// vcp_icp_gated whose rounds fit one scale for x and one for y beside the rotation and the translation (vcp.h)
+int vcp_icp_aniso(vcp_ctx* ctx, const double* source, int64_t ns, const double* target, int64_t nt, int32_t n_poses,
+                  const double* init_R, const double* init_T, const double* init_scale, int max_iter, int max_landmarks,
+                  const double* gates, int32_t n_gates, int32_t min_pairs, double ratio_min, double ratio_max,
+                  double inlier_dist, double M_best[16], int32_t* best, double* M_all, double* mean_dist,
+                  int32_t* inliers, int64_t* kept, int32_t* starved, double* scale, int32_t* unscaled) {
+  IcpVariant v = icp_variant(ICP_ANISO, gates, n_gates, min_pairs);
+  v.ratio_min = ratio_min;
+  v.ratio_max = ratio_max;
+  v.init_scale = init_scale;
+  IcpOutputs o{};
+  o.kept = kept;
+  o.starved = starved;
+  o.scale = scale;
+  o.unscaled2 = unscaled;
+  return icp_multistart_run(ctx, source, ns, target, nt, n_poses, init_R, init_T, max_iter, max_landmarks, inlier_dist,
+                            M_best, best, M_all, mean_dist, inliers, v, o);
+}
+
 // Host-side run of the Horn step the device executes per round (same source: horn() is __host__ __device__).
 int vcp_selftest_horn(const double sums[16], int64_t nd, double V[16], int use_v, double R1[9], double T1[3]) {
   if (!sums || !R1 || !T1 || nd <= 0 || (use_v && !V)) return VCP_ERR_ARG;
@@ -1749,6 +1886,25 @@ int vcp_selftest_horn_sim(const double sums[18], int64_t n, double V[16], int us
   return horn_sim(sums, (long long)n, c, ratio_min, ratio_max, R1s, T1, use_v ? V : nullptr, k_used, c_new);
 }
 
+// Host-side run of the anisotropic step (horn_aniso is __host__ __device__ too).  Returns 1, or 0 where the solve fails.
+int vcp_selftest_horn_aniso(const double sums[18], int64_t n, double V[16], int use_v, const double R[9],
+                            const double s[2], const double lo[2], const double hi[2], double R_new[9],
+                            double T_new[3], double s_new[2], int32_t* determined) {
+  if (!sums || !R || !s || !lo || !hi || !R_new || !T_new || !s_new || !determined || n <= 0 || (use_v && !V))
+    return VCP_ERR_ARG;
+  for (int a = 0; a < 2; a++)
+    if (!(s[a] > 0.0) || !sim_range_ok(lo[a], hi[a])) return VCP_ERR_ARG;
+  double S[18], Rn[9], Tn[3], sn[2], An[9];
+  for (int k = 0; k < 18; k++) S[k] = sums[k];
+  int det;
+  if (!horn_aniso(S, (long long)n, use_v ? V : nullptr, R, s, lo, hi, Rn, Tn, sn, An, &det)) return 0;
+  std::memcpy(R_new, Rn, sizeof(Rn));
+  std::memcpy(T_new, Tn, sizeof(Tn));
+  std::memcpy(s_new, sn, sizeof(sn));
+  *determined = det;
+  return 1;
+}
+
 // One round's passes from (R, T), behind vcp_icp_sums and its forms.  kind says which form; gate serves GATED, SIM (sums
 // [18]) and UNIQUE, m serves TRIMMED.  SumsOutputs: the verdicts a form returns beside the sums and nn.
 struct SumsOutputs {
@@ -1760,7 +1916,8 @@ struct SumsOutputs {
 static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],
                         const double T[3], double* sums, int32_t* nn, IcpKind kind, double gate, int64_t m,
                         const SumsOutputs& o) {
-  const bool gated = kind == ICP_GATED || kind == ICP_SIM || kind == ICP_UNIQUE, trimmed = kind == ICP_TRIMMED;
+  const bool gated = kind == ICP_GATED || kind == ICP_SIM || kind == ICP_UNIQUE || kind == ICP_ANISO;
+  const bool trimmed = kind == ICP_TRIMMED;
   const bool stored_nn = trimmed || kind == ICP_UNIQUE;  // the rounds that keep the index found in their own workspace
   if (!ctx) return VCP_ERR_ARG;
   if (nm <= 0) return vcp_fail(ctx, VCP_ERR_EMPTY, "empty model");
@@ -1787,6 +1944,7 @@ static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const dou
     SimSide sim;
     TrimSel sel;
     long long lost;
+    AnisoSide ani;
   } side{};
   IcpVariant v{};
   v.kind = kind;
@@ -1805,6 +1963,10 @@ static int icp_sums_run(vcp_ctx* ctx, const double* model, int64_t nm, const dou
   if (kind == ICP_SIM) {
     sums[16] = side.sim.s16;
     sums[17] = side.sim.s17;
+  }
+  if (kind == ICP_ANISO) {
+    sums[16] = side.ani.s16;
+    sums[17] = side.ani.s17;
   }
   if (gated) *o.kept = (int64_t)fin.kept;
   if (kind == ICP_UNIQUE) *o.lost = (int64_t)side.lost;
@@ -1837,6 +1999,14 @@ int vcp_icp_sums_sim(vcp_ctx* ctx, const double* model, int64_t nm, const double
   o.kept = kept;
   o.keep = keep;
   return icp_sums_run(ctx, model, nm, data, nd, R, T, sums, nn, ICP_SIM, gate, 0, o);
+}
+
+int vcp_icp_sums_aniso(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double A[9],
+                       const double T[3], double gate, double sums[18], int64_t* kept, int32_t* nn, uint8_t* keep) {
+  SumsOutputs o{};
+  o.kept = kept;
+  o.keep = keep;
+  return icp_sums_run(ctx, model, nm, data, nd, A, T, sums, nn, ICP_ANISO, gate, 0, o);
 }
 
 int vcp_icp_sums_unique(vcp_ctx* ctx, const double* model, int64_t nm, const double* data, int64_t nd, const double R[9],

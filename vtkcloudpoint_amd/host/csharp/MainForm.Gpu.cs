@@ -403,6 +403,64 @@ namespace vtkPointCloud
             ShowIcpSolution(SourcePolydata, TargetPolydata);
         }
 
+        // ICPGated() that fits the reference's OWN pose model: tmp_X = X * scale[0], tmp_Y = Y * scale[1], then a rigid
+        // motion (showTruesAndCenters, FrmMain.cs:3046-3055, then ICP()).  The motor's two axes do not have the same gain, so
+        // the two factors differ; the bounding boxes give them once, wrongly on a partial view or with one false cluster at
+        // the edge.  Here every round fits both factors by least squares on the centroids inside the gate, beside the
+        // rotation and the translation (vcp_icp_aniso).  The start is scale[0], scale[1] as they stand (the bounding-box
+        // rule, or ScaleCentersBySimilarity's k in both); each may change by a factor within [1 / maxRatio, maxRatio].  The
+        // RAW centroid coordinates go in.  On return scale[0], scale[1] and tmp_X, tmp_Y hold the fitted factors and M the
+        // rigid part, so that M applied to (tmp_X, tmp_Y, 0) is the pose found -- what ICP() leaves behind.
+        void ICPAnisotropic(int angles, double maxRatio, double gateStart, double gateEnd, double matchDistance)
+        {
+            ren = new vtk.vtkRenderer();
+            int ns = centers.Count;
+            double[] src = new double[3 * Math.Max(ns, 1)];
+            for (int i = 0; i < ns; i++) { src[3 * i] = centers[i].X; src[3 * i + 1] = centers[i].Y; src[3 * i + 2] = 0.0; }
+            double[] tgt = TruthArray();
+            int nt = tgt.Length / 3;
+            double[] initScale = new double[2 * angles];
+            for (int h = 0; h < angles; h++) { initScale[2 * h] = scale[0]; initScale[2 * h + 1] = scale[1]; }
+            const int steps = 10;
+            double[] gates = new double[steps];
+            for (int k = 0; k < steps; k++) gates[k] = gateStart * Math.Pow(gateEnd / gateStart, k / (steps - 1.0));
+            gates[0] = gateStart;
+            gates[steps - 1] = gateEnd;
+            double[] m16 = new double[16];
+            int[] inliers = new int[Math.Max(angles, 1)];
+            long[] kept = new long[Math.Max(angles, 1)];
+            int[] starved = new int[Math.Max(angles, 1)];
+            double[] fitted = new double[2 * Math.Max(angles, 1)];
+            int[] unscaled = new int[2 * Math.Max(angles, 1)];
+            int best;
+            // init_R null: the library's Rz(h * 2 pi / angles); init_T null: its centroid start under R diag(scale)
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_icp_aniso(lease.Ctx, src, ns, tgt, nt, angles, null, null, initScale, 100, 200,
+                    gates, steps, 3, 1.0 / maxRatio, maxRatio, matchDistance, m16, out best, null, null, inliers, kept, starved,
+                    fitted, unscaled));
+            scale[0] = fitted[2 * best];
+            scale[1] = fitted[2 * best + 1];
+            foreach (Point3D p in centers)
+            {
+                p.tmp_X = p.X * scale[0];
+                p.tmp_Y = p.Y * scale[1];
+            }
+            // m16 holds [R diag(sx, sy, 1) | t]: the rigid part is its first two columns over the factors
+            M = new vtk.vtkMatrix4x4();
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++)
+                    M.SetElement(r, c, r < 3 && c < 2 ? m16[4 * r + c] / scale[c] : m16[4 * r + c]);
+            vtk.vtkPolyData SourcePolydata = Tools.ArrayList2PolyData(1, this.centers, this.trueScale, this.centroidScale,
+                this.scale, this.clock, this.clock_y, this.clock_x);
+            vtk.vtkPolyData TargetPolydata = new vtk.vtkPolyData();
+            TargetPolydata.SetPoints(truePointCloud);
+            TargetPolydata.SetVerts(truePointVertices);
+            Console.WriteLine("刚性变换矩阵为：" + M + " (start " + best + " of " + angles + ", " + inliers[best] + " / " + ns
+                + ", " + kept[best] + " inside the gate, scale " + scale[0] + " x " + scale[1] + ", " + starved[best]
+                + " starved rounds, " + unscaled[2 * best] + " / " + unscaled[2 * best + 1] + " rounds without an x / y scale)");
+            ShowIcpSolution(SourcePolydata, TargetPolydata);
+        }
+
         // ICPGated() where a truth takes one centroid per round: of the centroids whose nearest truth is the same one, only
         // the closest enters that round's fit.  A target makes one centroid; where DBSCAN split it, or a reflection or an
         // edge return left a second cluster beside it, the second lies inside any gate that admits the real centroids and

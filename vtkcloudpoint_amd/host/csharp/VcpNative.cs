@@ -123,6 +123,20 @@ namespace vtkPointCloud
             out int best, double[] M_all, double[] mean_dist, int[] inliers, long[] kept, int[] starved, double[] ratio,
             int[] unscaled);
 
+        // anisotropic ICP: vcp_icp_gated whose round fits one scale for x and one for y, pose y = R diag(sx, sy, 1) d + t.
+        // One pass (the test handle: sums [18] over the raw landmarks under the pose A, T; nn and keep may be null), the
+        // step on the host (returns 1, 0 = failed; determined: bit a = axis a; V may be null with use_v = 0) and the loop;
+        // init_scale [2 n_poses] may be null (all 1), as may kept, starved, scale [2 n_poses] and unscaled [2 n_poses]
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_sums_aniso(IntPtr ctx, double[] model, long nm, double[] data,
+            long nd, double[] A, double[] T, double gate, double[] sums, out long kept, int[] nn, byte[] keep);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_selftest_horn_aniso(double[] sums, long n, double[] V, int use_v, double[] R,
+            double[] s, double[] lo, double[] hi, double[] R_new, double[] T_new, double[] s_new, out int determined);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_aniso(IntPtr ctx, double[] source, long ns, double[] target,
+            long nt, int n_poses, double[] init_R, double[] init_T, double[] init_scale, int max_iter, int max_landmarks,
+            double[] gates, int n_gates, int min_pairs, double ratio_min, double ratio_max, double inlier_dist,
+            double[] M_best, out int best, double[] M_all, double[] mean_dist, int[] inliers, long[] kept, int[] starved,
+            double[] scale, int[] unscaled);
+
         // congruent-pair global registration (no counterpart in the reference; bases = pairs of source indices)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_register_pairs(IntPtr ctx, double[] source, long ns, double[] target,
             long nt, int[] bases, int n_bases, double len_tol, int mirror, int max_landmarks, double inlier_dist,

@@ -253,6 +253,45 @@ def similarity_icp(centers, truths, gates, ratio_range, n_angles=1, mirror=False
     return ctx.icp_sim(src, tgt, gates, ratio_range, poses, init_T, max_iter, max_landmarks, min_pairs, inlier_dist)
 
 
+def bbox_scale_xy(centers, truths):
+    """(sx, sy): the reference's two factors, sx = the truths' x extent over the centroids' and sy likewise for y
+    (MainForm.showTruesAndCenters, FrmMain.cs:3046-3049), as a START value for anisotropic_icp.  Its weakness is the
+    bounding box's: the factors are only right when the scan covers the whole truth field, one false cluster outside
+    the field stretches an extent by its whole distance, and the boxes are taken along the centroids' own axes, so a
+    rotation between the two frames mixes the extents.  anisotropic_icp refines the start; it cannot repair one that
+    lies outside its ratio range."""
+    src, tgt = _points(centers), _points(truths)
+    return tuple((float(tgt[:, c].max()) - float(tgt[:, c].min())) / (float(src[:, c].max()) - float(src[:, c].min()))
+                 for c in (0, 1))
+
+
+def anisotropic_icp(centers, truths, scale0=None, ratio=(0.9, 1.1), gates=None, n_angles=1, mirror=False, init_T=None,
+                    max_iter=100, max_landmarks=200, min_pairs=3, inlier_dist=np.inf, ctx=None):
+    """gated_icp whose every round also fits one scale for x and one for y (vcp_icp_aniso): the pose is
+    truth ~ R diag(sx, sy, 1) centroid + t, the reference's tmp_X = X * scale[0], tmp_Y = Y * scale[1] followed by its
+    rigid ICP, with the two factors fitted by least squares on the kept pairs in every round instead of taken once from
+    two bounding boxes.  The motor's two axes do not have the same gain, so sx != sy is the normal case, and
+    similarity_icp's one factor leaves half the difference at the edge of the field.
+    scale0: None (1, 1), one (sx, sy) for every start, or [H, 2] (bbox_scale_xy gives the reference's value);
+    ratio = (lo, hi), lo <= 1 <= hi, bounds each scale to that multiple of its start; gates: None is the ungated loop.
+    n_angles may also be an [H, 3, 3] array of start ROTATIONS (the scales are applied to them by the library).  Returns
+    Context.icp_aniso's dict (gated_icp's plus scale [H, 2], unscaled [H, 2]); M holds [R diag(sx, sy, 1) | t]."""
+    ctx = ctx or default_context()
+    src = _points(centers)
+    tgt = _points(truths)
+    if isinstance(n_angles, (int, np.integer)):
+        poses = rotations_about_z(n_angles, mirror) if mirror else int(n_angles)
+        H = len(poses) if mirror else poses
+    else:
+        poses = np.asarray(n_angles, np.float64)
+        H = len(poses.reshape(-1, 9))
+    if scale0 is not None:
+        scale0 = np.asarray(scale0, np.float64)
+        scale0 = np.ascontiguousarray(np.broadcast_to(scale0.reshape(-1, 2), (H, 2)))
+    gates = [np.inf] if gates is None else gates
+    return ctx.icp_aniso(src, tgt, gates, ratio, poses, init_T, scale0, max_iter, max_landmarks, min_pairs, inlier_dist)
+
+
 def trim_schedule(start, end, rounds):
     """`rounds` keep shares that fall linearly from `start` to `end` (1 >= start >= end > 0): the first entry is exactly
     `start`, the last exactly `end`, and the list never rises.  rounds = 1 gives [end].  vcp_icp_trimmed holds the last
