@@ -4,11 +4,13 @@
 //   gather      random 16-B gather by index (the round-1 build)
 //   soa/aos     direct scatter through LDS cursors: every lane stores its record at its own slot
 //   staged      the chunk is first ordered by bucket in LDS, then consecutive lanes store consecutive slots
+//   flagship    aos16 against paired 32-byte stores at the shape of k_part_scatter on the 10 M-point benchmark cloud
 //   window*     the output direction: scattered 4+1+1-byte stores inside 2^15-entry windows, direct or LDS-staged
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -138,6 +140,103 @@ __global__ __launch_bounds__(PT) void k_scatter_staged(const double2* __restrict
   }
 }
 
+// The flagship shape of k_part_scatter (10 M records, ~3050 buckets, 251 chunks of 39936, 1024 threads): 16-byte records.
+//   aos16     every lane stores its record at its own slot (= k_scatter<2> at 1024 threads)
+//   paired    two records that share a 32-byte sector are stored together: an even-slot record whose partner has not
+//             arrived waits in LDS (one record per bucket), the odd-slot record that follows stores both back to back.
+//             `part_bench flagship` runs these two alone (the run to collect --pmc WRITE_SIZE on).
+constexpr int FPT = 1024;
+constexpr uint32_t NOSLOT = 0xFFFFFFFFu;
+__device__ __forceinline__ float4 rec16(double2 v, size_t i, uint32_t k) {
+  return make_float4((float)v.x, (float)v.y, __uint_as_float((uint32_t)i), __uint_as_float(k));
+}
+__global__ __launch_bounds__(FPT) void k_scatter16(const double2* __restrict__ xy, const uint32_t* __restrict__ key, size_t n,
+                                                  uint32_t B, uint32_t chunk, uint32_t nchunk, const uint32_t* __restrict__ base,
+                                                  float4* __restrict__ out) {
+  extern __shared__ uint32_t h[];
+  for (uint32_t k = threadIdx.x; k < B; k += FPT) h[k] = base[(size_t)k * nchunk + blockIdx.x];
+  __syncthreads();
+  size_t first = (size_t)blockIdx.x * chunk, last = first + chunk < n ? first + chunk : n;
+#pragma unroll 4
+  for (size_t i = first + threadIdx.x; i < last; i += FPT) {
+    const uint32_t k = key[i];
+    out[atomicAdd(&h[k], 1u)] = rec16(xy[i], i, k);
+  }
+}
+template <int AHEAD>  // trips whose loads are issued together, one group ahead of the group being scattered
+__global__ __launch_bounds__(FPT) void k_scatter16_paired(const double2* __restrict__ xy, const uint32_t* __restrict__ key,
+                                                         size_t n, uint32_t B, uint32_t chunk, uint32_t nchunk,
+                                                         const uint32_t* __restrict__ base, float4* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  float4* stash = reinterpret_cast<float4*>(lds);           // [B] last unpaired even-slot record of the bucket
+  uint32_t* h = reinterpret_cast<uint32_t*>(stash + B);     // [B] cursors
+  uint32_t* stash_slot = h + B;                             // [B] that record's slot, or NOSLOT
+  for (uint32_t k = threadIdx.x; k < B; k += FPT) {
+    h[k] = base[(size_t)k * nchunk + blockIdx.x];
+    stash_slot[k] = NOSLOT;
+  }
+  __syncthreads();
+  const size_t first = (size_t)blockIdx.x * chunk, last = first + chunk < n ? first + chunk : n;
+  const uint32_t trips = first < last ? (uint32_t)((last - first + FPT - 1) / FPT) : 0u;  // uniform over the workgroup
+  double2 nv[AHEAD];
+  uint32_t nk[AHEAD];
+  auto fetch = [&](uint32_t t0) {
+#pragma unroll
+    for (int u = 0; u < AHEAD; u++) {
+      const size_t i = first + (size_t)(t0 + u) * FPT + threadIdx.x;
+      nk[u] = NOSLOT;
+      if (i < last) {
+        nk[u] = key[i];
+        nv[u] = xy[i];
+      }
+    }
+  };
+  fetch(0);
+  for (uint32_t t0 = 0; t0 < trips; t0 += AHEAD) {
+    double2 v[AHEAD];
+    uint32_t kk[AHEAD];
+#pragma unroll
+    for (int u = 0; u < AHEAD; u++) {
+      v[u] = nv[u];
+      kk[u] = nk[u];
+    }
+    fetch(t0 + AHEAD);  // (past the chunk's end every lane is predicated off)
+#pragma unroll
+    for (int u = 0; u < AHEAD; u++) {
+      const bool take = kk[u] != NOSLOT;
+      const uint32_t k = take ? kk[u] : 0u;
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      uint32_t slot = 0;
+      if (take) {
+        r = rec16(v[u], first + (size_t)(t0 + u) * FPT + threadIdx.x, k);
+        slot = atomicAdd(&h[k], 1u);
+      }
+      __syncthreads();
+      bool keep = false;
+      if (take) {
+        if (slot & 1u) {
+          if (stash_slot[k] == slot - 1u) out[slot - 1u] = stash[k];  // the partner arrived in an earlier trip
+          out[slot] = r;
+        } else if (h[k] > slot + 1u) {
+          out[slot] = r;  // the partner arrived in this trip and stores its own half now
+        } else {
+          keep = true;    // the bucket's last record so far: at most one such lane per bucket and trip
+        }
+      }
+      __syncthreads();
+      if (keep) {
+        stash[k] = r;
+        stash_slot[k] = slot;
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < B; k += FPT) {
+    const uint32_t s = stash_slot[k];
+    if (s != NOSLOT && h[k] == s + 1u) out[s] = stash[k];  // never consumed: the chunk's run in this bucket ends on an even slot
+  }
+}
+
 // output direction: records (ord, word) grouped by windows of 2^15 ords; write labels[ord] (4 B), a[ord], b[ord] (1 B each)
 constexpr int OWSH = 15;
 __global__ __launch_bounds__(256) void k_window_direct(const uint2* __restrict__ rec, size_t n, int32_t* lab, uint8_t* a, uint8_t* b) {
@@ -180,7 +279,8 @@ __global__ __launch_bounds__(512) void k_window_staged(const uint2* __restrict__
   }
 }
 
-int main() {
+int main(int argc, char** argv) {
+  const bool flagship_only = argc > 1 && !strcmp(argv[1], "flagship");
   const size_t n = 10000000;
   std::mt19937 rng(7);
   std::vector<double2> hxy(n);
@@ -203,9 +303,55 @@ int main() {
     CK(hipGetLastError());
     printf("%-40s %.3f ms\n", name, ms / 10); fflush(stdout);
   };
+  std::vector<uint32_t> hkey(n), hc;
+  {
+    // the flagship shape of k_part_scatter: part_geom(10 M points, 49.8 M cells) = 3043 buckets, chunks of 39936
+    const uint32_t B = 3050, chunk = 39936, nchunk = (uint32_t)((n + chunk - 1) / chunk);
+    for (size_t i = 0; i < n; i++) hkey[i] = rng() % B;
+    CK(hipMemcpy(key, hkey.data(), n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_hist, dim3(nchunk), dim3(PT), B * 4, 0, key, n, B, chunk, nchunk, counts);
+    hc.resize((size_t)B * nchunk);
+    CK(hipMemcpy(hc.data(), counts, hc.size() * 4, hipMemcpyDeviceToHost));
+    uint32_t run = 0;
+    for (auto& c : hc) { uint32_t t = c; c = run; run += t; }
+    CK(hipMemcpy(counts, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
+    float4* out = reinterpret_cast<float4*>(oaos);  // hipMalloc: 256-byte aligned, so slot parity = 32-byte sector parity
+    const size_t lds_p = (size_t)B * 24;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter16_paired<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter16_paired<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
+    // every record exactly once, inside its bucket
+    auto check = [&](const char* name) {
+      std::vector<float4> ho(n);
+      CK(hipMemcpy(ho.data(), out, n * 16, hipMemcpyDeviceToHost));
+      std::vector<uint8_t> seen(n, 0);
+      size_t bad = 0;
+      for (size_t j = 0; j < n; j++) {
+        uint32_t idx, k;
+        memcpy(&idx, &ho[j].z, 4);
+        memcpy(&k, &ho[j].w, 4);
+        const bool ok = idx < n && k < B && !seen[idx] && hkey[idx] == k && j >= hc[(size_t)k * nchunk] &&
+                        (k + 1 == B || j < hc[(size_t)(k + 1) * nchunk]) && ho[j].x == (float)hxy[idx].x;
+        if (ok) seen[idx] = 1;
+        else bad++;
+      }
+      printf("%-40s %s (%zu bad slots)\n", name, bad ? "WRONG" : "every record once, in its bucket", bad);
+      if (bad) exit(1);
+    };
+    for (int rep = 0; rep < (flagship_only ? 1 : 2); rep++) {  // twice: the order of the variants is not what decides
+      CK(hipMemset(out, 0xFF, n * 16));
+      timeit("flagship aos16  B=3050 chunk=39936", [&] { hipLaunchKernelGGL(k_scatter16, dim3(nchunk), dim3(FPT), B * 4, 0, xy, key, n, B, chunk, nchunk, counts, out); });
+      if (rep == 0) check("  aos16");
+      CK(hipMemset(out, 0xFF, n * 16));
+      timeit("flagship paired B=3050 chunk=39936 ahead 1", [&] { hipLaunchKernelGGL(k_scatter16_paired<1>, dim3(nchunk), dim3(FPT), lds_p, 0, xy, key, n, B, chunk, nchunk, counts, out); });
+      if (rep == 0) check("  paired, ahead 1");
+      CK(hipMemset(out, 0xFF, n * 16));
+      timeit("flagship paired B=3050 chunk=39936 ahead 4", [&] { hipLaunchKernelGGL(k_scatter16_paired<4>, dim3(nchunk), dim3(FPT), lds_p, 0, xy, key, n, B, chunk, nchunk, counts, out); });
+      if (rep == 0) check("  paired, ahead 4");
+    }
+    if (flagship_only) return 0;
+  }
   timeit("copy 16+4 B", [&] { hipLaunchKernelGGL(k_copy, dim3(2048), dim3(256), 0, 0, xy, perm, oxy, oidx, n); });
   timeit("gather 16 B by random index", [&] { hipLaunchKernelGGL(k_gather, dim3((n + 255) / 256), dim3(256), 0, 0, xy, perm, oxy, n); });
-  std::vector<uint32_t> hkey(n), hc;
   for (uint32_t B : {1024u, 4096u, 8192u}) {
     for (size_t i = 0; i < n; i++) hkey[i] = rng() % B;
     CK(hipMemcpy(key, hkey.data(), n * 4, hipMemcpyHostToDevice));

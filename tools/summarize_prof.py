@@ -20,7 +20,7 @@ from collections import defaultdict
 PHASE_OF = {
     "k_bounds": "bounds", "k_bounds_final": "bounds",
     # grid build by partition (round 2) / by sort (fallback for huge grids)
-    "k_part_hist": "part_hist", "k_part_scatter": "part_scatter", "k_part_fine": "part_fine",
+    "k_part_hist": "part_hist", "k_part_scatter": "part_scatter", "k_part_scatter_pairs": "part_scatter", "k_part_fine": "part_fine",
     "k_cell_key": "cell_key", "rocprim_radix_sort": "cell_sort", "k_tile_marks": "cell_scan",
     "k_cellstart_tiles": "cell_scan", "k_gather": "scatter",
     # the small scans (chunk counts, work lists, seed ranks) are spread over three phases: listed, not attributed

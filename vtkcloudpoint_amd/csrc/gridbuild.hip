@@ -12,7 +12,9 @@
 //   (scan)          exclusive scan of counts in bucket-major order = where each chunk's share of each bucket starts
 //   k_part_scatter  per chunk: the scanned counts become per-bucket cursors in LDS; one returning LDS atomic per point
 //                   gives the slot of its record in the bucket-major record array -- each chunk owns a contiguous run
-//                   per bucket, so partial lines are completed in the writing XCD's L2
+//                   per bucket, so partial lines are completed in the writing XCD's L2.  Where 24 bytes per bucket fit the
+//                   LDS (up to 6826 buckets) k_part_scatter_pairs does this pass: the two records of a 32-byte sector
+//                   wait for each other in LDS and are stored together, which halves the write requests
 //   (k_part_split)  grids of more than 8192 buckets (very sparse: C5's 1.4 G cells): the coarse passes run on
 //                   super-buckets of up to 32 buckets and this pass splits each into its buckets, cursors in LDS
 //   k_part_fine     one workgroup per bucket: count the bucket's records per cell in LDS, scan, store the bucket's
@@ -75,13 +77,17 @@ __device__ __forceinline__ uint32_t rec_cell(const Rec& r, const GridP& g, uint3
 
 // caller-order point i -> its binary32 relative coordinates and cell
 template <int GD>
-__device__ __forceinline__ uint32_t point_cell(const double* __restrict__ c, int64_t i, int stride, const GridP& g, float* qf) {
-  double q[3];
+__device__ __forceinline__ uint32_t coords_cell(const double* q, const GridP& g, float* qf) {
   int cc[3];
-  load_in<GD>(c, i, stride, q);
 #pragma unroll
   for (int a = 0; a < GD; a++) qf[a] = rel32(q[a], g.mn[a], g.scale);
   return cell_of32<GD>(qf, g, cc);
+}
+template <int GD>
+__device__ __forceinline__ uint32_t point_cell(const double* __restrict__ c, int64_t i, int stride, const GridP& g, float* qf) {
+  double q[3];
+  load_in<GD>(c, i, stride, q);
+  return coords_cell<GD>(q, g, qf);
 }
 
 struct PartGeom {
@@ -174,6 +180,98 @@ __global__ __launch_bounds__(PT) void k_part_scatter(const double* __restrict__ 
     float qf[3];
     const uint32_t cell = point_cell<GD>(c, i, stride, g, qf);
     rec[atomicAdd(&h[cell >> csh], 1u)] = rec_make<GD>(qf, (uint32_t)i, cell);
+  }
+}
+
+// k_part_scatter with a PAIRING STASH.  A record is 16 bytes and memory is written in 32-byte sectors; in the kernel above
+// the two records of a sector leave a workgroup about 24 trips (~100 us) apart -- a (bucket, chunk) run is ~13 records on
+// the 10 M-point cloud, 3043 open buckets per workgroup -- and L2 has evicted the first half long before the second
+// arrives: WRITE_SIZE was 32 bytes per record, every record its own write request.  Here the two meet in time.  The
+// record array starts on a 32-byte boundary (build() checks it), so a record's SLOT PARITY is its half of the sector.
+// Per bucket LDS holds, beside the cursor, the last even-slot record whose partner has not come yet (stash, 16 B) and
+// that record's slot (stash_slot): 24 bytes per bucket.  Every trip of the chunk loop:
+//   a  make the record, take its slot from the cursor                                      | barrier
+//   c  odd slot: if the stash holds slot - 1, the partner came in an earlier trip -- store both, back to back
+//   d  even slot: if the cursor has passed slot + 1 the partner came in THIS trip and stores its half in the same
+//      instruction window (what L2 is seen to combine in k_out_scatter) -- store; otherwise this record is the last of
+//      its bucket so far (one such lane per bucket and trip) and is kept for f                    | barrier
+//   f  the kept records go to the stash
+// and after the loop the stashed records nobody consumed (the chunk's run ends on an even slot) are stored.  Both
+// barriers sit in uniform control flow: the trip count comes from the chunk bounds, a left-out point of a grouped call
+// is a predicate, not a `continue`.  The next trip's coordinates are loaded before this trip's barriers.
+// Measured (profiles/part_pairs_rocprof.md): the 10 M-point benchmark 150 -> 97 us, WRITE_SIZE 3.19e8 -> 1.88e8 B;
+// tools/micro/part_bench.hip at that shape 0.202 -> 0.114 ms, 3.19e8 -> 1.84e8 B.
+constexpr size_t PAIR_LDS = sizeof(Rec) + 8;  // bytes per bucket
+constexpr size_t LDS_CU = 160 * 1024;         // what one workgroup can have (vcp_launch_ok)
+
+template <int GD, bool GROUPED>
+__global__ __launch_bounds__(PT) void k_part_scatter_pairs(const double* __restrict__ c, int64_t n, int stride, GridP g,
+                                                          const int32_t* __restrict__ group, int glo, int ghi, uint32_t csh,
+                                                          uint32_t B, uint32_t chunk, uint32_t nchunk,
+                                                          const uint32_t* __restrict__ base, Rec* __restrict__ rec,
+                                                          uint32_t* __restrict__ pos) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  Rec* stash = reinterpret_cast<Rec*>(lds);                     // [B]
+  uint32_t* h = reinterpret_cast<uint32_t*>(stash + B);         // [B] cursors
+  uint32_t* stash_slot = h + B;                                 // [B] slot of the stashed record, NONE = nothing stashed
+  for (uint32_t k = threadIdx.x; k < B; k += PT) {
+    h[k] = base[(size_t)k * nchunk + blockIdx.x];
+    stash_slot[k] = NONE;
+  }
+  __syncthreads();
+  const int64_t first = (int64_t)blockIdx.x * chunk;
+  const int64_t last = min(first + (int64_t)chunk, n);
+  const uint32_t trips = first < last ? (uint32_t)((last - first + PT - 1) / PT) : 0u;  // the same for every lane
+  double nq[3] = {0.0, 0.0, 0.0};
+  bool ntake = false;
+  auto fetch = [&](int64_t i) {  // point i of the next trip: in the chunk, part of this call, its coordinates
+    ntake = i < last;
+    if (GROUPED && ntake) {
+      const int gg = group[i];
+      if (gg < glo || gg >= ghi) {
+        if (pos) pos[i] = NONE;  // left out of this call
+        ntake = false;
+      }
+    }
+    if (ntake) load_in<GD>(c, i, stride, nq);
+  };
+  fetch(first + threadIdx.x);
+  for (uint32_t t = 0; t < trips; t++) {
+    const int64_t i = first + (int64_t)t * PT + threadIdx.x;
+    const bool take = ntake;
+    const double q[3] = {nq[0], nq[1], nq[2]};
+    fetch(i + PT);
+    Rec r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint32_t b = 0, slot = 0;
+    if (take) {
+      float qf[3];
+      const uint32_t cell = coords_cell<GD>(q, g, qf);
+      r = rec_make<GD>(qf, (uint32_t)i, cell);
+      b = cell >> csh;
+      slot = atomicAdd(&h[b], 1u);
+    }
+    __syncthreads();
+    bool keep = false;
+    if (take) {
+      if (slot & 1u) {
+        if (stash_slot[b] == slot - 1u) rec[slot - 1u] = stash[b];
+        rec[slot] = r;
+      } else if (h[b] > slot + 1u) {
+        rec[slot] = r;
+      } else {
+        keep = true;
+      }
+    }
+    __syncthreads();
+    if (keep) {
+      stash[b] = r;
+      stash_slot[b] = slot;
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < B; k += PT) {
+    const uint32_t s = stash_slot[k];
+    if (s != NONE && h[k] == s + 1u) rec[s] = stash[k];
   }
 }
 
@@ -801,8 +899,19 @@ int build(vcp_ctx* ctx, const GridBuildArgs& a) {
                   a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, qcount, a.ctcount);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, counts, counts, (int64_t)nc, total));
   vcp_phase(ctx, "part_scatter");
-  VCP_LAUNCH(ctx, (k_part_scatter<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_h, st, a.d_coords, a.n, a.stride, a.g,
-                  a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, rec, a.pos);
+  // with the pairing stash where it fits the CU's LDS (up to 6826 super-buckets; VCP_PART_PAIRS=0: test switch, never)
+  static const bool pairs_on = env_int("VCP_PART_PAIRS", 1, 0, 1) != 0;
+  const size_t lds_p = (size_t)pg.NS * PAIR_LDS;
+  if (pairs_on && lds_p <= LDS_CU) {
+    if (reinterpret_cast<uintptr_t>(rec) & 31u)  // slot parity = sector parity rests on this (hipMalloc: 256 bytes)
+      return vcp_fail(ctx, VCP_ERR_HIP, "the record array is not 32-byte aligned");
+    VCP_TRY(allow_lds(ctx, k_part_scatter_pairs<GD, GROUPED>, lds_p));
+    VCP_LAUNCH(ctx, (k_part_scatter_pairs<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_p, st, a.d_coords, a.n, a.stride,
+                    a.g, a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, rec, a.pos);
+  } else {
+    VCP_LAUNCH(ctx, (k_part_scatter<GD, GROUPED>), dim3(pg.nchunk), dim3(PT), lds_h, st, a.d_coords, a.n, a.stride, a.g,
+                    a.d_group, a.glo, a.ghi, csh_a, pg.NS, pg.chunk, pg.nchunk, counts, rec, a.pos);
+  }
   const uint32_t* bstart = counts;
   uint32_t bstride = pg.nchunk;
   if (pg.a > 0) {
