@@ -1138,6 +1138,7 @@ int vcp_blocks_build(vcp_ctx* ctx, BlocksState* s, uint32_t S_lo, uint32_t S_hi,
       return v < 0 ? 0 : v > (int)VCP_BRUTE_MAX ? (int)VCP_BRUTE_MAX : v;
     }();
     s->brute_thr = (uint32_t)brute_env;
+    if (vcp_trace_on()) vcp_trace_line("blocks partition brute_thr=%u", s->brute_thr);
     if (s->brute_thr) VCP_TRY(vcp_blocks_ens(ctx, s->grp_big, (nl + 1) * 4));
   }
   // large blocks: descriptors, slices, sub-ranges (V <= m / 128 each, at least 2) and the general kernel's list

@@ -945,6 +945,7 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
   VCP_TRY(ens(ctx, s->newlab, (size_t)(m + 1) * 4));
   int32_t* newlab = s->newlab.as<int32_t>();
   bool by_sort = force_sort || getenv("VCP_BLOCKS_ORDER_SORT") != nullptr;  // (the variable: test switch)
+  if (vcp_trace_on()) vcp_trace_line("blocks order by_sort=%d", (int)by_sort);
   for (;;) {
     if (m > 0 && !by_sort) {
       VCP_LAUNCH(ctx, k_block_order, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize, order,
@@ -1027,6 +1028,7 @@ int finish_zero(vcp_ctx* ctx, bool sharded, int zero_last, bool* again) {
   B.r2 = 2.0 * s->eps * (1.0 + 1.0 / 1099511627776.0);
   static const bool band_off = getenv("VCP_NOISE_ALL") != nullptr;  // test switch: the whole zero list
   B.all_active = (s->d_key != s->d_motor || !(s->eps >= 0.0) || !std::isfinite(B.r2) || band_off) ? 1 : 0;
+  if (vcp_trace_on()) vcp_trace_line("blocks noise all_active=%d", (int)B.all_active);
   VCP_LAUNCH(ctx, k_zero_flag, dim3(vcp_blocks(m, BT)), dim3(BT), 0, st, newlab, order, m, zcnt, zcnt + nw + 2,
                   s->f_local, s->motor_bm.as<double>(), s->blk_t.as<uint32_t>(), B, acnt, acnt + nw + 2);
   VCP_TRY(vcp_exclusive_scan_u32(ctx, zcnt, zcnt, nw + 1, dmisc + 3));

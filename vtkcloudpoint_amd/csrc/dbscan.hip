@@ -1524,6 +1524,12 @@ unsigned list_perblk(int64_t n) {
 //   VCP_CORE_GLOBAL    grouped calls count through k_core instead of k_core_lds
 //   VCP_JOIN_ALL=0|1   whether every expanding point joins along its list (k_flatten0<2>) or only the roots, instead of
 //                      the choice by points per cell
+// (gridbuild.hip has VCP_PART_PAIRS, the block pipeline VCP_BRUTE_MAX, VCP_NOISE_ALL and VCP_BLOCKS_ORDER_SORT.)
+//   VCP_TRACE          no switch: changes neither result nor path.  Every kernel launch and every decision of the host
+//                      driver below goes to stderr as a `vcp-trace ...` line (vcp_ctx.hpp): run_dbscan writes the values
+//                      its stages choose by -- n, ncells, NB, core_cap, the screen, join_all, dense, part_out -- and the
+//                      two early outs name themselves.  tests/test_engine_paths_gpu.py holds every path to the CPU
+//                      oracle and reads from these lines that the path it means is the path that ran.
 struct Switches {
   int64_t cells_per_point;
   bool screen_off, lists_off, core_global;
@@ -1588,6 +1594,7 @@ struct Call {
   bool flags_set = false, part_out = false;
   ExactSrc xs{nullptr, nullptr, 0};   // stage_grid_build
   NbrOut no{nullptr, nullptr, 0, 0};  // stage_core
+  bool join_all = false, dense = false;  // stage_union: k_flatten0<2> instead of <1> (lists only); the chunk summary
 };
 void call_derive(Call& c) {
   const DbscanExt* ext = c.ext;
@@ -1759,6 +1766,7 @@ double box_measure(const double* h) {
 int run_all_pairs(vcp_ctx* ctx, const Call& c) {
   hipStream_t st = ctx->stream;
   const int64_t n = c.n;
+  if (vcp_trace_on()) vcp_trace_line("dbscan all_pairs n=%lld metric=%d min_pts=%d", (long long)n, c.metric, c.min_pts);
   vcp_phase(ctx, "all_pairs");
   VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, (size_t)(n + 2) * 4));
   uint32_t* f = ctx->b_seedflag.as<uint32_t>();
@@ -1950,7 +1958,7 @@ int stage_core(vcp_ctx* ctx, Call& c, const Workspace& ws, const Switches& sw) {
 
 // 6. components of the expanding points
 template <int GD, int METRIC, bool GROUPED>
-int stage_union(vcp_ctx* ctx, const Call& c, const Workspace& ws, const Switches& sw) {
+int stage_union(vcp_ctx* ctx, Call& c, const Workspace& ws, const Switches& sw) {
   hipStream_t st = ctx->stream;
   const int64_t n = c.n;
   const unsigned nb = c.nb, nbl = ws.nbl;
@@ -1961,7 +1969,7 @@ int stage_union(vcp_ctx* ctx, const Call& c, const Workspace& ws, const Switches
   const bool pre = GD == 2 || no.NB > 0;  // with lists the forest costs no search, so it pays in 3-D too
   if (no.NB > 0) {
     VCP_LAUNCH(ctx, k_union_init_list, dim3(nbl), dim3(TPB), 0, st, ws.flags, ws.parent, no, ws.wlE);
-    const bool all = sw.join_all >= 0 ? sw.join_all != 0 : (uint64_t)n >= (uint64_t)g.ncells;
+    const bool all = c.join_all = sw.join_all >= 0 ? sw.join_all != 0 : (uint64_t)n >= (uint64_t)g.ncells;
     if (all) VCP_LAUNCH(ctx, k_flatten0<2>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
     else VCP_LAUNCH(ctx, k_flatten0<1>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
     VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
@@ -1970,7 +1978,7 @@ int stage_union(vcp_ctx* ctx, const Call& c, const Workspace& ws, const Switches
                     ws.flags, ws.parent, ws.wlE, ws.sorted32, c.sc);
     VCP_LAUNCH(ctx, k_flatten0<0>, dim3(nbl), dim3(TPB), 0, st, ws.parent, ws.wlE, ws.flags, no);
   }
-  const bool dense = pre && (uint64_t)n > (uint64_t)DENSE_PER_CELL * g.ncells;
+  const bool dense = c.dense = pre && (uint64_t)n > (uint64_t)DENSE_PER_CELL * g.ncells;
   if (dense) {
     VCP_TRY(vcp_ensure(ctx, ctx->b_aux0, ((size_t)nb * (TPB / 64) + 2) * 4));  // one word per wave of k_chunkroot
     uint32_t* chunkroot = ctx->b_aux0.as<uint32_t>();
@@ -2118,6 +2126,13 @@ int run_dbscan(vcp_ctx* ctx, Call& c) {
   VCP_TRY(stage_grid_build(ctx, c, ws));
   VCP_TRY((stage_core<GD, METRIC, GROUPED>(ctx, c, ws, sw)));
   VCP_TRY((stage_union<GD, METRIC, GROUPED>(ctx, c, ws, sw)));
+  if (vcp_trace_on())  // what the stages above and below choose by
+    vcp_trace_line("dbscan n=%lld gd=%d metric=%d grouped=%d slab=%d ncells=%u D=%d,%d,%d cellw=%.9g NB=%d core_cap=%d "
+                   "screen=%d sc.lo=%.9g sc.hi=%.9g join_all=%d dense=%d part_out=%d min_pts=%d in_classed=%d",
+                   (long long)c.n, GD, METRIC, (int)GROUPED, (int)c.slab, c.g.ncells, c.g.D[0], c.g.D[1], c.g.D[2],
+                   1.0 / (c.g.inv_h * c.g.scale), c.no.NB,
+                   c.no.core_cap, (int)(c.sc.lo >= 0.0f || c.sc.hi < INFINITY), (double)c.sc.lo, (double)c.sc.hi,
+                   (int)c.join_all, (int)c.dense, (int)c.part_out, c.min_pts, (int)(c.d_in_classed != nullptr));
   VCP_TRY(stage_flatten_number<GROUPED>(ctx, c, ws));
   if (!GROUPED && c.slab) return VCP_OK;  // staged call: handed over, vcp_slab_finish does the rest
   VCP_TRY((stage_border<GD, METRIC, GROUPED>(ctx, c, ws)));
@@ -2164,6 +2179,7 @@ int run_slab_finish(vcp_ctx* ctx, const SlabState& ss, const uint32_t* d_map_rep
 int run_degenerate(vcp_ctx* ctx, const Call& c) {
   hipStream_t st = ctx->stream;
   const int64_t n = c.n;
+  if (vcp_trace_on()) vcp_trace_line("dbscan degenerate n=%lld metric=%d min_pts=%d", (long long)n, c.metric, c.min_pts);
   vcp_phase(ctx, "degenerate");
   VCP_TRY(vcp_ensure(ctx, ctx->b_seedflag, (size_t)(n + 2) * 4));
   VCP_TRY(vcp_ensure(ctx, ctx->b_misc, 64));

@@ -902,6 +902,9 @@ int build(vcp_ctx* ctx, const GridBuildArgs& a) {
   // with the pairing stash where it fits the CU's LDS (up to 6826 super-buckets; VCP_PART_PAIRS=0: test switch, never)
   static const bool pairs_on = env_int("VCP_PART_PAIRS", 1, 0, 1) != 0;
   const size_t lds_p = (size_t)pg.NS * PAIR_LDS;
+  if (vcp_trace_on())
+    vcp_trace_line("gridbuild scatter pairs_on=%d NS=%u lds_p=%zu stash=%d", (int)pairs_on, (unsigned)pg.NS, lds_p,
+                   (int)(pairs_on && lds_p <= LDS_CU));
   if (pairs_on && lds_p <= LDS_CU) {
     if (reinterpret_cast<uintptr_t>(rec) & 31u)  // slot parity = sector parity rests on this (hipMalloc: 256 bytes)
       return vcp_fail(ctx, VCP_ERR_HIP, "the record array is not 32-byte aligned");

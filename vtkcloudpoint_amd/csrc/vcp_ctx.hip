@@ -1,5 +1,9 @@
 // vcp_ctx.hip -- context lifetime, workspace, per-phase hipEvent timing and the u32 scan used
 // by the grid build and the canonical cluster numbering.
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 #include "vcp_ctx.hpp"
@@ -14,6 +18,56 @@ int vcp_fail(vcp_ctx* ctx, int code, const char* fmt, ...) {
   va_end(ap);
   if (ctx) ctx->err = buf; else g_create_err = buf;
   return code;
+}
+
+// ---- trace (vcp_ctx.hpp) ------------------------------------------------------------------------------------------------
+bool vcp_trace_on() {
+  static const bool on = [] {
+    const char* e = getenv("VCP_TRACE");
+    return e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
+  }();
+  return on;
+}
+
+// one write(2) per line: stderr's own buffering (and Python's, in the same process) never splits or reorders a line
+static void trace_write(const char* buf, size_t len) {
+  while (len > 0) {
+    const ssize_t w = write(2, buf, len);
+    if (w <= 0) return;
+    buf += w;
+    len -= (size_t)w;
+  }
+}
+
+void vcp_trace_launch(const char* kernel) {
+  char buf[512];
+  size_t k = (size_t)snprintf(buf, sizeof(buf), "vcp-trace launch ");
+  bool gap = false;  // whitespace seen since the last character written: runs collapse to one blank, the ends to none
+  const size_t k0 = k;
+  for (const char* c = kernel; *c && k + 2 < sizeof(buf); c++) {
+    if (*c == ' ' || *c == '\t' || *c == '\n') {
+      gap = true;
+      continue;
+    }
+    if (gap && k > k0) buf[k++] = ' ';
+    gap = false;
+    buf[k++] = *c;
+  }
+  buf[k++] = '\n';
+  trace_write(buf, k);
+}
+
+void vcp_trace_line(const char* fmt, ...) {
+  char buf[1024];
+  size_t k = (size_t)snprintf(buf, sizeof(buf), "vcp-trace ");
+  va_list ap;
+  va_start(ap, fmt);
+  const int w = vsnprintf(buf + k, sizeof(buf) - k - 1, fmt, ap);
+  va_end(ap);
+  if (w < 0) return;
+  k = std::min(k + (size_t)w, sizeof(buf) - 2);
+  buf[k++] = '\n';
+  trace_write(buf, k);
 }
 
 int vcp_bind(vcp_ctx* ctx) {

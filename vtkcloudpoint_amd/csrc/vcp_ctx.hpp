@@ -134,6 +134,16 @@ static_assert(vcp_launch_ok(dim3(1), dim3(64), 163840) && !vcp_launch_ok(dim3(1)
 static_assert(!vcp_launch_ok(dim3(0), dim3(64), 0) && !vcp_launch_ok(dim3(1, 1, 0), dim3(64), 0) &&
                   !vcp_launch_ok(dim3(1), dim3(64, 0), 0));
 
+// The launch and decision trace (VCP_TRACE set to anything but empty or 0; read once per process; off by default).  When it
+// is on, every VCP_LAUNCH writes `vcp-trace launch <kernel>` to stderr before the launch -- <kernel> is the macro's kernel
+// argument as written, whitespace collapsed, e.g. `k_flatten0<2>` or `(k_union<GD, METRIC, GROUPED, true, true>)` -- and
+// the host drivers write one `vcp-trace <what> key=value ...` line where they choose between paths (vcp_trace_line).
+// Each line is ONE unbuffered write, so it interleaves cleanly with whatever else the process writes there.  The tests
+// (tests/test_engine_paths_gpu.py) read the path a call took from these lines.
+bool vcp_trace_on();
+void vcp_trace_launch(const char* kernel);
+void vcp_trace_line(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+
 // Launches `kernel` (grid, block, dynamic LDS bytes, stream, arguments) in a function that returns a vcp status: a
 // dispatch that vcp_launch_ok refuses is VCP_ERR_TOO_LARGE before anything is enqueued, a launch error VCP_ERR_HIP, both
 // naming the kernel.  grid, block and lds are evaluated once; a templated kernel stays in parentheses.
@@ -144,6 +154,7 @@ static_assert(!vcp_launch_ok(dim3(0), dim3(64), 0) && !vcp_launch_ok(dim3(1, 1, 
     if (!vcp_launch_ok(g__, b__, l__))                                                                                 \
       return vcp_fail((ctx), VCP_ERR_TOO_LARGE, "%s: grid %ux%ux%u, block %ux%ux%u, lds %zu", #kernel, g__.x, g__.y,   \
                       g__.z, b__.x, b__.y, b__.z, l__);                                                                \
+    if (__builtin_expect(vcp_trace_on(), 0)) vcp_trace_launch(#kernel);                                                \
     hipLaunchKernelGGL(kernel, g__, b__, l__, stream, __VA_ARGS__);                                                    \
     const hipError_t e__ = hipGetLastError();                                                                          \
     if (e__ != hipSuccess) return vcp_fail((ctx), VCP_ERR_HIP, "%s: %s", #kernel, hipGetErrorString(e__));             \
