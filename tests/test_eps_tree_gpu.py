@@ -50,12 +50,13 @@ def test_identical_points(vcp_ctx):
     for metric in METRICS:
         g, _ = _check(vcp_ctx, np.full((5, _dim(metric)), 1.25), 3, 0.5, metric)   # every key ties but for the indices
         assert g["merge_a"].tolist() == [0] * 4 and g["merge_b"].tolist() == [1, 2, 3, 4]
-    # 3000 in one cell: the heavy kernels, 47 chunks of the one cell.  The walk accepts (0, 1), (0, 2), ... first: a star on index 0
-    n = 3000
-    star = dict(kdist=np.zeros(n), reach=np.zeros(n), n_merge=n - 1, merge_w=np.zeros(n - 1),
-                merge_a=np.zeros(n - 1, np.int32), merge_b=np.arange(1, n, dtype=np.int32), n_p=n)
-    for metric in (N.L1_2D, N.L2_3D):
-        _check(vcp_ctx, np.full((n, _dim(metric)), -7.5), 7, 0.125, metric, ref=star)
+    # 3000 in one cell: the heavy kernels, 47 chunks of the one cell.  The walk accepts (0, 1), (0, 2), ... first: a star on index 0.
+    # 591 = 9 * 64 + 15 and 592 = 9 * 64 + 16: the last chunk on either side of DENSE_CHUNK (the wave per slot, a lane per slot)
+    for n in (3000, 591, 592):
+        star = dict(kdist=np.zeros(n), reach=np.zeros(n), n_merge=n - 1, merge_w=np.zeros(n - 1),
+                    merge_a=np.zeros(n - 1, np.int32), merge_b=np.arange(1, n, dtype=np.int32), n_p=n)
+        for metric in (N.L1_2D, N.L2_3D):
+            _check(vcp_ctx, np.full((n, _dim(metric)), -7.5), 7, 0.125, metric, ref=star)
 
 
 def test_a_sparse_cell_beside_a_dense_one(vcp_ctx):

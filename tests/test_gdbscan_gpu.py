@@ -79,16 +79,17 @@ def test_identical_points(vcp_ctx):
         g, _ = _check(vcp_ctx, np.full((5, _dim(metric)), 1.25), 0.5, 5, metric)
         assert g["labels"].tolist() == [1] * 5 and g["wsum"].tolist() == [5] * 5
         _check(vcp_ctx, np.full((5, _dim(metric)), 1.25), 0.0, 6, metric)
-    # 3000 in one cell: the heavy kernels, 47 chunks of the one cell; every W is the total weight
-    n = 3000
-    w = (np.arange(n) % 4).astype(np.int32)
-    total = int(w.sum())
-    ref = dict(labels=np.ones(n, np.int32), is_core=np.ones(n, np.uint8), wsum=np.full(n, total, np.int64), cf=1)
-    none = dict(labels=np.zeros(n, np.int32), is_core=np.zeros(n, np.uint8), wsum=np.full(n, total, np.int64), cf=0)
-    for metric in (N.L1_2D, N.L2_3D):
-        c = np.full((n, _dim(metric)), -7.5)
-        _check(vcp_ctx, c, 0.125, total, metric, weights=w, ref=ref)
-        _check(vcp_ctx, c, 0.125, total + 1, metric, weights=w, ref=none)
+    # 3000 in one cell: the heavy kernels, 47 chunks of the one cell; every W is the total weight.  591 = 9 * 64 + 15 and
+    # 592 = 9 * 64 + 16: the last chunk on either side of DENSE_CHUNK (the wave per slot, a lane per slot)
+    for n in (3000, 591, 592):
+        w = (np.arange(n) % 4).astype(np.int32)
+        total = int(w.sum())
+        ref = dict(labels=np.ones(n, np.int32), is_core=np.ones(n, np.uint8), wsum=np.full(n, total, np.int64), cf=1)
+        none = dict(labels=np.zeros(n, np.int32), is_core=np.zeros(n, np.uint8), wsum=np.full(n, total, np.int64), cf=0)
+        for metric in (N.L1_2D, N.L2_3D):
+            c = np.full((n, _dim(metric)), -7.5)
+            _check(vcp_ctx, c, 0.125, total, metric, weights=w, ref=ref)
+            _check(vcp_ctx, c, 0.125, total + 1, metric, weights=w, ref=none)
 
 
 def test_a_sparse_cell_beside_a_dense_one(vcp_ctx):

@@ -1,9 +1,9 @@
 // regp_host_emulation.cpp -- runs the SOURCE of k_regp_search and k_regs_search (csrc/register.hip, copied into kernels.inc by
-// tools/regp_host_emulation.py) on the host: 256 real threads per workgroup, one workgroup after the other, with
+// tools/regp_host_emulation.py behind the grid, cell and row-range functions of csrc/epsgrid.hpp) on the host: 256 real threads per workgroup, one workgroup after the other, with
 // __syncthreads / __syncthreads_or / __ballot / __shfl built from std::barrier and the atomics from the compiler's
 // builtins.  It checks the queue, the barriers and the winner's word of the fused kernel where no GPU is at hand, and can
 // be built with -fsanitize=address,undefined.  The base table, the sorted lengths and the target grid are built here the
-// way k_regp_bases, the host code and mugrid.hpp build them.
+// way k_regp_bases, the host code and epsgrid.hpp build them.
 #include <atomic>
 #include <barrier>
 #include <cmath>
@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <algorithm>
 using std::isfinite; using std::floor; using std::sqrt; using std::fabs;
@@ -72,7 +73,6 @@ static unsigned long long atomicMax(unsigned long long* p, unsigned long long v)
   while (o < v && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
   return o;
 }
-struct MUGrid { double x0, y0, z0, inv_h; int Dx, Dy, Dz; };
 namespace mtc {
 inline void transform(const double* M, double c0, double c1, double c2, double m[3]) {
   for (int r = 0; r < 3; r++) m[r] = c0 * M[4 * r] + c1 * M[4 * r + 1] + c2 * M[4 * r + 2] + M[4 * r + 3];
@@ -105,25 +105,20 @@ int main(int argc, char** argv) {
   for (int b = 0; b < nb; b++) if (tab[b] > 0.0 && tab[b] < INFINITY) ord.push_back(b);
   std::sort(ord.begin(), ord.end(), [&](int x, int y) { return tab[x] < tab[y] || (tab[x] == tab[y] && x < y); });
   std::vector<double> sL; for (int b : ord) sL.push_back(tab[b]);
-  // the grid as k_mu_cell / k_mu_fill leave it (finite targets only; h = 0: one cell)
-  MUGrid g{0, 0, 0, 0.0, 1, 1, 1};
+  // the grid as eg_bin leaves it (finite targets only; h = 0: one cell)
+  EpsGrid g{0, 0, 0, 0.0, 1, 1, 1};
   const double h = pr[2];
   if (h > 0) {
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int i = 0; i < nt; i++) for (int c = 0; c < 3; c++) if (std::isfinite(tgt[3 * i + c])) { lo[c] = std::min(lo[c], tgt[3 * i + c]); hi[c] = std::max(hi[c], tgt[3 * i + c]); }
-    g = MUGrid{lo[0], lo[1], lo[2], 1.0 / h, (int)((hi[0] - lo[0]) / h) + 1, (int)((hi[1] - lo[1]) / h) + 1, (int)((hi[2] - lo[2]) / h) + 1};
+    g = EpsGrid{lo[0], lo[1], lo[2], 1.0 / h, (int)((hi[0] - lo[0]) / h) + 1, (int)((hi[1] - lo[1]) / h) + 1, (int)((hi[2] - lo[2]) / h) + 1};
   }
   const size_t nc = (size_t)g.Dx * g.Dy * g.Dz;
   std::vector<uint32_t> cellof(nt, 0xFFFFFFFFu), cellstart(nc + 1, 0), cur(nc, 0);
   for (int i = 0; i < nt; i++) {
     const double x = tgt[3 * i], y = tgt[3 * i + 1], z = tgt[3 * i + 2];
     if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) continue;
-    uint32_t c = 0;
-    if (g.inv_h != 0.0) {
-      int cx = (int)floor((x - g.x0) * g.inv_h), cy = (int)floor((y - g.y0) * g.inv_h), cz = (int)floor((z - g.z0) * g.inv_h);
-      cx = min(max(cx, 0), g.Dx - 1); cy = min(max(cy, 0), g.Dy - 1); cz = min(max(cz, 0), g.Dz - 1);
-      c = (uint32_t)(((size_t)cz * g.Dy + cy) * g.Dx + cx);
-    }
+    const uint32_t c = eg_cell_of(g, x, y, z);
     cellof[i] = c; cellstart[c + 1]++;
   }
   for (size_t c = 0; c < nc; c++) cellstart[c + 1] += cellstart[c];

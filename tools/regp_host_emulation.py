@@ -24,10 +24,14 @@ ap.add_argument("--sanitize", action="store_true", help="build with -fsanitize=a
 ap.add_argument("--quick", action="store_true", help="leave the two larger scenes out")
 args = ap.parse_args()
 WORK = tempfile.mkdtemp(prefix="regp_emu_")
-with open(os.path.join(ROOT, "vtkcloudpoint_amd", "csrc", "register.hip")) as f:
+CSRC = os.path.join(ROOT, "vtkcloudpoint_amd", "csrc")
+with open(os.path.join(CSRC, "epsgrid.hpp")) as f:
+    grid = f.read()
+with open(os.path.join(CSRC, "register.hip")) as f:
     text = f.read()
-with open(os.path.join(WORK, "kernels.inc"), "w") as f:     # from the first struct to the end of the search kernels
-    f.write(text[text.index("struct RGScan {"):text.index("// grid (source points, bases)")])
+with open(os.path.join(WORK, "kernels.inc"), "w") as f:
+    f.write(grid[grid.index("struct EpsGrid {"):grid.index("// ---- binning")])          # the grid, its cells and row ranges
+    f.write(text[text.index("struct RGScan {"):text.index("// grid (source points, bases)")])  # the first struct .. the search kernels
 subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-pthread", "-ffp-contract=off", "-I" + WORK]
                + (["-fsanitize=address,undefined"] if args.sanitize else [])
                + [os.path.join(ROOT, "tools", "regp_host_emulation.cpp"), "-o", os.path.join(WORK, "harness")], check=True)

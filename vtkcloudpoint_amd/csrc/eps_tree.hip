@@ -11,11 +11,9 @@
 // leaving a component belongs to the forest (cut property), so every round only adds forest edges, and the only cycle the
 // picks of a round can close is two components picking the SAME edge, which is emitted once.
 //
-// Candidates come from a uniform grid over the finite points, cell edge h >= eps_max (1 + 2^-20), doubled until the grid
-// has at most 2^22 cells (mugrid.hpp's rule and argument): every metric here is >= each coordinate difference, so all of
-// E lies in the 3^dim cells around a point.  The points are put in cell order as records (x, y, z or 0, kdist) plus the
-// original index; all per-vertex state is indexed by that slot.  The order INSIDE a cell is whatever the atomics give:
-// every reader takes a minimum over the cell.
+// Candidates come from epsgrid.hpp's grid over the finite points for eps_max: all of E lies in the 3^dim cells around a
+// point.  The points are put in cell order as records (x, y, z or 0, kdist) plus the original index; all per-vertex
+// state is indexed by that slot.  Every reader takes a minimum over a cell, whatever the order inside it.
 //
 // A round, over the slots of P that are not yet interior:
 //   k_et_best   the slot scans its cells for the minimum key (w, lo, hi) among edges to another component, keeps it and
@@ -35,108 +33,37 @@
 #include <cstring>
 
 #include "bounds.hpp"
+#include "epsgrid.hpp"
 #include "sort.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
-constexpr int ET = 256;                      // threads per workgroup
-constexpr uint32_t HEAVY = 512;              // more points than this in a slot's 3^dim cells: the heavy kernels
-constexpr uint32_t DENSE_CHUNK = 16;         // a heavy chunk with fewer slots: one wave per query
-constexpr uint32_t NOCELL = 0xFFFFFFFFu;
+constexpr int ET = 256;  // threads per workgroup
 constexpr unsigned long long NOKEY = ~0ull;
 constexpr uint8_t F_P = 1, F_INTERIOR = 2, F_HEAVY = 4;
 enum { C_EMIT = 0, C_P = 1, C_HEAVY = 2, C_ERR = 3, C_WORDS = 4 };
 
-// inv_h == 0: one cell (Dx = Dy = Dz = 1)
-struct ETGrid {
-  double x0, y0, z0, inv_h;
-  int Dx, Dy, Dz;
+// the finite points: records (x, y, z or 0, kdist) and the original index; a non-finite point gets its reach here
+template <int GD>
+struct ETSrc {
+  const double* c;
+  int stride;
+  const double* kdist;
+  double* reach;  // may be null
+  double4* rec;
+  int32_t* sidx;
+  __device__ void load(int64_t i, double* q) const { load_pt<GD>(c, i, stride, q); }
+  __device__ bool in_grid(int64_t, const double* q) const { return eg_finite(q); }
+  __device__ void outside(int64_t i) const {
+    if (reach) reach[i] = NAN;
+  }
+  __device__ void store(uint32_t s, int64_t i, const double* q) const {
+    rec[s] = make_double4(q[0], q[1], q[2], kdist[i]);
+    sidx[s] = (int32_t)i;
+  }
 };
 
-// cell edge >= eps_max (1 + 2^-20), doubled until the box has at most 2^22 cells; one cell when no such edge (or its
-// reciprocal) is a finite positive number
-ETGrid et_plan(const double lo[3], const double hi[3], double eps_max) {
-  ETGrid g{lo[0], lo[1], lo[2], 0.0, 1, 1, 1};
-  const double ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-  double h = eps_max * (1.0 + 1.0 / 1048576.0);
-  if (!std::isfinite(h) || !(h > 0.0)) return g;
-  for (int it = 0; it < 2200 && std::isfinite(h); it++, h *= 2.0) {
-    const double dx = ex / h, dy = ey / h, dz = ez / h;
-    if (!((dx + 1.0) * (dy + 1.0) * (dz + 1.0) <= 4194304.0)) continue;
-    const double inv = 1.0 / h;
-    if (!std::isfinite(inv) || !(inv > 0.0)) continue;
-    g.inv_h = inv;
-    g.Dx = (int)dx + 1;
-    g.Dy = (int)dy + 1;
-    g.Dz = (int)dz + 1;
-    return g;
-  }
-  return g;
-}
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-template <int GD>
-__device__ __forceinline__ void load_pt(const double* __restrict__ c, int64_t i, int stride, double* q) {
-#pragma unroll
-  for (int a = 0; a < GD; a++) q[a] = c[i * stride + a];
-  if (GD == 2) q[2] = 0.0;
-}
-
-__device__ __forceinline__ void cell_xyz(const ETGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-  cx = cy = cz = 0;
-  if (g.inv_h == 0.0) return;
-  cx = min(max((int)floor((x - g.x0) * g.inv_h), 0), g.Dx - 1);
-  cy = min(max((int)floor((y - g.y0) * g.inv_h), 0), g.Dy - 1);
-  cz = min(max((int)floor((z - g.z0) * g.inv_h), 0), g.Dz - 1);
-}
-
-__device__ __forceinline__ uint32_t cell_of(const ETGrid& g, double x, double y, double z) {
-  int cx, cy, cz;
-  cell_xyz(g, x, y, z, cx, cy, cz);
-  return (uint32_t)(((size_t)cz * g.Dy + cy) * g.Dx + cx);
-}
-
-// cell of every finite point (NOCELL otherwise) and the population of every cell; a non-finite point gets its reach here
-template <int GD>
-__global__ __launch_bounds__(ET) void k_et_cell(const double* __restrict__ c, int64_t n, int stride, ETGrid g,
-                                                uint32_t* __restrict__ cellof, uint32_t* __restrict__ count,
-                                                double* __restrict__ reach) {
-  const int64_t i = (int64_t)blockIdx.x * ET + threadIdx.x;
-  if (i >= n) return;
-  double q[3];
-  load_pt<GD>(c, i, stride, q);
-  uint32_t cell = NOCELL;
-  if (isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2])) {
-    cell = cell_of(g, q[0], q[1], q[2]);
-    atomicAdd(&count[cell], 1u);
-  } else if (reach) {
-    reach[i] = NAN;
-  }
-  cellof[i] = cell;
-}
-
-// the finite points cell by cell: (x, y, z or 0, kdist) and the original index
-template <int GD>
-__global__ __launch_bounds__(ET) void k_et_fill(const double* __restrict__ c, int64_t n, int stride,
-                                                const double* __restrict__ kdist, const uint32_t* __restrict__ cellof,
-                                                const uint32_t* __restrict__ cellstart, uint32_t* __restrict__ cur,
-                                                double4* __restrict__ rec, int32_t* __restrict__ sidx) {
-  const int64_t i = (int64_t)blockIdx.x * ET + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t cell = cellof[i];
-  if (cell == NOCELL) return;
-  const uint32_t s = cellstart[cell] + atomicAdd(&cur[cell], 1u);
-  double q[3];
-  load_pt<GD>(c, i, stride, q);
-  rec[s] = make_double4(q[0], q[1], q[2], kdist[i]);
-  sidx[s] = (int32_t)i;
-}
-
-struct ETArgs {
-  ETGrid g;
-  const uint32_t* cellstart;
-  const double4* rec;   // [nf] cell order
+struct ETArgs : EpsCells {  // rec: [nf] records
   const int32_t* sidx;  // [nf] original index of a slot
   double eps_max;
   uint32_t nf;
@@ -155,56 +82,6 @@ struct ETArgs {
   uint32_t cap;
 };
 
-// the distance expression of vcp_kdist / vcp_dbscan (binary64, left to right, -ffp-contract=off)
-template <int METRIC>
-__device__ __forceinline__ double dist(const double4& q, const double4& r) {
-  const double dx = q.x - r.x, dy = q.y - r.y;
-  if (METRIC == VCP_L1_2D) return fabs(dx) + fabs(dy);
-  if (METRIC == VCP_L2_2D) return sqrt(dx * dx + dy * dy);
-  const double dz = q.z - r.z;
-  return sqrt(dx * dx + dy * dy + dz * dz);
-}
-
-// the rows of the 3^dim cells around q: f(first slot, one past the last) per row of cells
-template <class F>
-__device__ __forceinline__ void et_rows(const ETArgs& a, const double4& q, F&& f) {
-  const ETGrid& g = a.g;
-  int cx, cy, cz;
-  cell_xyz(g, q.x, q.y, q.z, cx, cy, cz);
-  const int xa = max(cx - 1, 0), xb = min(cx + 1, g.Dx - 1);
-  const int ya = max(cy - 1, 0), yb = min(cy + 1, g.Dy - 1);
-  const int za = max(cz - 1, 0), zb = min(cz + 1, g.Dz - 1);
-  for (int z = za; z <= zb; z++)
-    for (int y = ya; y <= yb; y++) {
-      const size_t row = ((size_t)z * g.Dy + y) * g.Dx;
-      f(a.cellstart[row + xa], a.cellstart[row + xb + 1]);
-    }
-}
-
-// The candidates of q, four at a time so that their loads are in flight together: use(t, record) for every slot t of the
-// rows that want(t) accepts; lane `off` of `step` takes every step-th candidate.
-template <class Want, class Use>
-__device__ __forceinline__ void et_walk(const ETArgs& a, const double4& q, uint32_t off, uint32_t step, Want&& want,
-                                        Use&& use) {
-  et_rows(a, q, [&](uint32_t s0, uint32_t s1) {
-    for (uint32_t t = s0 + off; t < s1; t += 4u * step) {
-      double4 r[4];
-      bool ok[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t tu = t + (uint32_t)u * step;
-        ok[u] = tu < s1 && want(tu);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (ok[u]) r[u] = a.rec[t + (uint32_t)u * step];
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (ok[u]) use(t + (uint32_t)u * step, r[u]);
-    }
-  });
-}
-
 // components, words and flags of every slot; |P| and the list of heavy chunks (<= 64 consecutive slots of one heavy cell)
 __global__ __launch_bounds__(ET) void k_et_init(ETArgs a) {
   const uint32_t s = blockIdx.x * ET + threadIdx.x;
@@ -213,26 +90,18 @@ __global__ __launch_bounds__(ET) void k_et_init(ETArgs a) {
   if (s < a.nf) {
     const double4 q = a.rec[s];
     inp = q.w <= a.eps_max;
-    uint32_t total = 0;
-    et_rows(a, q, [&](uint32_t s0, uint32_t s1) { total += s1 - s0; });
-    const bool heavy_cell = total > HEAVY;  // the same for every slot of a cell
+    const bool heavy_cell = eg_heavy_cell(a, q);
     a.flags[s] = (uint8_t)((inp ? F_P : 0) | (heavy_cell ? F_HEAVY : 0));
-    hv = heavy_cell && ((s - a.cellstart[cell_of(a.g, q.x, q.y, q.z)]) & 63u) == 0;  // first slot of a chunk
+    hv = heavy_cell && eg_chunk_first(a, q, s);
     a.comp[s] = s;
     a.par[s] = s;
     a.bw[s] = NOKEY;
     a.cw[s] = NOKEY;
     a.ce[s] = NOKEY;
   }
-  const unsigned long long bp = __ballot(inp), bh = __ballot(hv);
+  const unsigned long long bp = __ballot(inp);
   if (bp && lane == 0) atomicAdd(&a.ctr[C_P], (uint32_t)__popcll(bp));
-  if (bh) {  // wave-uniform
-    const int leader = __ffsll((long long)bh) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&a.ctr[C_HEAVY], (uint32_t)__popcll(bh));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-    if (hv) a.heavy[base + (uint32_t)__popcll(bh & ((1ull << lane) - 1ull))] = s;
-  }
+  eg_list_chunks(hv, s, a.heavy, &a.ctr[C_HEAVY]);
 }
 
 struct Best {
@@ -246,7 +115,7 @@ __device__ __forceinline__ Best et_best(const ETArgs& a, uint32_t s, const doubl
   Best b{NOKEY, NOKEY, 0u};
   const uint32_t cs = a.comp[s];
   const uint32_t qi = (uint32_t)a.sidx[s];
-  et_walk(
+  eg_walk(
       a, q, off, step, [&](uint32_t t) { return a.comp[t] != cs; },  // 4 bytes decide it for most candidates of the later rounds
       [&](uint32_t t, const double4& r) {
         if (!(r.w <= a.eps_max)) return;
@@ -289,46 +158,32 @@ __global__ __launch_bounds__(ET) void k_et_best(ETArgs a) {
     et_keep(a, s, et_best<METRIC>(a, s, a.rec[s], 0u, 1u));
 }
 
-// one past the last slot of the chunk that starts at slot s0
-__device__ __forceinline__ uint32_t chunk_end(const ETArgs& a, uint32_t s0) {
-  const double4 q = a.rec[s0];
-  return min(s0 + 64u, a.cellstart[cell_of(a.g, q.x, q.y, q.z) + 1u]);
-}
-
-// One wave per heavy chunk.  The slots of a chunk share their cell and so their candidate rows: with a lane per slot the
-// wave walks the rows in step and every load serves all its lanes.  A chunk of only a few slots (a sparse cell beside a
-// dense one) would leave most lanes idle on a long walk: there the whole wave takes one slot at a time, the candidates
-// dealt over the lanes.
 template <int METRIC>
 __global__ __launch_bounds__(64) void k_et_best_heavy(ETArgs a, uint32_t nheavy) {
-  const uint32_t lane = threadIdx.x;
-  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
-    const uint32_t s0 = a.heavy[h], s1 = chunk_end(a, s0);
-    if (s1 - s0 >= DENSE_CHUNK) {  // wave-uniform
-      const uint32_t s = s0 + lane;
-      if (s >= s1 || a.flags[s] != (F_P | F_HEAVY)) continue;
-      if (et_still_best(a, s))
-        et_keep(a, s, Best{a.bw[s], a.be[s], a.bt[s]});
-      else
-        et_keep(a, s, et_best<METRIC>(a, s, a.rec[s], 0u, 1u));
-      continue;
-    }
-    for (uint32_t s = s0; s < s1; s++) {
-      if (a.flags[s] != (F_P | F_HEAVY)) continue;  // wave-uniform
-      if (et_still_best(a, s)) {
-        if (lane == 0) et_keep(a, s, Best{a.bw[s], a.be[s], a.bt[s]});
-        continue;
-      }
-      Best b = et_best<METRIC>(a, s, a.rec[s], lane, 64u);
+  eg_heavy(
+      a, a.heavy, nheavy,
+      [&](uint32_t s) {
+        if (a.flags[s] != (F_P | F_HEAVY)) return;
+        if (et_still_best(a, s))
+          et_keep(a, s, Best{a.bw[s], a.be[s], a.bt[s]});
+        else
+          et_keep(a, s, et_best<METRIC>(a, s, a.rec[s], 0u, 1u));
+      },
+      [&](uint32_t s, uint32_t lane) {
+        if (a.flags[s] != (F_P | F_HEAVY)) return;  // wave-uniform
+        if (et_still_best(a, s)) {
+          if (lane == 0) et_keep(a, s, Best{a.bw[s], a.be[s], a.bt[s]});
+          return;
+        }
+        Best b = et_best<METRIC>(a, s, a.rec[s], lane, 64u);
 #pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long ow = __shfl_xor(b.w, d, 64), oe = __shfl_xor(b.e, d, 64);
-        const uint32_t ot = (uint32_t)__shfl_xor((int)b.t, d, 64);
-        if (ow < b.w || (ow == b.w && oe < b.e)) b = Best{ow, oe, ot};
-      }
-      if (lane == 0) et_keep(a, s, b);
-    }
-  }
+        for (int d = 1; d < 64; d <<= 1) {
+          const unsigned long long ow = __shfl_xor(b.w, d, 64), oe = __shfl_xor(b.e, d, 64);
+          const uint32_t ot = (uint32_t)__shfl_xor((int)b.t, d, 64);
+          if (ow < b.w || (ow == b.w && oe < b.e)) b = Best{ow, oe, ot};
+        }
+        if (lane == 0) et_keep(a, s, b);
+      });
 }
 
 __global__ __launch_bounds__(ET) void k_et_name(ETArgs a) {
@@ -383,7 +238,7 @@ __global__ __launch_bounds__(ET) void k_et_flat(ETArgs a) {
 template <int METRIC>
 __device__ __forceinline__ double et_reach(const ETArgs& a, const double4& q, uint32_t off, uint32_t step) {
   double best = INFINITY;
-  et_walk(
+  eg_walk(
       a, q, off, step, [](uint32_t) { return true; },
       [&](uint32_t, const double4& r) {
         if (!(r.w <= a.eps_max)) return;
@@ -403,21 +258,14 @@ __global__ __launch_bounds__(ET) void k_et_reach(ETArgs a, double* __restrict__ 
 
 template <int METRIC>
 __global__ __launch_bounds__(64) void k_et_reach_heavy(ETArgs a, uint32_t nheavy, double* __restrict__ reach) {
-  const uint32_t lane = threadIdx.x;
-  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
-    const uint32_t s0 = a.heavy[h], s1 = chunk_end(a, s0);
-    if (s1 - s0 >= DENSE_CHUNK) {  // wave-uniform: a lane per slot
-      const uint32_t s = s0 + lane;
-      if (s < s1) reach[a.sidx[s]] = et_reach<METRIC>(a, a.rec[s], 0u, 1u);
-      continue;
-    }
-    for (uint32_t s = s0; s < s1; s++) {  // the wave per slot
-      double b = et_reach<METRIC>(a, a.rec[s], lane, 64u);
+  eg_heavy(
+      a, a.heavy, nheavy, [&](uint32_t s) { reach[a.sidx[s]] = et_reach<METRIC>(a, a.rec[s], 0u, 1u); },
+      [&](uint32_t s, uint32_t lane) {
+        double b = et_reach<METRIC>(a, a.rec[s], lane, 64u);
 #pragma unroll
-      for (int d = 1; d < 64; d <<= 1) b = fmin(b, __shfl_xor(b, d, 64));
-      if (lane == 0) reach[a.sidx[s]] = b;
-    }
-  }
+        for (int d = 1; d < 64; d <<= 1) b = fmin(b, __shfl_xor(b, d, 64));
+        if (lane == 0) reach[a.sidx[s]] = b;
+      });
 }
 
 // the sorted edges into the caller's arrays
@@ -466,7 +314,6 @@ int run_eps_tree(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, do
                  double* d_reach, int64_t* n_merge, double* d_merge_w, int32_t* d_merge_a, int32_t* d_merge_b,
                  int32_t* rounds_out) {
   hipStream_t st = ctx->stream;
-  const unsigned nb = vcp_blocks(n, ET);
 
   // 1. the grid over the finite points and the records in cell order
   vcp_phase(ctx, "epst_grid");
@@ -485,12 +332,6 @@ int run_eps_tree(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, do
   for (int t = 0; t < GD; t++)
     if (!std::isfinite(hi[t] - lo[t]))
       return vcp_fail(ctx, VCP_ERR_UNSUPPORTED, "the cloud's extent overflows binary64 (coordinate differences are infinite)");
-  const ETGrid g = et_plan(lo, hi, eps_max);
-  const size_t nc = (size_t)g.Dx * g.Dy * g.Dz;
-  const size_t cell_bytes = up16((nc + 1) * 4) + nc * 4;
-  VCP_TRY(vcp_ensure(ctx, ctx->b_et_cell, cell_bytes));
-  uint32_t* cellstart = ctx->b_et_cell.as<uint32_t>();
-  uint32_t* cur = reinterpret_cast<uint32_t*>(ctx->b_et_cell.as<char>() + up16((nc + 1) * 4));
   // per point: [rec 32 | bw 8 | be 8 | cw 8 | ce 8 | cellof 4 | sidx 4 | comp 4 | par 4 | bt 4 | heavy 4 | flags 1]
   const size_t nn = (size_t)n;
   const size_t o_bw = nn * 32, o_be = o_bw + nn * 8, o_cw = o_be + nn * 8, o_ce = o_cw + nn * 8, o_cell = o_ce + nn * 8,
@@ -506,11 +347,10 @@ int run_eps_tree(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, do
   double4* rec = reinterpret_cast<double4*>(dw);
   int32_t* sidx = reinterpret_cast<int32_t*>(dw + o_sidx);
 
-  VCP_HIP(ctx, hipMemsetAsync(cellstart, 0, cell_bytes, st));
   VCP_HIP(ctx, hipMemsetAsync(ctr, 0, 64, st));
-  VCP_LAUNCH(ctx, (k_et_cell<GD>), dim3(nb), dim3(ET), 0, st, d_coords, n, stride, g, cellof, cellstart, d_reach);
-  VCP_TRY(vcp_exclusive_scan_u32(ctx, cellstart, cellstart, (int64_t)nc + 1, nullptr));
-  VCP_LAUNCH(ctx, (k_et_fill<GD>), dim3(nb), dim3(ET), 0, st, d_coords, n, stride, d_kd, cellof, cellstart, cur, rec, sidx);
+  const EpsGrid g = eg_plan(lo, hi, eps_max);
+  const uint32_t* cellstart = nullptr;
+  VCP_TRY(eg_bin<ET>(ctx, ETSrc<GD>{d_coords, stride, d_kd, d_reach, rec, sidx}, n, g, cellof, ctx->b_et_cell, &cellstart));
 
   ETArgs a{};
   a.g = g;

@@ -11,15 +11,14 @@
 // is a translation unit of its own, in the manner of kdist.hip and eps_tree.hip, and it walks the neighbourhood three times
 // (count, union, border) where the engine walks once and keeps lists.
 //
-// Candidates come from a uniform grid over the finite points ON THE COORDINATES ONLY (aux is a filter, not an axis), cell
-// edge h >= eps (1 + 2^-20), doubled until the grid has at most 2^22 cells (eps_tree.hip's rule and argument): every metric
-// here is >= each coordinate difference, so all of N(i) lies in the 3^dim cells around i.  The points are put in cell
-// order as 32-byte records (x, y, z or 0, aux or 0) plus (weight, original index); all per-point state is indexed by that
-// slot.  The order INSIDE a cell is whatever the atomics give; nothing below depends on it: W is an integer sum, the
-// components are sets, they are numbered by their smallest ORIGINAL index and a border point takes a maximum.
+// Candidates come from epsgrid.hpp's grid over the finite points for eps, ON THE COORDINATES ONLY (aux is a filter, not an
+// axis): all of N(i) lies in the 3^dim cells around i.  The points are put in cell order as 32-byte records (x, y, z or
+// 0, aux or 0) plus (weight, original index); all per-point state is indexed by that slot.  Nothing below depends on the
+// order inside a cell: W is an integer sum, the components are sets, they are numbered by their smallest ORIGINAL index
+// and a border point takes a maximum.
 //
 //   k_gd_weights   any weight < 0 raises a counter word, read back with the bounds: nothing else has run by then
-//   k_gd_cell, scan, k_gd_fill, k_gd_init   the grid, the records, the per-slot state, the list of heavy chunks
+//   eg_bin (k_eg_cell, scan, k_eg_fill), k_gd_init   the grid, the records, the per-slot state, the list of heavy chunks
 //   k_gd_count     W and the core flag of every slot (stops at min_weight when the caller does not want W)
 //   k_gd_union     every core slot hooks itself to the core slots of its N with a smaller slot number: the larger root
 //                  under the smaller by compare-and-swap, so par[x] <= x always and no cycle can form.  par is read with
@@ -40,66 +39,14 @@
 #include <cstring>
 
 #include "bounds.hpp"
+#include "epsgrid.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
-constexpr int GT = 256;                      // threads per workgroup
-constexpr uint32_t HEAVY = 512;              // more points than this in a slot's 3^dim cells: the heavy kernels
-constexpr uint32_t DENSE_CHUNK = 16;         // a heavy chunk with fewer slots: one wave per slot
-constexpr uint32_t NOCELL = 0xFFFFFFFFu;
+constexpr int GT = 256;  // threads per workgroup
 constexpr uint32_t NOIDX = 0xFFFFFFFFu;
 constexpr uint8_t F_CORE = 1, F_HEAVY = 2;
-enum { C_NEG = 0, C_HEAVY = 1 };             // counter words (64 bytes of them)
-
-// inv_h == 0: one cell (Dx = Dy = Dz = 1)
-struct GDGrid {
-  double x0, y0, z0, inv_h;
-  int Dx, Dy, Dz;
-};
-
-// cell edge >= eps (1 + 2^-20), doubled until the box has at most 2^22 cells; one cell when no such edge (or its
-// reciprocal) is a finite positive number
-GDGrid gd_plan(const double lo[3], const double hi[3], double eps) {
-  GDGrid g{lo[0], lo[1], lo[2], 0.0, 1, 1, 1};
-  const double ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-  double h = eps * (1.0 + 1.0 / 1048576.0);
-  if (!std::isfinite(h) || !(h > 0.0)) return g;
-  for (int it = 0; it < 2200 && std::isfinite(h); it++, h *= 2.0) {
-    const double dx = ex / h, dy = ey / h, dz = ez / h;
-    if (!((dx + 1.0) * (dy + 1.0) * (dz + 1.0) <= 4194304.0)) continue;
-    const double inv = 1.0 / h;
-    if (!std::isfinite(inv) || !(inv > 0.0)) continue;
-    g.inv_h = inv;
-    g.Dx = (int)dx + 1;
-    g.Dy = (int)dy + 1;
-    g.Dz = (int)dz + 1;
-    return g;
-  }
-  return g;
-}
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-template <int GD>
-__device__ __forceinline__ void load_pt(const double* __restrict__ c, int64_t i, int stride, double* q) {
-#pragma unroll
-  for (int a = 0; a < GD; a++) q[a] = c[i * stride + a];
-  if (GD == 2) q[2] = 0.0;
-}
-
-__device__ __forceinline__ void cell_xyz(const GDGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-  cx = cy = cz = 0;
-  if (g.inv_h == 0.0) return;
-  cx = min(max((int)floor((x - g.x0) * g.inv_h), 0), g.Dx - 1);
-  cy = min(max((int)floor((y - g.y0) * g.inv_h), 0), g.Dy - 1);
-  cz = min(max((int)floor((z - g.z0) * g.inv_h), 0), g.Dz - 1);
-}
-
-__device__ __forceinline__ uint32_t cell_of(const GDGrid& g, double x, double y, double z) {
-  int cx, cy, cz;
-  cell_xyz(g, x, y, z, cx, cy, cz);
-  return (uint32_t)(((size_t)cz * g.Dy + cy) * g.Dx + cx);
-}
+enum { C_NEG = 0, C_HEAVY = 1 };  // counter words (64 bytes of them)
 
 // a weight < 0 anywhere raises the counter word
 __global__ __launch_bounds__(GT) void k_gd_weights(const int32_t* __restrict__ w, int64_t n, uint32_t* __restrict__ ctr) {
@@ -108,49 +55,30 @@ __global__ __launch_bounds__(GT) void k_gd_weights(const int32_t* __restrict__ w
   if (__ballot(neg) && (threadIdx.x & 63) == 0) atomicOr(&ctr[C_NEG], 1u);
 }
 
-// cell of every finite row (NOCELL otherwise) and the population of every cell; with min_weight <= 0 a row outside the
-// grid is a cluster of its own: its flag for the ranking
+// the rows with finite coordinates and aux: records (x, y, z or 0, aux or 0) and (weight or 1, original index); with
+// min_weight <= 0 a row outside the grid is a cluster of its own: its flag for the ranking
 template <int GD>
-__global__ __launch_bounds__(GT) void k_gd_cell(const double* __restrict__ c, int64_t n, int stride,
-                                                const double* __restrict__ aux, GDGrid g, int alone,
-                                                uint32_t* __restrict__ cellof, uint32_t* __restrict__ count,
-                                                uint32_t* __restrict__ rank) {
-  const int64_t i = (int64_t)blockIdx.x * GT + threadIdx.x;
-  if (i >= n) return;
-  double q[3];
-  load_pt<GD>(c, i, stride, q);
-  uint32_t cell = NOCELL;
-  if (isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]) && (!aux || isfinite(aux[i]))) {
-    cell = cell_of(g, q[0], q[1], q[2]);
-    atomicAdd(&count[cell], 1u);
-  } else if (alone) {
-    rank[i] = 1u;
+struct GDSrc {
+  const double* c;
+  int stride;
+  const double* aux;  // may be null
+  const int32_t* w;   // may be null
+  int alone;
+  uint32_t* rank;
+  double4* rec;
+  int2* wi;
+  __device__ void load(int64_t i, double* q) const { load_pt<GD>(c, i, stride, q); }
+  __device__ bool in_grid(int64_t i, const double* q) const { return eg_finite(q) && (!aux || isfinite(aux[i])); }
+  __device__ void outside(int64_t i) const {
+    if (alone) rank[i] = 1u;
   }
-  cellof[i] = cell;
-}
+  __device__ void store(uint32_t s, int64_t i, const double* q) const {
+    rec[s] = make_double4(q[0], q[1], q[2], aux ? aux[i] : 0.0);
+    wi[s] = make_int2(w ? w[i] : 1, (int)i);
+  }
+};
 
-// the finite rows cell by cell: (x, y, z or 0, aux or 0) and (weight or 1, original index)
-template <int GD>
-__global__ __launch_bounds__(GT) void k_gd_fill(const double* __restrict__ c, int64_t n, int stride,
-                                                const double* __restrict__ aux, const int32_t* __restrict__ w,
-                                                const uint32_t* __restrict__ cellof,
-                                                const uint32_t* __restrict__ cellstart, uint32_t* __restrict__ cur,
-                                                double4* __restrict__ rec, int2* __restrict__ wi) {
-  const int64_t i = (int64_t)blockIdx.x * GT + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t cell = cellof[i];
-  if (cell == NOCELL) return;
-  const uint32_t s = cellstart[cell] + atomicAdd(&cur[cell], 1u);
-  double q[3];
-  load_pt<GD>(c, i, stride, q);
-  rec[s] = make_double4(q[0], q[1], q[2], aux ? aux[i] : 0.0);
-  wi[s] = make_int2(w ? w[i] : 1, (int)i);
-}
-
-struct GDArgs {
-  GDGrid g;
-  const uint32_t* cellstart;  // [nc + 1]; cellstart[nc] = the number of slots
-  const double4* rec;         // [nf] cell order
+struct GDArgs : EpsCells {     // cellstart: [nc + 1], cellstart[nc] = the number of slots nf; rec: [nf]
   const int2* wi;             // [nf] (weight, original index) of a slot
   double eps, gate;           // gate 0 without aux: the records' fourth word is 0 then
   int64_t min_weight;
@@ -174,109 +102,31 @@ struct GDArgs {
 
 __device__ __forceinline__ uint32_t gd_nf(const GDArgs& a) { return a.cellstart[a.nc]; }
 
-// the distance expression of vcp_kdist / vcp_dbscan (binary64, left to right, -ffp-contract=off)
-template <int METRIC>
-__device__ __forceinline__ double dist(const double4& q, const double4& r) {
-  const double dx = q.x - r.x, dy = q.y - r.y;
-  if (METRIC == VCP_L1_2D) return fabs(dx) + fabs(dy);
-  if (METRIC == VCP_L2_2D) return sqrt(dx * dx + dy * dy);
-  const double dz = q.z - r.z;
-  return sqrt(dx * dx + dy * dy + dz * dz);
-}
-
 template <int METRIC>
 __device__ __forceinline__ bool near(const GDArgs& a, const double4& q, const double4& r) {
   return dist<METRIC>(q, r) <= a.eps && fabs(q.w - r.w) <= a.gate;
 }
 
-// the rows of the 3^dim cells around q: f(first slot, one past the last) per row of cells
-template <class F>
-__device__ __forceinline__ void gd_rows(const GDArgs& a, const double4& q, F&& f) {
-  if (a.none) return;
-  const GDGrid& g = a.g;
-  int cx, cy, cz;
-  cell_xyz(g, q.x, q.y, q.z, cx, cy, cz);
-  const int xa = max(cx - 1, 0), xb = min(cx + 1, g.Dx - 1);
-  const int ya = max(cy - 1, 0), yb = min(cy + 1, g.Dy - 1);
-  const int za = max(cz - 1, 0), zb = min(cz + 1, g.Dz - 1);
-  for (int z = za; z <= zb; z++)
-    for (int y = ya; y <= yb; y++) {
-      const size_t row = ((size_t)z * g.Dy + y) * g.Dx;
-      f(a.cellstart[row + xa], a.cellstart[row + xb + 1]);
-    }
-}
-
-// The candidates of q, four at a time so that their loads are in flight together: use(t, record) for every slot t of the
-// rows that want(t) accepts, until use returns true; lane `off` of `step` takes every step-th candidate.
+// eg_walk; eps NaN or < 0 (a.none): nobody has a candidate
 template <class Want, class Use>
 __device__ __forceinline__ void gd_walk(const GDArgs& a, const double4& q, uint32_t off, uint32_t step, Want&& want,
                                         Use&& use) {
-  bool stop = false;
-  gd_rows(a, q, [&](uint32_t s0, uint32_t s1) {
-    for (uint32_t t = s0 + off; t < s1 && !stop; t += 4u * step) {
-      double4 r[4];
-      bool ok[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t tu = t + (uint32_t)u * step;
-        ok[u] = tu < s1 && want(tu);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (ok[u]) r[u] = a.rec[t + (uint32_t)u * step];
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (ok[u] && !stop) stop = use(t + (uint32_t)u * step, r[u]);
-    }
-  });
+  if (!a.none) eg_walk(a, q, off, step, want, use);
 }
 
 // hooks and flags of every slot; the list of heavy chunks (<= 64 consecutive slots of one heavy cell)
 __global__ __launch_bounds__(GT) void k_gd_init(GDArgs a) {
   const uint32_t s = blockIdx.x * GT + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   bool hv = false;
   if (s < gd_nf(a)) {
     const double4 q = a.rec[s];
-    uint32_t total = 0;
-    gd_rows(a, q, [&](uint32_t s0, uint32_t s1) { total += s1 - s0; });
-    const bool heavy_cell = total > HEAVY;  // the same for every slot of a cell
+    const bool heavy_cell = !a.none && eg_heavy_cell(a, q);
     a.flags[s] = heavy_cell ? F_HEAVY : 0;
-    hv = heavy_cell && ((s - a.cellstart[cell_of(a.g, q.x, q.y, q.z)]) & 63u) == 0;  // first slot of a chunk
+    hv = heavy_cell && eg_chunk_first(a, q, s);
     a.par[s] = s;
     a.minidx[s] = NOIDX;
   }
-  const unsigned long long bh = __ballot(hv);
-  if (bh) {  // wave-uniform
-    const int leader = __ffsll((long long)bh) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&a.ctr[C_HEAVY], (uint32_t)__popcll(bh));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-    if (hv) a.heavy[base + (uint32_t)__popcll(bh & ((1ull << lane) - 1ull))] = s;
-  }
-}
-
-// one past the last slot of the chunk that starts at slot s0
-__device__ __forceinline__ uint32_t chunk_end(const GDArgs& a, uint32_t s0) {
-  const double4 q = a.rec[s0];
-  return min(s0 + 64u, a.cellstart[cell_of(a.g, q.x, q.y, q.z) + 1u]);
-}
-
-// One wave per heavy chunk.  The slots of a chunk share their cell and so their candidate rows: with a lane per slot the
-// wave walks the rows in step and every load serves all its lanes (per_lane(slot)).  A chunk of only a few slots (a sparse
-// cell beside a dense one) would leave most lanes idle on a long walk: there the whole wave takes one slot at a time, the
-// candidates dealt over the lanes (per_wave(slot, lane); wave-uniform).
-template <class PerLane, class PerWave>
-__device__ __forceinline__ void gd_heavy(const GDArgs& a, PerLane&& per_lane, PerWave&& per_wave) {
-  const uint32_t lane = threadIdx.x, nheavy = a.ctr[C_HEAVY];
-  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
-    const uint32_t s0 = a.heavy[h], s1 = chunk_end(a, s0);
-    if (s1 - s0 >= DENSE_CHUNK) {
-      if (s0 + lane < s1) per_lane(s0 + lane);
-      continue;
-    }
-    for (uint32_t s = s0; s < s1; s++) per_wave(s, lane);
-  }
+  eg_list_chunks(hv, s, a.heavy, &a.ctr[C_HEAVY]);
 }
 
 // ---- count ------------------------------------------------------------------------------------------------------------
@@ -309,8 +159,8 @@ __global__ __launch_bounds__(GT) void k_gd_count(GDArgs a) {
 
 template <int METRIC>
 __global__ __launch_bounds__(64) void k_gd_count_heavy(GDArgs a) {
-  gd_heavy(
-      a, [&](uint32_t s) { gd_keep(a, s, gd_count<METRIC>(a, a.rec[s], 0u, 1u, !a.exact)); },
+  eg_heavy(
+      a, a.heavy, a.ctr[C_HEAVY], [&](uint32_t s) { gd_keep(a, s, gd_count<METRIC>(a, a.rec[s], 0u, 1u, !a.exact)); },
       [&](uint32_t s, uint32_t lane) {
         long long W = gd_count<METRIC>(a, a.rec[s], lane, 64u, false);
 #pragma unroll
@@ -376,8 +226,8 @@ __global__ __launch_bounds__(GT) void k_gd_union(GDArgs a) {
 
 template <int METRIC>
 __global__ __launch_bounds__(64) void k_gd_union_heavy(GDArgs a) {
-  gd_heavy(
-      a,
+  eg_heavy(
+      a, a.heavy, a.ctr[C_HEAVY],
       [&](uint32_t s) {
         if (a.flags[s] & F_CORE) gd_union<METRIC>(a, s, 0u, 1u);
       },
@@ -447,8 +297,8 @@ __global__ __launch_bounds__(GT) void k_gd_border(GDArgs a) {
 
 template <int METRIC>
 __global__ __launch_bounds__(64) void k_gd_border_heavy(GDArgs a) {
-  gd_heavy(
-      a,
+  eg_heavy(
+      a, a.heavy, a.ctr[C_HEAVY],
       [&](uint32_t s) {
         if (!(a.flags[s] & F_CORE)) gd_border_keep(a, s, gd_border<METRIC>(a, a.rec[s], 0u, 1u));
       },
@@ -493,12 +343,7 @@ int run_gdbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, dou
 
   // 2. the grid over the finite rows and the records in cell order
   vcp_phase(ctx, "gdb_grid");
-  const GDGrid g = gd_plan(lo, hi, eps);
-  const size_t nc = (size_t)g.Dx * g.Dy * g.Dz;
-  const size_t cell_bytes = up16((nc + 1) * 4) + nc * 4;
-  VCP_TRY(vcp_ensure(ctx, ctx->b_gd_cell, cell_bytes));
-  uint32_t* cellstart = ctx->b_gd_cell.as<uint32_t>();
-  uint32_t* cur = reinterpret_cast<uint32_t*>(ctx->b_gd_cell.as<char>() + up16((nc + 1) * 4));
+  const EpsGrid g = eg_plan(lo, hi, eps);
   // per row: [rec 32 | wi 8 | cellof 4 | par 4 | comp 4 | minidx 4 | cid 4 | heavy 4], then [rank (n + 1) * 4 | flags n]
   const size_t nn = (size_t)n;
   const size_t o_wi = nn * 32, o_cell = o_wi + nn * 8, o_par = o_cell + nn * 4, o_comp = o_par + nn * 4,
@@ -508,15 +353,17 @@ int run_gdbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, dou
   char* dw = ctx->b_gd_work.as<char>();
   uint32_t* cellof = reinterpret_cast<uint32_t*>(dw + o_cell);
 
+  double4* rec = reinterpret_cast<double4*>(dw);
+  int2* wi = reinterpret_cast<int2*>(dw + o_wi);
+
   GDArgs a{};
   a.g = g;
-  a.cellstart = cellstart;
-  a.rec = reinterpret_cast<double4*>(dw);
-  a.wi = reinterpret_cast<int2*>(dw + o_wi);
+  a.rec = rec;
+  a.wi = wi;
   a.eps = eps;
   a.gate = d_aux ? gate : 0.0;
   a.min_weight = min_weight;
-  a.nc = (uint32_t)nc;
+  a.nc = (uint32_t)((size_t)g.Dx * g.Dy * g.Dz);
   a.none = !(eps >= 0.0);
   a.weighted = d_w != nullptr;
   a.exact = d_wsum != nullptr;
@@ -533,13 +380,9 @@ int run_gdbscan(vcp_ctx* ctx, const double* d_coords, int64_t n, int stride, dou
   a.is_core = d_is_core;
   a.wsum = reinterpret_cast<long long*>(d_wsum);
 
-  VCP_HIP(ctx, hipMemsetAsync(cellstart, 0, cell_bytes, st));
   VCP_HIP(ctx, hipMemsetAsync(a.rank, 0, (nn + 1) * 4, st));
-  VCP_LAUNCH(ctx, (k_gd_cell<GD>), dim3(nb), dim3(GT), 0, st, d_coords, n, stride, d_aux, g, (int)(min_weight <= 0), cellof,
-             cellstart, a.rank);
-  VCP_TRY(vcp_exclusive_scan_u32(ctx, cellstart, cellstart, (int64_t)nc + 1, nullptr));
-  VCP_LAUNCH(ctx, (k_gd_fill<GD>), dim3(nb), dim3(GT), 0, st, d_coords, n, stride, d_aux, d_w, cellof, cellstart, cur,
-             const_cast<double4*>(a.rec), const_cast<int2*>(a.wi));
+  VCP_TRY(eg_bin<GT>(ctx, GDSrc<GD>{d_coords, stride, d_aux, d_w, (int)(min_weight <= 0), a.rank, rec, wi}, n, g, cellof,
+                     ctx->b_gd_cell, &a.cellstart));
   VCP_LAUNCH(ctx, k_gd_init, dim3(nb), dim3(GT), 0, st, a);
 
   // 3. W and the core flags

@@ -7,9 +7,8 @@
 // once.  The key order is strict and total, so the smallest remaining key is always such a pair (the rounds end) and a
 // locally dominant pair is one the walk accepts (no smaller key touches either end).
 //
-// Candidates come from a uniform 3-D grid over the finite truths, cell edge h >= max_dist (1 + 2^-20), doubled until the
-// grid has at most 2^22 cells: a centroid meets the truths of its 3 x 3 x 3 cells.  max_dist = +inf, or an h that cannot
-// be represented, is ONE cell: all pairs, slow and correct.
+// Candidates come from epsgrid.hpp's grid over the finite truths for max_dist: a centroid meets the truths of the
+// 3 x 3 x 3 cells around it.
 //
 // A round is three kernels over the list of centroids that are still free and still have a free candidate:
 //   k_mu_best    every listed centroid scans its candidates among the free truths, keeps its own minimum (d, i) and
@@ -25,11 +24,12 @@
 #include <cmath>
 #include <cstring>
 
+#include "epsgrid.hpp"
 #include "match.hpp"
-#include "mugrid.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
+constexpr int MT = 128;
 constexpr int BATCH = 8;  // rounds per host synchronisation (even: the two lists swap back)
 constexpr unsigned long long NOKEY = ~0ull;
 
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(MT) void k_mu_init(const double* __restrict__ cente
 }
 
 struct MUScan {
-  MUGrid g;
+  EpsGrid g;
   const uint32_t* cellstart;
   const double* sxyz;
   const int32_t* sidx;
@@ -77,36 +77,16 @@ struct MUScan {
 // f(i, bits of d) for every candidate edge of m to a free truth
 template <class F>
 __device__ __forceinline__ void mu_candidates(const MUScan& q, const double* m, F&& f) {
-  const MUGrid& g = q.g;
-  int xa = 0, xb = 0, ya = 0, yb = 0, za = 0, zb = 0;
-  if (g.inv_h == 0.0) {
-    if (!(isfinite(m[0]) && isfinite(m[1]) && isfinite(m[2]))) return;
-  } else {
-    const double ux = (m[0] - g.x0) * g.inv_h, uy = (m[1] - g.y0) * g.inv_h, uz = (m[2] - g.z0) * g.inv_h;
-    // more than one cell outside the truths' box (or NaN): nothing within max_dist
-    if (!(ux >= -1.0 && ux < (double)g.Dx + 1.0 && uy >= -1.0 && uy < (double)g.Dy + 1.0 && uz >= -1.0 &&
-          uz < (double)g.Dz + 1.0))
-      return;
-    const int cx = (int)floor(ux), cy = (int)floor(uy), cz = (int)floor(uz);
-    xa = max(cx - 1, 0), xb = min(cx + 1, g.Dx - 1);
-    ya = max(cy - 1, 0), yb = min(cy + 1, g.Dy - 1);
-    za = max(cz - 1, 0), zb = min(cz + 1, g.Dz - 1);
-    if (xa > xb) return;
-  }
-  for (int z = za; z <= zb; z++) {
-    for (int y = ya; y <= yb; y++) {
-      const size_t row = ((size_t)z * g.Dy + y) * g.Dx;
-      const uint32_t s0 = q.cellstart[row + xa], s1 = q.cellstart[row + xb + 1];
-      for (uint32_t s = s0; s < s1; s++) {
-        const int i = q.sidx[s];
-        if (q.center_of[i] >= 0) continue;
-        const double dx = q.sxyz[3 * (size_t)s] - m[0], dy = q.sxyz[3 * (size_t)s + 1] - m[1],
-                     dz = q.sxyz[3 * (size_t)s + 2] - m[2];
-        const double d = sqrt(dx * dx + dy * dy + dz * dz);
-        if (d < q.max_dist && d < INFINITY) f(i, (unsigned long long)__double_as_longlong(d));
-      }
+  eg_query_rows(q.g, q.cellstart, m, [&](uint32_t s0, uint32_t s1) {
+    for (uint32_t s = s0; s < s1; s++) {
+      const int i = q.sidx[s];
+      if (q.center_of[i] >= 0) continue;
+      const double dx = q.sxyz[3 * (size_t)s] - m[0], dy = q.sxyz[3 * (size_t)s + 1] - m[1],
+                   dz = q.sxyz[3 * (size_t)s + 2] - m[2];
+      const double d = sqrt(dx * dx + dy * dy + dz * dz);
+      if (d < q.max_dist && d < INFINITY) f(i, (unsigned long long)__double_as_longlong(d));
     }
-  }
+  });
 }
 
 // ctr[0] = centroids in `list`, ctr[1] = pairs this round accepts, ctr[2] = centroids in the next list
@@ -244,10 +224,10 @@ int vcp_match_unique_dev(vcp_ctx* ctx, const double* d_centers, int32_t K, const
   bool have_grid = false;
   MUScan q{};
   {
-    MUGrid g{};
+    EpsGrid g{};
     const uint32_t* cellstart = nullptr;
-    VCP_TRY(mu_build_grid(ctx, d_truths, T, max_dist, MUGridWork{cellof, sxyz, sidx, d_box, d_part, &ctx->b_mu_cell}, &g,
-                          &cellstart, &have_grid));
+    VCP_TRY(eg_build_truths<MT>(ctx, d_truths, T, max_dist,
+                                TruthGridWork{cellof, sxyz, sidx, d_box, d_part, &ctx->b_mu_cell}, &g, &cellstart, &have_grid));
     if (have_grid) q = MUScan{g, cellstart, sxyz, sidx, d_center_of, max_dist};
   }
 

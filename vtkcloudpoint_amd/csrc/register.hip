@@ -17,8 +17,8 @@
 //                  There is no global list of hypotheses and no second sweep for the tie.
 //   k_regp_final   per base: the winner's word back to (score, f, i, j), M rebuilt from them by the same function, and the
 //                  inliers over all ns source points
-// The score is an existence test over the 3 x 3 x 3 cells of mugrid.hpp's grid over the targets (cell edge >= inlier_dist
-// (1 + 2^-20)).  Only integer atomics decide anything: the result does not depend on scheduling.
+// The score is an existence test over the 3 x 3 x 3 cells of epsgrid.hpp's grid over the targets for inlier_dist.  Only
+// integer atomics decide anything: the result does not depend on scheduling.
 //
 // vcp_register_sim is the same call with a scale: a base fits a target pair when k = Lv / Lu lies in
 // [scale_min, scale_max], and the pose carries k (rg_sim_pose_of).  The search and the final kernel are one source for both
@@ -33,12 +33,13 @@
 #include <numeric>
 #include <vector>
 
+#include "epsgrid.hpp"
 #include "match.hpp"
-#include "mugrid.hpp"
 #include "vcp_ctx.hpp"
 
 namespace {
 constexpr int RT = 256;          // threads of a search / final workgroup
+constexpr int RG_GRID_WG = 128;  // threads of a workgroup of the target grid's build
 constexpr int RG_QCAP = 2 * RT;  // hypotheses the LDS queue holds: it is scored once it holds more than RG_QCAP - RT, and a
                                  // round of pushes adds at most RT
 constexpr int RG_MAX_BASES = 4096;
@@ -46,7 +47,7 @@ constexpr int RG_MAX_TARGETS = 65536;
 constexpr unsigned long long RG_LOW = (1ull << 33) - 1ull;
 
 struct RGScan {
-  MUGrid g;
+  EpsGrid g;
   const uint32_t* cellstart;  // nullptr: no grid, nothing is within inlier_dist of anything
   const double* sxyz;
   double inlier_dist;
@@ -164,35 +165,17 @@ __global__ __launch_bounds__(RT) void k_regp_bases(const double* __restrict__ sr
 
 // does some target lie closer than inlier_dist to m?  vcp_match's distance, strict comparison
 __device__ __forceinline__ bool rg_exists(const RGScan& q, const double* m) {
-  const MUGrid& g = q.g;
   if (!q.cellstart) return false;
-  int xa = 0, xb = 0, ya = 0, yb = 0, za = 0, zb = 0;
-  if (g.inv_h == 0.0) {
-    if (!(isfinite(m[0]) && isfinite(m[1]) && isfinite(m[2]))) return false;
-  } else {
-    const double ux = (m[0] - g.x0) * g.inv_h, uy = (m[1] - g.y0) * g.inv_h, uz = (m[2] - g.z0) * g.inv_h;
-    // more than one cell outside the targets' box (or NaN): nothing within inlier_dist
-    if (!(ux >= -1.0 && ux < (double)g.Dx + 1.0 && uy >= -1.0 && uy < (double)g.Dy + 1.0 && uz >= -1.0 &&
-          uz < (double)g.Dz + 1.0))
-      return false;
-    const int cx = (int)floor(ux), cy = (int)floor(uy), cz = (int)floor(uz);
-    xa = max(cx - 1, 0), xb = min(cx + 1, g.Dx - 1);
-    ya = max(cy - 1, 0), yb = min(cy + 1, g.Dy - 1);
-    za = max(cz - 1, 0), zb = min(cz + 1, g.Dz - 1);
-    if (xa > xb) return false;
-  }
-  for (int z = za; z <= zb; z++) {
-    for (int y = ya; y <= yb; y++) {
-      const size_t row = ((size_t)z * g.Dy + y) * g.Dx;
-      const uint32_t s0 = q.cellstart[row + xa], s1 = q.cellstart[row + xb + 1];
-      for (uint32_t s = s0; s < s1; s++) {
-        const double dx = q.sxyz[3 * (size_t)s] - m[0], dy = q.sxyz[3 * (size_t)s + 1] - m[1],
-                     dz = q.sxyz[3 * (size_t)s + 2] - m[2];
-        if (sqrt(dx * dx + dy * dy + dz * dz) < q.inlier_dist) return true;
-      }
+  bool found = false;
+  eg_query_rows(q.g, q.cellstart, m, [&](uint32_t s0, uint32_t s1) {
+    for (uint32_t s = s0; s < s1; s++) {
+      const double dx = q.sxyz[3 * (size_t)s] - m[0], dy = q.sxyz[3 * (size_t)s + 1] - m[1],
+                   dz = q.sxyz[3 * (size_t)s + 2] - m[2];
+      if (sqrt(dx * dx + dy * dy + dz * dz) < q.inlier_dist) return found = true;
     }
-  }
-  return false;
+    return false;
+  });
+  return found;
 }
 
 // The pose of hypothesis (b, f, i, j) from the base table; SIM: the similarity pose and its scale.
@@ -522,14 +505,14 @@ int rg_run(vcp_ctx* ctx, const double* d_src, int64_t ns, const double* d_tgt, i
   q.inlier_dist = inlier_dist;
   {
     bool have = false;
-    MUGrid g{};
+    EpsGrid g{};
     const uint32_t* cellstart = nullptr;
     double* sxyz = reinterpret_cast<double*>(dt);
-    VCP_TRY(mu_build_grid(ctx, d_tgt, (int)nt, inlier_dist,
-                          MUGridWork{reinterpret_cast<uint32_t*>(dt + t_cell), sxyz, reinterpret_cast<int32_t*>(dt + t_idx),
-                                     reinterpret_cast<double*>(dt + t_box), reinterpret_cast<double*>(dt + t_box + 64),
-                                     &ctx->b_rg_cell},
-                          &g, &cellstart, &have));
+    VCP_TRY(eg_build_truths<RG_GRID_WG>(
+        ctx, d_tgt, (int)nt, inlier_dist,
+        TruthGridWork{reinterpret_cast<uint32_t*>(dt + t_cell), sxyz, reinterpret_cast<int32_t*>(dt + t_idx),
+                      reinterpret_cast<double*>(dt + t_box), reinterpret_cast<double*>(dt + t_box + 64), &ctx->b_rg_cell},
+        &g, &cellstart, &have));
     if (have) {
       q.g = g;
       q.cellstart = cellstart;

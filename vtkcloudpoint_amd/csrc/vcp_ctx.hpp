@@ -35,7 +35,7 @@ struct vcp_ctx {
   //   [0, 1024)     the DBSCAN engine's EnginePinned: bounds, two totals, counters (dbscan.hip); the block partition's bounds (blockpart.hip);
   //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
   //                 nearest-neighbour grid's bounds (nngrid.hip); at [0, 56) the truths' bounds of vcp_match_unique
-  //                 and the targets' bounds of vcp_register_pairs (mugrid.hpp) and the cloud's of vcp_eps_tree (eps_tree.hip);
+  //                 and the targets' bounds of vcp_register_pairs (epsgrid.hpp) and the cloud's of vcp_eps_tree (eps_tree.hip);
   //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
