@@ -930,6 +930,51 @@ int vcp_match_unique_dev(vcp_ctx* ctx, const double* d_centers, int32_t K, const
 int vcp_import_convert(vcp_ctx* ctx, const double* rows, int64_t n, double x_angle, double y_angle, int xdir,
                        int ydir, int dedupe, double* xyz, uint8_t* state, int64_t* kept, int64_t* duplicates);
 
+/* -- resident import: filter, dedupe with counts, compact ---------------------------------------------
+ * vcp_import_convert writes xyz and state for EVERY row and leaves the selection to the host.  This call keeps the scan on
+ * the device: it filters, finds the duplicate classes with their sizes, and writes the kept rows densely, in input order,
+ * in the layout vcp_dbscan_dev / vcp_gdbscan_dev / vcp_centroids_dev take.  With a group number per row it is also
+ * AddFolder's fixed-point import, typpe 3 / 4 (FrmMain.cs:1069-1085), whose duplicates are searched per file and whose
+ * kept row's ptsCount goes up (:1074, :1081): the producer of vcp_centroids_weighted's group / pts_count.
+ *   row        row i is rows[3i..3i+2] = (mx, my, D).  It is filtered iff D == 0 || D > 1000, the plain comparisons of
+ *              FrmMain.cs:1011: a NaN D is not filtered.  (tx, ty, tz) = (tmpx, tmpy, tmpz) and (X, Y, Z) are
+ *              vcp_import_convert's for x_angle, y_angle, xdir, ydir: bit for bit what it writes for that row on the same
+ *              device (the same kernel).  g_i = group[i], or 0 when group == NULL; any int32 is a valid group
+ *   classes    dedupe == 0: every unfiltered row is a class of its own.  dedupe != 0: unfiltered rows i, j are in one
+ *              class iff g_i == g_j && tx_i == tx_j && ty_i == ty_j && tz_i == tz_j under the C#'s `==`: -0 equals +0, and
+ *              a triple holding a NaN equals nothing, so its row is a class of its own.  The class keeps its smallest row
+ *              index, the first occurrence -- what the sequential FindAll / FindIndex keep.  group == NULL is typpe 1 (the
+ *              whole list), group = the file number is typpe 3 / 4
+ *   outputs    the m kept rows in ascending order of their input index (stable); the caller provides room for n entries;
+ *              each array may be NULL
+ *     src [m]        the input index of the kept row
+ *     motor [m*2]    its (mx, my)
+ *     dist [m]       its D
+ *     xyz [m*3]      its own (X, Y, Z): the first occurrence's bits, -0 included
+ *     count [m]      the size of its class (Point3D.ptsCount; 1 without dedupe)
+ *     group_out [m]  its g
+ *     row_to [n]     for every input row the compact position of its class's kept row, -1 for a filtered row: the labels
+ *                    of the raw rows are labels[row_to]
+ *     *m             required; *duplicates (may be NULL) = unfiltered rows - m
+ * With group == NULL, src is exactly the indices where vcp_import_convert(..., dedupe) has state == 1, xyz equals its
+ * xyz[src] bit for bit and duplicates equals its count; sum(count) == the number of unfiltered rows.
+ * Nothing is written on an error.  VCP_ERR_ARG: NULL ctx, NULL m, NULL rows with n > 0, n < 0, a direction outside 1..4;
+ * VCP_ERR_UNSUPPORTED: dedupe with directions other than xdir 2 / ydir 1, for the reason vcp_import_convert gives;
+ * VCP_ERR_TOO_LARGE: n >= 0x7FFFFFF0.  n == 0: *m = 0, VCP_OK.  The outputs must not overlap the inputs.
+ * The result is a function of the input alone: only integer atomics decide anything (a minimum for the kept index, a sum
+ * for the count); two calls give identical bits, and so does a call after any other call on the context.
+ * Timing phases: impc_convert, impc_dedupe, impc_compact (csrc/import.hip). */
+int vcp_import_compact(vcp_ctx* ctx, const double* rows, int64_t n, const int32_t* group, double x_angle, double y_angle,
+                       int xdir, int ydir, int dedupe, double* motor, double* xyz, double* dist, int32_t* src,
+                       int32_t* count, int32_t* group_out, int32_t* row_to, int64_t* m, int64_t* duplicates);
+/* Same with device pointers for rows, group and the seven arrays, on the context's stream under the vcp_set_stream
+ * contract; m and duplicates stay host pointers.  One synchronisation, for the two counts; returns when the result is in
+ * place. */
+int vcp_import_compact_dev(vcp_ctx* ctx, const double* d_rows, int64_t n, const int32_t* d_group, double x_angle,
+                           double y_angle, int xdir, int ydir, int dedupe, double* d_motor, double* d_xyz, double* d_dist,
+                           int32_t* d_src, int32_t* d_count, int32_t* d_group_out, int32_t* d_row_to, int64_t* m,
+                           int64_t* duplicates);
+
 /* -- truth-guided assignment -------------------------------------------------
  * Replaces the query of MainForm.refreshClusList (FrmMain.cs:3437-3467): per raw point (motor_x, motor_y)
  * the nearest truth (tmp_X, tmp_Y) with Euclidean distance < radius; among equal distances the LAST truth

@@ -37,6 +37,7 @@ SYMBOLS = [
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
     "vcp_gdbscan", "vcp_gdbscan_dev", "vcp_icp_sums_sim", "vcp_selftest_horn_sim", "vcp_icp_sim",
     "vcp_icp_sums_unique", "vcp_icp_unique", "vcp_icp_sums_aniso", "vcp_selftest_horn_aniso", "vcp_icp_aniso",
+    "vcp_import_compact", "vcp_import_compact_dev",
 ]
 
 
@@ -914,6 +915,39 @@ class Context:
                                            int(xdir), int(ydir), int(dedupe), _ptr(xyz), _ptr(state), C.byref(kept),
                                            C.byref(dup)))
         return dict(xyz=xyz, state=state, kept=kept.value, duplicates=dup.value)
+
+    def import_compact(self, rows, group=None, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True):
+        """vcp_import_compact: filter, duplicate classes with their sizes (per group when group [n] int32 is given) and
+        the kept rows written densely in input order.  Returns dict(motor [m,2], xyz [m,3], dist [m], src [m], count [m],
+        group [m], row_to [n] (-1 = filtered), m, duplicates)."""
+        rows = _f64(rows, 3)
+        n = len(rows)
+        if group is not None:
+            group = np.ascontiguousarray(group, np.int32).reshape(-1)
+            if len(group) != n:
+                raise ValueError("group has %d entries for %d rows" % (len(group), n))
+        motor, xyz, dist = np.zeros((n, 2)), np.zeros((n, 3)), np.zeros(n)
+        src, count, gout, row_to = (np.zeros(n, np.int32) for _ in range(4))
+        m, dup = C.c_int64(0), C.c_int64(0)
+        self._chk(lib().vcp_import_compact(self._h, _ptr(rows), C.c_int64(n), _ptr(group), C.c_double(x_angle),
+                                           C.c_double(y_angle), int(xdir), int(ydir), int(bool(dedupe)), _ptr(motor),
+                                           _ptr(xyz), _ptr(dist), _ptr(src), _ptr(count), _ptr(gout), _ptr(row_to),
+                                           C.byref(m), C.byref(dup)))
+        k = m.value
+        return dict(motor=motor[:k].copy(), xyz=xyz[:k].copy(), dist=dist[:k].copy(), src=src[:k].copy(),
+                    count=count[:k].copy(), group=gout[:k].copy(), row_to=row_to, m=k, duplicates=dup.value)
+
+    def import_compact_dev(self, d_rows, n, d_group=None, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True,
+                           d_motor=None, d_xyz=None, d_dist=None, d_src=None, d_count=None, d_group_out=None,
+                           d_row_to=None):
+        """Device-pointer form (ints from tensor.data_ptr()): d_rows float64 [n*3], d_group int32 [n] or None; every
+        output has room for n entries and may be None.  Returns (m, duplicates)."""
+        m, dup = C.c_int64(0), C.c_int64(0)
+        self._chk(lib().vcp_import_compact_dev(self._h, _ptr(d_rows), C.c_int64(n), _ptr(d_group), C.c_double(x_angle),
+                                               C.c_double(y_angle), int(xdir), int(ydir), int(bool(dedupe)),
+                                               _ptr(d_motor), _ptr(d_xyz), _ptr(d_dist), _ptr(d_src), _ptr(d_count),
+                                               _ptr(d_group_out), _ptr(d_row_to), C.byref(m), C.byref(dup)))
+        return m.value, dup.value
 
 
 def selftest_horn_sim(sums, n, c=1.0, ratio_range=(1.0, 1.0), V=None):

@@ -37,7 +37,10 @@ def multiplicity(rows):
     """(first_index, counts): the first occurrence of every distinct row of `rows` [n, d] in input order and how often the
     row occurs -- the import's duplicate removal with the count kept.  gdbscan(rows[first_index], ..., weights=counts) is
     then the clustering of the raw cloud, restricted to the first occurrences.  Rows are compared bit for bit (so -0.0
-    and 0.0 differ, and a NaN row equals a NaN row of the same bits)."""
+    and 0.0 differ, and a NaN row equals a NaN row of the same bits).
+    The device form is vcp_import_compact (Context.import_compact, io.import_scan_resident): its src and count are this
+    function's pair for the converted triples of a scan, computed without leaving HBM.  The one difference: the device
+    compares with the C#'s `==`, so there -0.0 equals 0.0 and a row holding a NaN equals nothing, itself included."""
     rows = np.ascontiguousarray(rows, np.float64)
     if rows.ndim != 2:
         raise ValueError("rows must be [n, d]")

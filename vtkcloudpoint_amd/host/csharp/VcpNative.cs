@@ -176,6 +176,15 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_import_convert(IntPtr ctx, double[] rows, long n, double x_angle,
             double y_angle, int xdir, int ydir, int dedupe, double[] xyz, byte[] state, out long kept, out long duplicates);
 
+        // the same with the kept rows written densely and the size of every duplicate class; group = the file number is
+        // AddFolder's typpe 3 / 4 (FrmMain.cs:1069-1085: count is Point3D.ptsCount).  Every array may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_import_compact(IntPtr ctx, double[] rows, long n, int[] group,
+            double x_angle, double y_angle, int xdir, int ydir, int dedupe, double[] motor, double[] xyz, double[] dist,
+            int[] src, int[] count, int[] group_out, int[] row_to, out long m, out long duplicates);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_import_compact_dev(IntPtr ctx, IntPtr d_rows, long n, IntPtr d_group,
+            double x_angle, double y_angle, int xdir, int ydir, int dedupe, IntPtr d_motor, IntPtr d_xyz, IntPtr d_dist,
+            IntPtr d_src, IntPtr d_count, IntPtr d_group_out, IntPtr d_row_to, out long m, out long duplicates);
+
         // query of MainForm.refreshClusList (FrmMain.cs:3452-3456)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_assign_truths(IntPtr ctx, double[] motor, long n, double[] truths_xy,
             int[] truth_ids, int T, double radius, int[] ids, out long outliers);
