@@ -1104,6 +1104,66 @@ int vcp_gdbscan_dev(vcp_ctx* ctx, const double* d_coords, int64_t n, int dim, in
                     const double* d_aux, double gate, const int32_t* d_weights, int64_t min_weight, int32_t cf_in,
                     int32_t* d_labels, uint8_t* d_is_core, int64_t* d_wsum, int32_t* cf_out);
 
+/* -- per-cluster quantiles and MAD outlier rejection -----------------------------------------------------
+ * Every other per-cluster number of this library is a mean (vcp_centroids, vcp_centroids_weighted) or a hull quantity
+ * (vcp_cluster_shapes).  These calls give order statistics per cluster or group: the reference has Tools.GetGroupingManOrMin
+ * (BC/Tools.cs:468-497: the min / max of Distance over all files, which seeds the dialog of SureDistanceFilter.cs:26-61) and
+ * one hand-typed band of Distance for every file (Tools.FilterByDistance_FixedPoint, BC/Tools.cs:438-461, confirmed by
+ * cleanDataByDistance2 :254-263) before getFixedPtsCentroid; one band cannot serve targets at different ranges.  All
+ * outputs are selections among the caller's binary64 values, plus one rounded subtraction for the deviation.
+ *   v_i        the value of row i is values[i * stride], stride >= 1 in doubles: a column of xyz is read in place.
+ *              group[i] in 0..K; 0 = in no group, the convention of vcp_centroids_weighted; group k holds the rows with
+ *              group[i] == k, c_k of them.  A label outside 0..K is VCP_ERR_INDEX, as in vcp_mcc
+ *   order      with u the bit pattern of v: key(v) = 0xFFFFFFFFFFFFFFFF for any NaN, else u ^ 0x8000000000000000 when the
+ *              sign bit is clear and ~u when it is set.  The unsigned order of the keys is the numeric order, with -0
+ *              before +0 and NaN last.  Ties between equal keys need no rule: the output is the value
+ *   rank       for a group of c >= 1 rows and q in [0, 1]: rank = (int64_t)floor(q * (double)(c - 1)), one multiplication
+ *              in binary64; q = 0 is the minimum, q = 1 the maximum (GetGroupingManOrMin per list), q = 0.5 the LOWER median
+ *   out        out[k * nq + j] = the value whose key has rank(q[j], c) (0-based, ascending) among the keys of group k + 1;
+ *              a NaN is returned as 0x7FF8000000000000.  An empty group gives that NaN for every j and count 0, as
+ *              vcp_centroids' empty clusters do.  counts [K] may be NULL
+ *   MAD        med_k = the q = 0.5 selection of group k; dev_i = fabs(v_i - med_k), one subtraction in binary64 (no FMA);
+ *              mad_k = the q = 0.5 selection of the group's dev; band = c_mad * mad_k; thr_k = band > floor ? band : floor,
+ *              so a NaN band gives floor (an empty group: med and mad NaN, thr = floor, kept 0);
+ *              reject[i] = group[i] >= 1 && !(dev_i <= thr_k): a NaN value is rejected, and floor = +inf rejects only
+ *              those; reject is 0 for the rows of group 0.  kept[k] = the rows of group k + 1 that are not rejected,
+ *              *n_rejected = the rejected rows in all.  All of med, mad, thr [K], reject [n], kept [K] and n_rejected are
+ *              required
+ * VCP_ERR_ARG: NULL ctx, a NULL required pointer (values or group with n > 0, q, out / med / mad / thr / kept with K > 0,
+ * reject with n > 0, n_rejected), n < 0, K < 0, stride < 1, nq < 1, a q that is NaN or outside [0, 1], c_mad or floor NaN
+ * or < 0; VCP_ERR_UNSUPPORTED: nq > VCP_CQ_NQ_MAX; VCP_ERR_TOO_LARGE: n >= 2^31; VCP_ERR_INDEX: a label outside 0..K, found
+ * on the device before any output is touched.  Nothing is written on an error.  n == 0 or K == 0: nothing to select; the
+ * outputs for K > 0 are the empty-group values (reject all 0 for K == 0), VCP_OK.
+ * The rows are grouped by a stable sort on the label (as vcp_centroids does), the keys gathered in that order, and every
+ * group is selected from by the class of its size: up to VCP_CQ_WAVE_MAX rows one wave ranks the keys by counting; up to
+ * VCP_CQ_WG_MAX rows one workgroup holds the keys in LDS and runs an 8-bit radix select, most significant digit first;
+ * larger groups share one histogram launch and one pick launch per digit.  The answer does not depend on the class, and all
+ * nq ranks of a call share the grouping and the gather.  The result is a function of the input alone: only integer
+ * comparisons and integer atomics decide which value is returned; two calls give identical bits, and so does a call after
+ * any other call on the context.  Timing phases: cq_group, cq_select, and cq_flag for the MAD form
+ * (csrc/cluster_quant.hip). */
+#define VCP_CQ_WAVE_MAX 64
+#define VCP_CQ_WG_MAX 4096
+#define VCP_CQ_NQ_MAX 16
+int vcp_cluster_quantiles(vcp_ctx* ctx, const double* values, int64_t stride, const int32_t* group, int64_t n, int32_t K,
+                          const double* q, int32_t nq, double* out, int64_t* counts);
+/* Same with device pointers for values, group, out and counts, on the context's stream under the vcp_set_stream contract;
+ * q stays a host pointer.  One synchronisation before the outputs are touched (the label check); returns when the result
+ * is in place. */
+int vcp_cluster_quantiles_dev(vcp_ctx* ctx, const double* d_values, int64_t stride, const int32_t* d_group, int64_t n,
+                              int32_t K, const double* q, int32_t nq, double* d_out, int64_t* d_counts);
+int vcp_cluster_mad(vcp_ctx* ctx, const double* values, int64_t stride, const int32_t* group, int64_t n, int32_t K,
+                    double c_mad, double floor, double* med, double* mad, double* thr, uint8_t* reject, int64_t* kept,
+                    int64_t* n_rejected);
+/* Same with device pointers for values, group, med, mad, thr, reject and kept; n_rejected stays a host pointer. */
+int vcp_cluster_mad_dev(vcp_ctx* ctx, const double* d_values, int64_t stride, const int32_t* d_group, int64_t n,
+                        int32_t K, double c_mad, double floor, double* d_med, double* d_mad, double* d_thr,
+                        uint8_t* d_reject, int64_t* d_kept, int64_t* n_rejected);
+/* Self-test of the key and the rank, compiled from the same __host__ __device__ source as the kernels: *key = key(v),
+ * *rank = the rank of q in a group of c rows.  Returns 1, or VCP_ERR_ARG for a NULL pointer, c < 1, or q that is NaN or
+ * outside [0, 1].  Needs no device and no context. */
+int vcp_selftest_rank_key(double v, double q, int64_t c, uint64_t* key, int64_t* rank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,8 @@ SYMBOLS = [
     "vcp_register_sim_dev", "vcp_selftest_register_sim_pose", "vcp_eps_tree", "vcp_eps_tree_dev",
     "vcp_gdbscan", "vcp_gdbscan_dev", "vcp_icp_sums_sim", "vcp_selftest_horn_sim", "vcp_icp_sim",
     "vcp_icp_sums_unique", "vcp_icp_unique", "vcp_icp_sums_aniso", "vcp_selftest_horn_aniso", "vcp_icp_aniso",
-    "vcp_import_compact", "vcp_import_compact_dev",
+    "vcp_import_compact", "vcp_import_compact_dev", "vcp_cluster_quantiles", "vcp_cluster_quantiles_dev",
+    "vcp_cluster_mad", "vcp_cluster_mad_dev", "vcp_selftest_rank_key",
 ]
 
 
@@ -948,6 +949,69 @@ class Context:
                                                _ptr(d_motor), _ptr(d_xyz), _ptr(d_dist), _ptr(d_src), _ptr(d_count),
                                                _ptr(d_group_out), _ptr(d_row_to), C.byref(m), C.byref(dup)))
         return m.value, dup.value
+
+    # -- per-cluster quantiles and MAD ---------------------------------------------------------------
+    @staticmethod
+    def _cq_host(values, group, stride):
+        values = np.ascontiguousarray(values, np.float64).reshape(-1)
+        group = np.ascontiguousarray(group, np.int32).reshape(-1)
+        n, stride = len(group), int(stride)
+        if stride >= 1 and n > 0 and len(values) < (n - 1) * stride + 1:
+            raise ValueError("values has %d doubles for %d rows at stride %d" % (len(values), n, stride))
+        return values, group, n, stride
+
+    def cluster_quantiles(self, values, group, K, q, stride=1):
+        """vcp_cluster_quantiles: row i has the value values.flat[i * stride] and the group group[i] in 0..K (0 = none).
+        Returns (out [K, nq] float64: the value of rank floor(q * (c - 1)) in every group, NaN for an empty one;
+        counts [K] int64)."""
+        values, group, n, stride = self._cq_host(values, group, stride)
+        q = np.ascontiguousarray(q, np.float64).reshape(-1)
+        out = np.zeros((max(int(K), 0), len(q)))
+        counts = np.zeros(max(int(K), 0), np.int64)
+        self._chk(lib().vcp_cluster_quantiles(self._h, _ptr(values), C.c_int64(stride), _ptr(group), C.c_int64(n),
+                                              C.c_int32(K), _ptr(q), C.c_int32(len(q)), _ptr(out), _ptr(counts)))
+        return out, counts
+
+    def cluster_quantiles_dev(self, d_values, stride, d_group, n, K, q, d_out, d_counts=None):
+        """Device-pointer form (ints from tensor.data_ptr()): d_values float64, d_group int32 [n], d_out float64
+        [K * nq], d_counts int64 [K] or None; q is a host sequence."""
+        q = np.ascontiguousarray(q, np.float64).reshape(-1)
+        self._chk(lib().vcp_cluster_quantiles_dev(self._h, _ptr(d_values), C.c_int64(stride), _ptr(d_group),
+                                                  C.c_int64(n), C.c_int32(K), _ptr(q), C.c_int32(len(q)), _ptr(d_out),
+                                                  _ptr(d_counts)))
+
+    def cluster_mad(self, values, group, K, c_mad=3.0, floor=0.0, stride=1):
+        """vcp_cluster_mad: per group the lower median, the median absolute deviation from it and the threshold
+        max(c_mad * mad, floor); a row of a group is rejected unless |v - med| <= thr.  Returns dict(med, mad, thr [K],
+        reject [n] uint8, kept [K] int64, n_rejected)."""
+        values, group, n, stride = self._cq_host(values, group, stride)
+        kk = max(int(K), 0)
+        med, mad, thr = np.zeros(kk), np.zeros(kk), np.zeros(kk)
+        reject, kept = np.zeros(n, np.uint8), np.zeros(kk, np.int64)
+        nr = C.c_int64(0)
+        self._chk(lib().vcp_cluster_mad(self._h, _ptr(values), C.c_int64(stride), _ptr(group), C.c_int64(n),
+                                        C.c_int32(K), C.c_double(c_mad), C.c_double(floor), _ptr(med), _ptr(mad),
+                                        _ptr(thr), _ptr(reject), _ptr(kept), C.byref(nr)))
+        return dict(med=med, mad=mad, thr=thr, reject=reject, kept=kept, n_rejected=nr.value)
+
+    def cluster_mad_dev(self, d_values, stride, d_group, n, K, c_mad, floor, d_med, d_mad, d_thr, d_reject, d_kept):
+        """Device-pointer form (ints from tensor.data_ptr()): d_med, d_mad, d_thr float64 [K], d_reject uint8 [n],
+        d_kept int64 [K].  Returns n_rejected."""
+        nr = C.c_int64(0)
+        self._chk(lib().vcp_cluster_mad_dev(self._h, _ptr(d_values), C.c_int64(stride), _ptr(d_group), C.c_int64(n),
+                                            C.c_int32(K), C.c_double(c_mad), C.c_double(floor), _ptr(d_med), _ptr(d_mad),
+                                            _ptr(d_thr), _ptr(d_reject), _ptr(d_kept), C.byref(nr)))
+        return nr.value
+
+
+def selftest_rank_key(v, q, c):
+    """vcp_selftest_rank_key: (key(v) as a Python int, the rank of q in a group of c rows), from the source the kernels
+    are compiled from (no device)."""
+    key, rank = C.c_uint64(0), C.c_int64(0)
+    rc = lib().vcp_selftest_rank_key(C.c_double(v), C.c_double(q), C.c_int64(int(c)), C.byref(key), C.byref(rank))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_rank_key")
+    return key.value, rank.value
 
 
 def selftest_horn_sim(sums, n, c=1.0, ratio_range=(1.0, 1.0), V=None):

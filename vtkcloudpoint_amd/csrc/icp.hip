@@ -36,6 +36,7 @@
 #include "horn.hpp"
 #include "match.hpp"
 #include "nngrid.hpp"
+#include "radix_pick.hpp"
 #include "reduce.hpp"
 #include "vcp_ctx.hpp"
 
@@ -817,33 +818,6 @@ __device__ __forceinline__ void trim_push(TrimPrefix& p, int d, uint32_t g, uint
   p.w2 |= w == 2 ? add : 0u;
   p.rank = rank;
 }
-// Thread t holds the count c of bin t; rank r, 1 <= r <= the total: the bin g with below(g) < r <= below(g) + c(g) and
-// the rank left in it, to every thread.  sh: 8 words of LDS, free again on return.
-__device__ __forceinline__ void trim_pick(uint32_t c, uint32_t r, uint32_t* sh, uint32_t& g, uint32_t& left) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += v;
-  }
-  if (threadIdx.x == 0) {
-    sh[4] = 0;
-    sh[5] = 1;
-  }
-  if (lane == 63) sh[w] = inc;
-  __syncthreads();
-  for (int u = 0; u < w; u++) inc += sh[u];
-  const uint32_t exc = inc - c;
-  if (exc < r && r <= inc) {
-    sh[4] = threadIdx.x;
-    sh[5] = r - exc;
-  }
-  __syncthreads();
-  g = sh[4];
-  left = sh[5];
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(ITPB) void k_icpt_select_wg(const IcpState* __restrict__ st, TrimArgs a, int L) {
   const int h = blockIdx.x;
@@ -863,7 +837,7 @@ __global__ __launch_bounds__(ITPB) void k_icpt_select_wg(const IcpState* __restr
     }
     __syncthreads();
     uint32_t g, left;
-    trim_pick(hist[threadIdx.x], p.rank, sh, g, left);
+    vcp_radix_pick(hist[threadIdx.x], p.rank, sh, g, left);
     trim_push(p, d, g, left);
   }
   if (threadIdx.x == 0) a.sel[h] = TrimSel{((unsigned long long)p.w0 << 32) | p.w1, p.w2, 0u};
@@ -885,7 +859,7 @@ __global__ __launch_bounds__(ITPB) void k_icpt_hist(const IcpState* __restrict__
   } else {
     p = slot[d - 1];
     uint32_t g, left;
-    trim_pick(ghist[(d - 1) * ITPB + threadIdx.x], p.rank, sh, g, left);
+    vcp_radix_pick(ghist[(d - 1) * ITPB + threadIdx.x], p.rank, sh, g, left);
     trim_push(p, d - 1, g, left);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) slot[d] = p;
@@ -912,7 +886,7 @@ __global__ __launch_bounds__(ITPB) void k_icpt_select_fin(const IcpState* __rest
   ghist += (size_t)h * TRIM_DIGITS * ITPB;
   TrimPrefix p = slot[(size_t)h * TRIM_DIGITS + TRIM_DIGITS - 1];
   uint32_t g, left;
-  trim_pick(ghist[(TRIM_DIGITS - 1) * ITPB + threadIdx.x], p.rank, sh, g, left);
+  vcp_radix_pick(ghist[(TRIM_DIGITS - 1) * ITPB + threadIdx.x], p.rank, sh, g, left);
   trim_push(p, TRIM_DIGITS - 1, g, left);
   if (threadIdx.x == 0) a.sel[h] = TrimSel{((unsigned long long)p.w0 << 32) | p.w1, p.w2, 0u};
   for (int d = 0; d < TRIM_DIGITS; d++) ghist[d * ITPB + threadIdx.x] = 0;

@@ -36,7 +36,8 @@ struct vcp_ctx {
   //                 the finish stage's counters (blocks.hip); the k-distance bounds (kdist.hip); at [512, 568) the
   //                 nearest-neighbour grid's bounds (nngrid.hip); at [0, 56) the truths' bounds of vcp_match_unique
   //                 and the targets' bounds of vcp_register_pairs (epsgrid.hpp) and the cloud's of vcp_eps_tree (eps_tree.hip);
-  //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip)
+  //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip); at [0, 72) the counters of
+  //                 vcp_cluster_quantiles / vcp_cluster_mad and at [128, 264) their ranks on the way up (cluster_quant.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //                 and of vcp_eps_tree (eps_tree.hip); the cluster count of vcp_gdbscan (gdbscan.hip)
@@ -73,6 +74,9 @@ struct vcp_ctx {
   // trimmed ICP (icp.hip): per (pose, landmark) the distance key and the index found, then the select's prefixes and
   // histograms; unique-correspondence ICP: the same keys and indices, then per (pose, target) the winner's slot
   DevBuf b_icpt;
+  // per-cluster quantiles and MAD (cluster_quant.hip): values and groups, then the outputs, of the host forms; the segment
+  // tables, counters and ranks; the large segments' select states and histograms.  The keys in segment order are b_aux4
+  DevBuf b_cq_in, b_cq_out, b_cq_misc, b_cq_large;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

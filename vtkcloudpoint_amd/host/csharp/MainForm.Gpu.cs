@@ -624,6 +624,37 @@ namespace vtkPointCloud
             for (int j = 0; j < K; j++) if (filtered[j] != 0) filterID.Add(j + 1);
         }
 
+        // Beside RejectPtsByDistanceFromFixed (FrmMain.cs:1759-1764), which confirms the one band of Distance the
+        // SureDistanceFilter dialog applied to every file (Tools.FilterByDistance_FixedPoint, Tools.cs:438-461): here every
+        // file gets its own band, |Distance - median| <= max(c * MAD, floor) (vcp_cluster_mad), so that targets at
+        // different ranges are cleaned alike.  Sets isFilterByDistance the way the dialog does, then removes the marked
+        // points like Tools.cleanDataByDistance2 (Tools.cs:259-262); Tools.getFixedPtsCentroid follows as before.
+        // Returns the number of points removed.  An empty clusList removes nothing.
+        public long RejectPtsByDistanceRobust(double c, double floor)
+        {
+            int K = clusList == null ? 0 : clusList.Count, n = 0;
+            for (int i = 0; i < K; i++) n += clusList[i].li.Count;
+            if (K == 0 || n == 0) return 0;
+            double[] dist = new double[n], med = new double[K], mad = new double[K], thr = new double[K];
+            int[] group = new int[n];
+            byte[] reject = new byte[n];
+            long[] kept = new long[K];
+            int t = 0;
+            for (int i = 0; i < K; i++)
+                foreach (Point3D p in clusList[i].li) { dist[t] = p.Distance; group[t] = i + 1; t++; }
+            long rejected;
+            using (VcpNative.Lease lease = VcpNative.Rent())
+                VcpNative.Check(lease, VcpNative.vcp_cluster_mad(lease.Ctx, dist, 1, group, n, K, c, floor, med, mad, thr,
+                    reject, kept, out rejected));
+            t = 0;
+            for (int i = 0; i < K; i++)
+                foreach (Point3D p in clusList[i].li) p.isFilterByDistance = reject[t++] != 0;
+            for (int i = 0; i < K; i++)
+                clusList[i].li.RemoveAll(delegate(Point3D p) { return p.isFilterByDistance; });
+            this.FixedPointMatchingToolStripMenuItem.Enabled = true;
+            return rejected;
+        }
+
         // FrmMain.cs:3743-3746
         public void removePointByRadius()
         {

@@ -185,6 +185,16 @@ namespace vtkPointCloud
             double x_angle, double y_angle, int xdir, int ydir, int dedupe, IntPtr d_motor, IntPtr d_xyz, IntPtr d_dist,
             IntPtr d_src, IntPtr d_count, IntPtr d_group_out, IntPtr d_row_to, out long m, out long duplicates);
 
+        // order statistics per cluster or group (vcp.h: vcp_cluster_quantiles; per list what Tools.GetGroupingManOrMin,
+        // Tools.cs:468-497, takes over all lists): values[i * stride], group 0 = none; counts may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_quantiles(IntPtr ctx, double[] values, long stride,
+            int[] group, long n, int K, double[] q, int nq, double[] output, long[] counts);
+        // a band of Distance per group from the median absolute deviation, where Tools.FilterByDistance_FixedPoint
+        // (Tools.cs:438-461) applies one band to every file: reject[i] != 0 is Point3D.isFilterByDistance
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_mad(IntPtr ctx, double[] values, long stride,
+            int[] group, long n, int K, double c_mad, double floor, double[] med, double[] mad, double[] thr, byte[] reject,
+            long[] kept, out long n_rejected);
+
         // query of MainForm.refreshClusList (FrmMain.cs:3452-3456)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_assign_truths(IntPtr ctx, double[] motor, long n, double[] truths_xy,
             int[] truth_ids, int T, double radius, int[] ids, out long outliers);
@@ -231,6 +241,11 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_gdbscan_dev(IntPtr ctx, IntPtr d_coords, long n, int dim, int metric,
             double eps, IntPtr d_aux, double gate, IntPtr d_weights, long min_weight, int cf_in, IntPtr d_labels, IntPtr d_is_core,
             IntPtr d_wsum, out int cf_out);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_quantiles_dev(IntPtr ctx, IntPtr d_values, long stride,
+            IntPtr d_group, long n, int K, double[] q, int nq, IntPtr d_out, IntPtr d_counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_mad_dev(IntPtr ctx, IntPtr d_values, long stride,
+            IntPtr d_group, long n, int K, double c_mad, double floor, IntPtr d_med, IntPtr d_mad, IntPtr d_thr,
+            IntPtr d_reject, IntPtr d_kept, out long n_rejected);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_icp_dev(IntPtr ctx, IntPtr d_model, long nm, IntPtr d_data, long nd,
             double tol, int max_iter, int stop_rule, double[] R, double[] T, out double sse, out double rmse, out int iters);
         // block pipeline in stages (per-block step sharded over GPUs, distributed.py: sharded_blocks)
