@@ -1164,6 +1164,62 @@ int vcp_cluster_mad_dev(vcp_ctx* ctx, const double* d_values, int64_t stride, co
  * outside [0, 1].  Needs no device and no context. */
 int vcp_selftest_rank_key(double v, double q, int64_t c, uint64_t* key, int64_t* rank);
 
+/* -- scan text on the device: bytes in, resident rows out --------------------------------------------------
+ * The reference's scan files hold one point per line, `motor_x<TAB>motor_y<TAB>Distance` (FileMap.ReadFile,
+ * FrmMain.cs:1005-1009; written back by BC/Tools.cs:233).  The bytes of one or many files go in; rows [n, 3] and the file
+ * number of every row come out in the layout vcp_import_compact_dev(d_rows, d_group) takes.  In BOTH forms text is a HOST
+ * buffer; "_dev" means that d_rows [cap * 3] and d_group [cap] are device pointers, written on the context's stream under
+ * the vcp_set_stream contract.  group may be NULL.  The result equals vtkcloudpoint_amd.io.read_scan_text bit for bit.
+ *   segments   seg_off [nseg + 1] ascends from seg_off[0] = 0 to seg_off[nseg] = nbytes; segment k is file k; seg_off ==
+ *              NULL means one segment (nseg is not read).  Every non-empty segment must end with '\n' (nseg byte reads on
+ *              the host; else VCP_ERR_ARG): no line and no "\r\n" pair then spans two files
+ *   bytes      \t \n \r and 0x20..0x7E except '_'.  Any other byte: VCP_ERR_UNSUPPORTED with err[0] = the offset of the first
+ *              one (a device minimum).  On those bytes a reader in Python differs from any simple grammar (GB2312 pairs,
+ *              str.splitlines on 0x0B 0x0C 0x1C-0x1E 0x85, 1_0 == 10); callers fall back to their own reader
+ *   lines      the terminators are "\r\n", '\n' and a '\r' that no '\n' follows; *n = their number; an empty line between
+ *              two terminators is a line.  seg_first [nseg + 1] (may be NULL) = the first line of every segment;
+ *              group[j] = the segment that holds the first byte of line j
+ *   fields     a line is split at '\t'; the first three fields are read, further fields are ignored whatever they hold
+ *   a number   sp* [+-]? (D+ ('.' D*)? | '.' D+) ([eE] [+-]? D+)? sp*  (D a decimal digit, sp a blank), or inf, infinity,
+ *              nan with an optional sign in any letter case: what Python's float() accepts on supported bytes.  The value
+ *              is the correctly rounded binary64 (nearest, ties to even); -0 gives -0.0; nan and +nan give
+ *              0x7FF8000000000000, -nan gives 0xFFF8000000000000
+ *   classes    with w the mantissa's digits as an integer (leading zeros stripped, trailing zeros counted), nd the number
+ *              of those digits and e10 the exponent minus the number of fraction digits (vcp_selftest_parse_field
+ *              returns the class):
+ *                1  w == 0, or w <= 2^53 and -22 <= e10 <= 22: (double)w * 1e{e10} or (double)w / 1e{-e10}, one IEEE
+ *                   operation on an exact power (Clinger's fast path)
+ *                2  otherwise nd <= 19 and -19 <= e10 <= 19: w * 10^e10 in integers -- an exact 128-bit product, or a
+ *                   128-by-64-bit long division with a sticky bit -- rounded by hand
+ *                3  any other number (more digits, larger exponents, the names): parsed on the host, locale-independent
+ *                   and correctly rounded
+ *                0  not a number
+ *              Classes 1 and 2 are decided and evaluated on the device.  The lines with a class-3 field go to a list the
+ *              library sorts; it parses them from text on the host and patches rows with one upload and one scatter
+ *              kernel on the context's stream.  *n_host = the number of such lines
+ *   errors     the first line, in input order, with fewer than three fields (kind 1) or a non-number among its first three
+ *              fields (kind 2; the field count is checked first): VCP_ERR_ARG with err = {line within its segment
+ *              (1-based), segment, kind}.  *n and *n_host are then NOT written and the contents of rows and group are
+ *              unspecified: validating before writing would mean parsing twice.  err may be NULL
+ *   counting   rows == NULL (d_rows == NULL): count-only -- the bytes and the segment rule are checked, *n and seg_first
+ *              are written, nothing is parsed.  n > cap: VCP_ERR_INDEX, and *n IS written, so that the caller can come
+ *              back with room
+ * Limits: nbytes >= 2^32 or n >= 0x7FFFFFF0: VCP_ERR_TOO_LARGE.  nbytes == 0: *n = 0, VCP_OK.  VCP_ERR_ARG also for a
+ * NULL ctx, n or text (nbytes > 0), nseg < 1 with a seg_off, cap < 0.
+ * The result is a function of the input alone: integer minima, and a list that is sorted before use, are the only
+ * atomics that decide anything.  Workspace: the text, 4 bytes per VCP_TXT_CHUNK bytes, 12 bytes per line.  Timing phases:
+ * txt_upload, txt_index, txt_parse, txt_patch (csrc/scantext.hip, csrc/scantext.hpp). */
+#define VCP_TXT_CHUNK 16384 /* bytes one workgroup indexes */
+int vcp_parse_scan_text(vcp_ctx* ctx, const char* text, uint64_t nbytes, const uint64_t* seg_off, int32_t nseg, int64_t cap,
+                        double* rows, int32_t* group, int64_t* seg_first, int64_t* n, int64_t* n_host, int64_t err[3]);
+int vcp_parse_scan_text_dev(vcp_ctx* ctx, const char* text, uint64_t nbytes, const uint64_t* seg_off, int32_t nseg,
+                            int64_t cap, double* d_rows, int32_t* d_group, int64_t* seg_first, int64_t* n,
+                            int64_t* n_host, int64_t err[3]);
+/* One field through the source the kernels compile (csrc/scantext.hpp): returns the class; for classes 1..3 *v = the
+ * value (class 3 through the host's parser), for class 0 *v is untouched.  VCP_ERR_ARG for a NULL v, len < 0 or a NULL s
+ * with len > 0.  Needs no device and no context. */
+int vcp_selftest_parse_field(const char* s, int64_t len, double* v);
+
 #ifdef __cplusplus
 }
 #endif

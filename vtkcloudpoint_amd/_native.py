@@ -38,7 +38,8 @@ SYMBOLS = [
     "vcp_gdbscan", "vcp_gdbscan_dev", "vcp_icp_sums_sim", "vcp_selftest_horn_sim", "vcp_icp_sim",
     "vcp_icp_sums_unique", "vcp_icp_unique", "vcp_icp_sums_aniso", "vcp_selftest_horn_aniso", "vcp_icp_aniso",
     "vcp_import_compact", "vcp_import_compact_dev", "vcp_cluster_quantiles", "vcp_cluster_quantiles_dev",
-    "vcp_cluster_mad", "vcp_cluster_mad_dev", "vcp_selftest_rank_key",
+    "vcp_cluster_mad", "vcp_cluster_mad_dev", "vcp_selftest_rank_key", "vcp_parse_scan_text",
+    "vcp_parse_scan_text_dev", "vcp_selftest_parse_field",
 ]
 
 
@@ -950,6 +951,78 @@ class Context:
                                                _ptr(d_group_out), _ptr(d_row_to), C.byref(m), C.byref(dup)))
         return m.value, dup.value
 
+    # -- scan text ---------------------------------------------------------------------------------
+    def _txt_fail(self, rc, err):
+        e = VcpError(rc, (lib().vcp_last_error(self._h) or b"").decode())
+        e.err = tuple(int(x) for x in err)      # UNSUPPORTED: (offset, 0, 0); a bad line: (line, segment, kind)
+        return e
+
+    @staticmethod
+    def _txt_args(data, seg_off):
+        """(text argument, nbytes, seg_off, nseg): data is bytes, or a contiguous uint8 numpy array read in place."""
+        if isinstance(data, np.ndarray):
+            if data.dtype != np.uint8 or data.ndim != 1 or not data.flags.c_contiguous:
+                raise ValueError("text must be bytes or a contiguous 1-D uint8 array")
+            text, nbytes = _ptr(data), data.size
+        else:
+            text = bytes(data)
+            nbytes = len(text)
+        if seg_off is None:
+            return text, nbytes, None, 1
+        seg_off = np.ascontiguousarray(seg_off, np.uint64).reshape(-1)
+        return text, nbytes, seg_off, len(seg_off) - 1
+
+    def parse_scan_text(self, data, seg_off=None, count_only=False):
+        """vcp_parse_scan_text: data = the bytes of the scan files one after the other, seg_off [nseg + 1] their offsets
+        (None: one file).  Returns dict(rows [n, 3] float64, group [n] int32, seg_first [nseg + 1] int64, n, n_host);
+        count_only leaves rows and group None.  A VcpError of this call carries .err = the call's err[3] and, for
+        VCP_ERR_INDEX, .n."""
+        text, nbytes, seg_off, nseg = self._txt_args(data, seg_off)
+        first = np.zeros(nseg + 1, np.int64)
+        n, nh = C.c_int64(0), C.c_int64(0)
+        err = (C.c_int64 * 3)()
+        if count_only:
+            rc = lib().vcp_parse_scan_text(self._h, text, C.c_uint64(nbytes), _ptr(seg_off), C.c_int32(nseg),
+                                           C.c_int64(0), None, None, _ptr(first), C.byref(n), C.byref(nh), err)
+            if rc != 0:
+                raise self._txt_fail(rc, err)
+            return dict(rows=None, group=None, seg_first=first, n=n.value, n_host=0)
+        # Room for one line per 16 bytes (an F6 line has 27 or more), so that the text is uploaded once; a text of shorter
+        # lines comes back with VCP_ERR_INDEX and its n, and is parsed again with exactly that room.
+        cap = nbytes // 16 + 1024
+        while True:
+            rows = np.zeros((cap, 3))
+            group = np.zeros(cap, np.int32)
+            rc = lib().vcp_parse_scan_text(self._h, text, C.c_uint64(nbytes), _ptr(seg_off), C.c_int32(nseg),
+                                           C.c_int64(cap), _ptr(rows), _ptr(group), _ptr(first), C.byref(n),
+                                           C.byref(nh), err)
+            if rc != -4 or n.value <= cap:
+                break
+            cap = n.value
+        if rc != 0:
+            raise self._txt_fail(rc, err)
+        k = n.value
+        if cap > k + k // 4:                              # do not keep the unused room alive
+            rows, group = rows[:k].copy(), group[:k].copy()
+        return dict(rows=rows[:k], group=group[:k], seg_first=first, n=k, n_host=nh.value)
+
+    def parse_scan_text_dev(self, data, cap, d_rows, d_group=None, seg_off=None):
+        """Device-pointer form (ints from tensor.data_ptr()): data stays host bytes; d_rows float64 [cap * 3] (None:
+        count-only), d_group int32 [cap] or None.  Returns dict(seg_first, n, n_host).  A VcpError carries .err and, for
+        VCP_ERR_INDEX (n > cap), .n."""
+        text, nbytes, seg_off, nseg = self._txt_args(data, seg_off)
+        first = np.zeros(nseg + 1, np.int64)
+        n, nh = C.c_int64(0), C.c_int64(0)
+        err = (C.c_int64 * 3)()
+        rc = lib().vcp_parse_scan_text_dev(self._h, text, C.c_uint64(nbytes), _ptr(seg_off), C.c_int32(nseg),
+                                           C.c_int64(cap), _ptr(d_rows), _ptr(d_group), _ptr(first), C.byref(n),
+                                           C.byref(nh), err)
+        if rc != 0:
+            e = self._txt_fail(rc, err)
+            e.n = n.value
+            raise e
+        return dict(seg_first=first, n=n.value, n_host=nh.value)
+
     # -- per-cluster quantiles and MAD ---------------------------------------------------------------
     @staticmethod
     def _cq_host(values, group, stride):
@@ -1012,6 +1085,18 @@ def selftest_rank_key(v, q, c):
     if rc < 0:
         raise VcpError(rc, "vcp_selftest_rank_key")
     return key.value, rank.value
+
+
+def selftest_parse_field(s):
+    """vcp_selftest_parse_field: (class 0..3, value or None for class 0) of one field (bytes or str), from the source the
+    kernels are compiled from (no device)."""
+    if isinstance(s, str):
+        s = s.encode("latin-1")
+    v = C.c_double(0.0)
+    rc = lib().vcp_selftest_parse_field(s, C.c_int64(len(s)), C.byref(v))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_parse_field")
+    return rc, (v.value if rc else None)
 
 
 def selftest_horn_sim(sums, n, c=1.0, ratio_range=(1.0, 1.0), V=None):

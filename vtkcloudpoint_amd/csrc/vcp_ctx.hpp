@@ -37,7 +37,8 @@ struct vcp_ctx {
   //                 nearest-neighbour grid's bounds (nngrid.hip); at [0, 56) the truths' bounds of vcp_match_unique
   //                 and the targets' bounds of vcp_register_pairs (epsgrid.hpp) and the cloud's of vcp_eps_tree (eps_tree.hip);
   //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip); at [0, 72) the counters of
-  //                 vcp_cluster_quantiles / vcp_cluster_mad and at [128, 264) their ranks on the way up (cluster_quant.hip)
+  //                 vcp_cluster_quantiles / vcp_cluster_mad and at [128, 264) their ranks on the way up (cluster_quant.hip);
+  //                 at [0, 24) the counters of vcp_parse_scan_text (scantext.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //                 and of vcp_eps_tree (eps_tree.hip); the cluster count of vcp_gdbscan (gdbscan.hip)
@@ -77,6 +78,9 @@ struct vcp_ctx {
   // per-cluster quantiles and MAD (cluster_quant.hip): values and groups, then the outputs, of the host forms; the segment
   // tables, counters and ranks; the large segments' select states and histograms.  The keys in segment order are b_aux4
   DevBuf b_cq_in, b_cq_out, b_cq_misc, b_cq_large;
+  // scan text (scantext.hip): the copy of the text; one word per chunk; counters, seg_off and seg_first; line_start and
+  // the host list; rows and group of the host form; the host-parsed values on their way up
+  DevBuf b_tx_text, b_tx_chunk, b_tx_misc, b_tx_line, b_tx_out, b_tx_patch;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

@@ -185,6 +185,15 @@ namespace vtkPointCloud
             double x_angle, double y_angle, int xdir, int ydir, int dedupe, IntPtr d_motor, IntPtr d_xyz, IntPtr d_dist,
             IntPtr d_src, IntPtr d_count, IntPtr d_group_out, IntPtr d_row_to, out long m, out long duplicates);
 
+        // the scan files' text parsed on the GPU (vcp.h: vcp_parse_scan_text; what FileMap.ReadFile + Convert.ToDouble do,
+        // FrmMain.cs:1005-1009): text = File.ReadAllBytes of the files one after the other, each ending with '\n';
+        // seg_off [nseg + 1] their offsets (null: one file).  rows == null / d_rows == IntPtr.Zero counts the lines;
+        // VCP_ERR_UNSUPPORTED (-8) means bytes outside the device reader's set: read that file the old way.  err [3]
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_parse_scan_text(IntPtr ctx, byte[] text, ulong nbytes, ulong[] seg_off,
+            int nseg, long cap, double[] rows, int[] group, long[] seg_first, out long n, out long n_host, long[] err);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_parse_scan_text_dev(IntPtr ctx, byte[] text, ulong nbytes, ulong[] seg_off,
+            int nseg, long cap, IntPtr d_rows, IntPtr d_group, long[] seg_first, out long n, out long n_host, long[] err);
+
         // order statistics per cluster or group (vcp.h: vcp_cluster_quantiles; per list what Tools.GetGroupingManOrMin,
         // Tools.cs:468-497, takes over all lists): values[i * stride], group 0 = none; counts may be null
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_quantiles(IntPtr ctx, double[] values, long stride,

@@ -1,5 +1,6 @@
 """The reference's text formats on either side of the path (host side; the numeric work of an import runs on the
-GPU through vcp_import_convert, or through vcp_import_compact where the result stays on the device or carries counts).
+GPU through vcp_import_convert, or through vcp_import_compact where the result stays on the device or carries counts;
+parse_scan_text / read_scan_text_fast / read_folder_resident read the scan files' text on the GPU as well).
 
 * scan files          one point per line, `motor_x<TAB>motor_y<TAB>Distance` -- what MainForm.AddFolder reads
                       (FrmMain.cs:1005-1009 via FileMap.ReadFile, BaseClass/FileMap.cs:16-33) and what
@@ -121,6 +122,202 @@ def import_scan_resident(rows, group=None, x_angle=0.0, y_angle=0.0, xdir=2, ydi
                                     src.data_ptr(), count.data_ptr(), gout.data_ptr(), row_to.data_ptr())
     return dict(motor=motor[:m], xyz=xyz[:m], dist=dist[:m], src=src[:m], count=count[:m], group=gout[:m],
                 row_to=row_to[:n], m=m, duplicates=dup)
+
+
+# ---- the device reader of scan files (vcp_parse_scan_text) -------------------------------------------------------------
+class ScanTextError(ValueError):
+    """A bad line found by the device reader: .line (1-based within its file), .segment (the file's number), .kind
+    (1 = fewer than three fields, 2 = not a number)."""
+
+    def __init__(self, line, segment, kind, name=None):
+        self.line, self.segment, self.kind = int(line), int(segment), int(kind)
+        what = "expected motor_x<TAB>motor_y<TAB>Distance" if self.kind == 1 else "not a number"
+        super().__init__("%s:%d: %s" % (name if name is not None else "segment %d" % self.segment, self.line, what))
+
+
+def _join_segments(data):
+    """One bytes object and seg_off for a bytes object or a list of them; a non-empty file without a final '\n' gets
+    one ("...\r" becomes "...\r\n", still one terminator)."""
+    parts = [data] if isinstance(data, (bytes, bytearray, memoryview)) else list(data)
+    parts = [bytes(p) for p in parts]
+    parts = [p if (not p or p.endswith(b"\n")) else p + b"\n" for p in parts]
+    seg_off = np.zeros(len(parts) + 1, np.uint64)
+    seg_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+    return b"".join(parts), seg_off
+
+
+def parse_scan_text(data, resident=False, ctx=None):
+    """The bytes of one scan file, or a list with the bytes of several, parsed on the GPU.  Returns dict(rows [n, 3]
+    float64, group [n] int32 = the file of every row, seg_first [files + 1], n, n_host = the lines whose numbers the host
+    had to read): numpy arrays, or with resident=True torch tensors on the context's device, the layout
+    import_scan_resident takes.  rows equal read_scan_text's bit for bit.  A bad line raises ScanTextError; bytes outside
+    the device reader's set raise _native.VcpError with code -8 (VCP_ERR_UNSUPPORTED) and .err[0] = the offset."""
+    text, seg_off = _join_segments(data)
+    return _parse_joined(text, seg_off, resident, ctx)
+
+
+def _parse_joined(text, seg_off, resident, ctx):
+    """parse_scan_text on the joined text (bytes or a uint8 numpy array) and its seg_off."""
+    from . import _native, runtime
+    ctx = ctx or runtime.default_context()
+    try:
+        if not resident:
+            return ctx.parse_scan_text(text, seg_off) if len(seg_off) > 1 else dict(
+                rows=np.zeros((0, 3)), group=np.zeros(0, np.int32), seg_first=np.zeros(1, np.int64), n=0, n_host=0)
+        import torch
+        # Room for one line per 16 bytes (an F6 line has 27 or more), so that the text is uploaded once; a text of shorter
+        # lines comes back with VCP_ERR_INDEX and its n, and is parsed again with exactly that room.
+        cap = len(text) // 16 + 1024
+        res = dict(seg_first=np.zeros(len(seg_off), np.int64), n=0, n_host=0)
+        while len(seg_off) > 1 and len(text) > 0:
+            rows = torch.empty((cap, 3), dtype=torch.float64, device="cuda")
+            group = torch.empty(cap, dtype=torch.int32, device="cuda")
+            torch.cuda.current_stream().synchronize()    # the library runs on the context's stream, not on torch's
+            try:
+                res = ctx.parse_scan_text_dev(text, cap, rows.data_ptr(), group.data_ptr(), seg_off)
+                break
+            except _native.VcpError as e:
+                if e.code != -4:
+                    raise
+                cap = e.n
+        n = res["n"]
+        if n == 0:
+            rows = torch.empty((0, 3), dtype=torch.float64, device="cuda")
+            group = torch.empty(0, dtype=torch.int32, device="cuda")
+        elif cap > n + n // 4:                             # do not keep the unused room alive
+            rows, group = rows[:n].clone(), group[:n].clone()
+        return dict(rows=rows[:n], group=group[:n], seg_first=res["seg_first"], n=n, n_host=res["n_host"])
+    except _native.VcpError as e:
+        if e.code == -1 and getattr(e, "err", (0, 0, 0))[2] in (1, 2):
+            raise ScanTextError(*e.err) from None
+        raise
+
+
+def read_scan_text_fast(path, ctx=None):
+    """read_scan_text with the parse on the GPU: the same array, the same ValueError text; a file with bytes the device
+    reader does not take goes through read_scan_text."""
+    from . import _native
+    with open(path, "rb") as f:
+        data = f.read()
+    try:
+        return parse_scan_text(data, ctx=ctx)["rows"]
+    except ScanTextError as e:
+        raise ValueError(str(ScanTextError(e.line, e.segment, e.kind, name=path))) from None
+    except _native.VcpError as e:
+        if e.code != -8:
+            raise
+        return read_scan_text(path)
+
+
+def _rows_from_bytes(data, name, line0=0):
+    """read_scan_text on bytes already in memory (the same decoding, line splitting and errors); line0 = the lines of
+    the file that precede them."""
+    import io as _io
+    rows = []
+    text = _io.TextIOWrapper(_io.BytesIO(data), encoding="gb2312", errors="replace").read()
+    for ln, line in enumerate(text.splitlines(), line0 + 1):
+        parts = line.split("\t")
+        if len(parts) < 3:
+            raise ValueError("%s:%d: expected motor_x<TAB>motor_y<TAB>Distance" % (name, ln))
+        try:
+            rows.append((float(parts[0]), float(parts[1]), float(parts[2])))
+        except ValueError:
+            raise ValueError("%s:%d: not a number" % (name, ln))
+    return np.array(rows, dtype=np.float64).reshape(-1, 3)
+
+
+def _batches(files, max_bytes):
+    """Pieces (file number, bytes or None = the whole file, lines of the file before the piece, length) in order,
+    grouped so that no group exceeds max_bytes with the '\n' a piece may receive; a larger file is read here and cut
+    after a line end."""
+    batch, size = [], 0
+    for k, f in enumerate(files):
+        data, line0, length = None, 0, os.path.getsize(f)
+        if length + 1 > max_bytes:
+            with open(f, "rb") as fh:
+                data = fh.read()
+            while len(data) + 1 > max_bytes:
+                cut = max(data.rfind(b"\n", 0, max_bytes - 1), data.rfind(b"\r", 0, max_bytes - 2)) + 1
+                if cut <= 0:
+                    raise ValueError("%s: a line longer than %d bytes" % (f, max_bytes))
+                if data[cut - 1:cut] == b"\r" and data[cut:cut + 1] == b"\n":
+                    cut += 1                                # never between the two bytes of one terminator
+                if batch:
+                    yield batch
+                    batch, size = [], 0
+                yield [(k, data[:cut], line0, cut)]
+                line0 += data.count(b"\n", 0, cut) + data.count(b"\r", 0, cut) - data.count(b"\r\n", 0, cut)
+                data = data[cut:]
+            length = len(data)
+        if size + length + 1 > max_bytes and batch:
+            yield batch
+            batch, size = [], 0
+        batch.append((k, data, line0, length))
+        size += length + 1
+    if batch:
+        yield batch
+
+
+def _load_batch(batch, files):
+    """The pieces of a batch one after the other in ONE uint8 array (a whole file is read straight into it), every
+    non-empty piece ending with '\n'; returns (text, seg_off)."""
+    buf = np.empty(sum(length + 1 for _, _, _, length in batch), np.uint8)
+    view, o, seg_off = memoryview(buf), 0, np.zeros(len(batch) + 1, np.uint64)
+    for i, (k, data, _, length) in enumerate(batch):
+        if data is None:
+            with open(files[k], "rb") as fh:
+                got = fh.readinto(view[o:o + length])
+        else:
+            got = len(data)
+            view[o:o + got] = data
+        o += got
+        if got and buf[o - 1] != 10:
+            buf[o] = 10                                    # "...\r" becomes "...\r\n": still one terminator
+            o += 1
+        seg_off[i + 1] = o
+    return buf[:o], seg_off
+
+
+def read_folder_resident(files, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe=True, by_file=False, ctx=None,
+                         max_bytes=(1 << 32) - 4096):
+    """File -> resident import without a host parse: the files' bytes are uploaded in batches below 4 GiB (a larger file
+    is cut at a line end), parsed on the GPU and handed to import_scan_resident as device tensors.  by_file: the file
+    number is the group (duplicates are classes within a file, AddFolder's typpe 3 / 4); otherwise one class space over
+    all files (typpe 1 / 2).  Returns import_scan_resident's dict plus rows [n, 3], file [n] (int32, the file of every
+    raw row), n and n_host.  A batch with bytes the device reader does not take is parsed on the host, as read_scan_text
+    does, and uploaded.  A bad line raises the ValueError read_scan_text raises."""
+    import torch
+    from . import _native, runtime
+    ctx = ctx or runtime.default_context()
+    files = list(files)
+    rows, group, n_host = [], [], 0
+    for batch in _batches(files, max_bytes):
+        ks = np.array([piece[0] for piece in batch], np.int32)
+        text, seg_off = _load_batch(batch, files)
+        try:
+            r = _parse_joined(text, seg_off, True, ctx)
+        except ScanTextError as e:
+            k = int(ks[e.segment])      # a piece of a cut file starts past the file's first line
+            raise ValueError(str(ScanTextError(e.line + batch[e.segment][2], k, e.kind, name=files[k]))) from None
+        except _native.VcpError as e:
+            if e.code != -8:
+                raise
+            host = [_rows_from_bytes(text[int(seg_off[i]):int(seg_off[i + 1])].tobytes(), files[piece[0]], piece[2])
+                    for i, piece in enumerate(batch)]
+            fk = [np.full(len(h), k, np.int32) for h, k in zip(host, ks)]
+            rows.append(torch.from_numpy(np.concatenate(host).reshape(-1, 3)).cuda())
+            group.append(torch.from_numpy(np.concatenate(fk)).cuda())
+            continue
+        rows.append(r["rows"])
+        group.append(torch.from_numpy(ks).cuda()[r["group"].long()])
+        n_host += r["n_host"]
+    if not rows:
+        rows, group = [torch.zeros((0, 3), dtype=torch.float64, device="cuda")], [torch.zeros(0, dtype=torch.int32, device="cuda")]
+    d_rows = torch.cat(rows) if len(rows) > 1 else rows[0]
+    d_file = torch.cat(group) if len(group) > 1 else group[0]
+    res = import_scan_resident(d_rows, d_file if by_file else None, x_angle, y_angle, xdir, ydir, dedupe, ctx=ctx)
+    res.update(rows=d_rows, file=d_file, n=len(d_rows), n_host=n_host)
+    return res
 
 
 def add_fixed_folder(files, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, typpe=3, ctx=None):
