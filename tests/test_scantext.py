@@ -5,6 +5,7 @@ import random
 
 import pytest
 
+import scantext_corpus as K
 import scantext_ref as R
 from vtkcloudpoint_amd import _native as N
 
@@ -18,20 +19,15 @@ def check(s):
     return want_c
 
 
-EDGE = ["1.", ".5", "+.5e-3", " 1 ", "-0", "1e", ".", "e5", "+ 1", "", "  ", "INF", "-Infinity", "-nan", "0x10", "1d5",
-        "1,5"]
-
-
-@pytest.mark.parametrize("s", EDGE)
+@pytest.mark.parametrize("s", K.EDGE)
 def test_edge_list(s):
     check(s)
 
 
 def test_edge_classes_as_stated():
     """The classes of the edge list by hand, so that a reference that called everything class 0 would not pass."""
-    want = {"1.": 1, ".5": 1, "+.5e-3": 1, " 1 ": 1, "-0": 1, "1e": 0, ".": 0, "e5": 0, "+ 1": 0, "": 0, "  ": 0, "INF": 3,
-            "-Infinity": 3, "-nan": 3, "0x10": 0, "1d5": 0, "1,5": 0}
-    for s, c in want.items():
+    assert sorted(K.EDGE_CLASSES) == sorted(K.EDGE)
+    for s, c in K.EDGE_CLASSES.items():
         assert R.field_class(s)[0] == c and N.selftest_parse_field(s)[0] == c, s
     assert R.bits(N.selftest_parse_field("-0")[1]) == 0x8000000000000000
     assert R.bits(N.selftest_parse_field("nan")[1]) == 0x7FF8000000000000
@@ -40,14 +36,8 @@ def test_edge_classes_as_stated():
 
 
 def test_class_boundaries():
-    p53 = 2 ** 53
-    cases = {
-        str(p53): 1, str(p53 + 1): 2, "%de22" % p53: 1, "%de23" % p53: 3, "%de-22" % p53: 1, "%de-23" % p53: 3,
-        "1e22": 1, "1e23": 3, "1e-22": 1, "1e-23": 3, "3e19": 1, "3e-19": 1,
-        "9" * 19: 2, "9" * 20: 3, "1" + "0" * 19: 3, "9" * 19 + "e19": 2, "9" * 19 + "e20": 3, "9" * 19 + "e-19": 2,
-        "9" * 19 + "e-20": 3, "0." + "9" * 19: 2, "0.0" + "9" * 19: 3, str(p53 + 1) + "e19": 2, str(p53 + 1) + "e-19": 2,
-        str(p53 + 1) + "e20": 3, "0e999999999999999999999": 1, "-0.000e-5": 1, "1.e5": 1, "1.E+05": 1, "00012.500": 1,
-    }
+    cases = K.boundaries()
+    assert len(cases) == 29
     for s, c in cases.items():
         assert check(s) == c, s
 
@@ -56,66 +46,112 @@ def test_halfway_cases_of_binary64():
     """Decimal strings of at most 19 digits that lie exactly between two neighbouring doubles, and their neighbours one
     unit of the last digit away: ties to even, and the sticky bit of the division."""
     n = 0
-    for m in (2 ** 53 + 1, 2 ** 53 + 3, 2 ** 54 + 2, 2 ** 54 + 6, 2 ** 60 + 2 ** 7, 2 ** 60 + 3 * 2 ** 7, 2 ** 63 + 2 ** 10,
-              2 ** 63 + 3 * 2 ** 10):
-        for d in (-1, 0, 1):
-            assert check(str(m + d)) == (1 if m + d <= 2 ** 53 else 2)
-            n += 1
-    # m + 1/2 for odd and even m of 53 bits, written exactly: (2m + 1) * 5^k / 10^k with k fraction digits
-    for m in (2 ** 52 + 1, 2 ** 52 + 2, 2 ** 52 + 12345, 2 ** 53 - 2):
-        for sh in (1, 2, 3, 4, 5):                 # the tie at m + 1/2 scaled by 2^-sh: sh + 1 fraction digits
-            num = (2 * m + 1) * 5 ** (sh + 1)      # value = num / 10^(sh + 1), exactly (2m + 1) / 2^(sh + 1)
-            s = str(num)
-            if len(s) > 19:
-                continue
-            for d in (-1, 0, 1):
-                t = str(num + d)
-                assert check(t[:-(sh + 1)] + "." + t[-(sh + 1):]) == 2
-                assert check(t + "e-%d" % (sh + 1)) == 2
-                n += 2
+    for s, c in K.halfway():
+        assert check(s) == c, s
+        n += 1
     assert n >= 60
 
 
 def test_long_and_extreme_fields():
-    assert check("0" * 400 + "1.5") == 1
-    assert check("0." + "0" * 400 + "15") == 3
-    assert check("0" * 400) == 1
-    for s in ("1e400", "1e-400", "-1e400", "-1e-400", "4.9e-324", "2.4703282292062327e-324", "2.4703282292062328e-324",
-              "2.2250738585072011e-308", "1.7976931348623157e308", "1.7976931348623159e308", "17976931348623157" + "0" * 292,
-              "1" + "0" * 30, "123456789012345678901234567890", "0.1" + "0" * 30 + "1", "9007199254740993.00000000000000001"):
-        assert check(s) == 3, s
+    cases = K.long_and_extreme()
+    assert len(cases) == 18 and cases[0] == ("0" * 400 + "1.5", 1) and sum(c == 3 for _, c in cases) == 16
+    for s, c in cases:
+        assert check(s) == c, s
 
 
 def test_random_w_e_strings():
     """200 000 seeded "<w>e<e>" strings with 1 to 19 digits and |e| <= 19."""
-    rng = random.Random(20240611)
+    strings = K.random_w_e()
+    assert len(strings) == 200000
     seen = {1: 0, 2: 0}
-    for _ in range(200000):
-        nd = rng.randint(1, 19)
-        w = rng.randint(10 ** (nd - 1), 10 ** nd - 1)
-        seen[check("%de%d" % (w, rng.randint(-19, 19)))] += 1
+    for s in strings:
+        seen[check(s)] += 1
     assert seen[1] > 100000 and seen[2] > 20000       # 17 to 19 digits are class 2: 3 lengths of 19
 
 
 def test_random_17_to_19_digit_strings():
     """The class-2 share of the family above is one in six; 50 000 more with 17 to 19 digits, as repr and %.18e write
     them (a point inside the digits)."""
-    rng = random.Random(99)
+    strings = K.random_17_to_19_digits()
+    assert len(strings) == 50000
     n2 = 0
-    for _ in range(50000):
-        nd = rng.randint(17, 19)
-        w = str(rng.randint(10 ** (nd - 1), 10 ** nd - 1))
-        e = rng.randint(-19, 19) + (nd - 1)
-        n2 += check("%s.%se%+03d" % (w[0], w[1:], e)) == 2
+    for s in strings:
+        n2 += check(s) == 2
     assert n2 > 45000
 
 
 def test_f6_strings():
     """20 000 strings of the form the reference writes ("F6"): all class 1."""
-    rng = random.Random(7)
-    for _ in range(20000):
-        v = rng.choice((rng.uniform(-360, 360), rng.uniform(0, 1000), rng.uniform(-1e6, 1e6)))
-        assert check("%.6f" % v) == 1
+    strings = K.f6()
+    assert len(strings) == 20000
+    for s in strings:
+        assert check(s) == 1
+
+
+def test_just_below_a_power_of_two():
+    """2^k * (1 - 2^-55), k = -3 .. 126, in 19 digits: class 2, and the rounding carries out of the mantissa to 2^k."""
+    strings = K.below_power_of_two()
+    assert len(strings) == 130
+    for k, s in zip(range(-3, 127), strings):
+        assert check(s) == 2, s
+        assert R.bits(N.selftest_parse_field(s)[1]) == (k + 1023) << 52, s
+        assert R.bits(N.selftest_parse_field("-" + s)[1]) == 1 << 63 | (k + 1023) << 52, s
+
+
+def test_ties_on_the_product_path():
+    """w * 10^z exactly between two doubles, and w - 1, w + 1: the exact 128-bit product and the tie rule."""
+    strings = K.product_ties()
+    assert len(strings) >= 1000 and len(strings) % 3 == 0
+    for i in range(0, len(strings), 3):
+        below, tie, above = (N.selftest_parse_field(s)[1] for s in strings[i:i + 3])
+        assert all(check(s) == 2 for s in strings[i:i + 3])
+        assert R.bits(above) - R.bits(below) == 1 and R.bits(tie) % 2 == 0, strings[i + 1]     # neighbours; the even one
+
+
+def test_census_of_the_corpus():
+    """What tests/test_scantext_gpu.py hands the device: it cannot pass by being empty-handed."""
+    fields = K.value_fields()
+    assert len(set(fields)) == len(fields) and all(R.field_class(s)[0] in (1, 2, 3) for s in fields)
+    c = K.census(fields)
+    print(len(fields), sorted(c.items()))
+    for cell in ((1, 1), (1, -1), (2, 1), (2, -1)):
+        assert c[cell] >= 40000, (cell, c[cell])
+    ties = K.product_ties()
+    assert len(ties) >= 1000 and K.census(ties) == {(2, 1): len(ties)}
+    assert all(R.NUMBER.match(s).group(5) in "1234567" for s in ties)                 # e10 > 0
+    assert len(K.below_power_of_two()) == 130 and set(K.census(K.below_power_of_two())) <= {(2, 1), (2, -1)}
+    inside = set(fields)
+    assert all(s in inside for s in ties) and all(s in inside for s in K.below_power_of_two())
+    assert all((s in inside) == (c0 != 0) for s, c0 in K.EDGE_CLASSES.items())
+    text = K.lines(fields)
+    assert text.count(b"\n") == (len(fields) + 2) // 3 and text.endswith(b"\n") and R.supported(text)
+    back = [f.decode() for ln in text.split(b"\n")[:-1] for f in ln.split(b"\t")]
+    assert back[:len(fields)] == fields and all(f == "1" for f in back[len(fields):])
+
+
+def fuzz_covers(s, count):
+    """The conditions on fuzz_scantext.summary, for this file and for the bounded sweep of tests/test_scantext_gpu.py."""
+    return (s["cases"] == count and all(s["defects"][d] >= 1 for d in ("few", "class0", "byte", "both"))
+            and s["no_line"] >= 1 and s["over_stage"] >= 1 and s["many_segments"] >= 1 and s["class2_pos"] >= 1
+            and s["class2_neg"] >= 1 and s["host_lines"] >= 1)
+
+
+def test_the_fuzz_list_is_a_function_of_the_seed_and_not_empty_handed():
+    import os
+    import re
+    import fuzz_scantext as F
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "vcp.h")) as f:
+        assert re.search(r"^#define VCP_TXT_CHUNK %d\b" % F.CHUNK, f.read(), flags=re.M)
+    with open(os.path.join(root, "vtkcloudpoint_amd", "csrc", "scantext.hip")) as f:
+        assert re.search(r"^constexpr int STAGE_BYTES = %d;" % F.STAGE_BYTES, f.read(), flags=re.M)
+    count, seed = F.SUITE
+    lst = F.cases(count, seed)
+    assert lst == F.cases(count, seed) and lst != F.cases(count, seed + 1)
+    s = F.summary(lst, [F.expect(c) for c in lst])
+    print(s)
+    assert fuzz_covers(s, count), s
+    assert 0 < s["resident"] < count
 
 
 def test_argument_errors():

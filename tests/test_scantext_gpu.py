@@ -1,20 +1,37 @@
 """vcp_parse_scan_text on the MI355X against io.read_scan_text on a temporary file: rows by their bits (NaN signs and -0
 count), group, seg_first, n, n_host, the three errors with read_scan_text's own ValueError text, the fallback, count-only,
 independence from the context's history, read_folder_resident and the caller's stream -- on the smallest texts at which
-each mechanism can go wrong (a chunk is VCP_TXT_CHUNK = 16384 bytes, a parse workgroup 256 lines, its LDS span 32 KiB)."""
+each mechanism can go wrong (a chunk is VCP_TXT_CHUNK = 16384 bytes, a parse workgroup 256 lines, its LDS span 32 KiB).
+The second half holds the device compile of csrc/scantext.hpp to the corpus of tests/scantext_corpus.py under both parse
+kernels, and walks the staging decision, the indexing kernels' lane, wave and chunk boundaries, the host list and the
+segment search at size; tests/fuzz_scantext.py supplies a bounded randomised sweep."""
+import os
 import random
+import re
 
 import numpy as np
 import pytest
 import torch
 
+import scantext_corpus as K
 import scantext_ref as R
 from vtkcloudpoint_amd import _native as N
 from vtkcloudpoint_amd import io as vio
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 16384
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _constant(path, pattern):
+    with open(os.path.join(ROOT, *path)) as f:
+        return int(re.search(pattern, f.read(), flags=re.M).group(1))
+
+
+# read out of the sources, so that a change of either moves the tests with it
+CHUNK = _constant(("include", "vcp.h"), r"^#define VCP_TXT_CHUNK (\d+)\b")
+STAGE_BYTES = _constant(("vtkcloudpoint_amd", "csrc", "scantext.hip"), r"^constexpr int STAGE_BYTES = (\d+);")
+TT = 256                                                         # lines per parse workgroup
 
 
 def u64(a):
@@ -294,3 +311,278 @@ def test_stream_contract(tmp_path, chunk_text):
         assert group.cpu().tolist() == [0] * (n - 1) + [1]
     finally:
         rig.close()
+
+
+# ---- the device compile of csrc/scantext.hpp on the corpus of tests/test_scantext.py, both parse kernels ---------------
+KERNELS = pytest.mark.parametrize("direct", [False, True], ids=["staged", "direct"])
+
+
+def _kernel(monkeypatch, direct):
+    """The library reads VCP_TXT_DIRECT at every call: unset = k_txt_parse<true>, "1" = k_txt_parse<false>."""
+    if direct:
+        monkeypatch.setenv("VCP_TXT_DIRECT", "1")
+    else:
+        monkeypatch.delenv("VCP_TXT_DIRECT", raising=False)
+
+
+def _split(text):
+    """The lines of a text of supported bytes, as the contract cuts them."""
+    parts = re.split(b"\r\n|\n|\r", text)
+    return parts[:-1] if parts and parts[-1] == b"" else parts
+
+
+def _host_lines(text):
+    """Lines with a class-3 field among the first three, by the restatement."""
+    return sum(any(R.field_class(f.decode("ascii"))[0] == 3 for f in ln.split(b"\t")[:3]) for ln in _split(text))
+
+
+def _difference(text, got, want):
+    """None, or the first field whose bits differ: its text, the bits wanted and the bits got."""
+    g, w = u64(got), u64(want)
+    if g.shape != w.shape:
+        return "%d rows for %d" % (len(g), len(w))
+    d = np.argwhere(g != w)
+    if len(d) == 0:
+        return None
+    i, k = (int(x) for x in d[0])
+    return "line %d field %d %r: want %016x, got %016x (%d fields differ)" % (
+        i + 1, k, _split(text)[i].split(b"\t")[k][:60], int(w[i, k]), int(g[i, k]), len(d))
+
+
+def held(ctx, text, want=None, n_host=None):
+    """Host form and resident form against _rows_from_bytes, by bits; n_host against the restatement's classes."""
+    want = vio._rows_from_bytes(text, "text") if want is None else want
+    n_host = _host_lines(text) if n_host is None else n_host
+    got = vio.parse_scan_text(text, ctx=ctx)
+    bad = _difference(text, got["rows"], want)
+    assert bad is None, "host form: " + bad
+    assert got["n"] == len(want) and got["n_host"] == n_host
+    res = vio.parse_scan_text(text, resident=True, ctx=ctx)
+    bad = _difference(text, res["rows"].cpu().numpy(), want)
+    assert bad is None, "resident form: " + bad
+    assert res["n"] == len(want) and res["n_host"] == n_host
+    return got
+
+
+@pytest.fixture(scope="module")
+def corpus():
+    """(text, rows of the reference, lines with a class-3 field): computed once, left unchanged."""
+    text = K.lines(K.value_fields())
+    return text, vio._rows_from_bytes(text, "corpus"), _host_lines(text)
+
+
+@KERNELS
+def test_device_evaluates_the_host_corpus(vcp_ctx, corpus, monkeypatch, direct):
+    """Every value string of tests/scantext_corpus.py (its census is asserted in tests/test_scantext.py), three to a
+    line, in one call per kernel: both branches of eval_class2, ties, the sticky bit, the mantissa carry, the class
+    boundaries and class 1 beyond F6 text, as the device compiler emits them."""
+    _kernel(monkeypatch, direct)
+    text, want, n_host = corpus
+    assert len(want) == (len(K.value_fields()) + 2) // 3 and n_host >= 7
+    held(vcp_ctx, text, want, n_host)
+
+
+def test_chunk_straddles_direct(vcp_ctx, tmp_path, chunk_text, monkeypatch):
+    _kernel(monkeypatch, True)
+    assert same(vcp_ctx, tmp_path, chunk_text, n_host=0)["n"] > 4 * 256
+
+
+@KERNELS
+def test_class_zero_fields_in_every_position(vcp_ctx, tmp_path, monkeypatch, direct):
+    _kernel(monkeypatch, direct)
+    zero = [s for s in K.EDGE if K.EDGE_CLASSES[s] == 0]
+    assert len(zero) == 9
+    good = b"1\t2\t3\n"
+    for s in zero:
+        for k in range(3):
+            f = [b"1.5", b"-2", b"3e2"]
+            f[k] = s.encode()
+            msg = _both_raise(vcp_ctx, tmp_path, good * 2 + b"\t".join(f) + b"\n" + good)
+            assert msg.endswith(":3: not a number"), (s, k, msg)
+
+
+# ---- the staging decision of k_txt_parse<true> ------------------------------------------------------------------------
+def _starts(text):
+    return [0] + [m.end() for m in re.finditer(b"\r\n|\n|\r", text)]
+
+
+_TIES = []
+
+
+def _class2_line(i):
+    """A product tie, a halfway case of the division and a mantissa carry on one line."""
+    if not _TIES:
+        _TIES.extend((K.product_ties(), [s for s, c in K.halfway() if c == 2], K.below_power_of_two()))
+    t, h, p = _TIES
+    return ("%s\t%s\t%s\n" % (t[(3 * i + 1) % len(t)], h[(7 * i) % len(h)], p[i % 130])).encode()
+
+
+def _staging_text(r, span):
+    """Workgroup 0: 256 lines of r (mod 16) bytes in all; workgroup 1: 256 lines whose span from line_start[256] & ~15 is
+    `span`, its first and last lines class-2 ties; workgroup 2: a short tail."""
+    rng = random.Random(16 * span + r)
+    wg0 = bytearray(b"".join(_line(rng, k) for k in range(TT - 1)))
+    body = b"1.25\t-0\t7"
+    wg0 += body + b" " * ((r - len(wg0) - len(body) - 1) % 16) + b"\n"
+    assert len(wg0) % 16 == r
+    room = span - r                                              # the bytes of workgroup 1
+    ls = [_class2_line(r)] + [_line(rng, k) for k in range(TT - 2)] + [_class2_line(r + 16)]
+    spare = room - sum(len(x) for x in ls)
+    assert spare >= 2 * TT
+    out = bytearray()
+    for k, ln in enumerate(ls):
+        p = spare // TT + (k < spare % TT)                       # blanks behind the third number, then an ignored field
+        term = ln[len(ln.rstrip(b"\r\n")):]
+        out += ln[:len(ln) - len(term)] + b" " * (p // 3) + b"\t" + b"z" * (p - p // 3 - 1) + term
+    assert len(out) == room
+    text = bytes(wg0 + out) + b"".join(_line(rng, k) for k in range(5))
+    st = _starts(text)
+    assert len(st) == 2 * TT + 5 + 1 and st[2 * TT] - (st[TT] & ~15) == span and st[TT] & 15 == r
+    return text
+
+
+@pytest.mark.parametrize("delta", [-1, 0, 1])
+def test_staging_boundary(vcp_ctx, delta):
+    """A workgroup whose span is STAGE_BYTES - 1, STAGE_BYTES (both staged) or STAGE_BYTES + 1 (read from global memory),
+    at each of the sixteen residues of line_start[j0] & 15."""
+    for r in range(16):
+        text = _staging_text(r, STAGE_BYTES + delta)
+        held(vcp_ctx, text, n_host=0)
+
+
+def test_staged_and_unstaged_workgroups_alternate(vcp_ctx):
+    """About 2 000 lines: the lines of every other workgroup carry 150 to 400 bytes (256 of them exceed STAGE_BYTES),
+    the others are plain, so that one launch holds both kinds side by side."""
+    rng = random.Random(41)
+    ls = []
+    for k in range(2000):
+        ln = _class2_line(k) if k % 5 == 0 else _line(rng, k)
+        if (k // TT) % 2:
+            term = ln[len(ln.rstrip(b"\r\n")):]
+            p = rng.randint(150, 400) - len(ln)
+            ln = ln[:len(ln) - len(term)] + b" " * (p // 4) + b"\t" + b"y" * (p - p // 4 - 1) + term
+        ls.append(ln)
+    text = b"".join(ls)
+    st = _starts(text)
+    spans = [st[min(j + TT, 2000)] - (st[j] & ~15) for j in range(0, 2000, TT)]
+    kinds = [s <= STAGE_BYTES for s in spans]
+    assert kinds == [k % 2 == 0 for k in range(len(spans))]
+    held(vcp_ctx, text, n_host=0)
+
+
+# ---- the indexing kernels at lane (64 bytes), wave (4 096) and chunk boundaries ---------------------------------------
+@pytest.mark.parametrize("term", [b"\n", b"\r\n", b"\r"])
+def test_terminator_on_lane_wave_and_chunk_boundaries(vcp_ctx, term):
+    for edge in (64, 4096, CHUNK):
+        for at in range(edge - 2, edge + 3):                     # the terminator's first byte
+            rng = random.Random(at)
+            buf = _pad_line(_fill(bytearray(), rng, at), at + len(term), term)
+            assert buf[at:at + len(term)] == term and buf[at - 1:at] not in (b"\r", b"\n")
+            text = bytes(buf) + b"".join(_line(rng, k) for k in range(3)) + b"9\t8\t7\n"
+            held(vcp_ctx, text, n_host=0)
+
+
+def test_texts_of_exactly_a_lane_and_a_chunk(vcp_ctx):
+    for nbytes in (63, 64, 65, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK):
+        for term in (b"\n", b"\r\n"):
+            rng = random.Random(nbytes)
+            text = bytes(_pad_line(_fill(bytearray(), rng, nbytes), nbytes, term))
+            assert len(text) == nbytes
+            held(vcp_ctx, text, n_host=0)
+            cnt = vcp_ctx.parse_scan_text(text, count_only=True)
+            assert cnt["n"] == len(_split(text))
+
+
+def test_unsupported_byte_at_lane_and_chunk_boundaries(vcp_ctx):
+    rng = random.Random(12)
+    wide = lambda k: b"1.25\t-0\t7\t" + b"z" * k + b"\n"         # an ignored fourth field of k bytes
+    buf = bytearray(wide(100))
+    buf = _fill(buf, rng, CHUNK - 64) + wide(200)
+    buf = _fill(buf, rng, 2 * CHUNK + 3000)
+    buf += wide(100 + (20 - (len(buf) + 111)) % 64)
+    text = bytes(buf)
+    nbytes = len(text)
+    assert nbytes % 64 == 20 and nbytes > 2 * CHUNK
+    held(vcp_ctx, text, n_host=0)
+    last_lane = nbytes // 64 * 64 + 3
+    for at in (0, 63, 64, CHUNK - 1, CHUNK, nbytes - 2, last_lane):
+        assert at == 0 or text[at:at + 1] == b"z"
+        for second in (None, nbytes - 2):
+            if second is not None and second // CHUNK <= at // CHUNK:
+                continue
+            t = bytearray(text)
+            t[at] = 0x85
+            if second is not None:
+                t[second] = 0x7F
+            with pytest.raises(N.VcpError) as e:
+                vcp_ctx.parse_scan_text(bytes(t))
+            assert e.value.code == -8 and e.value.err[0] == at, (at, second, e.value.err)
+            assert R.supported(t[:at]) and not R.supported(t[:at + 1])
+
+
+# ---- the host list and the segments at size --------------------------------------------------------------------------
+def _host_line(i):
+    three = ("1e400", "-1e-400", "nan", "-inf", "%d" % (10 ** 24 + 7919 * i), "%de-320" % (i + 1), "-1e%d" % (400 + i),
+             "0.%030d" % (i + 1))[i % 8]
+    f = ["%d.5" % i, "-%d.25e-3" % i, "%d" % (7 * i)]
+    f[i % 3] = three
+    assert R.field_class(three)[0] == 3
+    return "\t".join(f).encode() + (b"\n", b"\r\n", b"\r")[i % 3]
+
+
+def test_a_thousand_host_lines(vcp_ctx):
+    host = [_host_line(i) for i in range(1000)]
+    text = b"".join(host)
+    got = held(vcp_ctx, text, n_host=1000)
+    assert len(np.unique(u64(got["rows"]), axis=0)) == 1000
+    rng = random.Random(77)
+    mixed = b"".join(b"".join(_line(rng, 3 * i + k) for k in range(3)) + host[i] for i in range(1000))
+    held(vcp_ctx, mixed, n_host=1000)
+
+
+def test_a_thousand_segments(vcp_ctx):
+    rng = random.Random(1000)
+    segs = []
+    for k in range(1000):
+        n = 0 if (k < 4 or k >= 990 or rng.random() < 0.32) else rng.randint(1, 5)
+        if k == 700:
+            n = 3
+        s = b"".join(_host_line(rng.randrange(1000)) if rng.random() < 0.05 else _line(rng, rng.randrange(3)) for _ in range(n))
+        if n and rng.random() < 0.3:
+            s = s.rstrip(b"\r\n") + rng.choice((b"", b"\r"))         # the wrapper appends the '\n'
+        segs.append(s)
+    assert 250 < sum(not s for s in segs) < 450
+    want = [vio._rows_from_bytes(s, "segment %d" % k) for k, s in enumerate(segs)]
+    counts = [len(w) for w in want]
+    text, seg_off = vio._join_segments(segs)
+    for resident in (False, True):
+        got = vio.parse_scan_text(segs, resident=resident, ctx=vcp_ctx)
+        rows, group = (got[k].cpu().numpy() if resident else got[k] for k in ("rows", "group"))
+        bad = _difference(text, rows, np.concatenate(want))
+        assert bad is None, bad
+        assert group.tolist() == [k for k, c in enumerate(counts) for _ in range(c)]
+        assert got["seg_first"].tolist() == [0] + np.cumsum(counts).tolist() and got["n"] == sum(counts)
+        assert got["n_host"] == _host_lines(text)
+    cnt = vcp_ctx.parse_scan_text(text, seg_off, count_only=True)
+    assert cnt["n"] == got["n"] and cnt["seg_first"].tolist() == got["seg_first"].tolist()
+    lines700 = _split(segs[700])
+    segs[700] = lines700[0] + b"\n" + b"1\tx\t3\n" + lines700[2] + b"\n"
+    with pytest.raises(N.VcpError) as e:
+        vcp_ctx.parse_scan_text(*vio._join_segments(segs))
+    assert e.value.code == -1 and e.value.err == (2, 700, 2)
+    with pytest.raises(vio.ScanTextError) as e:
+        vio.parse_scan_text(segs, ctx=vcp_ctx)
+    with pytest.raises(ValueError) as w:
+        vio._rows_from_bytes(segs[700], "segment 700")
+    assert str(e.value) == str(w.value)
+
+
+def test_bounded_fuzz(vcp_ctx):
+    """tests/fuzz_scantext.py: SUITE cases; what the list covers is asserted in tests/test_scantext.py as well."""
+    import fuzz_scantext as F
+    from test_scantext import fuzz_covers
+    count, seed = F.SUITE
+    lst = F.cases(count, seed)
+    s = F.summary(lst, [F.check(vcp_ctx, c) for c in lst])
+    print(s)
+    assert fuzz_covers(s, count), s
