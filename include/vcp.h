@@ -1220,6 +1220,48 @@ int vcp_parse_scan_text_dev(vcp_ctx* ctx, const char* text, uint64_t nbytes, con
  * with len > 0.  Needs no device and no context. */
 int vcp_selftest_parse_field(const char* s, int64_t len, double* v);
 
+/* -- export text on the device: resident rows in, the file's bytes out ------------------------------------
+ * The inverse of vcp_parse_scan_text: the lines the reference's exports write one Point3D at a time (BC/Tools.cs:233, 295,
+ * 341, 374: the filtered scan, the cluster export, the centroid export), built from columns that stay where they are.
+ *   line j     [id[r] TAB] a[r * stride_a] TAB b[r * stride_b] TAB c[r * stride_c] EOL with r = order[j], j = 0..m-1;
+ *              order == NULL: r = j, and m must equal n.  id == NULL: no id column.  Strides are in doubles, >= 1: the
+ *              columns of one [n, 3] array (stride 3), separate arrays, or the same array three times, all read in place.
+ *              eol 0 = "\n", 1 = "\r\n"
+ *   a number   the bytes of Python's '%.*f' % (bit, v), 0 <= bit <= 15: the exact binary value rounded to `bit` decimals,
+ *              ties to even; '-' whenever the sign bit is set (-0.0 and -1e-9 give -0.000000); no decimal point at
+ *              bit == 0; no leading zeros but the single 0.  Supported: v finite, |v| < 1e15.  An id prints as '%d'
+ *   order      m entries, repeats and subsets allowed.  The first j whose entry is outside [0, n): VCP_ERR_INDEX with
+ *              err = {j, entry}
+ *   text       a HOST buffer of cap bytes in BOTH forms; "_dev" means that d_id, d_a, d_b, d_c and d_order are device
+ *              pointers, read on the context's stream under the vcp_set_stream contract.  The bytes are built in the
+ *              workspace and copied down.  *nbytes is written whenever the inputs are valid; text == NULL is count-only;
+ *              *nbytes > cap: VCP_ERR_INDEX with *nbytes written, so that the caller can come back with room, text untouched
+ *   unsupported  the first line j, in output order, that holds a NaN, an infinity or a magnitude >= 1e15, and its first
+ *              such column: VCP_ERR_UNSUPPORTED with err = {j, column 0..2} (an integer device minimum); text untouched,
+ *              *nbytes not written.  There is no approximation and no host fallback in the library: callers format such a
+ *              call themselves.  A bad entry of order is reported before an unsupported value
+ * No line is longer than VCP_FMT_LINE_MAX bytes: an 11-byte id, three fields of at most 32 bytes ('-', 15 digits, '.',
+ * 15 digits: 10^15 itself appears only at bit 0, as 16 digits without a point), three tabs and "\r\n".
+ * Limits: a text of 2^32 bytes or more: VCP_ERR_TOO_LARGE, found from the exact 64-bit byte count.  m == 0: *nbytes = 0,
+ * VCP_OK.  VCP_ERR_ARG: NULL ctx, NULL nbytes, a NULL column with m > 0, a stride < 1, bit outside 0..15, eol outside
+ * 0..1, n < 0, m < 0, order == NULL with m != n.  err may be NULL.
+ * The result is a function of the input alone: integer minima are the only atomics that decide anything.  Workspace: 4
+ * bytes per 256 lines and the text (the host form: its inputs as well).  Timing phases: fmt_len, fmt_write, fmt_download
+ * (csrc/scanfmt.hip, csrc/scanfmt.hpp). */
+#define VCP_FMT_LINE_MAX 112
+int vcp_format_rows(vcp_ctx* ctx, const int32_t* id, const double* a, int64_t stride_a, const double* b, int64_t stride_b,
+                    const double* c, int64_t stride_c, const int64_t* order, int64_t n, int64_t m, int bit, int eol,
+                    char* text, uint64_t cap, uint64_t* nbytes, int64_t err[2]);
+int vcp_format_rows_dev(vcp_ctx* ctx, const int32_t* d_id, const double* d_a, int64_t stride_a, const double* d_b,
+                        int64_t stride_b, const double* d_c, int64_t stride_c, const int64_t* d_order, int64_t n, int64_t m,
+                        int bit, int eol, char* text, uint64_t cap, uint64_t* nbytes, int64_t err[2]);
+/* One number through the source the kernels compile (csrc/scanfmt.hpp): returns 1 with the field's bytes in out (no
+ * terminator) and their number in *len, or 0 for an unsupported v, nothing written.  VCP_ERR_ARG for a NULL out or len, bit
+ * outside 0..15, or cap smaller than the field (*len is written then, out is not).  Needs no device and no context. */
+int vcp_selftest_format_field(double v, int bit, char* out, int64_t cap, int64_t* len);
+/* The 64-bit sum vcp_format_rows takes its byte count from, run on n words the caller supplies (a device pointer). */
+int vcp_selftest_format_total_dev(vcp_ctx* ctx, const uint32_t* d_totals, int64_t n, uint64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

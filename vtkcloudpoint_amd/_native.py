@@ -39,7 +39,8 @@ SYMBOLS = [
     "vcp_icp_sums_unique", "vcp_icp_unique", "vcp_icp_sums_aniso", "vcp_selftest_horn_aniso", "vcp_icp_aniso",
     "vcp_import_compact", "vcp_import_compact_dev", "vcp_cluster_quantiles", "vcp_cluster_quantiles_dev",
     "vcp_cluster_mad", "vcp_cluster_mad_dev", "vcp_selftest_rank_key", "vcp_parse_scan_text",
-    "vcp_parse_scan_text_dev", "vcp_selftest_parse_field",
+    "vcp_parse_scan_text_dev", "vcp_selftest_parse_field", "vcp_format_rows", "vcp_format_rows_dev",
+    "vcp_selftest_format_field", "vcp_selftest_format_total_dev",
 ]
 
 
@@ -1023,6 +1024,78 @@ class Context:
             raise e
         return dict(seg_first=first, n=n.value, n_host=nh.value)
 
+    # -- export text ---------------------------------------------------------------------------------
+    def _fmt_fail(self, rc, err, nbytes):
+        e = VcpError(rc, (lib().vcp_last_error(self._h) or b"").decode())
+        e.err = (int(err[0]), int(err[1]))
+        e.nbytes = nbytes.value
+        return e
+
+    @staticmethod
+    def _fmt_col(x):
+        """(array kept alive, address, stride in doubles) of a float64 column: a 1-D view with a positive stride is read
+        in place, anything else through a contiguous copy."""
+        x = np.asarray(x)
+        if not (x.dtype == np.float64 and x.ndim == 1 and x.dtype.isnative and len(x) > 0 and x.strides[0] > 0 and
+                x.strides[0] % 8 == 0):
+            x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        return x, x.ctypes.data, (x.strides[0] // 8 if len(x) else 1)
+
+    def format_rows(self, a, b, c, ids=None, order=None, bit=6, eol=1, out=None, count_only=False):
+        """vcp_format_rows: line j = `[ids[r] TAB] a[r] TAB b[r] TAB c[r] EOL`, r = order[j] (None: r = j), every number as
+        '%.*f' % (bit, v); eol 0 = "\n", 1 = "\r\n".  a, b, c are float64 numpy columns of one length; strided 1-D views
+        (rows[:, k]) are read in place.  out: a writable uint8 numpy array that receives the text; None: one is made, by
+        a count-only call first.  Returns the text as a uint8 array (a view of out), or with count_only its length.  A
+        VcpError of this call carries .err = the call's err[2] and .nbytes."""
+        (a, pa, sa), (b, pb, sb), (c, pc, sc) = (self._fmt_col(x) for x in (a, b, c))
+        n = len(a)
+        if len(b) != n or len(c) != n:
+            raise ValueError("columns of %d, %d and %d rows" % (n, len(b), len(c)))
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("ids has %d entries for %d rows" % (len(ids), n))
+        if order is not None:
+            order = np.ascontiguousarray(order, np.int64).reshape(-1)
+        m = n if order is None else len(order)
+        nbytes = C.c_uint64(0)
+        err = (C.c_int64 * 2)()
+        while True:
+            rc = lib().vcp_format_rows(self._h, _ptr(ids), C.c_void_p(pa), C.c_int64(sa), C.c_void_p(pb), C.c_int64(sb),
+                                       C.c_void_p(pc), C.c_int64(sc), _ptr(order), C.c_int64(n), C.c_int64(m),
+                                       C.c_int(bit), C.c_int(eol), _ptr(out),
+                                       C.c_uint64(0 if out is None else out.nbytes), C.byref(nbytes), err)
+            if rc != 0:
+                raise self._fmt_fail(rc, err, nbytes)
+            if count_only:
+                return nbytes.value
+            if out is not None:
+                return out[:nbytes.value]
+            out = np.empty(max(nbytes.value, 1), np.uint8)
+
+    def format_rows_dev(self, d_a, stride_a, d_b, stride_b, d_c, stride_c, n, d_ids=None, d_order=None, m=None, bit=6,
+                        eol=1, out=None):
+        """Device-pointer form (ints from tensor.data_ptr()): d_a, d_b, d_c float64 read at their strides, d_ids int32 [n]
+        or None, d_order int64 [m] or None (then m = n).  out: a writable uint8 numpy array that receives the text (None:
+        count-only).  Returns the number of bytes.  A VcpError carries .err and, for VCP_ERR_INDEX with too small an out,
+        .nbytes."""
+        m = int(n if m is None else m)
+        nbytes = C.c_uint64(0)
+        err = (C.c_int64 * 2)()
+        rc = lib().vcp_format_rows_dev(self._h, _ptr(d_ids), _ptr(d_a), C.c_int64(stride_a), _ptr(d_b),
+                                       C.c_int64(stride_b), _ptr(d_c), C.c_int64(stride_c), _ptr(d_order), C.c_int64(n),
+                                       C.c_int64(m), C.c_int(bit), C.c_int(eol), _ptr(out),
+                                       C.c_uint64(0 if out is None else out.nbytes), C.byref(nbytes), err)
+        if rc != 0:
+            raise self._fmt_fail(rc, err, nbytes)
+        return nbytes.value
+
+    def selftest_format_total_dev(self, d_totals, n):
+        """vcp_selftest_format_total_dev: the 64-bit sum of n uint32 words on the device."""
+        total = C.c_uint64(0)
+        self._chk(lib().vcp_selftest_format_total_dev(self._h, _ptr(d_totals), C.c_int64(n), C.byref(total)))
+        return total.value
+
     # -- per-cluster quantiles and MAD ---------------------------------------------------------------
     @staticmethod
     def _cq_host(values, group, stride):
@@ -1097,6 +1170,19 @@ def selftest_parse_field(s):
     if rc < 0:
         raise VcpError(rc, "vcp_selftest_parse_field")
     return rc, (v.value if rc else None)
+
+
+def selftest_format_field(v, bit, cap=64):
+    """vcp_selftest_format_field: the bytes of '%.*f' % (bit, v) from the source the kernels are compiled from (no
+    device), or None for a value the device formatter does not take."""
+    out = C.create_string_buffer(max(int(cap), 1))
+    n = C.c_int64(-1)
+    rc = lib().vcp_selftest_format_field(C.c_double(v), C.c_int(bit), out, C.c_int64(cap), C.byref(n))
+    if rc < 0:
+        e = VcpError(rc, "vcp_selftest_format_field")
+        e.len = n.value
+        raise e
+    return out.raw[:n.value] if rc else None
 
 
 def selftest_horn_sim(sums, n, c=1.0, ratio_range=(1.0, 1.0), V=None):

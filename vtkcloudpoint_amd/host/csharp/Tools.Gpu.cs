@@ -368,5 +368,68 @@ namespace vtkPointCloud
             }
             return bestIv;
         }
+
+        // ---- the exports: one call builds the file's bytes (vcp.h: vcp_format_rows) -------------------------------------
+        // The text of `[clusterId TAB] motor_x TAB motor_y TAB Distance` lines, "F<bit>", "\r\n": what the WriteLine loops
+        // below wrote.  null when a value is outside what the device formats (a NaN, an infinity, 1e15 and more): the
+        // caller then runs the original loop.  "F<bit>" of .NET 3.5 rounds a 15-digit expansion, the library the exact
+        // binary value: the bytes agree on values read from text with at most `bit` decimals and 15 significant digits
+        // (INTEGRATION.md).
+        static byte[] FormatPoints(List<Point3D> pts, bool withId, int bit)
+        {
+            int n = pts.Count;
+            if (n == 0) return new byte[0];
+            double[] a = new double[n], b = new double[n], d = new double[n];
+            int[] id = withId ? new int[n] : null;
+            for (int i = 0; i < n; i++)
+            {
+                Point3D p = pts[i];
+                a[i] = p.motor_x; b[i] = p.motor_y; d[i] = p.Distance;
+                if (withId) id[i] = p.clusterId;
+            }
+            long[] err = new long[2];
+            ulong nbytes;
+            using (VcpNative.Lease c = VcpNative.Rent())
+            {
+                int rc = VcpNative.vcp_format_rows(c.Ctx, id, a, 1, b, 1, d, 1, null, n, n, bit, 1, null, 0, out nbytes, err);
+                if (rc == -8) return null;
+                VcpNative.Check(c, rc);
+                byte[] text = new byte[nbytes];
+                VcpNative.Check(c, VcpNative.vcp_format_rows(c.Ctx, id, a, 1, b, 1, d, 1, null, n, n, bit, 1, text, nbytes,
+                    out nbytes, err));
+                return text;
+            }
+        }
+
+        // The write loop of Tools.cleanDataByDistance (Tools.cs:229-244, after the dialog): replace the StreamWriter block
+        // by `Tools.WriteScanPoints(saveFile1.FileName, rawData, bit); skipRecru = false;`
+        public static void WriteScanPoints(string path, List<Point3D> rawData, int bit)
+        {
+            byte[] text = FormatPoints(rawData, false, bit);
+            if (text != null) { System.IO.File.WriteAllBytes(path, text); return; }
+            using (System.IO.StreamWriter ssw = new System.IO.StreamWriter(path, false))
+                foreach (Point3D p3d in rawData)
+                    ssw.WriteLine(p3d.motor_x.ToString("F" + bit) + "\t" + p3d.motor_y.ToString("F" + bit) + "\t" + p3d.Distance.ToString("F" + bit));
+        }
+
+        // The write loop of Tools.cleanDataByDistance2 (Tools.cs:289-306): every li in list order, no id column
+        public static void WriteFixedPoints(string path, List<ClusObj> clusList, int bit)
+        {
+            List<Point3D> all = new List<Point3D>();
+            for (int i = 0; i < clusList.Count; i++) all.AddRange(clusList[i].li);
+            WriteScanPoints(path, all, bit);
+        }
+
+        // Tools.exportClustersPointsFile, Tools.cs:364-387 (x_angle and y_angle are unused there as well)
+        static public void exportClustersPointsFile(List<ClusObj> clusList, int bit, double x_angle, double y_angle, string ss)
+        {
+            List<Point3D> all = new List<Point3D>();
+            for (int j = 0; j < clusList.Count; j++) all.AddRange(clusList[j].li);
+            byte[] text = FormatPoints(all, true, bit);
+            if (text != null) { System.IO.File.WriteAllBytes(ss, text); return; }
+            using (System.IO.StreamWriter sw = new System.IO.StreamWriter(ss, false))
+                foreach (Point3D p3d in all)
+                    sw.WriteLine(p3d.clusterId + "\t" + p3d.motor_x.ToString("F" + bit) + "\t" + p3d.motor_y.ToString("F" + bit) + "\t" + p3d.Distance.ToString("F" + bit));
+        }
     }
 }

@@ -194,6 +194,17 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_parse_scan_text_dev(IntPtr ctx, byte[] text, ulong nbytes, ulong[] seg_off,
             int nseg, long cap, IntPtr d_rows, IntPtr d_group, long[] seg_first, out long n, out long n_host, long[] err);
 
+        // the exports' text built on the GPU (vcp.h: vcp_format_rows; what the WriteLine loops of Tools.cs:233, 295, 341, 374
+        // write): line j = [id[r] TAB] a[r * stride_a] TAB b[..] TAB c[..] EOL, r = order[j] (null: r = j, m == n), "F<bit>";
+        // eol 1 = "\r\n" (StreamWriter.WriteLine).  text == null counts the bytes into nbytes; VCP_ERR_UNSUPPORTED (-8)
+        // means a NaN, an infinity or 1e15 and more: write that file the old way.  err [2]
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_format_rows(IntPtr ctx, int[] id, double[] a, long stride_a,
+            double[] b, long stride_b, double[] c, long stride_c, long[] order, long n, long m, int bit, int eol,
+            byte[] text, ulong cap, out ulong nbytes, long[] err);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_format_rows_dev(IntPtr ctx, IntPtr d_id, IntPtr d_a, long stride_a,
+            IntPtr d_b, long stride_b, IntPtr d_c, long stride_c, IntPtr d_order, long n, long m, int bit, int eol,
+            byte[] text, ulong cap, out ulong nbytes, long[] err);
+
         // order statistics per cluster or group (vcp.h: vcp_cluster_quantiles; per list what Tools.GetGroupingManOrMin,
         // Tools.cs:468-497, takes over all lists): values[i * stride], group 0 = none; counts may be null
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_quantiles(IntPtr ctx, double[] values, long stride,

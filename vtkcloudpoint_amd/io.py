@@ -1,6 +1,7 @@
 """The reference's text formats on either side of the path (host side; the numeric work of an import runs on the
 GPU through vcp_import_convert, or through vcp_import_compact where the result stays on the device or carries counts;
-parse_scan_text / read_scan_text_fast / read_folder_resident read the scan files' text on the GPU as well).
+parse_scan_text / read_scan_text_fast / read_folder_resident read the scan files' text on the GPU as well, and
+format_scan_text / write_*_fast / export_resident build the exports' text there).
 
 * scan files          one point per line, `motor_x<TAB>motor_y<TAB>Distance` -- what MainForm.AddFolder reads
                       (FrmMain.cs:1005-1009 via FileMap.ReadFile, BaseClass/FileMap.cs:16-33) and what
@@ -318,6 +319,181 @@ def read_folder_resident(files, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, dedupe
     res = import_scan_resident(d_rows, d_file if by_file else None, x_angle, y_angle, xdir, ydir, dedupe, ctx=ctx)
     res.update(rows=d_rows, file=d_file, n=len(d_rows), n_host=n_host)
     return res
+
+
+# ---- the device writer of the exports (vcp_format_rows) ---------------------------------------------------------------
+# Lines per call: no call can reach 4 GiB of text, whatever the values (_native: VCP_FMT_LINE_MAX = 112 bytes a line).
+_FMT_LINES = (1 << 32) // 112 - 1
+
+
+def _format_host(a, b, c, ids, order, bit, eol):
+    """The text as the Python writers build it (write_scan_text, write_clusters_text): one '%.*f' per number."""
+    a, b, c = (np.asarray(x, np.float64).reshape(-1).tolist() for x in (a, b, c))
+    rows = range(len(a)) if order is None else np.asarray(order, np.int64).reshape(-1).tolist()
+    for r in rows:
+        if not 0 <= r < len(a):
+            raise IndexError("order holds %d for %d rows" % (r, len(a)))
+    num = "%%.%df\t%%.%df\t%%.%df" % (bit, bit, bit) + eol
+    if ids is None:
+        return "".join([num % (a[r], b[r], c[r]) for r in rows]).encode("ascii")
+    ids = np.asarray(ids).reshape(-1).tolist()
+    return "".join([("%d\t" + num) % (ids[r], a[r], b[r], c[r]) for r in rows]).encode("ascii")
+
+
+def _format_parts(a, b, c, ids, order, bit, eol, ctx, max_lines):
+    """The pieces of the text, in order, as uint8 arrays (one per call of at most max_lines lines); a call that meets a
+    value the device formatter does not take raises _native.VcpError with code -8."""
+    import torch
+    from . import runtime
+    if eol not in ("\n", "\r\n"):
+        raise ValueError("eol must be '\\n' or '\\r\\n'")
+    e = 1 if eol == "\r\n" else 0
+    ctx = ctx or runtime.default_context()
+    resident = any(torch.is_tensor(x) for x in (a, b, c))
+    if not resident:
+        a, b, c = (np.asarray(x, np.float64) for x in (a, b, c))
+        a, b, c = (x if x.ndim == 1 else x.reshape(-1) for x in (a, b, c))
+        ids = None if ids is None else np.ascontiguousarray(ids.cpu().numpy() if torch.is_tensor(ids) else ids, np.int32)
+        order = None if order is None else np.ascontiguousarray(
+            order.cpu().numpy() if torch.is_tensor(order) else order, np.int64).reshape(-1)
+        m = len(a) if order is None else len(order)
+        for j0 in range(0, m, max_lines):
+            j1 = min(j0 + max_lines, m)
+            if order is None:
+                yield ctx.format_rows(a[j0:j1], b[j0:j1], c[j0:j1], None if ids is None else ids[j0:j1], None, bit, e)
+            else:
+                yield ctx.format_rows(a, b, c, ids, order[j0:j1], bit, e)
+        return
+    cols = []
+    for x in (a, b, c):
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(x, np.float64).reshape(-1)).cuda()
+        if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
+            raise ValueError("a column must be a 1-D float64 tensor on the GPU (or a numpy array)")
+        if len(x) > 0 and x.stride(0) < 1:
+            x = x.contiguous()
+        cols.append(x)
+    a, b, c = cols
+    dev, n = a.device, len(a)
+    if len(b) != n or len(c) != n:
+        raise ValueError("columns of %d, %d and %d rows" % (n, len(b), len(c)))
+    if ids is not None:
+        ids = (ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(ids, np.int32))).to(
+            device=dev, dtype=torch.int32).contiguous().reshape(-1)
+        if len(ids) != n:
+            raise ValueError("ids has %d entries for %d rows" % (len(ids), n))
+    if order is not None:
+        order = (order if torch.is_tensor(order) else torch.from_numpy(np.ascontiguousarray(order, np.int64))).to(
+            device=dev, dtype=torch.int64).contiguous().reshape(-1)
+    m = n if order is None else len(order)
+    torch.cuda.current_stream(dev).synchronize()     # the library runs on the context's stream, not on torch's
+    for j0 in range(0, m, max_lines):
+        j1 = min(j0 + max_lines, m)
+        if order is None:
+            pa, pb, pc = (x[j0:j1] for x in (a, b, c))
+            args = (pa.data_ptr(), max(pa.stride(0), 1), pb.data_ptr(), max(pb.stride(0), 1), pc.data_ptr(),
+                    max(pc.stride(0), 1), j1 - j0, None if ids is None else ids[j0:j1].data_ptr(), None, j1 - j0)
+        else:
+            args = (a.data_ptr(), max(a.stride(0), 1), b.data_ptr(), max(b.stride(0), 1), c.data_ptr(),
+                    max(c.stride(0), 1), n, None if ids is None else ids.data_ptr(), order[j0:j1].data_ptr(), j1 - j0)
+        nbytes = ctx.format_rows_dev(*args, bit=bit, eol=e)      # count-only: one pass over the lines, no text
+        out = np.empty(max(nbytes, 1), np.uint8)
+        ctx.format_rows_dev(*args, bit=bit, eol=e, out=out)
+        yield out[:nbytes]
+
+
+def _format_or_fall_back(a, b, c, ids, order, bit, eol, ctx, max_lines):
+    """The list of pieces (uint8 arrays or bytes) of the whole text: the device's, or on VCP_ERR_UNSUPPORTED the host
+    writer's for the whole call."""
+    import torch
+    from . import _native
+    try:
+        return list(_format_parts(a, b, c, ids, order, bit, eol, ctx, max_lines))
+    except _native.VcpError as e:
+        if e.code != -8:
+            raise
+    host = [None if x is None else (x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)) for x in (a, b, c, ids, order)]
+    return [_format_host(host[0], host[1], host[2], host[3], host[4], bit, eol)]
+
+
+def format_scan_text(a, b, c, ids=None, order=None, bit=6, eol="\r\n", ctx=None, max_lines=_FMT_LINES):
+    """The export's text built on the GPU (vcp_format_rows): line j is `[ids[r] TAB] a[r] TAB b[r] TAB c[r] eol` with
+    r = order[j] (None: every row in turn), numbers as '%.*f' % (bit, v) and ids as '%d' -- byte for byte what
+    write_scan_text / write_clusters_text write.  a, b, c: 1-D float64 numpy arrays, or torch tensors on the context's
+    device; strided views (rows[:, k]) are read in place, without a copy.  ids int32 [n] and order int64 [m] likewise.
+    The text is built in calls of at most max_lines lines, each below 4 GiB.  A call with a value the device formatter
+    does not take (NaN, an infinity, 1e15 or more in magnitude) is formatted by the host writer instead.  An entry of order
+    outside the rows raises _native.VcpError with code -4 and .err = (line, entry)."""
+    parts = _format_or_fall_back(a, b, c, ids, order, bit, eol, ctx, max_lines)
+    if len(parts) == 1:
+        return parts[0] if isinstance(parts[0], bytes) else parts[0].tobytes()
+    return b"".join(p if isinstance(p, bytes) else p.tobytes() for p in parts)
+
+
+def _write_parts(path, parts):
+    with open(path, "wb") as f:
+        for p in parts:
+            f.write(p if isinstance(p, bytes) else memoryview(p))
+
+
+def _three_columns(x):
+    """(a, b, c) of rows [n, 3] (numpy or torch: its columns, as views) or of a sequence of three columns."""
+    if hasattr(x, "ndim") and x.ndim == 2:
+        if x.shape[1] != 3:
+            raise ValueError("rows must be [n, 3]")
+        return x[:, 0], x[:, 1], x[:, 2]
+    a, b, c = x
+    return a, b, c
+
+
+def write_scan_text_fast(path, rows_or_columns, bit=6, ctx=None):
+    """write_scan_text with the text built on the GPU: rows [n, 3] = (motor_x, motor_y, Distance) or three columns, numpy
+    or torch device tensors.  The file is byte-identical to write_scan_text's on the same data."""
+    a, b, c = _three_columns(rows_or_columns)
+    _write_parts(path, _format_or_fall_back(a, b, c, None, None, bit, "\r\n", ctx, _FMT_LINES))
+
+
+def cluster_order(labels):
+    """The rows with label >= 1 in the order of the cluster export: stably sorted by label, which is clusList order with
+    every li in input order (Tools.GetClusList).  A torch tensor gives a tensor on its device, built there."""
+    import torch
+    if torch.is_tensor(labels):
+        idx = torch.nonzero(labels.reshape(-1) >= 1).reshape(-1)
+        return idx[torch.sort(labels.reshape(-1)[idx], stable=True)[1]]
+    labels = np.asarray(labels).reshape(-1)
+    idx = np.nonzero(labels >= 1)[0]
+    return idx[np.argsort(labels[idx], kind="stable")]
+
+
+def write_clusters_text_fast(path, labels, motor_x, motor_y, dist, bit=6, ctx=None):
+    """write_clusters_text with the text built on the GPU: labels [n] (0 = none) and the three columns of the same rows,
+    numpy or torch device tensors.  The file is byte-identical to write_clusters_text's on GetClusList's clusList."""
+    _write_parts(path, _format_or_fall_back(motor_x, motor_y, dist, labels, cluster_order(labels), bit, "\r\n", ctx,
+                                            _FMT_LINES))
+
+
+def write_centroids_text_fast(path, c3, bit, ctx=None):
+    """Tools.exportClustersCenterFile (BaseClass/Tools.cs:322-354): one `X<TAB>Y<TAB>Z` line per centre, "F<bit>"; c3 is
+    [K, 3], numpy or a torch device tensor (xyz of the centroid calls, read in place)."""
+    a, b, c = _three_columns(c3)
+    _write_parts(path, _format_or_fall_back(a, b, c, None, None, bit, "\r\n", ctx, _FMT_LINES))
+
+
+def export_resident(path, imp, labels=None, keep=None, bit=6, ctx=None):
+    """The exports from the tensors of import_scan_resident (imp["motor"] [m, 2], imp["dist"] [m]): the scan export
+    (write_scan_text) when labels is None, the cluster export (write_clusters_text) of the device labels [m] otherwise.
+    keep: an optional boolean device mask [m]; a row with keep false is left out, as cleanDataByDistance's RemoveAll and
+    cluster_mad's rejection leave it out.  The order is built on the device; nothing but the text comes down."""
+    import torch
+    motor, dist = imp["motor"], imp["dist"]
+    mx, my = motor[:, 0], motor[:, 1]
+    if labels is None:
+        order = None if keep is None else torch.nonzero(keep.reshape(-1)).reshape(-1)
+        ids = None
+    else:
+        ids = labels.reshape(-1).to(torch.int32)
+        order = cluster_order(ids if keep is None else torch.where(keep.reshape(-1), ids, torch.zeros_like(ids)))
+    _write_parts(path, _format_or_fall_back(mx, my, dist, ids, order, bit, "\r\n", ctx, _FMT_LINES))
 
 
 def add_fixed_folder(files, x_angle=0.0, y_angle=0.0, xdir=2, ydir=1, typpe=3, ctx=None):
