@@ -1262,6 +1262,25 @@ int vcp_selftest_format_field(double v, int bit, char* out, int64_t cap, int64_t
 /* The 64-bit sum vcp_format_rows takes its byte count from, run on n words the caller supplies (a device pointer). */
 int vcp_selftest_format_total_dev(vcp_ctx* ctx, const uint32_t* d_totals, int64_t n, uint64_t* total);
 
+/* Self-test of the wave and workgroup idioms the kernels share (csrc/wave.hpp): ONE workgroup of tb
+ * threads (64, 256, 512 or 1024) over d_words [n] and d_flags [n], 0 <= n <= tb; thread t holds v = d_words[t] and
+ * p = d_flags[t] != 0, and v = 0, p = false from t = n on.  d_out [VCP_WAVE_ROWS][tb], row r of thread t, sums modulo 2^32:
+ *    0  the sum of v over the threads before t          1  the same, from the form that also returns  2  the sum over all
+ *    3, 4, 5  sum, minimum, maximum of v over t's wave   6  the OR of v over t's wave (through the 64-bit form)
+ *    7  the p threads of t's wave                        8  the p threads of the workgroup in thread 0, 0xFFFFFFFF elsewhere
+ *    9, 10  the same for p and for odd v, from the two-predicate form
+ *   11  p: the p threads before t; otherwise 0          12  the p threads before t   13  the p threads of the workgroup
+ *   14  p: t's slot from the wave-aggregated append on *d_counter, which the caller has set to a start value and which
+ *       ends at start + the p threads; otherwise 0xFFFFFFFF
+ *   15  the maximum of v over the lanes of t's wave up to t   16  the sum of v over the lanes of t's half-wave up to t
+ *   17  v of thread t - 1 (of t itself in lane 0 of a wave)
+ *   18 .. 23  with s = (v - 2^31) * 2^20 as a signed 64-bit integer: low and high word of the sum (modulo 2^64), of the
+ *       maximum and of the minimum of s over t's wave
+ * Device pointers; returns when d_out is in place.  VCP_ERR_ARG: another tb, n outside [0, tb], a NULL pointer. */
+#define VCP_WAVE_ROWS 24
+int vcp_selftest_wave_dev(vcp_ctx* ctx, const uint32_t* d_words, const uint8_t* d_flags, int64_t n, int tb,
+                          uint32_t* d_counter, uint32_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,7 @@ SYMBOLS = [
     "vcp_import_compact", "vcp_import_compact_dev", "vcp_cluster_quantiles", "vcp_cluster_quantiles_dev",
     "vcp_cluster_mad", "vcp_cluster_mad_dev", "vcp_selftest_rank_key", "vcp_parse_scan_text",
     "vcp_parse_scan_text_dev", "vcp_selftest_parse_field", "vcp_format_rows", "vcp_format_rows_dev",
-    "vcp_selftest_format_field", "vcp_selftest_format_total_dev",
+    "vcp_selftest_format_field", "vcp_selftest_format_total_dev", "vcp_selftest_wave_dev",
 ]
 
 
@@ -1095,6 +1095,13 @@ class Context:
         total = C.c_uint64(0)
         self._chk(lib().vcp_selftest_format_total_dev(self._h, _ptr(d_totals), C.c_int64(n), C.byref(total)))
         return total.value
+
+    def selftest_wave_dev(self, d_words, d_flags, n, tb, d_counter, d_out):
+        """vcp_selftest_wave_dev: the helpers of csrc/wave.hpp run by one workgroup of tb threads on n uint32 words and n
+        uint8 flags; d_counter (one uint32, set by the caller) takes the append, d_out [24, tb] uint32 the rows
+        include/vcp.h lists.  Device pointers."""
+        self._chk(lib().vcp_selftest_wave_dev(self._h, _ptr(d_words), _ptr(d_flags), C.c_int64(n), C.c_int(tb),
+                                              _ptr(d_counter), _ptr(d_out)))
 
     # -- per-cluster quantiles and MAD ---------------------------------------------------------------
     @staticmethod

@@ -34,6 +34,7 @@
 #include "blocks_state.hpp"
 #include "bounds.hpp"
 #include "reduce.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int BT = 256;
@@ -162,15 +163,10 @@ __device__ __forceinline__ void find_bin(const uint32_t* h, unsigned long long r
   for (int q = 0; q < 4; q++) v[q] = h[4u * t + q];
   const uint32_t loc = v[0] + v[1] + v[2] + v[3];
   const int lane = t & 63, w = t >> 6;
-  uint32_t inc = loc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t x = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += x;
-  }
+  const uint32_t inc = wave_incl<WaveAdd>(loc, lane);
   if (lane == 63) wsum[w] = inc;
   __syncthreads();
-  unsigned long long cum = inc - loc;
+  unsigned long long cum = inc - loc;  // (the bins before: in 64 bits, like rank)
   for (int k = 0; k < w; k++) cum += wsum[k];
 #pragma unroll
   for (int q = 0; q < 4; q++) {
@@ -225,6 +221,7 @@ __global__ __launch_bounds__(PT) void k_sel_collect(const double* __restrict__ k
       mx = fmax(mx, v.x);
       my = fmax(my, v.y);
     }
+    // (by hand: wave.hpp's wave_append changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
     const unsigned long long mask = __ballot(c == 0);
     if (mask) {  // one append per wave
       const int leader = __ffsll((long long)mask) - 1;
@@ -473,12 +470,7 @@ __global__ __launch_bounds__(PT) void k_blk_split(const Rec32* __restrict__ rec,
       loc += v[q];
     }
     const int lane = t & 63, w = t >> 6;
-    uint32_t inc = loc;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t x = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += x;
-    }
+    const uint32_t inc = wave_incl<WaveAdd>(loc, lane);
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
     uint32_t cum = s + inc - loc;
@@ -638,6 +630,7 @@ __global__ __launch_bounds__(BT) void k_big_scan(const BigInfo* __restrict__ bin
       loc += v[k];
     }
     const int lane = t & 63, w = t >> 6;
+    // (by hand: wave.hpp's wave_incl changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
     uint32_t inc = loc;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -820,6 +813,7 @@ __global__ __launch_bounds__(BIG ? 1024 : 128) void k_blk_sort(const Rec32* __re
           }
         }
       }
+      // (by hand: wave.hpp's wave_all per value changes this kernel's instructions, profiles/wave_refactor_codegen.md)
 #pragma unroll
       for (int d = 32; d > 0; d >>= 1) {
         kmn = min(kmn, (unsigned long long)__shfl_xor((long long)kmn, d, 64));
@@ -862,17 +856,7 @@ __global__ __launch_bounds__(BIG ? 1024 : 128) void k_blk_sort(const Rec32* __re
         v[k] = cnt[t * PER + k];
         loc += v[k];
       }
-      const int lane = t & 63, w = t >> 6;
-      uint32_t inc = loc;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t x = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += x;
-      }
-      if (lane == 63) wsum[w] = inc;
-      __syncthreads();
-      uint32_t cum = inc - loc;
-      for (int k = 0; k < w; k++) cum += wsum[k];
+      uint32_t cum = block_excl(loc, wsum);
 #pragma unroll
       for (uint32_t k = 0; k < PER; k++) {
         cnt[t * PER + k] = cum;

@@ -22,6 +22,7 @@
 
 #include "blocks_state.hpp"
 #include "sort.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int BT = 256;
@@ -68,6 +69,7 @@ __global__ __launch_bounds__(NW == 1 ? BT : 64 * NW) void k_block_stats(const in
     if (l == 0) Z++;
     else K = max(K, (uint32_t)l);
   }
+  // (by hand: wave.hpp's wave_all per value changes this kernel's instructions, profiles/wave_refactor_codegen.md)
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
     K = max(K, (uint32_t)__shfl_xor((int)K, d, 64));
@@ -156,12 +158,7 @@ __global__ __launch_bounds__(BT) void k_block_order(const int32_t* __restrict__ 
     for (uint32_t k0 = 0; k0 <= K; k0 += 64) {
       const uint32_t k = k0 + lane;
       const uint32_t v = k <= K ? cnt[g][k] : 0u;
-      uint32_t inc = v;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-      }
+      const uint32_t inc = wave_incl<WaveAdd>(v, lane);
       if (k <= K) cnt[g][k] = carry + inc - v;  // first final position of id k
       carry += __shfl(inc, 63, 64);
     }
@@ -227,16 +224,7 @@ __global__ __launch_bounds__(64 * OBW) void k_block_order_big(const int32_t* __r
       v[k] = cnt[tid * PER + k];
       loc += v[k];
     }
-    uint32_t inc = loc;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t x = __shfl_up(inc, d, 64);
-      if ((int)lane >= d) inc += x;
-    }
-    if (lane == 63u) wsum[w] = inc;
-    __syncthreads();
-    uint32_t cum = s0 + inc - loc;
-    for (uint32_t k = 0; k < w; k++) cum += wsum[k];
+    uint32_t cum = block_excl(loc, wsum, s0);
 #pragma unroll
     for (uint32_t k = 0; k < PER; k++) {
       cnt[tid * PER + k] = cum;

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "dbscan_engine.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int PT = 256;
@@ -63,8 +64,8 @@ __global__ __launch_bounds__(PT) void k_dbp_count(const double* __restrict__ c, 
     }
   }
   if (p < n) core[p] = (live && (long long)cnt >= (long long)min_pts) ? 1 : 0;
-  const unsigned long long m = __ballot(live);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctr[0], (unsigned long long)__popcll(m));
+  const uint32_t nl = wave_count(live);
+  if ((threadIdx.x & 63) == 0 && nl) atomicAdd(&ctr[0], (unsigned long long)nl);
 }
 
 // next[0] <- the first i >= from that is shown, not classed and has a large enough neighbourhood (NONE: none)
@@ -128,8 +129,8 @@ __global__ __launch_bounds__(PT) void k_dbp_final(int64_t n, const uint8_t* __re
     if (is_core) is_core[i] = (shown && !cls0 && core[i]) ? 1 : 0;  // isKeyPoint ran on it (at its turn or when reached)
     if (is_classed) is_classed[i] = classed[i];
   }
-  const unsigned long long m = __ballot(turn);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctr[2], (unsigned long long)__popcll(m));
+  const uint32_t nt = wave_count(turn);
+  if ((threadIdx.x & 63) == 0 && nt) atomicAdd(&ctr[2], (unsigned long long)nt);
 }
 }  // namespace
 

@@ -40,6 +40,7 @@
 #include "bounds.hpp"
 #include "dbscan_engine.hpp"
 #include "grid_common.hpp"
+#include "wave.hpp"
 
 using namespace vcpg;
 
@@ -223,19 +224,9 @@ __device__ __forceinline__ uint32_t wl_fetch(const WorkList& w) {
 // per-block entry counts of both lists (no atomics: one slot per block of TPB positions)
 __device__ __forceinline__ void wl_count(bool isE, bool isB, uint32_t blk, uint32_t* __restrict__ cntE,
                                          uint32_t* __restrict__ cntB) {
-  __shared__ unsigned wc[2][TPB / 64];
-  const unsigned long long mE = __ballot(isE), mB = __ballot(isB);
-  if ((threadIdx.x & 63) == 0) {
-    wc[0][threadIdx.x >> 6] = (unsigned)__popcll(mE);
-    wc[1][threadIdx.x >> 6] = (unsigned)__popcll(mB);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned a = 0, b = 0;
-    for (int k = 0; k < TPB / 64; k++) {
-      a += wc[0][k];
-      b += wc[1][k];
-    }
+  __shared__ uint32_t wc[2 * TPB / 64];
+  uint32_t a, b;
+  if (block_count<TPB>(isE, isB, wc, a, b)) {
     cntE[blk] = a;
     cntB[blk] = b;
   }
@@ -264,6 +255,7 @@ __global__ __launch_bounds__(TPB) void k_wl_fill(const uint8_t* __restrict__ fla
   const uint8_t fl = p < nin ? flags[p] : 0;
   const bool isE = fl & F_EXPAND, isB = fl & F_BCAND;
   __shared__ unsigned wo[2][TPB / 64];
+  // (by hand: wave.hpp's block_rank changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
   const unsigned long long mE = __ballot(isE), mB = __ballot(isB);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) {
@@ -1037,6 +1029,7 @@ __global__ __launch_bounds__(TPB) void k_flatten(uint32_t* __restrict__ parent, 
     uint32_t lr = __shfl(r, leader, 64);
     bool mine = (r == lr);
     uint32_t m = mine ? v : NONE;
+    // (by hand: wave.hpp's wave_all changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, d, 64));
     // FILTER (grids with a point or more per cell): read first -- in a cloud that is one large component every wave would
@@ -1368,15 +1361,9 @@ __global__ __launch_bounds__(TPB) void k_slab_count(const uint32_t* __restrict__
   const uint32_t nin = *ct.nin;
   int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
   const bool root = p < nin && (flags[p] & F_EXPAND) && parent[p] == (uint32_t)p;
-  __shared__ unsigned wc[TPB / 64];
-  const unsigned long long m = __ballot(root);
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned a = 0;
-    for (int k = 0; k < TPB / 64; k++) a += wc[k];
-    blkcnt[blockIdx.x] = a;
-  }
+  __shared__ uint32_t wc[TPB / 64];
+  uint32_t a;
+  if (block_count<TPB>(root, wc, a)) blkcnt[blockIdx.x] = a;
 }
 
 __global__ __launch_bounds__(TPB) void k_slab_fill(const uint32_t* __restrict__ parent, const uint8_t* __restrict__ flags,
@@ -1386,17 +1373,9 @@ __global__ __launch_bounds__(TPB) void k_slab_fill(const uint32_t* __restrict__ 
   const uint32_t nin = *ct.nin;
   int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
   const bool root = p < nin && (flags[p] & F_EXPAND) && parent[p] == (uint32_t)p;
-  __shared__ unsigned wc[TPB / 64];
-  const unsigned long long m = __ballot(root);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wc[w] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (root) {
-    unsigned before = 0;
-    for (int k = 0; k < w; k++) before += wc[k];
-    before += (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-    comps[blkscan[blockIdx.x] + before] = minord[p];
-  }
+  __shared__ uint32_t wc[TPB / 64];
+  const uint32_t before = block_rank(root, wc);
+  if (root) comps[blkscan[blockIdx.x] + before] = minord[p];
 }
 
 __global__ __launch_bounds__(TPB) void k_slab_out(int64_t n, const uint32_t* __restrict__ pos,

@@ -36,6 +36,7 @@
 #include "epsgrid.hpp"
 #include "sort.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int ET = 256;  // threads per workgroup
@@ -99,8 +100,8 @@ __global__ __launch_bounds__(ET) void k_et_init(ETArgs a) {
     a.cw[s] = NOKEY;
     a.ce[s] = NOKEY;
   }
-  const unsigned long long bp = __ballot(inp);
-  if (bp && lane == 0) atomicAdd(&a.ctr[C_P], (uint32_t)__popcll(bp));
+  const uint32_t np = wave_count(inp);
+  if (np && lane == 0) atomicAdd(&a.ctr[C_P], np);
   eg_list_chunks(hv, s, a.heavy, &a.ctr[C_HEAVY]);
 }
 

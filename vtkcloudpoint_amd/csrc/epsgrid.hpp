@@ -12,6 +12,7 @@
 
 #include "bounds.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr uint32_t NOCELL = 0xFFFFFFFFu;
@@ -288,15 +289,8 @@ __device__ __forceinline__ bool eg_chunk_first(const EpsCells& c, const double4&
 // The list of heavy chunks: every lane of a wave calls this, with first = "my slot s begins a chunk of a heavy cell"; those
 // slots are appended to list[] and counted in *count.
 __device__ __forceinline__ void eg_list_chunks(bool first, uint32_t s, uint32_t* list, uint32_t* count) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long bh = __ballot(first);
-  if (bh) {  // wave-uniform
-    const int leader = __ffsll((long long)bh) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(bh));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-    if (first) list[base + (uint32_t)__popcll(bh & ((1ull << lane) - 1ull))] = s;
-  }
+  const uint32_t slot = wave_append(first, count);
+  if (first) list[slot] = s;
 }
 
 // one past the last slot of the chunk that starts at slot s0

@@ -41,6 +41,7 @@
 #include "bounds.hpp"
 #include "epsgrid.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int GT = 256;  // threads per workgroup
@@ -162,9 +163,7 @@ __global__ __launch_bounds__(64) void k_gd_count_heavy(GDArgs a) {
   eg_heavy(
       a, a.heavy, a.ctr[C_HEAVY], [&](uint32_t s) { gd_keep(a, s, gd_count<METRIC>(a, a.rec[s], 0u, 1u, !a.exact)); },
       [&](uint32_t s, uint32_t lane) {
-        long long W = gd_count<METRIC>(a, a.rec[s], lane, 64u, false);
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) W += __shfl_xor(W, d, 64);
+        const long long W = wave_all<WaveAdd>(gd_count<METRIC>(a, a.rec[s], lane, 64u, false));
         if (lane == 0) gd_keep(a, s, W);
       });
 }
@@ -304,9 +303,7 @@ __global__ __launch_bounds__(64) void k_gd_border_heavy(GDArgs a) {
       },
       [&](uint32_t s, uint32_t lane) {
         if (a.flags[s] & F_CORE) return;  // wave-uniform
-        long long key = gd_border<METRIC>(a, a.rec[s], lane, 64u);
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) key = max(key, (long long)__shfl_xor(key, d, 64));
+        const long long key = wave_all<WaveMax>(gd_border<METRIC>(a, a.rec[s], lane, 64u));
         if (lane == 0) gd_border_keep(a, s, key);
       });
 }

@@ -34,6 +34,7 @@
 #include <unordered_map>
 
 #include "grid_common.hpp"
+#include "wave.hpp"
 
 using namespace vcpg;
 
@@ -349,12 +350,7 @@ __global__ __launch_bounds__(FT) void k_part_split(const Rec* __restrict__ rec, 
   __syncthreads();
   if (threadIdx.x < 32) {
     const uint32_t v = h[threadIdx.x];
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const uint32_t t = __shfl_up(inc, d, 64);
-      if ((int)threadIdx.x >= d) inc += t;
-    }
+    const uint32_t inc = wave_incl<WaveAdd, 32>(v, (int)threadIdx.x);
     const uint32_t first = s + inc - v;
     h[threadIdx.x] = first;
     const uint32_t bk = (S << a) + threadIdx.x;
@@ -438,12 +434,7 @@ __global__ __launch_bounds__(FS) void k_part_fine_small(const Rec* __restrict__ 
   // B. word starts: exclusive scan of the NW (<= 512 = FS) counts
   {
     const uint32_t v = threadIdx.x < NW ? ws[threadIdx.x] : 0u;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += t;
-    }
+    const uint32_t inc = wave_incl<WaveAdd>(v, lane);
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
     uint32_t pre = inc - v;
@@ -475,14 +466,8 @@ __global__ __launch_bounds__(FS) void k_part_fine_small(const Rec* __restrict__ 
     }
   }
   {
-    const unsigned long long dm = __ballot(popl);
-    if (lane == 0) wsum[w] = (uint32_t)__popcll(dm);
-    __syncthreads();
-    uint32_t before = (uint32_t)__popcll(dm & ((1ull << lane) - 1ull)), tot = 0;
-    for (int k = 0; k < FS / 64; k++) {
-      if (k < w) before += wsum[k];
-      tot += wsum[k];
-    }
+    uint32_t tot;
+    const uint32_t before = block_rank<FS>(popl, wsum, tot);
     if (threadIdx.x == 0) s_np = tot;
     if (threadIdx.x < NW) wpi[threadIdx.x] = popl ? (uint16_t)before : (uint16_t)0xFFFFu;
   }
@@ -517,6 +502,7 @@ __global__ __launch_bounds__(FS) void k_part_fine_small(const Rec* __restrict__ 
       const uint32_t pi = wpi[wd];
       if (pi == 0xFFFFu) continue;
       const uint32_t c = st32[pi][li];
+      // (by hand: wave.hpp's wave_incl changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
       uint32_t inc = c;  // (a cell of a bucket of <= 4096 records holds < 65536)
 #pragma unroll
       for (int d = 1; d < 32; d <<= 1) {
@@ -611,17 +597,7 @@ __global__ __launch_bounds__(FT) void k_part_fine(const Rec* __restrict__ rec, u
   const uint32_t first = threadIdx.x * PER;
   uint32_t loc = 0;
   for (uint32_t k = 0; k < PER; k++) loc += cnt[padded(first + k)];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = loc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  uint32_t pre = s + inc - loc;
-  for (int k = 0; k < w; k++) pre += wsum[k];
+  uint32_t pre = block_excl(loc, wsum, s);
   // second pass of the scan; the thread's run of PER cells is part of ONE word of the cell table (PER <= 16): its bits of
   // the two population planes are built on the way and OR-ed together over the 32 / PER threads that share the word
   const uint32_t NW = CPB >> 5;
@@ -637,6 +613,7 @@ __global__ __launch_bounds__(FT) void k_part_fine(const Rec* __restrict__ rec, u
       plo |= (c & 1u) << (bit0 + k);
       phi |= (c >> 1) << (bit0 + k);
     }
+    // (by hand: the number of steps is a run-time value; wave.hpp's wave_all is a whole-wave reduce)
     for (uint32_t d = 1; d < 32u / PER; d <<= 1) {
       plo |= (uint32_t)__shfl_xor((int)plo, (int)d, 64);
       phi |= (uint32_t)__shfl_xor((int)phi, (int)d, 64);
@@ -652,14 +629,8 @@ __global__ __launch_bounds__(FT) void k_part_fine(const Rec* __restrict__ rec, u
     // populous words (some cell with 3 or more points) keep their 32 starts in full: they are numbered inside the
     // workgroup and take consecutive slots behind ONE atomic per bucket (a single hot word serialises at ~11 ns)
     const bool popl = threadIdx.x < NW && (w_lo[threadIdx.x] & w_hi[threadIdx.x]) != 0u;
-    const unsigned long long dm = __ballot(popl);
-    if (lane == 0) wsum[w] = (uint32_t)__popcll(dm);
-    __syncthreads();
-    uint32_t before = (uint32_t)__popcll(dm & ((1ull << lane) - 1ull)), tot = 0;
-    for (int k = 0; k < FT / 64; k++) {
-      if (k < w) before += wsum[k];
-      tot += wsum[k];
-    }
+    uint32_t tot;
+    const uint32_t before = block_rank<FT>(popl, wsum, tot);
     if (threadIdx.x == 0) s_dbase = tot ? atomicAdd(&ctcount[0], tot) : 0u;
     __syncthreads();
     if (threadIdx.x < NW) {

@@ -28,6 +28,7 @@
 #include <cmath>
 
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int MT = 256;
@@ -233,9 +234,7 @@ __device__ __forceinline__ void cluster_fit(const double* __restrict__ cxy, cons
     alive_local += keep;
   }
   {
-    unsigned v = alive_local;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor((int)v, d, 64);
+    const unsigned v = wave_all<WaveAdd>(alive_local);
     __syncthreads();
     if ((tid & 63) == 0) s_alive[tid >> 6] = v;
     __syncthreads();

@@ -1476,6 +1476,7 @@ __global__ __launch_bounds__(ITPB) void k_icpms_score(const double* __restrict__
     hit = bd < max_dist && sub == 0;
   }
   __shared__ uint32_t wc[ITPB / 64];
+  // (by hand: wave.hpp's block_count changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
   const unsigned long long b = __ballot(hit);
   if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(b);
   __syncthreads();

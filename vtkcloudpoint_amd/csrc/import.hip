@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int IT = 256;
@@ -116,19 +117,9 @@ __global__ __launch_bounds__(IT) void k_import_mark(const double* __restrict__ q
     kept = !isdup;
     dup = isdup;
   }
-  __shared__ unsigned wc[2][IT / 64];
-  const unsigned long long mk = __ballot(kept), md = __ballot(dup);
-  if ((threadIdx.x & 63) == 0) {
-    wc[0][threadIdx.x >> 6] = (unsigned)__popcll(mk);
-    wc[1][threadIdx.x >> 6] = (unsigned)__popcll(md);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned a = 0, b = 0;
-    for (int k = 0; k < IT / 64; k++) {
-      a += wc[0][k];
-      b += wc[1][k];
-    }
+  __shared__ uint32_t wc[2 * IT / 64];
+  uint32_t a, b;
+  if (block_count<IT>(kept, dup, wc, a, b)) {
     if (a) atomicAdd(&counters[2 * (blockIdx.x & 15)], (unsigned long long)a);
     if (b) atomicAdd(&counters[2 * (blockIdx.x & 15) + 1], (unsigned long long)b);
   }
@@ -185,15 +176,9 @@ __global__ __launch_bounds__(IT) void k_impc_flag(const uint8_t* __restrict__ st
   int64_t i = (int64_t)blockIdx.x * IT + threadIdx.x;
   const bool unf = i < n && state[i] != 0;
   if (i < n) keep[i] = unf && (!slot || table[2 * (size_t)slot[i]] == (uint32_t)i);
-  __shared__ unsigned wc[IT / 64];
-  const unsigned long long mu = __ballot(unf);
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (unsigned)__popcll(mu);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned a = 0;
-    for (int k = 0; k < IT / 64; k++) a += wc[k];
-    if (a) atomicAdd(&counters[blockIdx.x & 15], (unsigned long long)a);
-  }
+  __shared__ uint32_t wc[IT / 64];
+  uint32_t a;
+  if (block_count<IT>(unf, wc, a) && a) atomicAdd(&counters[blockIdx.x & 15], (unsigned long long)a);
 }
 
 struct ImpcOut {

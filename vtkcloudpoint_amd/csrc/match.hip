@@ -11,6 +11,7 @@
 #include "match.hpp"
 #include <cstring>
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int MT = 128;
@@ -47,8 +48,8 @@ __global__ __launch_bounds__(MT) void k_match(const double* __restrict__ centers
       is_matched[j] = hit ? 1 : 0;
     }
   }
-  unsigned long long b = __ballot(hit);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+  const uint32_t c = wave_count(hit);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 // MainForm.refreshClusList (FrmMain.cs:3437-3467): nearest truth within `radius` per raw point; among equal
 // distances the LAST truth in list order wins (OrderByDescending + Reverse), id 0 = none.
@@ -76,6 +77,7 @@ __global__ __launch_bounds__(256) void k_assign_truths(const double* __restrict_
     none = id == 0;
   }
   __shared__ unsigned wc[4];
+  // (by hand: wave.hpp's block_count changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
   unsigned long long b = __ballot(none);
   if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (unsigned)__popcll(b);
   __syncthreads();
@@ -126,6 +128,7 @@ __global__ __launch_bounds__(256) void k_assign_truths_grid(const double* __rest
     none = id == 0;
   }
   __shared__ unsigned wc[4];
+  // (by hand: wave.hpp's block_count changes this kernel's instruction stream, profiles/wave_refactor_codegen.md)
   unsigned long long b = __ballot(none);
   if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (unsigned)__popcll(b);
   __syncthreads();

@@ -27,6 +27,7 @@
 #include "epsgrid.hpp"
 #include "match.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int MT = 128;
@@ -152,15 +153,9 @@ __global__ __launch_bounds__(MT) void k_mu_accept(const int32_t* __restrict__ li
       }
     }
   }
-  const unsigned long long bk = __ballot(keep), ba = __ballot(acc);
-  if (bk) {  // wave-uniform
-    const int leader = __ffsll((long long)bk) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&ctr[2], (uint32_t)__popcll(bk));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-    if (keep) list_nxt[base + (uint32_t)__popcll(bk & ((1ull << lane) - 1ull))] = j;
-  }
-  if (ba && lane == 0) atomicAdd(&ctr[1], (uint32_t)__popcll(ba));
+  const uint32_t slot = wave_append(keep, &ctr[2]), na = wave_count(acc);
+  if (keep) list_nxt[slot] = j;
+  if (na && lane == 0) atomicAdd(&ctr[1], na);
 }
 
 // the counters of one batch: (BATCH + 1) pairs of words, all zero but the first list's length

@@ -5,16 +5,14 @@
 
 #include <cstdint>
 
+#include "wave.hpp"
+
 // Thread t holds the count c of bin t; rank r, 1 <= r <= the total: the bin g with below(g) < r <= below(g) + c(g) and
 // the rank left in it, to every thread.  sh: 8 words of LDS, free again on return.
 __device__ __forceinline__ void vcp_radix_pick(uint32_t c, uint32_t r, uint32_t* sh, uint32_t& g, uint32_t& left) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += v;
-  }
+  const int lane = threadIdx.x & 63;
+  uint32_t inc = wave_incl<WaveAdd>(c, lane);
+  const int w = threadIdx.x >> 6;
   if (threadIdx.x == 0) {
     sh[4] = 0;
     sh[5] = 1;

@@ -36,6 +36,7 @@
 #include "epsgrid.hpp"
 #include "match.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int RT = 256;          // threads of a search / final workgroup
@@ -225,7 +226,7 @@ __device__ __forceinline__ void rg_flush(const RGSearch& a, int i, const uint32_
           mtc::transform(M, p[0], p[1], p[2], m);
           hit = rg_exists(a.q, m);
         }
-        cnt += (uint32_t)__popcll(__ballot(hit));
+        cnt += wave_count(hit);
       }
     }
     if (lane == 0) {
@@ -253,7 +254,7 @@ __device__ __forceinline__ bool rg_fits(const RGSearch& a, double Lv, const doub
 // The search of one workgroup (target i = blockIdx.x); sL, qe and qn are the kernel's LDS.
 template <bool SIM>
 __device__ __forceinline__ void rg_search(const RGSearch& a, double* sL, uint32_t* qe, uint32_t* qn) {
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   for (int k = tid; k < a.nv; k += RT) sL[k] = a.sL[k];
   if (tid == 0) *qn = 0;
   __syncthreads();
@@ -283,15 +284,8 @@ __device__ __forceinline__ void rg_search(const RGSearch& a, double* sL, uint32_
     }
     // a round: every lane that still has a hypothesis queues one; the queue is scored when the next round might not fit
     while (__syncthreads_or(live)) {
-      const unsigned long long bal = __ballot(live);
-      if (bal) {  // wave-uniform
-        const int leader = __ffsll((long long)bal) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(qn, (uint32_t)__popcll(bal));
-        base = (uint32_t)__shfl((int)base, leader, 64);
-        if (live)
-          qe[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)j | ((uint32_t)f << 16) | ((uint32_t)k << 17);
-      }
+      const uint32_t slot = wave_append(live, qn);
+      if (live) qe[slot] = (uint32_t)j | ((uint32_t)f << 16) | ((uint32_t)k << 17);
       if (live && ++f == a.nf) {
         f = 0;
         k++;
@@ -371,14 +365,8 @@ __device__ __forceinline__ void rg_final(const double* __restrict__ src, int64_t
     mtc::transform(M, src[3 * p], src[3 * p + 1], src[3 * p + 2], m);
     hit = rg_exists(q, m);
   }
-  const unsigned long long bal = __ballot(hit);
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < RT / 64; w++) t += wc[w];
-    if (t) atomicAdd(&inliers[b], t);
-  }
+  uint32_t t;
+  if (block_count<RT>(hit, wc, t) && t) atomicAdd(&inliers[b], t);
 }
 
 __global__ __launch_bounds__(RT) void k_regp_final(const double* __restrict__ src, int64_t ns,

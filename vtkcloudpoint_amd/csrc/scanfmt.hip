@@ -17,6 +17,7 @@
 
 #include "scanfmt.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 static_assert(sfx::LINE_BYTES_MAX == VCP_FMT_LINE_MAX, "include/vcp.h: VCP_FMT_LINE_MAX");
 
@@ -60,8 +61,7 @@ __global__ __launch_bounds__(TT) void k_fmt_len(const Cols q, uint32_t* __restri
     else if (st == 1) atomicMin(&counters[0], (unsigned long long)j);
     else atomicMin(&counters[1], (unsigned long long)j << 2 | (unsigned)(st - 2));
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) len += (unsigned)__shfl_xor((int)len, d, 64);
+  len = wave_all<WaveAdd>(len);
   __shared__ unsigned wt[TT / 64];
   if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = len;
   __syncthreads();
@@ -77,8 +77,7 @@ __global__ __launch_bounds__(TT) void k_fmt_sum(const uint32_t* __restrict__ wg_
                                                unsigned long long* __restrict__ total) {
   unsigned long long s = 0;
   for (int64_t i = threadIdx.x; i < nb; i += TT) s += wg_total[i];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) s += (unsigned long long)__shfl_xor((long long)s, d, 64);
+  s = wave_all<WaveAdd>(s);
   __shared__ unsigned long long wt[TT / 64];
   if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -106,20 +105,8 @@ __global__ __launch_bounds__(TT) void k_fmt_write(const Cols q, const uint32_t* 
     live = load_line(q, j, &id, f) == 0;  // k_fmt_len found every line of this call good
     if (live) len = (unsigned)sfx::line_len(q.id != nullptr, id, f, q.bit, q.eol);
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned inc = len;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = (unsigned)__shfl_up((int)inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wt[w] = inc;
-  __syncthreads();
-  unsigned before = inc - len, tot = 0;
-  for (int k = 0; k < TT / 64; k++) {
-    if (k < w) before += wt[k];
-    tot += wt[k];
-  }
+  uint32_t tot;
+  const uint32_t before = block_excl<TT>(len, wt, tot);
   const uint32_t base = wg_off[blockIdx.x];
   if (STAGE) {
     const unsigned mis = base & 15u;

@@ -21,6 +21,7 @@
 
 #include "scantext.hpp"
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int TT = 256;
@@ -63,11 +64,8 @@ __global__ __launch_bounds__(TT) void k_txt_count(const unsigned char* __restric
   uint32_t b = NOBAD;
   unsigned c = 0;
   if (i0 < nbytes) c = (unsigned)__popcll(term_mask(text, nbytes, i0, &b));
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    c += (unsigned)__shfl_xor((int)c, d, 64);
-    b = min(b, (uint32_t)__shfl_xor((int)b, d, 64));
-  }
+  c = wave_all<WaveAdd>(c);
+  b = wave_all<WaveMin>(b);
   __shared__ unsigned wc[TT / 64], wb[TT / 64];
   if ((threadIdx.x & 63) == 0) {
     wc[threadIdx.x >> 6] = c;
@@ -96,19 +94,8 @@ __global__ __launch_bounds__(TT) void k_txt_index(const unsigned char* __restric
   uint64_t m = 0;
   if (i0 < nbytes) m = term_mask(text, nbytes, i0, &b);
   const unsigned c = (unsigned)__popcll(m);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned inc = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = (unsigned)__shfl_up((int)inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  __shared__ unsigned wt[TT / 64];
-  if (lane == 63) wt[w] = inc;
-  __syncthreads();
-  unsigned before = inc - c;
-  for (int k = 0; k < w; k++) before += wt[k];
-  uint32_t pos = chunk_base[blockIdx.x] + before + 1u;
+  __shared__ uint32_t wt[TT / 64];
+  uint32_t pos = block_excl(c, wt, chunk_base[blockIdx.x]) + 1u;
   while (m) {
     const int bit = __ffsll((long long)m) - 1;
     m &= m - 1;

@@ -8,6 +8,7 @@
 
 #include "hull.hpp"
 #include "sort.hpp"
+#include "wave.hpp"
 
 namespace {
 constexpr int FT = 256;
@@ -47,8 +48,8 @@ __global__ __launch_bounds__(FT) void k_filter_clusters(const double* __restrict
     }
     filtered[k] = f ? 1 : 0;
   }
-  const unsigned long long bal = __ballot(f);
-  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_filtered, (uint32_t)__popcll(bal));
+  const uint32_t c = wave_count(f);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_filtered, c);
 }
 
 // keep[i] and its 32-bit twin for the scan; counters: [1] kept points, [2] labels outside 0..K
@@ -64,16 +65,9 @@ __global__ __launch_bounds__(FT) void k_filter_points(const int32_t* __restrict_
     if (keep) keep[i] = kp ? 1 : 0;
     if (flag) flag[i] = kp ? 1u : 0u;
   }
-  __shared__ uint32_t s_kept[FT / 64], s_bad[FT / 64];
-  const unsigned long long bk = __ballot(kp), bb = __ballot(bad);
-  if ((threadIdx.x & 63) == 0) {
-    s_kept[threadIdx.x >> 6] = (uint32_t)__popcll(bk);
-    s_bad[threadIdx.x >> 6] = (uint32_t)__popcll(bb);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t a = 0, b = 0;
-    for (int w = 0; w < FT / 64; w++) a += s_kept[w], b += s_bad[w];
+  __shared__ uint32_t wc[2 * FT / 64];
+  uint32_t a, b;
+  if (block_count<FT>(kp, bad, wc, a, b)) {
     if (a) atomicAdd(counters + 1, a);
     if (b) atomicAdd(counters + 2, b);
   }

@@ -5,8 +5,10 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "vcp_ctx.hpp"
+#include "wave.hpp"
 
 static thread_local std::string g_create_err;
 
@@ -155,14 +157,7 @@ __device__ __forceinline__ uint32_t sop(uint32_t a, uint32_t b) {
 }
 
 template <bool MX>
-__device__ __forceinline__ uint32_t wave_incl(uint32_t v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t t = __shfl_up(v, d, 64);
-    if (lane >= d) v = sop<MX>(v, t);
-  }
-  return v;
-}
+using SOp = std::conditional_t<MX, WaveMax, WaveAdd>;
 
 template <bool VEC>
 __device__ __forceinline__ uint4 ld4(const uint32_t* __restrict__ in, int64_t i, int64_t n) {
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(ST) void k_scan(const uint32_t* __restrict__ in, ui
   for (int k = 0; k < SCH; k++) v[k] = ld4<VEC>(in, base + ((int64_t)k * ST + threadIdx.x) * 4, n);
 #pragma unroll
   for (int k = 0; k < SCH; k++) {
-    inc[k] = wave_incl<MX>(sop<MX>(sop<MX>(v[k].x, v[k].y), sop<MX>(v[k].z, v[k].w)), lane);
+    inc[k] = wave_incl<SOp<MX>>(sop<MX>(sop<MX>(v[k].x, v[k].y), sop<MX>(v[k].z, v[k].w)), lane);
     if (lane == 63) sm[k][w] = inc[k];
   }
   __syncthreads();
@@ -241,9 +236,7 @@ __global__ __launch_bounds__(ST) void k_scan(const uint32_t* __restrict__ in, ui
         const unsigned long long incm = __ballot(stt == SD_INC);
         const int first = __ffsll((long long)incm) - 1;  // nearest tile with a known prefix; -1: 64 aggregates, go on
         uint32_t x = (first < 0 || lane <= first) ? val : 0u;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) x = sop<MX>(x, (uint32_t)__shfl_xor((int)x, d, 64));
-        carry = sop<MX>(carry, x);
+        carry = sop<MX>(carry, wave_all<SOp<MX>>(x));
         if (first >= 0) break;
         j0 -= 64;
       }
@@ -259,7 +252,7 @@ __global__ __launch_bounds__(ST) void k_scan(const uint32_t* __restrict__ in, ui
 #pragma unroll
   for (int k = 0; k < SCH; k++) {
     const int64_t i = base + ((int64_t)k * ST + threadIdx.x) * 4;
-    uint32_t prev = __shfl_up(inc[k], 1, 64);
+    uint32_t prev = wave_prev(inc[k]);
     if (lane == 0) prev = 0;
     const uint32_t p0 = sop<MX>(sop<MX>(carry, pre[k]), prev);
     const uint32_t o1 = sop<MX>(p0, v[k].x), o2 = sop<MX>(o1, v[k].y), o3 = sop<MX>(o2, v[k].z);
