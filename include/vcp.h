@@ -1164,6 +1164,63 @@ int vcp_cluster_mad_dev(vcp_ctx* ctx, const double* d_values, int64_t stride, co
  * outside [0, 1].  Needs no device and no context. */
 int vcp_selftest_rank_key(double v, double q, int64_t c, uint64_t* key, int64_t* rank);
 
+/* -- per-cluster covariance, principal axes and the ellipse numbers -----------------------------------------
+ * vcp_cluster_shapes describes a cluster by extreme values (hull, circle, rectangle): one stray point moves them by its full
+ * distance, a hull beyond 2048 points fails the call, a cluster of <= 3 points is not judged, and it is 2-D only.  The second
+ * central moments have none of these limits: per cluster the mean, the population covariance, its eigenvalues and principal
+ * axes, and four numbers derived from them.  2 sqrt(lambda) is the radius of a uniformly filled disc (variance r^2 / 4 on
+ * every axis); in 3-D the axis of the smallest eigenvalue is the surface normal and lambda_3 / (lambda_1 + lambda_2 +
+ * lambda_3) measures how flat the cluster is.  The outputs feed vcp_cluster_filter as they stand (radius = 2 shape[0],
+ * rect_len = 2 (shape[0], shape[1]), valid for both flags).
+ *   pts        row i is pts[i * ld + 0 .. dim), dim = 2 or 3, ld >= dim in doubles: xyz[:, :2], motor, or columns of a
+ *              wider resident array are read in place
+ *   labels     [n] in 0..K, 0 = in no cluster
+ *   weights    [n] int32 >= 0 (the count of vcp_import_compact), or NULL for 1
+ * Definition.  All arithmetic binary64, every operation rounded on its own (no FMA contraction), / and sqrt correctly
+ * rounded.  The members of cluster k in ascending point index; every sum below through the fixed tree of vcp_centroids:
+ * chunks of 16384 consecutive members, in a chunk 256 threads strided (thread t adds members t, t + 256, ... from +0.0),
+ * per wave of 64 the shuffle tree at offsets 32, 16, 8, 4, 2, 1, the 4 waves in order, the chunks in order from 0.0.
+ *   1. W      = sum w                                       integers: exact; (double)W below
+ *   2. m_a    = (sum fl(w x_a)) / W                         with weights == NULL: vcp_centroids' mean of the same numbers, bit
+ *                                                           for bit (1.0 * x is x)
+ *   3. d_a    = fl(x_a - m_a);  p_ab = fl(fl(w d_a) d_b)    a <= b; with no weights fl(d_a d_b), the same bits
+ *   4. S_ab   = sum p_ab;  cov_ab = S_ab / W                the population covariance, one division
+ *   5. eval, evec = the eigen-solve of cov by csrc/symeig.hpp (cyclic Jacobi; the operation sequence is in its header):
+ *               eigenvalues descending, equal ones in the order of their diagonal position; eigenvector j is ROW j of evec,
+ *               its component of largest magnitude (the first such) positive, so det(evec) may be -1; a non-finite entry
+ *               of cov gives NaN in all of eval and evec; an all-zero cov gives +0 and the identity; a negative computed
+ *               eigenvalue (rounding, a rank-deficient cluster) is reported as computed
+ *   6. shape  = (sigma_max, sigma_min_inplane, flatness, tilt): sigma = sqrt(eval > 0 ? eval : 0) of eval[0] and eval[1];
+ *               flatness = eval[2] / ((eval[0] + eval[1]) + eval[2]), 0 when that sum is 0, and +0 for dim 2;
+ *               tilt = fabs(evec[2][2]), the z-component of the last axis, and 1 for dim 2; all four NaN where eval is NaN
+ * The sums are centred, in two passes, on purpose: a cloud at 1e8 from the origin loses every digit of a covariance formed
+ * from raw moments (DESIGN.md section 33 has the bound of this form and the counter-example).
+ * Outputs, each of which may be NULL: mean [K*dim]; cov [K*dim(dim+1)/2] packed by rows of the upper triangle, (xx, xy, yy)
+ * or (xx, xy, xz, yy, yz, zz); eval [K*dim]; evec [K*dim*dim]; shape [K*4]; valid [K] = 1 when W >= 2 and every entry of
+ * mean and cov is finite; counts [K] = W.  A NaN is written as 0x7FF8000000000000.
+ *   a cluster without members, or of total weight 0:   counts 0, valid 0, NaN in every double output (0 / 0)
+ *   total weight 1:                                     cov +0 (for a finite point), eval +0, evec the identity, valid 0
+ * Errors, found before any output is touched; nothing is written on an error.  VCP_ERR_ARG: NULL ctx, n < 0, K < 0, dim not
+ * 2 or 3, ld < dim, NULL pts or labels with n > 0, a negative weight (found on the device); VCP_ERR_INDEX: a label outside
+ * 0..K (found on the device); VCP_ERR_TOO_LARGE: n >= 0x7FFFFFF0, as vcp_centroids_dev.  K == 0 or n == 0: nothing to sum;
+ * the outputs for K > 0 are the empty-cluster values, VCP_OK.
+ * Every cluster takes the same road whatever its size (chunk partials, then one thread per cluster), and the result is a
+ * function of the input alone: two calls give identical bits, and so does a call after any other call on the context.
+ * Timing phases: moments_group, moments_mean, moments_cov (csrc/cluster_moments.hip). */
+int vcp_cluster_moments(vcp_ctx* ctx, const double* pts, int64_t ld, int dim, const int32_t* labels,
+                        const int32_t* weights, int64_t n, int32_t K, double* mean, double* cov, double* eval,
+                        double* evec, double* shape, uint8_t* valid, int64_t* counts);
+/* Same with device pointers, on the context's stream under the vcp_set_stream contract.  One synchronisation before the
+ * outputs are touched (the label and weight check); returns when the result is in place. */
+int vcp_cluster_moments_dev(vcp_ctx* ctx, const double* d_pts, int64_t ld, int dim, const int32_t* d_labels,
+                            const int32_t* d_weights, int64_t n, int32_t K, double* d_mean, double* d_cov,
+                            double* d_eval, double* d_evec, double* d_shape, uint8_t* d_valid, int64_t* d_counts);
+/* The eigen-solve of step 5 on the host, compiled from the same __host__ __device__ source as the kernel: s_packed holds the
+ * upper triangle by rows (3 or 6 doubles), eval [dim], evec [dim*dim]; *sweeps (may be NULL) = the Jacobi sweeps made.
+ * Returns 1, or VCP_ERR_ARG for a NULL s_packed, eval or evec or a dim that is not 2 or 3.  Needs no device and no
+ * context. */
+int vcp_selftest_sym_eig(int dim, const double* s_packed, double* eval, double* evec, int* sweeps);
+
 /* -- scan text on the device: bytes in, resident rows out --------------------------------------------------
  * The reference's scan files hold one point per line, `motor_x<TAB>motor_y<TAB>Distance` (FileMap.ReadFile,
  * FrmMain.cs:1005-1009; written back by BC/Tools.cs:233).  The bytes of one or many files go in; rows [n, 3] and the file

@@ -4,3 +4,19 @@ The compute lives in libvcp.so (hand-written HIP for gfx950 behind the C-ABI of 
 this package is the thin host-side mirror of the reference's class surface.
 """
 __version__ = "0.1.0"
+
+
+_LAZY = {
+    "cluster_quantiles": "robust", "cluster_medians": "robust", "cluster_mad": "robust", "robust_fixed_centroids": "robust",
+    "cluster_moments": "moments", "ellipse_radius": "moments", "ellipse_sides": "moments", "filter_by_moments": "moments",
+    "ClusterMoments": "moments",
+}
+
+
+def __getattr__(name):
+    """The per-cluster statistics by name (robust.py, moments.py), imported on first use: importing the package loads
+    neither numpy nor the library."""
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -41,6 +41,7 @@ SYMBOLS = [
     "vcp_cluster_mad", "vcp_cluster_mad_dev", "vcp_selftest_rank_key", "vcp_parse_scan_text",
     "vcp_parse_scan_text_dev", "vcp_selftest_parse_field", "vcp_format_rows", "vcp_format_rows_dev",
     "vcp_selftest_format_field", "vcp_selftest_format_total_dev", "vcp_selftest_wave_dev",
+    "vcp_cluster_moments", "vcp_cluster_moments_dev", "vcp_selftest_sym_eig",
 ]
 
 
@@ -1155,6 +1156,71 @@ class Context:
                                             C.c_int32(K), C.c_double(c_mad), C.c_double(floor), _ptr(d_med), _ptr(d_mad),
                                             _ptr(d_thr), _ptr(d_reject), _ptr(d_kept), C.byref(nr)))
         return nr.value
+
+    # -- per-cluster covariance, principal axes and the ellipse numbers --------------------------------
+    def cluster_moments(self, pts, labels, K, weights=None, dim=None, ld=None, outputs=None):
+        """vcp_cluster_moments.  pts [n, c] float64: row i is pts[i, :dim] (dim defaults to c); a view with a row stride,
+        such as xyz[:, :2] or wide[:, 3:6], is read in place.  With ld given, pts is a flat buffer and row i is
+        pts[i * ld + 0 .. dim).  labels [n] in 0..K (0 = none), weights int32 >= 0 or None.  Returns dict(mean [K, dim],
+        cov [K, dim (dim + 1) / 2], eval [K, dim], evec [K, dim, dim] (eigenvector j = evec[k, j]), shape [K, 4],
+        valid [K] uint8, counts [K] int64); `outputs` names the ones wanted (the others are passed as NULL)."""
+        labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        n = len(labels)
+        pts = np.asarray(pts, np.float64)
+        if ld is None:
+            if pts.ndim != 2 or pts.shape[0] != n:
+                raise ValueError("pts must be [n, c] with one row per label")
+            dim = pts.shape[1] if dim is None else int(dim)
+            if n > 1 and not (pts.strides[1] == 8 and pts.strides[0] % 8 == 0 and pts.strides[0] >= 8 * max(dim, 1)):
+                pts = np.ascontiguousarray(pts)
+            ld = pts.strides[0] // 8 if n > 1 else max(pts.shape[1], dim)
+            if n == 1:
+                pts = np.ascontiguousarray(pts)
+        else:
+            ld, dim = int(ld), int(dim)
+            pts = np.ascontiguousarray(pts).reshape(-1)
+            if dim in (2, 3) and ld >= dim and n > 0 and len(pts) < (n - 1) * ld + dim:
+                raise ValueError("pts has %d doubles for %d rows of %d at ld %d" % (len(pts), n, dim, ld))
+        weights = None if weights is None else np.ascontiguousarray(weights, np.int32).reshape(-1)
+        if weights is not None and len(weights) != n:
+            raise ValueError("weights has %d entries for %d labels" % (len(weights), n))
+        kk, d = max(int(K), 0), dim if dim in (2, 3) else 3
+        out = dict(mean=np.zeros((kk, d)), cov=np.zeros((kk, d * (d + 1) // 2)), eval=np.zeros((kk, d)),
+                   evec=np.zeros((kk, d, d)), shape=np.zeros((kk, 4)), valid=np.zeros(kk, np.uint8),
+                   counts=np.zeros(kk, np.int64))
+        if outputs is not None:
+            out = {k: v for k, v in out.items() if k in outputs}
+        g = out.get
+        self._chk(lib().vcp_cluster_moments(self._h, _ptr(pts), C.c_int64(ld), C.c_int(dim), _ptr(labels), _ptr(weights),
+                                            C.c_int64(n), C.c_int32(K), _ptr(g("mean")), _ptr(g("cov")), _ptr(g("eval")),
+                                            _ptr(g("evec")), _ptr(g("shape")), _ptr(g("valid")), _ptr(g("counts"))))
+        return out
+
+    def cluster_moments_dev(self, d_pts, ld, dim, d_labels, d_weights, n, K, d_mean=None, d_cov=None, d_eval=None,
+                            d_evec=None, d_shape=None, d_valid=None, d_counts=None):
+        """Device-pointer form (ints from tensor.data_ptr()): d_pts float64, d_labels and d_weights (or None) int32 [n];
+        the outputs float64 but d_valid uint8 [K] and d_counts int64 [K], any of them None."""
+        self._chk(lib().vcp_cluster_moments_dev(self._h, _ptr(d_pts), C.c_int64(ld), C.c_int(dim), _ptr(d_labels),
+                                                _ptr(d_weights), C.c_int64(n), C.c_int32(K), _ptr(d_mean), _ptr(d_cov),
+                                                _ptr(d_eval), _ptr(d_evec), _ptr(d_shape), _ptr(d_valid), _ptr(d_counts)))
+
+
+def selftest_sym_eig(S):
+    """vcp_selftest_sym_eig: S is a symmetric [2, 2] or [3, 3] matrix (its upper triangle is read) or the packed upper
+    triangle (3 or 6 doubles).  Returns (eval [dim], evec [dim, dim] with eigenvector j in row j, sweeps), from the source
+    the kernel is compiled from (no device)."""
+    S = np.asarray(S, np.float64)
+    if S.ndim == 2:
+        dim = S.shape[0]
+        S = S[np.triu_indices(dim)]
+    else:
+        dim = {3: 2, 6: 3}.get(len(S), 0)
+    S = np.ascontiguousarray(S)
+    ev, V, sw = np.zeros(max(dim, 1)), np.zeros((max(dim, 1), max(dim, 1))), C.c_int(0)
+    rc = lib().vcp_selftest_sym_eig(C.c_int(dim), _ptr(S), _ptr(ev), _ptr(V), C.byref(sw))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_sym_eig")
+    return ev, V, sw.value
 
 
 def selftest_rank_key(v, q, c):

@@ -39,7 +39,7 @@ struct vcp_ctx {
   //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip); at [0, 72) the counters of
   //                 vcp_cluster_quantiles / vcp_cluster_mad and at [128, 264) their ranks on the way up (cluster_quant.hip);
   //                 at [0, 24) the counters of vcp_parse_scan_text (scantext.hip); at [0, 32) those of vcp_format_rows
-  //                 (scanfmt.hip)
+  //                 (scanfmt.hip); at [0, 32) the counters of vcp_cluster_moments (cluster_moments.hip)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //                 and of vcp_eps_tree (eps_tree.hip); the cluster count of vcp_gdbscan (gdbscan.hip)
@@ -84,6 +84,9 @@ struct vcp_ctx {
   DevBuf b_tx_text, b_tx_chunk, b_tx_misc, b_tx_line, b_tx_out, b_tx_patch;
   // export text (scanfmt.hip): columns, ids and order of the host form; one word per workgroup; counters; the text
   DevBuf b_fm_in, b_fm_wg, b_fm_misc, b_fm_text;
+  // per-cluster moments (cluster_moments.hip): points, labels and weights, then the outputs, of the host form; the segment
+  // tables, the counters, and per cluster the total weight and the mean.  The chunk partials are b_aux4
+  DevBuf b_cm_in, b_cm_out, b_cm_misc;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

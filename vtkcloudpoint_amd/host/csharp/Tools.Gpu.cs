@@ -215,6 +215,52 @@ namespace vtkPointCloud
             return rects;
         }
 
+        // The moment ellipse of one cluster (vcp.h, "per-cluster covariance"): centre, the semi-axes 2 sigma (the longer
+        // first), the unit direction of the longer one, flatness and tilt (0 and 1 for the 2-D view).  clusID = position + 1.
+        public class Ellipse2D
+        {
+            public int clusID;
+            public double[] center, axis;          // 2 entries, or 3 with is3D
+            public double a, b, flatness, tilt;
+            public double Aspect { get { return a / b; } }   // +inf on a line
+        }
+
+        // Beside getCircles / getRectangles: one ellipse per cluster of two or more points with finite moments, of
+        // (X, Y, Z) with is3D, else of (motor_x, motor_y).  No hull: no limit on the size of a cluster.
+        static public List<Ellipse2D> getEllipses(List<ClusObj> clusList, bool is3D)
+        {
+            List<Ellipse2D> ells = new List<Ellipse2D>();
+            int K = clusList.Count, n = 0, d = is3D ? 3 : 2;
+            for (int j = 0; j < K; j++) n += clusList[j].li.Count;
+            if (K == 0 || n == 0) return ells;
+            double[] pts = new double[d * n];
+            int[] lab = new int[n];
+            int t = 0;
+            for (int j = 0; j < K; j++)
+                foreach (Point3D p in clusList[j].li)
+                {
+                    if (is3D) { pts[3 * t] = p.X; pts[3 * t + 1] = p.Y; pts[3 * t + 2] = p.Z; }
+                    else { pts[2 * t] = p.motor_x; pts[2 * t + 1] = p.motor_y; }
+                    lab[t] = j + 1; t++;
+                }
+            double[] mean = new double[d * K], evec = new double[d * d * K], shape = new double[4 * K];
+            byte[] valid = new byte[K];
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_cluster_moments(c.Ctx, pts, d, d, lab, null, n, K, mean, null, null, evec, shape,
+                    valid, null));
+            for (int j = 0; j < K; j++)
+            {
+                if (valid[j] == 0) continue;
+                Ellipse2D e = new Ellipse2D();
+                e.clusID = j + 1; e.center = new double[d]; e.axis = new double[d];
+                Array.Copy(mean, d * j, e.center, 0, d);
+                Array.Copy(evec, d * d * j, e.axis, 0, d);
+                e.a = 2.0 * shape[4 * j]; e.b = 2.0 * shape[4 * j + 1]; e.flatness = shape[4 * j + 2]; e.tilt = shape[4 * j + 3];
+                ells.Add(e);
+            }
+            return ells;
+        }
+
         // Tools.removeFilterPointFromClustering, Tools.cs:70-74: the stable RemoveAll, with the membership test of
         // filterID.Contains done once per listed id on the GPU side of vcp_cluster_filter.  Any int may be listed, 0 (the
         // noise points) and negative ids too, as Contains takes them; the arrays are as long as the list, not as its largest id

@@ -209,6 +209,11 @@ namespace vtkPointCloud
         // Tools.cs:468-497, takes over all lists): values[i * stride], group 0 = none; counts may be null
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_quantiles(IntPtr ctx, double[] values, long stride,
             int[] group, long n, int K, double[] q, int nq, double[] output, long[] counts);
+        // mean, covariance, principal axes and the ellipse numbers of every cluster (vcp.h: vcp_cluster_moments): row i is
+        // pts[i * ld + 0 .. dim), dim 2 or 3; weights may be null (1); every output may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_moments(IntPtr ctx, double[] pts, long ld, int dim,
+            int[] labels, int[] weights, long n, int K, double[] mean, double[] cov, double[] eval, double[] evec, double[] shape,
+            byte[] valid, long[] counts);
         // a band of Distance per group from the median absolute deviation, where Tools.FilterByDistance_FixedPoint
         // (Tools.cs:438-461) applies one band to every file: reject[i] != 0 is Point3D.isFilterByDistance
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_mad(IntPtr ctx, double[] values, long stride,
@@ -263,6 +268,9 @@ namespace vtkPointCloud
             IntPtr d_wsum, out int cf_out);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_quantiles_dev(IntPtr ctx, IntPtr d_values, long stride,
             IntPtr d_group, long n, int K, double[] q, int nq, IntPtr d_out, IntPtr d_counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_moments_dev(IntPtr ctx, IntPtr d_pts, long ld, int dim,
+            IntPtr d_labels, IntPtr d_weights, long n, int K, IntPtr d_mean, IntPtr d_cov, IntPtr d_eval, IntPtr d_evec, IntPtr d_shape,
+            IntPtr d_valid, IntPtr d_counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_mad_dev(IntPtr ctx, IntPtr d_values, long stride,
             IntPtr d_group, long n, int K, double c_mad, double floor, IntPtr d_med, IntPtr d_mad, IntPtr d_thr,
             IntPtr d_reject, IntPtr d_kept, out long n_rejected);

@@ -195,7 +195,41 @@ def removeFilterPointFromClustering(dataSet, filterID):
     dataSet[:] = [p for p in dataSet if p.clusterId not in ids]
 
 
+class Ellipse2D:
+    """The moment ellipse of one cluster (include/vcp.h, "per-cluster covariance"): centre, the semi-axes 2 sigma (the
+    longer first), the unit direction of the longer one and clusID = position + 1, like the circles.  With is3D the
+    moments are those of (X, Y, Z): centre and axis are 3-D, and flatness / tilt say how flat the cluster is and how far
+    its normal leans from Z; for the 2-D view they are 0 and 1."""
+
+    def __init__(self, center, a, b, axis, flatness, tilt, cluID=0):
+        self.center = np.array(center, np.float64)
+        self.a, self.b = float(a), float(b)
+        self.axis = np.array(axis, np.float64)
+        self.flatness, self.tilt, self.clusID = float(flatness), float(tilt), int(cluID)
+        self.radius = self.a
+
+
+def getEllipses(clusList, is3D, ctx=None):
+    """Beside getCircles / getRectangles: one Ellipse2D per cluster of two or more points with finite moments
+    (vcp_cluster_moments): (X, Y, Z) with is3D, else (motor_x, motor_y).  No hull: no limit on the cluster's size, and one
+    stray point moves the axes by 1 / count of its distance, not by all of it."""
+    ctx = ctx or default_context()
+    K = len(clusList)
+    pts, lab = [], []
+    for j, ob in enumerate(clusList):
+        for p in ob.li:
+            pts.append((p.X, p.Y, p.Z) if is3D else (p.motor_x, p.motor_y))
+            lab.append(j + 1)
+    if K == 0 or not pts:
+        return []
+    dim = 3 if is3D else 2
+    r = ctx.cluster_moments(np.array(pts, np.float64).reshape(-1, dim), np.array(lab, np.int32), K)
+    return [Ellipse2D(r["mean"][j], 2.0 * r["shape"][j, 0], 2.0 * r["shape"][j, 1], r["evec"][j, 0], r["shape"][j, 2],
+                      r["shape"][j, 3], j + 1) for j in range(K) if r["valid"][j]]
+
+
 Tools.getRectangles = staticmethod(getRectangles)
+Tools.getEllipses = staticmethod(getEllipses)
 Tools.filterClusters = staticmethod(filterClusters)
 Tools.removeFilterPointFromClustering = staticmethod(removeFilterPointFromClustering)
 
