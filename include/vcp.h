@@ -1221,6 +1221,70 @@ int vcp_cluster_moments_dev(vcp_ctx* ctx, const double* d_pts, int64_t ld, int d
  * context. */
 int vcp_selftest_sym_eig(int dim, const double* s_packed, double* eval, double* evec, int* sweeps);
 
+/* -- per-cluster least-squares sphere (3-D) and circle (2-D) fit ---------------------------------------------
+ * The instrument is the origin of X, Y, Z (vcp_import_convert), so a target is seen from one side: the mean of the returns
+ * of a sphere of radius R lies about 2R/3 in front of its centre, on the line to the instrument, and a half-hidden disc has
+ * its mean in the visible half.  Taken over a field these shifts are a radial shrink, which no rigid fit absorbs.  The
+ * least-squares fit gives the centre the returns lie around, with the radius free or fixed to the known target radius, and
+ * a radius, a residual and a coverage number to judge the cluster by.
+ *   pts, ld, dim, labels, weights     exactly as in vcp_cluster_moments (dim 2: circle, dim 3: sphere)
+ *   fixed_radius   0: the radius is fitted; finite and > 0: it is this value
+ *   rounds         Gauss-Newton rounds, 0..64
+ * Definition.  All arithmetic binary64, every operation rounded on its own (no FMA contraction), / and sqrt correctly
+ * rounded.  The members of cluster k in ascending point index; every sum through the fixed tree of vcp_centroids, as stated
+ * for vcp_cluster_moments.  x . y for vectors of dim 2 is fl(fl(x0 y0) + fl(x1 y1)), of dim 3 fl(that + fl(x2 y2)).
+ *   1. W, m, d_a = fl(x_a - m_a)      steps 1 to 3 of vcp_cluster_moments: counts and m are its bits.  Everything below works
+ *                                     on d and on u = c - m, never on raw coordinates: a field at 1e8 keeps its digits
+ *   2. the algebraic start (Kasa, centred):
+ *        S_ab = sum fl(fl(w d_a) d_b)  (a <= b; vcp_cluster_moments' S);   q = d . d;   T_a = sum fl(fl(w q) d_a)
+ *        u0   = the solution of S u0 = h, h_a = fl(T_a * 0.5), by csrc/spdsolve.hpp (L D L^T; the operation sequence is in
+ *               its header; it fails when a pivot is not finite and > 0)
+ *        r0   = sqrt(fl(u0 . u0 + fl(tr / W))),  tr = fl(S_00 + S_11), for dim 3 fl(that + S_22)
+ *        alg  = (fl(m_a + u0_a), r0);   u = u0;   r_ref = fixed_radius > 0 ? fixed_radius : r0
+ *   3. `rounds` times, on the residual rho_i - r:
+ *        e = fl(d - u);  rho = sqrt(e . e);  nu_a = fl(e_a / rho), and nu = 0 for a member with rho == 0: it lies on the
+ *        current centre, has no direction, and adds fl(w * 0) to every sum with nu in it
+ *        N_ab = sum fl(fl(w nu_a) nu_b) (a <= b);  b_a = sum fl(w nu_a);  R = sum fl(w rho);  g_a = sum fl(fl(w rho) nu_a)
+ *        free:   M_ab = fl(N_ab - fl(fl(b_a b_b) / W));  y_a = fl(g_a - fl(fl(R b_a) / W));  r_ref = fl(R / W)
+ *        fixed:  M = N;                                  y_a = fl(g_a - fl(fixed_radius * b_a))
+ *        delta = the solution of M delta = y (spdsolve.hpp);   u_a = fl(u_a + delta_a);   step = sqrt(delta . delta)
+ *      The free form is the normal equations of (u, r) with r eliminated.  delta = +M^-1 y: the other sign diverges.
+ *   4. the closing pass, at the last u:  e, rho, nu as in 3;  c = fl(rho - r_ref)
+ *        b_a = sum fl(w nu_a);   C1 = sum fl(w c);   C2 = sum fl(fl(w c) c);   cbar = fl(C1 / W)
+ *        free:   radius = fl(r_ref + cbar)  (= sum w rho / W, summed around r_ref, the radius the last round saw, or r0);
+ *                rms = sqrt(max(fl(fl(C2 / W) - fl(cbar cbar)), 0))
+ *        fixed:  radius = fixed_radius;   rms = sqrt(fl(C2 / W))
+ *        centre_a = fl(m_a + u_a);   cap = fl(sqrt(b . b) / W);   step = the last round's (0 for rounds == 0)
+ *      rms is formed from the centred c, never from sum rho^2 - ...  cap tells how much of the target was seen: about 0
+ *      for a whole sphere, 2/3 for a cap seen from afar, towards 1 for a sliver, where the fit is ill-conditioned.
+ *   5. valid = 1 when W >= dim + 1 (free) or W >= dim (fixed), no solve of the call failed for the cluster, and every double
+ *      output of the cluster is finite.  An invalid cluster has NaN (0x7FF8000000000000) in every double output and keeps
+ *      its counts: too few members, coincident, collinear or (dim 3) coplanar members (a pivot of 0), a non-finite
+ *      coordinate, a cluster without members or of total weight 0 (counts 0).  Once a solve fails the cluster stays invalid;
+ *      every cluster runs every round, and nothing the host decides depends on the data after the label and weight check.
+ * Outputs, each of which may be NULL: centre [K*dim]; radius, rms, cap, step [K]; alg [K*(dim+1)]; valid [K]; counts [K] = W.
+ * Errors, found before any output is touched; nothing is written on an error.  Those of vcp_cluster_moments, and
+ * VCP_ERR_ARG for a fixed_radius that is negative, NaN or infinite and for rounds outside 0..64; VCP_ERR_NOMEM when the
+ * workspace of n * (8 dim + 4) bytes cannot be had (there is no second road).  K == 0 or n == 0 as in vcp_cluster_moments.
+ * The result is a function of the input alone: two calls give identical bits, and so does a call after any other call on
+ * the context.  Timing phases: spheres_group, spheres_start, spheres_rounds (csrc/cluster_spheres.hip, DESIGN.md section
+ * 34). */
+int vcp_cluster_spheres(vcp_ctx* ctx, const double* pts, int64_t ld, int dim, const int32_t* labels,
+                        const int32_t* weights, int64_t n, int32_t K, double fixed_radius, int rounds, double* centre,
+                        double* radius, double* rms, double* cap, double* step, double* alg, uint8_t* valid,
+                        int64_t* counts);
+/* Same with device pointers, on the context's stream under the vcp_set_stream contract.  One synchronisation before the
+ * outputs are touched (the label and weight check); returns when the result is in place. */
+int vcp_cluster_spheres_dev(vcp_ctx* ctx, const double* d_pts, int64_t ld, int dim, const int32_t* d_labels,
+                            const int32_t* d_weights, int64_t n, int32_t K, double fixed_radius, int rounds,
+                            double* d_centre, double* d_radius, double* d_rms, double* d_cap, double* d_step,
+                            double* d_alg, uint8_t* d_valid, int64_t* d_counts);
+/* The solve of steps 2 and 3 on the host, compiled from the same __host__ __device__ source as the kernels: s_packed holds
+ * the upper triangle by rows (3 or 6 doubles), b and x [dim]; *ok (may be NULL) = 1, or 0 when a pivot was not finite and
+ * > 0 (x is then NaN).  Returns 1, or VCP_ERR_ARG for a NULL s_packed, b or x or a dim that is not 2 or 3 (nothing is
+ * written).  Needs no device and no context. */
+int vcp_selftest_spd_solve(int dim, const double* s_packed, const double* b, double* x, int* ok);
+
 /* -- scan text on the device: bytes in, resident rows out --------------------------------------------------
  * The reference's scan files hold one point per line, `motor_x<TAB>motor_y<TAB>Distance` (FileMap.ReadFile,
  * FrmMain.cs:1005-1009; written back by BC/Tools.cs:233).  The bytes of one or many files go in; rows [n, 3] and the file

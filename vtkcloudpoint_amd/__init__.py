@@ -10,11 +10,12 @@ _LAZY = {
     "cluster_quantiles": "robust", "cluster_medians": "robust", "cluster_mad": "robust", "robust_fixed_centroids": "robust",
     "cluster_moments": "moments", "ellipse_radius": "moments", "ellipse_sides": "moments", "filter_by_moments": "moments",
     "ClusterMoments": "moments",
+    "cluster_spheres": "spheres", "sphere_centres": "spheres", "filter_by_spheres": "spheres", "ClusterSpheres": "spheres",
 }
 
 
 def __getattr__(name):
-    """The per-cluster statistics by name (robust.py, moments.py), imported on first use: importing the package loads
+    """The per-cluster statistics by name (robust.py, moments.py, spheres.py), imported on first use: importing the package loads
     neither numpy nor the library."""
     if name in _LAZY:
         import importlib

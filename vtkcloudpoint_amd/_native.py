@@ -42,6 +42,7 @@ SYMBOLS = [
     "vcp_parse_scan_text_dev", "vcp_selftest_parse_field", "vcp_format_rows", "vcp_format_rows_dev",
     "vcp_selftest_format_field", "vcp_selftest_format_total_dev", "vcp_selftest_wave_dev",
     "vcp_cluster_moments", "vcp_cluster_moments_dev", "vcp_selftest_sym_eig",
+    "vcp_cluster_spheres", "vcp_cluster_spheres_dev", "vcp_selftest_spd_solve",
 ]
 
 
@@ -89,6 +90,33 @@ def _ptr(a):
     if isinstance(a, int):
         return C.c_void_p(a)
     return C.c_void_p(a.ctypes.data)
+
+
+def _cluster_rows(pts, labels, weights, dim, ld):
+    """The (pts, labels, weights, n, dim, ld) that vcp_cluster_moments and vcp_cluster_spheres take: pts [n, c] float64
+    whose rows are read in place at their stride where that is a whole number of doubles (else copied), or with ld given a
+    flat buffer; labels and weights int32 [n]."""
+    labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+    n = len(labels)
+    pts = np.asarray(pts, np.float64)
+    if ld is None:
+        if pts.ndim != 2 or pts.shape[0] != n:
+            raise ValueError("pts must be [n, c] with one row per label")
+        dim = pts.shape[1] if dim is None else int(dim)
+        if n > 1 and not (pts.strides[1] == 8 and pts.strides[0] % 8 == 0 and pts.strides[0] >= 8 * max(dim, 1)):
+            pts = np.ascontiguousarray(pts)
+        ld = pts.strides[0] // 8 if n > 1 else max(pts.shape[1], dim)
+        if n == 1:
+            pts = np.ascontiguousarray(pts)
+    else:
+        ld, dim = int(ld), int(dim)
+        pts = np.ascontiguousarray(pts).reshape(-1)
+        if dim in (2, 3) and ld >= dim and n > 0 and len(pts) < (n - 1) * ld + dim:
+            raise ValueError("pts has %d doubles for %d rows of %d at ld %d" % (len(pts), n, dim, ld))
+    weights = None if weights is None else np.ascontiguousarray(weights, np.int32).reshape(-1)
+    if weights is not None and len(weights) != n:
+        raise ValueError("weights has %d entries for %d labels" % (len(weights), n))
+    return pts, labels, weights, n, dim, ld
 
 
 def _f64(a, cols=None):
@@ -1164,26 +1192,7 @@ class Context:
         pts[i * ld + 0 .. dim).  labels [n] in 0..K (0 = none), weights int32 >= 0 or None.  Returns dict(mean [K, dim],
         cov [K, dim (dim + 1) / 2], eval [K, dim], evec [K, dim, dim] (eigenvector j = evec[k, j]), shape [K, 4],
         valid [K] uint8, counts [K] int64); `outputs` names the ones wanted (the others are passed as NULL)."""
-        labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
-        n = len(labels)
-        pts = np.asarray(pts, np.float64)
-        if ld is None:
-            if pts.ndim != 2 or pts.shape[0] != n:
-                raise ValueError("pts must be [n, c] with one row per label")
-            dim = pts.shape[1] if dim is None else int(dim)
-            if n > 1 and not (pts.strides[1] == 8 and pts.strides[0] % 8 == 0 and pts.strides[0] >= 8 * max(dim, 1)):
-                pts = np.ascontiguousarray(pts)
-            ld = pts.strides[0] // 8 if n > 1 else max(pts.shape[1], dim)
-            if n == 1:
-                pts = np.ascontiguousarray(pts)
-        else:
-            ld, dim = int(ld), int(dim)
-            pts = np.ascontiguousarray(pts).reshape(-1)
-            if dim in (2, 3) and ld >= dim and n > 0 and len(pts) < (n - 1) * ld + dim:
-                raise ValueError("pts has %d doubles for %d rows of %d at ld %d" % (len(pts), n, dim, ld))
-        weights = None if weights is None else np.ascontiguousarray(weights, np.int32).reshape(-1)
-        if weights is not None and len(weights) != n:
-            raise ValueError("weights has %d entries for %d labels" % (len(weights), n))
+        pts, labels, weights, n, dim, ld = _cluster_rows(pts, labels, weights, dim, ld)
         kk, d = max(int(K), 0), dim if dim in (2, 3) else 3
         out = dict(mean=np.zeros((kk, d)), cov=np.zeros((kk, d * (d + 1) // 2)), eval=np.zeros((kk, d)),
                    evec=np.zeros((kk, d, d)), shape=np.zeros((kk, 4)), valid=np.zeros(kk, np.uint8),
@@ -1203,6 +1212,52 @@ class Context:
         self._chk(lib().vcp_cluster_moments_dev(self._h, _ptr(d_pts), C.c_int64(ld), C.c_int(dim), _ptr(d_labels),
                                                 _ptr(d_weights), C.c_int64(n), C.c_int32(K), _ptr(d_mean), _ptr(d_cov),
                                                 _ptr(d_eval), _ptr(d_evec), _ptr(d_shape), _ptr(d_valid), _ptr(d_counts)))
+
+    # -- per-cluster least-squares sphere / circle fit ---------------------------------------------------
+    def cluster_spheres(self, pts, labels, K, weights=None, dim=None, ld=None, fixed_radius=0.0, rounds=12, outputs=None):
+        """vcp_cluster_spheres.  pts, labels, weights, dim and ld as in cluster_moments (a strided view is read in place).
+        fixed_radius 0 fits the radius, > 0 fixes it; rounds 0..64 Gauss-Newton rounds.  Returns dict(centre [K, dim],
+        radius, rms, cap, step [K], alg [K, dim + 1] (the algebraic start: centre, radius), valid [K] uint8, counts [K]
+        int64); `outputs` names the ones wanted (the others are passed as NULL)."""
+        pts, labels, weights, n, dim, ld = _cluster_rows(pts, labels, weights, dim, ld)
+        kk, d = max(int(K), 0), dim if dim in (2, 3) else 3
+        out = dict(centre=np.zeros((kk, d)), radius=np.zeros(kk), rms=np.zeros(kk), cap=np.zeros(kk), step=np.zeros(kk),
+                   alg=np.zeros((kk, d + 1)), valid=np.zeros(kk, np.uint8), counts=np.zeros(kk, np.int64))
+        if outputs is not None:
+            out = {k: v for k, v in out.items() if k in outputs}
+        g = out.get
+        self._chk(lib().vcp_cluster_spheres(self._h, _ptr(pts), C.c_int64(ld), C.c_int(dim), _ptr(labels), _ptr(weights),
+                                            C.c_int64(n), C.c_int32(K), C.c_double(fixed_radius), C.c_int(rounds),
+                                            _ptr(g("centre")), _ptr(g("radius")), _ptr(g("rms")), _ptr(g("cap")),
+                                            _ptr(g("step")), _ptr(g("alg")), _ptr(g("valid")), _ptr(g("counts"))))
+        return out
+
+    def cluster_spheres_dev(self, d_pts, ld, dim, d_labels, d_weights, n, K, fixed_radius, rounds, d_centre=None,
+                            d_radius=None, d_rms=None, d_cap=None, d_step=None, d_alg=None, d_valid=None, d_counts=None):
+        """Device-pointer form (ints from tensor.data_ptr()): d_pts float64, d_labels and d_weights (or None) int32 [n];
+        the outputs float64 but d_valid uint8 [K] and d_counts int64 [K], any of them None."""
+        self._chk(lib().vcp_cluster_spheres_dev(self._h, _ptr(d_pts), C.c_int64(ld), C.c_int(dim), _ptr(d_labels),
+                                                _ptr(d_weights), C.c_int64(n), C.c_int32(K), C.c_double(fixed_radius),
+                                                C.c_int(rounds), _ptr(d_centre), _ptr(d_radius), _ptr(d_rms), _ptr(d_cap),
+                                                _ptr(d_step), _ptr(d_alg), _ptr(d_valid), _ptr(d_counts)))
+
+
+def selftest_spd_solve(S, b):
+    """vcp_selftest_spd_solve: S is a symmetric [2, 2] or [3, 3] matrix (its upper triangle is read) or the packed upper
+    triangle (3 or 6 doubles), b [dim].  Returns (x [dim], ok), from the source the kernels are compiled from (no
+    device)."""
+    S = np.asarray(S, np.float64)
+    if S.ndim == 2:
+        dim = S.shape[0]
+        S = S[np.triu_indices(dim)]
+    else:
+        dim = {3: 2, 6: 3}.get(len(S), 0)
+    S, b = np.ascontiguousarray(S), np.ascontiguousarray(b, np.float64)
+    x, ok = np.zeros(max(dim, 1)), C.c_int(0)
+    rc = lib().vcp_selftest_spd_solve(C.c_int(dim), _ptr(S), _ptr(b), _ptr(x), C.byref(ok))
+    if rc < 0:
+        raise VcpError(rc, "vcp_selftest_spd_solve")
+    return x, ok.value
 
 
 def selftest_sym_eig(S):

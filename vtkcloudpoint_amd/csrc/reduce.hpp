@@ -51,3 +51,29 @@ __device__ __forceinline__ void block_fold(const double (&v)[N], F, double* __re
     out[threadIdx.x] = r;
   }
 }
+
+// The same fold of sums when the caller knows, wave by wave, whether any lane of the wave added a term (`wave_has_terms` is
+// wave-uniform).  A wave whose lanes all hold the +0.0 they started from sums to +0.0 through the shuffle tree, so it writes
+// +0.0 without the shuffles: the same bits as block_fold with FoldSum.  With clusters far smaller than a workgroup most waves
+// are such waves, and the shuffles are what a fold costs.
+template <int TB, int N>
+__device__ __forceinline__ void block_fold_sum_sparse(const double (&v)[N], bool wave_has_terms, double* __restrict__ out) {
+  __shared__ double sm[TB / 64][N];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (wave_has_terms) {
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+      const double r = wave_sum(v[k]);
+      if (lane == 0) sm[w][k] = r;
+    }
+  } else if (lane < N) {
+    sm[w][lane] = 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    double r = sm[0][threadIdx.x];
+#pragma unroll
+    for (int j = 1; j < TB / 64; j++) r = r + sm[j][threadIdx.x];
+    out[threadIdx.x] = r;
+  }
+}

@@ -39,7 +39,7 @@ struct vcp_ctx {
   //                 at [0, 128) the weight check and the bounds of vcp_gdbscan (gdbscan.hip); at [0, 72) the counters of
   //                 vcp_cluster_quantiles / vcp_cluster_mad and at [128, 264) their ranks on the way up (cluster_quant.hip);
   //                 at [0, 24) the counters of vcp_parse_scan_text (scantext.hip); at [0, 32) those of vcp_format_rows
-  //                 (scanfmt.hip); at [0, 32) the counters of vcp_cluster_moments (cluster_moments.hip)
+  //                 (scanfmt.hip); at [0, 32) the counters of vcp_cluster_moments and vcp_cluster_spheres (cluster_seg.hpp)
   //   [1024, 2048)  the partition's SelState (blockpart.hip); the all-pairs kernel's counters (blocks.hip: blocks_cluster);
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //                 and of vcp_eps_tree (eps_tree.hip); the cluster count of vcp_gdbscan (gdbscan.hip)
@@ -87,6 +87,10 @@ struct vcp_ctx {
   // per-cluster moments (cluster_moments.hip): points, labels and weights, then the outputs, of the host form; the segment
   // tables, the counters, and per cluster the total weight and the mean.  The chunk partials are b_aux4
   DevBuf b_cm_in, b_cm_out, b_cm_misc;
+  // per-cluster sphere / circle fit (cluster_spheres.hip): points, labels and weights, then the outputs, of the host form;
+  // the same tables as b_cm_misc with the per-cluster fit state behind them; the centred rows d (one plane per coordinate)
+  // and the weights in (label, index) order, which every round streams.  The chunk partials are b_aux4
+  DevBuf b_cs_in, b_cs_out, b_cs_misc, b_cs_d;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
   // timing

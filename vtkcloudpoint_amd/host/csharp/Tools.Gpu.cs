@@ -261,6 +261,51 @@ namespace vtkPointCloud
             return ells;
         }
 
+        // The least-squares sphere (is3D) or circle of one cluster (vcp.h, "per-cluster least-squares sphere"): the centre the
+        // returns lie around (their mean sits 2/3 of a radius in front of it), the radius, the rms of the residuals and cap,
+        // which says how one-sided the returns are (2/3 for a sphere seen from afar).  clusID = position + 1.
+        public class Sphere
+        {
+            public int clusID;
+            public double[] center;                // 2 entries, or 3 with is3D
+            public double radius, rms, cap;
+        }
+
+        // Beside getCircles / getRectangles / getEllipses: one Sphere per cluster with a valid fit, of (X, Y, Z) with is3D,
+        // else of (motor_x, motor_y).  radius 0 fits the radius; a value > 0 fixes it to the known target radius.
+        static public List<Sphere> getSpheres(List<ClusObj> clusList, bool is3D, double radius)
+        {
+            List<Sphere> sph = new List<Sphere>();
+            int K = clusList.Count, n = 0, d = is3D ? 3 : 2;
+            for (int j = 0; j < K; j++) n += clusList[j].li.Count;
+            if (K == 0 || n == 0) return sph;
+            double[] pts = new double[d * n];
+            int[] lab = new int[n];
+            int t = 0;
+            for (int j = 0; j < K; j++)
+                foreach (Point3D p in clusList[j].li)
+                {
+                    if (is3D) { pts[3 * t] = p.X; pts[3 * t + 1] = p.Y; pts[3 * t + 2] = p.Z; }
+                    else { pts[2 * t] = p.motor_x; pts[2 * t + 1] = p.motor_y; }
+                    lab[t] = j + 1; t++;
+                }
+            double[] centre = new double[d * K], rad = new double[K], rms = new double[K], cap = new double[K];
+            byte[] valid = new byte[K];
+            using (VcpNative.Lease c = VcpNative.Rent())
+                VcpNative.Check(c, VcpNative.vcp_cluster_spheres(c.Ctx, pts, d, d, lab, null, n, K, radius, 12, centre, rad, rms,
+                    cap, null, null, valid, null));
+            for (int j = 0; j < K; j++)
+            {
+                if (valid[j] == 0) continue;
+                Sphere s = new Sphere();
+                s.clusID = j + 1; s.center = new double[d];
+                Array.Copy(centre, d * j, s.center, 0, d);
+                s.radius = rad[j]; s.rms = rms[j]; s.cap = cap[j];
+                sph.Add(s);
+            }
+            return sph;
+        }
+
         // Tools.removeFilterPointFromClustering, Tools.cs:70-74: the stable RemoveAll, with the membership test of
         // filterID.Contains done once per listed id on the GPU side of vcp_cluster_filter.  Any int may be listed, 0 (the
         // noise points) and negative ids too, as Contains takes them; the arrays are as long as the list, not as its largest id

@@ -214,6 +214,11 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_moments(IntPtr ctx, double[] pts, long ld, int dim,
             int[] labels, int[] weights, long n, int K, double[] mean, double[] cov, double[] eval, double[] evec, double[] shape,
             byte[] valid, long[] counts);
+        // least-squares sphere (dim 3) or circle (dim 2) of every cluster (vcp.h: vcp_cluster_spheres): pts, ld, dim, labels and
+        // weights as in vcp_cluster_moments; fixed_radius 0 fits the radius, > 0 fixes it; rounds 0..64; every output may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_spheres(IntPtr ctx, double[] pts, long ld, int dim,
+            int[] labels, int[] weights, long n, int K, double fixed_radius, int rounds, double[] centre, double[] radius, double[] rms,
+            double[] cap, double[] step, double[] alg, byte[] valid, long[] counts);
         // a band of Distance per group from the median absolute deviation, where Tools.FilterByDistance_FixedPoint
         // (Tools.cs:438-461) applies one band to every file: reject[i] != 0 is Point3D.isFilterByDistance
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_mad(IntPtr ctx, double[] values, long stride,
@@ -271,6 +276,9 @@ namespace vtkPointCloud
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_moments_dev(IntPtr ctx, IntPtr d_pts, long ld, int dim,
             IntPtr d_labels, IntPtr d_weights, long n, int K, IntPtr d_mean, IntPtr d_cov, IntPtr d_eval, IntPtr d_evec, IntPtr d_shape,
             IntPtr d_valid, IntPtr d_counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_spheres_dev(IntPtr ctx, IntPtr d_pts, long ld, int dim,
+            IntPtr d_labels, IntPtr d_weights, long n, int K, double fixed_radius, int rounds, IntPtr d_centre, IntPtr d_radius, IntPtr d_rms,
+            IntPtr d_cap, IntPtr d_step, IntPtr d_alg, IntPtr d_valid, IntPtr d_counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int vcp_cluster_mad_dev(IntPtr ctx, IntPtr d_values, long stride,
             IntPtr d_group, long n, int K, double c_mad, double floor, IntPtr d_med, IntPtr d_mad, IntPtr d_thr,
             IntPtr d_reject, IntPtr d_kept, out long n_rejected);

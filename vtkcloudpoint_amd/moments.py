@@ -22,6 +22,30 @@ def _is_dev(*arrays):
     return any(torch.is_tensor(a) for a in arrays)
 
 
+def _dev_rows(points, labels, weights, dim):
+    """The (points, labels, weights, n, dim, ld) of the device-pointer forms from torch tensors on the GPU: checked, the
+    labels and weights flat, the rows read in place at their stride where the columns are contiguous (else copied)."""
+    import torch
+    if not (torch.is_tensor(points) and torch.is_tensor(labels) and (weights is None or torch.is_tensor(weights))):
+        raise ValueError("points, labels and weights must all be torch tensors on the GPU, or all numpy arrays")
+    if points.dtype != torch.float64 or not points.is_cuda or points.dim() != 2:
+        raise ValueError("points must be a float64 [n, c] tensor on the GPU (or a numpy array)")
+    if labels.dtype != torch.int32 or not labels.is_cuda:
+        raise ValueError("labels must be an int32 tensor on the GPU (or a numpy array)")
+    if weights is not None and (weights.dtype != torch.int32 or not weights.is_cuda):
+        raise ValueError("weights must be an int32 tensor on the GPU (or a numpy array)")
+    labels = labels.contiguous().reshape(-1)
+    weights = None if weights is None else weights.contiguous().reshape(-1)
+    n = labels.numel()
+    if points.shape[0] != n or (weights is not None and weights.numel() != n):
+        raise ValueError("points, labels and weights disagree on n")
+    dim = points.shape[1] if dim is None else int(dim)
+    if n > 1 and not (points.stride(1) == 1 and points.stride(0) >= max(dim, 1)):
+        points = points.contiguous()
+    ld = int(points.stride(0)) if n > 1 else max(points.shape[1], dim)
+    return points, labels, weights, n, dim, ld
+
+
 class ClusterMoments:
     """What cluster_moments returns: mean [K, dim], cov [K, dim (dim + 1) / 2] (xx, xy, (xz,) yy, (yz, zz)), eval [K, dim]
     descending, evec [K, dim, dim] (eigenvector j of cluster k is evec[k, j]), shape [K, 4] = (sigma_max,
@@ -63,23 +87,7 @@ def cluster_moments(points, labels, K, weights=None, dim=None, ctx=None):
     K = int(K)
     if _is_dev(points, labels, weights):
         import torch
-        if not (torch.is_tensor(points) and torch.is_tensor(labels) and (weights is None or torch.is_tensor(weights))):
-            raise ValueError("points, labels and weights must all be torch tensors on the GPU, or all numpy arrays")
-        if points.dtype != torch.float64 or not points.is_cuda or points.dim() != 2:
-            raise ValueError("points must be a float64 [n, c] tensor on the GPU (or a numpy array)")
-        if labels.dtype != torch.int32 or not labels.is_cuda:
-            raise ValueError("labels must be an int32 tensor on the GPU (or a numpy array)")
-        if weights is not None and (weights.dtype != torch.int32 or not weights.is_cuda):
-            raise ValueError("weights must be an int32 tensor on the GPU (or a numpy array)")
-        labels = labels.contiguous().reshape(-1)
-        weights = None if weights is None else weights.contiguous().reshape(-1)
-        n = labels.numel()
-        if points.shape[0] != n or (weights is not None and weights.numel() != n):
-            raise ValueError("points, labels and weights disagree on n")
-        dim = points.shape[1] if dim is None else int(dim)
-        if n > 1 and not (points.stride(1) == 1 and points.stride(0) >= max(dim, 1)):
-            points = points.contiguous()
-        ld = int(points.stride(0)) if n > 1 else max(points.shape[1], dim)
+        points, labels, weights, n, dim, ld = _dev_rows(points, labels, weights, dim)
         d, kk, dev = (dim if dim in (2, 3) else 3), max(K, 0), points.device
         z = lambda shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)
         out = dict(mean=z((kk, d)), cov=z((kk, d * (d + 1) // 2)), eval=z((kk, d)), evec=z((kk, d, d)), shape=z((kk, 4)),

@@ -228,8 +228,38 @@ def getEllipses(clusList, is3D, ctx=None):
                       r["shape"][j, 3], j + 1) for j in range(K) if r["valid"][j]]
 
 
+class Sphere:
+    """The least-squares sphere (is3D) or circle of one cluster (include/vcp.h, "per-cluster least-squares sphere"):
+    center, radius, the rms of the residuals, cap (how one-sided the returns are: 2/3 for a sphere seen from afar) and
+    clusID = position + 1, like the circles."""
+
+    def __init__(self, center, radius, rms, cap, cluID=0):
+        self.center = np.array(center, np.float64)
+        self.radius, self.rms, self.cap, self.clusID = float(radius), float(rms), float(cap), int(cluID)
+
+
+def getSpheres(clusList, is3D, radius=None, rounds=12, ctx=None):
+    """Beside getCircles / getRectangles / getEllipses: one Sphere per cluster with a valid fit (vcp_cluster_spheres) of
+    (X, Y, Z) with is3D, else of (motor_x, motor_y); radius=None fits the radius, a value fixes it to the target's.  The
+    center is where the target is; the cluster's mean lies 2/3 of a radius in front of it."""
+    ctx = ctx or default_context()
+    K = len(clusList)
+    pts, lab = [], []
+    for j, ob in enumerate(clusList):
+        for p in ob.li:
+            pts.append((p.X, p.Y, p.Z) if is3D else (p.motor_x, p.motor_y))
+            lab.append(j + 1)
+    if K == 0 or not pts:
+        return []
+    dim = 3 if is3D else 2
+    r = ctx.cluster_spheres(np.array(pts, np.float64).reshape(-1, dim), np.array(lab, np.int32), K,
+                            fixed_radius=0.0 if radius is None else float(radius), rounds=rounds)
+    return [Sphere(r["centre"][j], r["radius"][j], r["rms"][j], r["cap"][j], j + 1) for j in range(K) if r["valid"][j]]
+
+
 Tools.getRectangles = staticmethod(getRectangles)
 Tools.getEllipses = staticmethod(getEllipses)
+Tools.getSpheres = staticmethod(getSpheres)
 Tools.filterClusters = staticmethod(filterClusters)
 Tools.removeFilterPointFromClustering = staticmethod(removeFilterPointFromClustering)
 
