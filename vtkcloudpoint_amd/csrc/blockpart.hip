@@ -1005,7 +1005,9 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
   VCP_LAUNCH(ctx, k_sel_init, dim3(1), dim3(PT), 0, st, d_sel, ghist, (uint64_t)s->take, (uint32_t)n);
   SelState* hs = reinterpret_cast<SelState*>(reinterpret_cast<char*>(ctx->pinned) + 1024);
   bool done = false;
+  uint32_t passes = 0;  // global select passes (for the trace)
   for (uint32_t pass = 0; pass < 8 && !done; pass++) {
+    passes++;
     VCP_LAUNCH(ctx, k_sel_hist, dim3(nchunk), dim3(PT), 0, st, d_key, n, out, (uint32_t)chunk, pass, d_sel, ghist);
     VCP_LAUNCH(ctx, k_sel_pick, dim3(1), dim3(PT), 0, st, d_sel, ghist);
     VCP_LAUNCH(ctx, k_sel_collect, dim3(nchunk), dim3(PT), 0, st, d_key, n, out, (uint32_t)chunk, d_sel,
@@ -1083,6 +1085,9 @@ int vcp_blocks_plan(vcp_ctx* ctx, BlocksState* s, const double* d_key, const dou
     VCP_HIP(ctx, hipMemcpyAsync(s->h_sbstart.data(), s->sbstart.p, ((size_t)NS + 1) * 4, hipMemcpyDeviceToHost, st));
     VCP_HIP(ctx, hipStreamSynchronize(st));
   }
+  if (vcp_trace_on())
+    vcp_trace_line("blocks plan n=%lld take=%d passes=%u nblocks=%lld rows=%d cols=%d fsh=%u NS=%u nchunk=%u keyed=%d",
+                   (long long)n, s->take, passes, (long long)s->nblocks, s->rows, s->cols, fsh, NS, nchunk, (int)keyed);
   s->planned = true;
   return VCP_OK;
 }
@@ -1195,6 +1200,11 @@ int vcp_blocks_build(vcp_ctx* ctx, BlocksState* s, uint32_t S_lo, uint32_t S_hi,
   VCP_HIP(ctx, hipStreamSynchronize(st));
   s->m = S_hi > S_lo ? s->h_blockstart[(size_t)s->b_hi] : 0;
   s->nbig = hs->nbig;
+  // (the counters as the last kernel left them: nfall includes the sub-ranges the LIST sort passed on)
+  if (vcp_trace_on())
+    vcp_trace_line("blocks build S_lo=%u S_hi=%u b_lo=%lld b_hi=%lld m=%lld nbig=%u nbinfo=%u nslice=%u nvirt=%u nfall=%u", S_lo,
+                   S_hi, (long long)s->b_lo, (long long)s->b_hi, (long long)s->m, hs->nbig, hs->nbinfo, hs->nslice, hs->nvirt,
+                   hs->nfall);
   s->virt_clean = true;
   s->built = true;
   return VCP_OK;

@@ -808,6 +808,9 @@ int blocks_cluster(vcp_ctx* ctx, int32_t lo, int32_t hi, int32_t* d_local, int64
   } else {
     pts_big = 1;
   }
+  if (vcp_trace_on())
+    vcp_trace_line("blocks cluster lo=%d hi=%d pts_small=%llu pts_big=%llu any_mid=%d", lo, hi, (unsigned long long)pts_small,
+                   (unsigned long long)pts_big, (int)any_mid);
   // The small blocks run on a second stream beside the engine's launches (their outputs are disjoint: positions of d_local,
   // counters of their own); both are joined before the host reads anything.
   int64_t ev = 0;
@@ -880,7 +883,7 @@ int blocks_cluster(vcp_ctx* ctx, int32_t lo, int32_t hi, int32_t* d_local, int64
 //   zero    (after the ranks have told each other who has to zero whose last entry) the zero list: Z, positions
 //   zcoords the coordinates of the zero list (the input of the global noise pass) and the merge order
 // The single-device call runs them back to back.
-int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_sort) {
+int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_sort, bool retry = false) {
   BlocksState* s = ctx->blocks;
   hipStream_t st = ctx->stream;
   const int64_t m = s->m, nb = s->b_hi - s->b_lo;  // blocks of the share
@@ -933,7 +936,7 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
   VCP_TRY(ens(ctx, s->newlab, (size_t)(m + 1) * 4));
   int32_t* newlab = s->newlab.as<int32_t>();
   bool by_sort = force_sort || getenv("VCP_BLOCKS_ORDER_SORT") != nullptr;  // (the variable: test switch)
-  if (vcp_trace_on()) vcp_trace_line("blocks order by_sort=%d", (int)by_sort);
+  if (vcp_trace_on()) vcp_trace_line(retry ? "blocks order by_sort=%d retry=1" : "blocks order by_sort=%d", (int)by_sort);
   for (;;) {
     if (m > 0 && !by_sort) {
       VCP_LAUNCH(ctx, k_block_order, dim3(nbw), dim3(BT), 0, st, d_local, blockstart, nb, kb, cstart, csize, order,
@@ -969,6 +972,7 @@ int finish_local(vcp_ctx* ctx, const int32_t* d_local, bool sharded, bool force_
     VCP_HIP(ctx, hipStreamSynchronize(st));
     if (hp[4] == 0 || by_sort) break;
     by_sort = true;  // some block has more than CS_CAP cluster ids: once more, order by the library sort
+    if (vcp_trace_on()) vcp_trace_line("blocks order by_sort=1 retry=1");
     VCP_HIP(ctx, hipMemsetAsync(dmisc + 2, 0, 4, st));
     VCP_HIP(ctx, hipMemsetAsync(dmisc + 5, 0, 4, st));
   }
@@ -1063,7 +1067,7 @@ int blocks_finish(vcp_ctx* ctx, const int32_t* d_local, int64_t evals_blocks, in
   VCP_TRY(finish_local(ctx, d_local, false, false));
   VCP_TRY(finish_zero(ctx, false, 0, &again));
   if (again) {  // some block has more than CS_CAP cluster ids: once more, order by the library sort
-    VCP_TRY(finish_local(ctx, d_local, false, true));
+    VCP_TRY(finish_local(ctx, d_local, false, true, true));
     VCP_TRY(finish_zero(ctx, false, 0, nullptr));
   }
   if (s->f_err != 0)
