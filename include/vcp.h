@@ -85,6 +85,23 @@ int vcp_release_workspace(vcp_ctx* ctx);
  * *total.  Device pointers; returns when the result is in place. */
 int vcp_selftest_scan_dev(vcp_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, int64_t n, int op, uint32_t* total);
 
+/* Test hook: overwrite everything a call may not rely on.  armed != 0: waits for the context's stream, fills every
+ * workspace buffer the context lists over its whole capacity, the pinned scratch and the staging area with the 32-bit
+ * `word`, waits again, and reports the device buffers filled and their bytes -- device memory only, the two pinned areas
+ * are not counted -- (either pointer may be NULL).  The context
+ * stays armed: from then on every fresh allocation of the workspace and of the staging area is filled with the word
+ * before its first use, so fresh memory never looks initialised.  armed == 0 disarms and fills nothing.
+ * Left alone: the buffers that carry state across calls by design (the scan's descriptors, the output partition's window
+ * cursors: the array k_poison_left_alone in csrc/vcp_ctx.hip gives the reasons) and the buffers a staged state owns.
+ * For use between independent calls ONLY: never between the stages of the vcp_blocks_... or vcp_slab_... sequences, whose
+ * later stages read what the earlier ones left in the workspace.  The steady-state path pays one never-taken branch
+ * where a buffer grows. */
+int vcp_selftest_poison(vcp_ctx* ctx, int armed, uint32_t word, uint64_t* filled_bytes, int32_t* filled_bufs);
+/* Test hook: sets the generation number of the scan's descriptors (30 bits; VCP_ERR_ARG beyond), to reach its wrap
+ * (memset, restart at 1) without 2^30 scans.  Only raise it: a generation the context has used may still stand in a
+ * descriptor. */
+int vcp_selftest_scan_generation(vcp_ctx* ctx, uint32_t gen);
+
 /* Self-test of the Horn step of vcp_icp (BC/ICP.cs:53-124, intended arithmetic), run on the HOST from the same source
  * the device executes per round: sums[16] as vcp_icp_sums returns them, nd data points.  use_v != 0: V [16] is the
  * eigenvector basis of a previous round (warm start; a basis that is not orthonormal to 1e-9 -- NaN included -- is

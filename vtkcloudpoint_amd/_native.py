@@ -43,6 +43,7 @@ SYMBOLS = [
     "vcp_selftest_format_field", "vcp_selftest_format_total_dev", "vcp_selftest_wave_dev",
     "vcp_cluster_moments", "vcp_cluster_moments_dev", "vcp_selftest_sym_eig",
     "vcp_cluster_spheres", "vcp_cluster_spheres_dev", "vcp_selftest_spd_solve",
+    "vcp_selftest_poison", "vcp_selftest_scan_generation",
 ]
 
 
@@ -135,10 +136,12 @@ class Context:
         if rc != 0:
             raise VcpError(rc, (lib().vcp_last_error(None) or b"").decode())
 
+    _borrowed = False  # True: the handle belongs to a MultiContext (MultiContext.ctx), which destroys it
+
     def close(self):
-        if self._h:
+        if self._h and not self._borrowed:
             lib().vcp_destroy(self._h)
-            self._h = C.c_void_p()
+        self._h = C.c_void_p()
 
     def __del__(self):
         try:
@@ -159,6 +162,19 @@ class Context:
         self._chk(lib().vcp_selftest_scan_dev(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_int64(n), C.c_int(op),
                                               C.byref(tot)))
         return tot.value
+
+    def selftest_poison(self, word, armed=True):
+        """Test hook (vcp_selftest_poison): fill the workspace, the pinned scratch and the staging area with the 32-bit
+        word and arm the context, so that every later allocation is filled too; armed=False disarms.  Between independent
+        calls only.  Returns (bytes of device memory filled, device buffers filled)."""
+        nbytes, nbufs = C.c_uint64(0), C.c_int32(0)
+        self._chk(lib().vcp_selftest_poison(self._h, C.c_int(1 if armed else 0), C.c_uint32(word & 0xFFFFFFFF),
+                                            C.byref(nbytes), C.byref(nbufs)))
+        return nbytes.value, nbufs.value
+
+    def selftest_scan_generation(self, gen):
+        """Test hook: set the generation number of the scan's descriptors (to reach its 30-bit wrap)."""
+        self._chk(lib().vcp_selftest_scan_generation(self._h, C.c_uint32(gen)))
 
     def release_workspace(self):
         """Free the device workspace kept between calls (it is re-allocated on demand)."""
@@ -1408,6 +1424,15 @@ class MultiContext:
 
     def count(self):
         return int(lib().vcp_multi_count(self._h))
+
+    def ctx(self, i):
+        """The context of device i as a Context that does not own it (vcp_multi_ctx: borrowed; closing it does nothing)."""
+        h = lib().vcp_multi_ctx(self._h, int(i))
+        if not h:
+            raise IndexError("no context %d" % i)
+        c = Context.__new__(Context)
+        c._h, c._borrowed = C.c_void_p(h), True
+        return c
 
     def dbscan_blocks(self, motor, eps, min_pts, pts_in_cell, small_max=3, key_xy=None):
         motor = _f64(motor, 2)

@@ -78,6 +78,22 @@ int vcp_bind(vcp_ctx* ctx) {
   return VCP_OK;
 }
 
+// ---- the workspace poison (vcp_selftest_poison below) -----------------------------------------------------------------------
+// `bytes` of device memory at p, filled with the 32-bit word on the context's stream: whole words, then the odd tail
+// byte by byte (the word's low bytes, as the next word would have started).
+static int poison_dev(vcp_ctx* ctx, void* p, size_t bytes, uint32_t word) {
+  if (bytes / 4) VCP_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)word, bytes / 4, ctx->stream));
+  for (size_t k = bytes & ~(size_t)3; k < bytes; k++)
+    VCP_HIP(ctx, hipMemsetD8Async(reinterpret_cast<hipDeviceptr_t>(static_cast<char*>(p) + k),
+                                  (unsigned char)(word >> (8 * (k & 3))), 1, ctx->stream));
+  return VCP_OK;
+}
+// the same for pinned host memory nothing on the device is using
+static void poison_host(void* p, size_t bytes, uint32_t word) {
+  unsigned char* c = static_cast<unsigned char*>(p);
+  for (size_t k = 0; k < bytes; k++) c[k] = (unsigned char)(word >> (8 * (k & 3)));
+}
+
 int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes, bool listed) {
   if (bytes == 0) bytes = 16;
   if (b.cap >= bytes) return VCP_OK;
@@ -98,6 +114,9 @@ int vcp_ensure(vcp_ctx* ctx, DevBuf& b, size_t bytes, bool listed) {
     return vcp_fail(ctx, VCP_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
   }
   b.cap = want;
+  // fresh memory never looks initialised while the poison is armed (ordered on the stream before whatever the caller
+  // enqueues next, the zero-fill of a buffer in k_poison_left_alone included)
+  if (__builtin_expect(ctx->poison_armed, 0)) VCP_TRY(poison_dev(ctx, b.p, b.cap, ctx->poison_word));
   return VCP_OK;
 }
 
@@ -320,8 +339,17 @@ void* vcp_stage(vcp_ctx* ctx, size_t bytes) {
     return nullptr;
   }
   ctx->stage_bytes = want;
+  if (__builtin_expect(ctx->poison_armed, 0)) poison_host(ctx->stage, want, ctx->poison_word);
   return ctx->stage;
 }
+
+// The workspace buffers that carry state from one call to the next BY DESIGN: vcp_selftest_poison leaves them alone.
+// Everything else in vcp_ctx::bufs, the pinned scratch and the staging area hold nothing a call may rely on.  One entry
+// per line, the reason behind it (tests/test_poison_cases.py reads this array and holds its own table to it).
+static DevBuf vcp_ctx::* const k_poison_left_alone[] = {
+    &vcp_ctx::b_scan_tmp,  // the scan's ticket and generation-stamped descriptors: k_scan takes its tile from the ticket and its look-back spins on the descriptors (above k_scan); scan_u32 zero-fills fresh memory, the last ticket holder resets the ticket
+    &vcp_ctx::b_outcur,    // the output partition's window cursors: k_out_scatter places records from them, k_out_write leaves them zero for the next call; output_partition zero-fills fresh memory only (gridbuild.hip)
+};
 
 // ------------------------------------------------------------------------------------------
 extern "C" {
@@ -372,6 +400,44 @@ int vcp_selftest_scan_dev(vcp_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, i
   VCP_HIP(ctx, hipMemcpyAsync(h, d_tot, 4, hipMemcpyDeviceToHost, ctx->stream));
   VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (total) *total = h[0];
+  return VCP_OK;
+}
+
+int vcp_selftest_poison(vcp_ctx* ctx, int armed, uint32_t word, uint64_t* filled_bytes, int32_t* filled_bufs) {
+  if (!ctx) return VCP_ERR_ARG;
+  if (filled_bytes) *filled_bytes = 0;
+  if (filled_bufs) *filled_bufs = 0;
+  if (!armed) {
+    ctx->poison_armed = false;
+    return VCP_OK;
+  }
+  VCP_TRY(vcp_bind(ctx));
+  VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->poison_armed = true;
+  ctx->poison_word = word;
+  uint64_t bytes = 0;
+  int32_t nb = 0;
+  for (DevBuf* b : ctx->bufs) {
+    if (!b->p || !b->cap) continue;
+    bool skip = false;
+    for (DevBuf vcp_ctx::* const m : k_poison_left_alone) skip = skip || b == &(ctx->*m);
+    if (skip) continue;
+    VCP_TRY(poison_dev(ctx, b->p, b->cap, word));
+    bytes += b->cap;
+    nb++;
+  }
+  poison_host(ctx->pinned, ctx->pinned_bytes, word);  // allocated once by vcp_create: it never grows
+  if (ctx->stage) poison_host(ctx->stage, ctx->stage_bytes, word);
+  VCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (filled_bytes) *filled_bytes = bytes;  // device memory only: the two pinned areas would hide an empty list
+  if (filled_bufs) *filled_bufs = nb;
+  return VCP_OK;
+}
+
+int vcp_selftest_scan_generation(vcp_ctx* ctx, uint32_t gen) {
+  if (!ctx) return VCP_ERR_ARG;
+  if (gen > 0x3FFFFFFFu) return vcp_fail(ctx, VCP_ERR_ARG, "the scan's generation has 30 bits");
+  ctx->scan_gen = gen;
   return VCP_OK;
 }
 

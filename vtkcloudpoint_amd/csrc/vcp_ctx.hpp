@@ -50,6 +50,9 @@ struct vcp_ctx {
   void* stage = nullptr;
   size_t stage_bytes = 0;
   uint32_t scan_gen = 0;  // generation number of the scan descriptors in b_scan_tmp (vcp_ctx.hip: k_scan)
+  // vcp_selftest_poison (vcp_ctx.hip): while armed, every fresh allocation is filled with the word before first use
+  bool poison_armed = false;
+  uint32_t poison_word = 0;
   // workspace
   std::vector<DevBuf*> bufs;
   DevBuf b_cellof, b_rank, b_sidx, b_flags, b_parent, b_minord, b_seedflag,
