@@ -17,7 +17,9 @@
 //                   wait for each other in LDS and are stored together, which halves the write requests
 //   (k_part_split)  grids of more than 8192 buckets (very sparse: C5's 1.4 G cells): the coarse passes run on
 //                   super-buckets of up to 32 buckets and this pass splits each into its buckets, cursors in LDS
-//   k_part_fine     one workgroup per bucket: count the bucket's records per cell in LDS, scan, store the bucket's
+//   k_part_fine*    (k_part_fine_small: buckets of few records, per word of 32 cells; k_part_fine_mid: the others of up to
+//                   8192 records, two workgroups per CU; k_part_fine: the rest, and every handed-on bucket of a 3-D build)
+//                   one workgroup per bucket: count the bucket's records per cell in LDS, scan, store the bucket's
 //                   slice of the CELL TABLE (grid_common.hpp: CellTab -- two bit planes + a start per word of 32 cells,
 //                   full starts only for words with a populous cell; written exactly once, never zero-filled), then
 //                   assemble the bucket in LDS in its final order and store it as full lines: binary32 coordinates,
@@ -32,6 +34,7 @@
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
+#include <vector>
 
 #include "grid_common.hpp"
 #include "wave.hpp"
@@ -554,6 +557,175 @@ __global__ __launch_bounds__(FS) void k_part_fine_small(const Rec* __restrict__ 
   fine_flush<GD, GROUPED, FS>(s, m, s32, sidx, ord, in_classed, group, sorted32, sord, sidx_out, sgroup, flags, pos);
 }
 
+// ---- fine pass, handed-on buckets of up to mcap records ------------------------------------------------------------
+// The buckets k_part_fine_small hands on (bstate 1) that hold at most mcap = 8192 records: on the 10 M-point cloud 2213 of
+// the 2230 (1385 of up to 4096 records, 828 of up to 8192).  k_part_fine works such a bucket with 120 KB of LDS, one
+// workgroup per CU, walks its records in loops whose every load is waited for before the next is issued, and reads them
+// once more per window of 4096.  This kernel does the same work in 80 KB and 64 VGPRs, two workgroups per CU (2-D only:
+// the 3-D instantiation does not fit 64 VGPRs without scratch, so 3-D builds keep the old path):
+//   records   the at most mcap / FT = 8 records of a thread are loaded with one batch of loads (index clamped to the
+//             bucket's last record, so that no load sits in a branch with its use) and stay in registers from the counting
+//             pass to the placing pass: no second global read.  The indices of records 4 .. 7 wait in LDS (park) -- with
+//             them in registers the kernel spilled 44 bytes per lane to scratch, 100 MB per build
+//   counters  16 bits per cell, two cells per word, counted with a 32-bit LDS atomic of 1 or 0x10000 (st32 of
+//             k_part_fine_small); at most 8192 records per bucket, so no half-word carries and starts and cursors relative
+//             to the bucket's first position fit as well.  A thread scans 16 consecutive cells = two 16-byte pieces, and
+//             the two pieces live in two planes of the array (cells 0-7 of every run, then cells 8-15 of every run):
+//             consecutive lanes then read and write consecutive 16-byte slots, conflict-free without a pad word.  The second
+//             pass of the scan reads the counts again, one piece at a time (eight count registers less)
+//   staging   a part of mstg = 2048 positions at a time: every thread puts the records whose final position falls into the
+//             part, barrier, fine_flush, barrier
+// The table words (ctwords, ctdense, one atomic on ctcount per bucket) are produced as in k_part_fine.  Buckets done here
+// are marked bstate 2.  LDS: 32 KB counters + 24 KB staging (dynamic) + 16 KB park + 6 KB table words = 79 952 B.
+constexpr uint32_t mcap(int gd) { return gd == 2 ? 8192u : 4096u; }  // records per bucket
+constexpr uint32_t mstg(int gd) { return gd == 2 ? 2048u : 1024u; }  // records staged per flush
+constexpr size_t mid_lds(int gd, uint32_t cpb) { return (size_t)cpb * 2 + (size_t)mstg(gd) * ((gd == 2 ? 8 : 16) + 4); }
+
+// cell (relative to the bucket) -> index of its 16-bit counter: run of 16 cells c >> 4, piece (c >> 3) & 1, cell in the piece
+__device__ __forceinline__ uint32_t mid_slot(uint32_t c, uint32_t half) {
+  return ((c >> 3) & 1u) * half + ((c >> 4) << 3) + (c & 7u);
+}
+
+template <int GD, bool GROUPED>
+__global__ __launch_bounds__(FT, 8) void k_part_fine_mid(const Rec* __restrict__ rec, const uint32_t* __restrict__ bstart,
+                                                     uint32_t bstride, const uint32_t* __restrict__ total, uint32_t B,
+                                                     uint32_t csh, GridP g, const uint32_t* __restrict__ ord,
+                                                     const uint8_t* __restrict__ in_classed, const int32_t* __restrict__ group,
+                                                     uint4* __restrict__ ctwords, uint32_t* __restrict__ ctdense,
+                                                     uint32_t* __restrict__ ctcount, uint8_t* __restrict__ bstate,
+                                                     float* __restrict__ sorted32, uint32_t* __restrict__ sord,
+                                                     uint32_t* __restrict__ sidx_out, int32_t* __restrict__ sgroup,
+                                                     uint8_t* __restrict__ flags, uint32_t* __restrict__ pos) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  __shared__ uint32_t wsum[FT / 64];
+  __shared__ uint32_t w_lo[512], w_hi[512], w_slot[512];  // the bucket's words of the cell table (2^14 cells at most)
+  __shared__ uint32_t s_dbase;
+  constexpr uint32_t WCAP = mcap(GD), STG = mstg(GD);
+  constexpr uint32_t FPR = GD == 2 ? 2 : 4;  // staged floats per record
+  constexpr int MRPT = WCAP / FT;            // records per thread
+  static_assert(WCAP % FT == 0 && WCAP % STG == 0 && WCAP <= 0xFFFFu, "k_part_fine_mid: window shape");
+  const uint32_t b = blockIdx.x;
+  if (bstate[b] != 1) return;  // done by k_part_fine_small
+  uint32_t s, e;
+  bucket_range(bstart, bstride, total, b, B, s, e);
+  const uint32_t m = e - s;
+  if (m > WCAP || m == 0u) return;  // k_part_fine's
+  const uint32_t CPB = 1u << csh, HALF = CPB >> 1, c0 = b << csh;
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(lds);                      // [CPB / 2]: two 16-bit counters per word
+  float* s32 = reinterpret_cast<float*>(lds + (size_t)CPB * 2);          // [STG * FPR]
+  uint32_t* sidx = reinterpret_cast<uint32_t*>(s32 + (size_t)STG * FPR); // [STG]
+  // the thread's records: loaded once, kept to the end
+  Rec r[MRPT];
+  uint32_t idx[MRPT], cl[MRPT];  // the point's index; its cell relative to the bucket, NONE = no record
+  // the indices of the records MRPT / 2 .. wait in LDS for the staging (64 registers hold 8 records only just)
+  __shared__ uint32_t park[MRPT / 2][FT];
+#pragma unroll
+  for (int k = 0; k < MRPT; k++) {
+    const uint32_t j = s + (uint32_t)k * FT + threadIdx.x;
+    r[k] = rec[min(j, e - 1u)];  // (all loads in flight together: no load sits in a branch with its use)
+  }
+#pragma unroll
+  for (int k = 0; k < MRPT; k++) {
+    const uint32_t c = rec_cell<GD>(r[k], g, idx[k]) - c0;
+    cl[k] = s + (uint32_t)k * FT + threadIdx.x < e ? c : NONE;
+    if (k >= MRPT / 2) park[k - MRPT / 2][threadIdx.x] = idx[k];
+  }
+  uint4* cnt4 = reinterpret_cast<uint4*>(lds);
+  for (uint32_t k = threadIdx.x; k < CPB / 8; k += FT) cnt4[k] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < MRPT; k++)
+    if (cl[k] != NONE) atomicAdd(&cnt[mid_slot(cl[k], HALF) >> 1], (cl[k] & 1u) ? 0x10000u : 1u);
+  __syncthreads();
+  // exclusive scan of the CPB counters: thread t < CPB / 16 owns cells 16 t .. 16 t + 15 = one piece in either plane
+  const uint32_t NA = CPB >> 4, NW = CPB >> 5;
+  const bool act = threadIdx.x < NA;
+  uint32_t loc = 0;
+  if (act) {
+    const uint4 a = cnt4[threadIdx.x], c = cnt4[NA + threadIdx.x];
+    loc = a.x + a.y + a.z + a.w + c.x + c.y + c.z + c.w;  // (both halves at once: no carry, the bucket holds < 65536)
+    loc = (loc & 0xFFFFu) + (loc >> 16);
+  }
+  uint32_t pre = block_excl(loc, wsum);  // relative to the bucket's first position
+  {
+    // second pass (the counts are read again, one piece at a time); the thread's 16 cells are half a word of the cell
+    // table: its bits of the two population planes are built on the way and OR-ed over the two threads that share the word
+    const uint32_t wstart = s + pre, bit0 = (threadIdx.x & 1u) << 4;
+    uint32_t plo = 0u, phi = 0u;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      uint4 a = make_uint4(0u, 0u, 0u, 0u);
+      if (act) a = cnt4[h * NA + threadIdx.x];
+      uint32_t v[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const uint32_t n0 = v[k] & 0xFFFFu, n1 = v[k] >> 16;
+        v[k] = pre | ((pre + n0) << 16);  // (a start is at most mcap: 16 bits)
+        pre += n0 + n1;
+        const uint32_t q0 = min(n0, 3u), q1 = min(n1, 3u);
+        plo |= ((q0 & 1u) | ((q1 & 1u) << 1)) << (bit0 + 8 * h + 2 * k);
+        phi |= ((q0 >> 1) | ((q1 >> 1) << 1)) << (bit0 + 8 * h + 2 * k);
+      }
+      if (act) cnt4[h * NA + threadIdx.x] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+    plo |= (uint32_t)__shfl_xor((int)plo, 1, 64);
+    phi |= (uint32_t)__shfl_xor((int)phi, 1, 64);
+    if (act && (threadIdx.x & 1u) == 0u) {  // the word's first thread
+      w_lo[threadIdx.x >> 1] = plo;
+      w_hi[threadIdx.x >> 1] = phi;
+      w_slot[threadIdx.x >> 1] = wstart;  // (its slot is settled below; until then the start of the word's first cell)
+    }
+  }
+  __syncthreads();
+  {
+    // populous words keep their 32 starts in full, numbered inside the workgroup behind ONE atomic per bucket (k_part_fine)
+    const bool popl = threadIdx.x < NW && (w_lo[threadIdx.x] & w_hi[threadIdx.x]) != 0u;
+    uint32_t tot;
+    const uint32_t before = block_rank<FT>(popl, wsum, tot);
+    if (threadIdx.x == 0) {
+      s_dbase = tot ? atomicAdd(&ctcount[0], tot) : 0u;
+      bstate[b] = 2;
+    }
+    __syncthreads();
+    if (threadIdx.x < NW) {
+      const uint32_t slot = popl ? s_dbase + before : NONE;
+      const uint32_t wpos = w_slot[threadIdx.x];
+      w_slot[threadIdx.x] = slot;
+      const size_t W = (size_t)(c0 >> 5) + threadIdx.x;
+      if (W < vcp_ct_words(g.ncells))
+        ctwords[W] = make_uint4(w_lo[threadIdx.x], w_hi[threadIdx.x], wpos, slot);
+    }
+    __syncthreads();
+    const uint16_t* cnt16 = reinterpret_cast<const uint16_t*>(lds);
+    const uint32_t hw = threadIdx.x >> 5, li = threadIdx.x & 31u;  // half-waves: one populous word (128 bytes) each
+    for (uint32_t j = hw; j < NW; j += FT / 32) {
+      const uint32_t slot = w_slot[j];
+      if (slot != NONE) ctdense[(size_t)slot * 32u + li] = s + cnt16[mid_slot(32u * j + li, HALF)];
+    }
+  }
+  __syncthreads();
+  // the scanned counters serve as per-cell cursors: every record's final position, relative to the bucket
+#pragma unroll
+  for (int k = 0; k < MRPT; k++) {
+    if (cl[k] != NONE) {
+      const bool up = (cl[k] & 1u) != 0u;
+      const uint32_t old = atomicAdd(&cnt[mid_slot(cl[k], HALF) >> 1], up ? 0x10000u : 1u);
+      cl[k] = up ? old >> 16 : old & 0xFFFFu;  // the cell has served: the position takes its register
+    }
+  }
+  for (uint32_t w0 = 0; w0 < m; w0 += STG) {  // (uniform)
+#pragma unroll
+    for (int k = 0; k < MRPT; k++) {
+      const uint32_t q = cl[k] - w0;  // wraps below the part; NONE stays beyond it
+      if (q < STG) stage_put<GD>(s32, sidx, q, r[k], k >= MRPT / 2 ? park[k - MRPT / 2][threadIdx.x] : idx[k]);
+    }
+    __syncthreads();
+    fine_flush<GD, GROUPED>(s + w0, min(STG, m - w0), s32, sidx, ord, in_classed, group, sorted32, sord, sidx_out, sgroup,
+                            flags, pos);
+    __syncthreads();
+  }
+}
+
 template <int GD, bool GROUPED>
 __global__ __launch_bounds__(FT) void k_part_fine(const Rec* __restrict__ rec, uint32_t* __restrict__ rk,
                                                  const uint32_t* __restrict__ bstart, uint32_t bstride,
@@ -571,7 +743,7 @@ __global__ __launch_bounds__(FT) void k_part_fine(const Rec* __restrict__ rec, u
   __shared__ uint32_t w_lo[512], w_hi[512], w_slot[512];  // the bucket's words of the cell table (2^14 cells at most)
   __shared__ uint32_t s_dbase;
   const uint32_t b = blockIdx.x;
-  if (bstate[b] == 0) return;  // done by k_part_fine_small
+  if (bstate[b] != 1) return;  // done by k_part_fine_small (0) or k_part_fine_mid (2)
   constexpr uint32_t WCAP = wcap(GD);
   constexpr uint32_t FPR = GD == 2 ? 2 : 4;  // staged floats per record
   const uint32_t CPB = 1u << csh;
@@ -730,27 +902,39 @@ __global__ __launch_bounds__(FT) void k_part_fine_windows(const Rec* __restrict_
 // 10 M points, against 0.15 ms for the same stores made straight from the lanes -- tools/micro/part_bench.hip).
 // OWSH (log2 of the window) is chosen per call: 15 from 8 M points (longer runs per window in the scatter pass: 0.086 ms
 // against 0.134 ms at 13 for 10 M points), 14 / 13 below, so that smaller clouds still fill the CUs with windows.
-constexpr int OT = 1024, OPT = 16;  // scatter pass: OT * OPT positions per workgroup (longer runs per window)
+constexpr int OT = 1024, OPT = 10;  // scatter pass: OT * OPT positions per workgroup.  Two workgroups per CU (58 VGPRs); 977
+                                    // workgroups on 512 places for 10 M points.  Measured 63.9 us at 10, 64.9 at 12, 70.4 at 16
+                                    // (profiles/fine_mid_rocprof.md); the parent, one workgroup per CU at 16: 84.0
 constexpr int OWT = 512;           // write pass: one workgroup per window
 
 template <int OWSH>
-__global__ __launch_bounds__(OT) void k_out_scatter(const uint32_t* __restrict__ sord, const uint32_t* __restrict__ labk,
+__global__ __launch_bounds__(OT, 8) void k_out_scatter(const uint32_t* __restrict__ sord, const uint32_t* __restrict__ labk,
                                                    int64_t n, uint32_t OB, uint32_t* __restrict__ gcur,
                                                    uint2* __restrict__ rec) {
   extern __shared__ uint32_t h[];
   for (uint32_t k = threadIdx.x; k < OB; k += OT) h[k] = 0;
   __syncthreads();
   const int64_t first = (int64_t)blockIdx.x * (OT * OPT);
-  uint32_t o[OPT], w[OPT], r[OPT];
+  // ranks inside the workgroup's run of a window are below OT * OPT: two per register
+  static_assert(OPT % 2 == 0 && OT * OPT <= 65536, "k_out_scatter: packed ranks");
+  uint32_t o[OPT], w[OPT], r[OPT / 2];
+  // all loads first: inside `if (p < n)` next to the atomic that needs it, every load was waited for before the next was
+  // issued -- OPT memory latencies in a row.  A position behind n reads the last point's words and drops them.
+  const uint32_t cnt = (uint32_t)min((int64_t)(OT * OPT), n - first);  // positions of this workgroup (at least one)
+  const uint32_t* __restrict__ so = sord + first;
+  const uint32_t* __restrict__ la = labk + first;
 #pragma unroll
   for (int k = 0; k < OPT; k++) {
-    const int64_t p = first + (int64_t)k * OT + threadIdx.x;
-    o[k] = NONE;
-    if (p < n) {
-      o[k] = sord[p];
-      w[k] = labk[p];
-      r[k] = atomicAdd(&h[o[k] >> OWSH], 1u);
-    }
+    const uint32_t q = min((uint32_t)k * OT + threadIdx.x, cnt - 1u);
+    o[k] = so[q];
+    w[k] = la[q];
+  }
+#pragma unroll
+  for (int k = 0; k < OPT / 2; k++) r[k] = 0u;
+#pragma unroll
+  for (int k = 0; k < OPT; k++) {
+    if ((uint32_t)k * OT + threadIdx.x < cnt) r[k >> 1] |= atomicAdd(&h[o[k] >> OWSH], 1u) << (16 * (k & 1));
+    else o[k] = NONE;
   }
   __syncthreads();
   // claim this workgroup's run in every window it touches (one returning atomic per touched window)
@@ -763,7 +947,7 @@ __global__ __launch_bounds__(OT) void k_out_scatter(const uint32_t* __restrict__
   for (int k = 0; k < OPT; k++) {
     if (o[k] == NONE) continue;
     const uint32_t bk = o[k] >> OWSH;
-    rec[((size_t)bk << OWSH) + h[bk] + r[k]] = make_uint2(o[k], w[k]);
+    rec[((size_t)bk << OWSH) + h[bk] + ((r[k >> 1] >> (16 * (k & 1))) & 0xFFFFu)] = make_uint2(o[k], w[k]);
   }
 }
 
@@ -905,6 +1089,18 @@ int build(vcp_ctx* ctx, const GridBuildArgs& a) {
   VCP_LAUNCH(ctx, (k_part_fine_small<GD, GROUPED>), dim3(pg.B), dim3(FS), 0, st, rec, bstart, bstride, total, pg.B, pg.csh,
                   a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount, bstate, a.sorted32, a.sord,
                   a.sidx, a.sgroup, a.flags, a.pos);
+  // the handed-on buckets of one window: two workgroups per CU (VCP_FINE_MID=0: test switch, every bucket the old way)
+  // 2-D only: the 3-D instantiation needs 67 VGPRs (7 waves per SIMD: one workgroup per CU again) or, bounded to 64, spills
+  static const bool mid_env = env_int("VCP_FINE_MID", 1, 0, 1) != 0;
+  const bool mid_on = mid_env && GD == 2;
+  const size_t lds_m = mid_lds(GD, CPB);
+  if (vcp_trace_on()) vcp_trace_line("gridfine mid_on=%d lds_m=%zu", (int)mid_on, lds_m);
+  if constexpr (GD == 2) if (mid_on) {
+    VCP_TRY(allow_lds(ctx, k_part_fine_mid<GD, GROUPED>, lds_m));
+    VCP_LAUNCH(ctx, (k_part_fine_mid<GD, GROUPED>), dim3(pg.B), dim3(FT), lds_m, st, rec, bstart, bstride, total, pg.B,
+                    pg.csh, a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount, bstate, a.sorted32,
+                    a.sord, a.sidx, a.sgroup, a.flags, a.pos);
+  }
   VCP_LAUNCH(ctx, (k_part_fine<GD, GROUPED>), dim3(pg.B), dim3(FT), lds_f, st, rec, ctx->b_rank.as<uint32_t>(), bstart,
                   bstride, total, pg.B, pg.csh, a.g, a.d_ord, a.d_in_classed, a.d_group, a.ctwords, a.ctdense, a.ctcount,
                   a.sorted32, a.sord, a.sidx, a.sgroup, a.flags, a.pos, queue, qcount, bstate);
@@ -916,6 +1112,14 @@ int build(vcp_ctx* ctx, const GridBuildArgs& a) {
     VCP_LAUNCH(ctx, (k_part_fine_windows<GD, GROUPED>), dim3(gw), dim3(FT), lds_w, st, rec, ctx->b_rank.as<uint32_t>(),
                     bstart, bstride, total, pg.B, a.g, a.d_ord, a.d_in_classed, a.d_group, ct, a.sorted32,
                     a.sord, a.sidx, a.sgroup, a.flags, a.pos, queue, qcount);
+  }
+  if (vcp_trace_on()) {  // which kernel took how many buckets (0 small, 2 mid, 1 k_part_fine): read back under the trace only
+    std::vector<uint8_t> hs(pg.B);
+    VCP_HIP(ctx, hipMemcpyAsync(hs.data(), bstate, pg.B, hipMemcpyDeviceToHost, st));
+    VCP_HIP(ctx, hipStreamSynchronize(st));
+    unsigned cnt[3] = {0u, 0u, 0u};
+    for (uint8_t v : hs) cnt[v < 3 ? v : 1]++;
+    vcp_trace_line("gridfine small=%u mid=%u big=%u", cnt[0], cnt[2], cnt[1]);
   }
   return VCP_OK;
 }
