@@ -11,11 +11,13 @@ _LAZY = {
     "cluster_moments": "moments", "ellipse_radius": "moments", "ellipse_sides": "moments", "filter_by_moments": "moments",
     "ClusterMoments": "moments",
     "cluster_spheres": "spheres", "sphere_centres": "spheres", "filter_by_spheres": "spheres", "ClusterSpheres": "spheres",
+    "extract_planes": "planes", "plane_score": "planes", "planes_from_triples": "planes", "plane_label": "planes",
+    "plane_residuals": "planes", "remove_planes": "planes", "plane_score_shape": "planes", "Planes": "planes",
 }
 
 
 def __getattr__(name):
-    """The per-cluster statistics by name (robust.py, moments.py, spheres.py), imported on first use: importing the package loads
+    """The per-cluster statistics and the plane extraction by name (robust.py, moments.py, spheres.py, planes.py), imported on first use: importing the package loads
     neither numpy nor the library."""
     if name in _LAZY:
         import importlib

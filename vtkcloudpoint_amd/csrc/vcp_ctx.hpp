@@ -44,6 +44,8 @@ struct vcp_ctx {
   //                 DB's counters (dbdead.hip, dbpairs.hip); the round counters of vcp_match_unique (match_unique.hip)
   //                 and of vcp_eps_tree (eps_tree.hip); the cluster count of vcp_gdbscan (gdbscan.hip)
   //   [2048, 2064)  DB pair by pair: next seed / frontier size (dbpairs.hip)
+  //   [4096, 4224)  plane extraction (planes.hip): m, the winner, the refit's count and plane, the rows labelled.  Clear of
+  //                 [0, 32), which the refit's vcp_cluster_moments_dev writes between them
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
   // pinned staging area of the host-buffer entry points with several small arrays (vcp_stage; grown on demand, <= 64 MiB)
@@ -96,6 +98,9 @@ struct vcp_ctx {
   DevBuf b_cs_in, b_cs_out, b_cs_misc, b_cs_d;
   struct BlocksState* blocks = nullptr;  // staged block-partitioned pipeline (blocks.hip)
   struct SlabState* slab = nullptr;      // staged exact multi-GPU DBSCAN (dbscan.hip: vcp_slab_*)
+  // plane extraction (planes.hip, which describes them): its workspace buffers b_pl_*.  They are listed in `bufs` like
+  // the members above (freed with the workspace, filled by vcp_selftest_poison); the struct itself goes with the context
+  struct PlanesWs* planes = nullptr;
   // timing
   bool timing = false;
   std::vector<Phase> phases;
