@@ -13,12 +13,14 @@ _LAZY = {
     "cluster_spheres": "spheres", "sphere_centres": "spheres", "filter_by_spheres": "spheres", "ClusterSpheres": "spheres",
     "extract_planes": "planes", "plane_score": "planes", "planes_from_triples": "planes", "plane_label": "planes",
     "plane_residuals": "planes", "remove_planes": "planes", "plane_score_shape": "planes", "Planes": "planes",
+    "point_features": "features", "sor_keep": "features", "centre_votes": "features", "point_features_shape": "features",
+    "PointFeatures": "features",
 }
 
 
 def __getattr__(name):
-    """The per-cluster statistics and the plane extraction by name (robust.py, moments.py, spheres.py, planes.py), imported on first use: importing the package loads
-    neither numpy nor the library."""
+    """The per-cluster statistics, the plane extraction and the per-point features by name (robust.py, moments.py,
+    spheres.py, planes.py, features.py), imported on first use: importing the package loads neither numpy nor the library."""
     if name in _LAZY:
         import importlib
         return getattr(importlib.import_module("." + _LAZY[name], __name__), name)

@@ -132,13 +132,16 @@ __host__ __device__ inline int sym_eig(const double* s, double* eval, double* ev
         big = fabs(v[k]);
         neg = v[k] < 0.0;
       }
+    // selects, not stores under a branch: for D = 2 the compiler folds `if (rank == j) eval[j] = ...` over j = 0, 1 into
+    // eval[rank] = ..., a dynamic index, and the caller's arrays go to scratch.  Every rank is taken exactly once, so
+    // every entry is written; the first pass reads nothing (i == 0 selects against a constant).
 #pragma unroll
-    for (int j = 0; j < D; j++)
-      if (rank == j) {
-        eval[j] = lam[i];
+    for (int j = 0; j < D; j++) {
+      const bool here = rank == j;
+      eval[j] = here ? lam[i] : (i == 0 ? 0.0 : eval[j]);
 #pragma unroll
-        for (int k = 0; k < D; k++) evec[j * D + k] = neg ? -v[k] : v[k];
-      }
+      for (int k = 0; k < D; k++) evec[j * D + k] = here ? (neg ? -v[k] : v[k]) : (i == 0 ? 0.0 : evec[j * D + k]);
+    }
   }
   return sweeps;
 }

@@ -389,6 +389,7 @@ int vcp_create(int device_id, vcp_ctx** out) {
 void vcp_blocks_state_free(vcp_ctx* ctx);  // blocks.hip
 void vcp_slab_state_free(vcp_ctx* ctx);    // dbscan.hip
 void vcp_planes_ws_free(vcp_ctx* ctx);     // planes.hip: after the buffers it holds have left ctx->bufs
+void vcp_features_ws_free(vcp_ctx* ctx);   // point_features.hip: likewise
 
 int vcp_selftest_scan_dev(vcp_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, int64_t n, int op, uint32_t* total) {
   if (!ctx) return VCP_ERR_ARG;
@@ -472,6 +473,7 @@ void vcp_destroy(vcp_ctx* ctx) {
     b->p = nullptr;
   }
   vcp_planes_ws_free(ctx);
+  vcp_features_ws_free(ctx);
   for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->stage) (void)hipHostFree(ctx->stage);

@@ -101,6 +101,7 @@ struct vcp_ctx {
   // plane extraction (planes.hip, which describes them): its workspace buffers b_pl_*.  They are listed in `bufs` like
   // the members above (freed with the workspace, filled by vcp_selftest_poison); the struct itself goes with the context
   struct PlanesWs* planes = nullptr;
+  struct FeaturesWs* features = nullptr;  // per-point features (point_features.hip): b_pf_*, held the same way
   // timing
   bool timing = false;
   std::vector<Phase> phases;
